@@ -19,7 +19,7 @@ noise/utils/adv/attack.py:20-23).  The bf16 engine's figure for the same step fo
 error; BASELINE configs 4 and 5 (ViT-B/16 x ImageNet-C, ResNet-50 adversarial training) follow as `secondary`, three
 steps each; the oracle on the host cores as `cpu_baseline`.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 """
 import argparse
@@ -65,7 +65,15 @@ def parse():
     ap.add_argument('--spawn-check', action='store_true',
                     help='launch-path self test (no GPU work): every rank joins a gloo group, rank 0 prints one JSON line '
                          'with the world size it saw -- covers the --gpus N re-launch on a CPU-only box')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='headline workload: after the timed steps, write what the last timed step computed to DIR/<name>.npy '
+                         '(float32 / float64, rank 0); the same arguments give the same inputs, so two builds compare output for output')
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if args.dump_outputs and args.workload != 'headline':
+        ap.error('--dump-outputs covers the headline workload only')
+    return args
 
 
 def _free_port():
@@ -144,7 +152,9 @@ class HipEngine:
         return self.eval_engs[k % len(self.eval_engs)].logits_from_u8(u8, self.MEAN, self.STD)
 
 
-def one_step(images, labels, path, step_idx, rank, B):
+def one_step(images, labels, path, step_idx, rank, B, keep=None):
+    """One step of the headline workload -> (correct top-1 over the five corrupted batches, correct top-1 under PGD-7).  With `keep` (a
+    dict) the step also leaves there the device arrays it computed: the corrupted batches, their logits, x_adv and its logits."""
     from robustart_amd.noise import imagenet_c as C, adv
     base = (step_idx * 1_000_003 + rank * B)          # global sample index of this rank's first image
     main = torch.cuda.current_stream()
@@ -166,12 +176,16 @@ def one_step(images, labels, path, step_idx, rank, B):
             logits = path.logits_from_u8(bufs[sev - 1], k)
             _, _, pred = adv.logit_loss(logits, labels, 0, None, 1.0, want_grad=False)
             parts.append((pred.long() == labels).sum())
+            if keep is not None:
+                keep['logits_sev%d' % sev] = logits
     x01 = C.to_unit_nchw(images, one_step.extra.setdefault(('x01', images.shape), torch.empty(B, 3, H, W, device=images.device)))
     x_adv = adv.pgd_linf(x01, labels, path.f_model, 2 / 255, 3 / 40, 7, seed=1, sample_offset=base)
     with torch.no_grad():
         logits = path.f_model(x_adv).float()
     _, _, pred = adv.logit_loss(logits, labels, 0, None, 1.0, want_grad=False)
     correct_adv = (pred.long() == labels).sum()
+    if keep is not None:
+        keep.update(corrupted=list(bufs), x_adv=x_adv, logits_adv=logits, correct_per_severity=list(parts), correct_adv=correct_adv)
     for sd in sides:
         if sd is not main:
             main.wait_stream(sd)                       # join: the step is complete when every stream's part is
@@ -184,6 +198,31 @@ one_step.extra = {}
 # only while the five evaluations last, a quarter of the step): N = 2 / 3 / 4 gave 184.0 / 184.2 / 184.2 ms per step against 183.5-184.1 for
 # this form and 191.7 on one stream -- the step is bound by what its kernels need from the chip, not by gaps between them.
 
+
+
+DUMP_SAMPLE = 1 << 19                  # flat positions sampled from each 38.5 M-element output of a step (B = 256)
+
+
+def dump_outputs(out_dir, kept):
+    """--dump-outputs: the arrays the last timed step computed, as DIR/<name>.npy (about 23 MB at B = 256).  Logits and counts are
+    written whole; the five corrupted u8 NHWC batches and x_adv (NCHW) are too large, so a fixed sample of DUMP_SAMPLE flat positions
+    (numpy seed 0, sorted, the same for every run of a batch size) stands in for each, its positions in sample_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = kept['x_adv'].numel()
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(DUMP_SAMPLE, n), replace=False))
+    idx_dev = torch.from_numpy(idx).to(kept['x_adv'].device)
+    arrays = {'sample_index': idx.astype(np.float64),
+              'x_adv_sample': kept['x_adv'].reshape(-1)[idx_dev].float(),
+              'logits_adv': kept['logits_adv'].float(),
+              'correct_per_severity': torch.stack(kept['correct_per_severity']).double(),
+              'correct_adv': kept['correct_adv'].double().reshape(1)}
+    for sev in range(1, 6):
+        assert kept['corrupted'][sev - 1].numel() == n
+        arrays['corrupted_sev%d_sample' % sev] = kept['corrupted'][sev - 1].reshape(-1)[idx_dev].float()
+        arrays['logits_sev%d' % sev] = kept['logits_sev%d' % sev].float()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a.cpu().numpy() if torch.is_tensor(a) else a)
 
 
 def measure_gaussian_roofline(B, device, launches=40, npairs=9):
@@ -923,12 +962,15 @@ def main():
     barrier()
     t0 = time.perf_counter()
     acc = None
+    kept = {} if args.dump_outputs and rank == 0 else None
     for i in range(args.steps):
-        acc = one_step(images, labels, path, args.warmup + i, rank, B)
+        acc = one_step(images, labels, path, args.warmup + i, rank, B, keep=kept if i == args.steps - 1 else None)
     torch.cuda.synchronize()
     t_local = time.perf_counter() - t0
     barrier()
     dt = time.perf_counter() - t0
+    if kept is not None:
+        dump_outputs(args.dump_outputs, kept)     # before the blocks below reuse the step's buffers
     if dist is not None:
         ta = time.perf_counter()
         t = torch.tensor([dt], device=device, dtype=torch.float64)

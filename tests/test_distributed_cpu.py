@@ -44,7 +44,9 @@ idx = S.shard_indices(22, rank, world)
 out = {'rank': rank, 'world': world, 'res': res, 'params_identical_across_ranks': same, 'n_local': len(idx),
        'first': idx[0], 'loss': loss, 'merged': [(r['index'], r['prediction'], r['label']) for r in merged]}
 print('RESULT ' + json.dumps(out))
-if dist.is_initialized(): dist.destroy_process_group()
+if dist.is_initialized():
+    dist.barrier()
+    dist.destroy_process_group()
 '''
 
 

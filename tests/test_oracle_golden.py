@@ -15,6 +15,16 @@ from oracle import attacks_ref as A
 GOLD = os.path.join(os.path.dirname(__file__), 'golden')
 
 
+@pytest.fixture(scope='module', autouse=True)
+def _onednn_off():
+    """oneDNN's CPU convolutions sum in an order that depends on the thread count (TinyNet's input gradients differ in the last bits
+    between 8 and 128 threads, which APGD-L1 amplifies past its tolerance); torch's own convolutions do not, and reproduce the fixtures."""
+    prev = torch.backends.mkldnn.enabled
+    torch.backends.mkldnn.enabled = False
+    yield
+    torch.backends.mkldnn.enabled = prev
+
+
 def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
@@ -285,19 +295,28 @@ SQUARE_LP_CASES = (('L2', 0.5, 60), ('L2', 2.0, 25), ('L1', 12.0, 60), ('L1', 40
 
 def test_square_l2_l1_match_reference():
     """SquareAttack norm 'L2' / 'L1' (square.py:123-190, 296-530) restated: with torch's random stream replayed in the reference's call
-    order the best point of EVERY image after the run (attack_single_run) and perturb()'s output are bit-identical."""
+    order the best point of EVERY image after the run (attack_single_run) and perturb()'s output are bit-identical.
+    The reference's own L2 outputs differ in the last bit between x86 CPUs (float32 normalising sums), so the fixture holds them as run on
+    two CPUs (`square/L2/...` and `square_alt/L2/...`, tests/golden/make_golden.py square_lp_alt): every L2 array must equal the SAME
+    recorded run, the one the first L2 case selects."""
     g = np.load(os.path.join(GOLD, 'square_lp_ref.npz'))
     net = make_tinynet()
     model_fn = lambda z: net(A.normalize(z))  # noqa: E731
     x, y = torch.from_numpy(g['x']), torch.from_numpy(g['y'])
+    l2_run = None
     for norm, eps, nq in SQUARE_LP_CASES:
         d = A.TorchStreamDraws(0)
         d.reseed()
         xb = A.square_lp_single_run(model_fn, x, y, eps, nq, 0.8, False, norm, d)
-        np.testing.assert_array_equal(xb.numpy(), g[f'square/{norm}/{eps}/x_best'])
+        run = 'square'
+        if norm == 'L2':
+            if l2_run is None:
+                l2_run = next((r for r in ('square', 'square_alt') if np.array_equal(xb.numpy(), g[f'{r}/L2/{eps}/x_best'])), 'square')
+            run = l2_run
+        np.testing.assert_array_equal(xb.numpy(), g[f'{run}/{norm}/{eps}/x_best'])
         d.reseed()
         adv = A.square_lp_perturb(model_fn, x, y, eps, nq, 0.8, False, norm, d)
-        np.testing.assert_array_equal(adv.numpy(), g[f'square/{norm}/{eps}/adv'])
+        np.testing.assert_array_equal(adv.numpy(), g[f'{run}/{norm}/{eps}/adv'])
         r = (xb - x).flatten(1)
         assert ((r.norm(dim=1) if norm == 'L2' else r.abs().sum(1)) <= eps * (1 + 1e-5)).all() and xb.min() >= -1e-6 and xb.max() <= 1 + 1e-6   # (L1: x + delta + projection, no clamp)
 
