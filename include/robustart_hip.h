@@ -54,7 +54,7 @@ enum {
  * its tap arrays from 16 to 32 entries and gained dst_pair_off / res_pair_off; several attack entries gained a per-row
  * sample-index pointer; round 4 -> 5: rart_stencil_fixed_point_info added).  A caller compiled against another header must refuse to run:
  * compare with rart_version(). */
-#define RART_ABI_VERSION 109
+#define RART_ABI_VERSION 110
 int rart_version(void);
 const char* rart_last_error_string(void);
 /* name of corruption id (static string), NULL if out of range */
@@ -863,6 +863,33 @@ typedef struct rart_pack_job {
   void* out;
 } rart_pack_job;
 int rart_pack_jobs_bf16(const rart_pack_job* jobs_device, int n_jobs, int blocks_per_job, rart_stream_t stream);
+
+/* ---- ConvNeXt-B (model `convnext_base`, csrc/convnext.hip; robustart_amd/model/convnext_engine.py) ---------------------------------
+ * Activations NHWC [n][h][w][c].  *_bf16: bf16 tensors; *_pair: PAIRS of bf16 planes (value = hi + lo, see rart_gemm_pair_bf16), given as
+ * explicit hi / lo pointers.  fp32 arithmetic in both.  Reference: timm's ConvNeXt block (robustart_amd/model/convnext_torch.py).
+ * rart_cnx_dwconv_ln_*: out = LayerNorm_c(depthwise 7x7 pad 3 convolution of x + b_dw) * gamma + beta (eps), the conv output y kept in
+ *   y_keep / y_hi, y_lo (nullable: the backward's LayerNorm input).  w_dw: fp32 [49][c], row dy * 7 + dx = weight[c][0][dy][dx].
+ *   One workgroup per (image, row), the row's conv outputs in LDS: c % 8 == 0, c <= 1024, w * c <= 16384, n, h <= 65535; x must not
+ *   alias out; activation pointers 8-byte, w_dw / b_dw 16-byte aligned. */
+int rart_cnx_dwconv_ln_bf16(const void* x, const float* w_dw, const float* b_dw, const float* gamma, const float* beta, void* out,
+                            void* y_keep, int n, int h, int w, int c, float eps, rart_stream_t stream);
+int rart_cnx_dwconv_ln_pair(const void* x_hi, const void* x_lo, const float* w_dw, const float* b_dw, const float* gamma, const float* beta,
+                            void* out_hi, void* out_lo, void* y_hi, void* y_lo, int n, int h, int w, int c, float eps, rart_stream_t stream);
+/* rart_cnx_dwconv_bwd_*: the depthwise convolution's backward to the input, dx = res + sum over taps of dz at (y + 3 - dy, x + 3 - dx)
+ *   times w_dw[dy * 7 + dx] (res nullable, may alias dx; dz must not).  dz is the LayerNorm backward's output (rart_layernorm_bwd_*
+ *   of the fc1 input gradient against y_keep).  Shape limits as the forward. */
+int rart_cnx_dwconv_bwd_bf16(const void* dz, const float* w_dw, const void* res, void* dx, int n, int h, int w, int c, rart_stream_t stream);
+int rart_cnx_dwconv_bwd_pair(const void* dz_hi, const void* dz_lo, const float* w_dw, const void* res_hi, const void* res_lo, void* dx_hi,
+                             void* dx_lo, int n, int h, int w, int c, rart_stream_t stream);
+/* rart_cnx_pool_bwd_*: dz[b][p][c] = dpool[b][c] / hw, the global average pool's backward (no ReLU mask; c % 8 == 0). */
+int rart_cnx_pool_bwd_bf16(const void* dpool, void* dz, int n, int hw, int c, rart_stream_t stream);
+int rart_cnx_pool_bwd_pair(const void* dpool_hi, const void* dpool_lo, void* dz_hi, void* dz_lo, int n, int hw, int c, rart_stream_t stream);
+/* rart_cnx_patchify: src fp32 NCHW in [0,1] (src_is_u8 = 0) or uint8 NHWC (1) -> (x - mean) / std as hi and lo bf16 planes
+ *   [n][(h / patch) * (w / patch)][ld], column c * patch^2 + r * patch + s; columns 3 patch^2 .. ld are zero (the stem's K padded to the
+ *   GEMM granularity).  patch 1..8 dividing h and w, ld % 8 == 0.  (rart_vit_patchify keeps its patch % 8 == 0 rule.)  The matching
+ *   backward is rart_vit_unpatchify_from_f32 with the same patch and ld. */
+int rart_cnx_patchify(const void* src, int src_is_u8, void* hi, void* lo, int n, int h, int w, int patch, int ld, const float* mean_host,
+                      const float* std_host, rart_stream_t stream);
 
 #ifdef __cplusplus
 }

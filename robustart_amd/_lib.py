@@ -13,7 +13,7 @@ c_void_p, c_int, c_size_t, c_u64, c_float = (ctypes.c_void_p, ctypes.c_int, ctyp
                                               ctypes.c_uint64, ctypes.c_float)
 c_double = ctypes.c_double
 
-ABI_VERSION = 109        # == RART_ABI_VERSION of include/robustart_hip.h; load() refuses a library built from another header
+ABI_VERSION = 110        # == RART_ABI_VERSION of include/robustart_hip.h; load() refuses a library built from another header
 
 # name -> (restype, argtypes); every symbol include/robustart_hip.h declares
 SIGNATURES = {
@@ -145,6 +145,13 @@ SIGNATURES = {
     'rart_f32_to_pair_rows': (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_int, c_void_p]),
     'rart_engine_stem_col2im_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'rart_f32_to_bf16_rows': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'rart_cnx_dwconv_ln_bf16': (c_int, [c_void_p] * 7 + [c_int] * 4 + [c_float, c_void_p]),
+    'rart_cnx_dwconv_ln_pair': (c_int, [c_void_p] * 10 + [c_int] * 4 + [c_float, c_void_p]),
+    'rart_cnx_dwconv_bwd_bf16': (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
+    'rart_cnx_dwconv_bwd_pair': (c_int, [c_void_p] * 7 + [c_int] * 4 + [c_void_p]),
+    'rart_cnx_pool_bwd_bf16': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'rart_cnx_pool_bwd_pair': (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p]),
+    'rart_cnx_patchify': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'rart_vit_patchify': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                   c_void_p]),
     'rart_vit_add_pos_cls': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

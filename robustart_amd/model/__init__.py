@@ -1,13 +1,14 @@
 """Model zoo entry point -- mirrors RobustART/model/__init__.py:1 (`get_model`).
 
-Only the two architectures BASELINE.json names are in scope:
-`resnet50_official` (forward + backward-to-input HIP engine: engine.py) and `vit_base` / `vit_b16_224`
-(forward HIP engine: vit_engine.py)."""
+Three architectures: `resnet50_official` (forward + backward-to-input HIP engine: engine.py), `vit_base` / `vit_b16_224`
+(forward + backward-to-input HIP engine: vit_engine.py) and `convnext_base` (forward + backward-to-input HIP engine:
+convnext_engine.py; no train engine).  kwargs `num_classes` and `drop_path_rate` are accepted (drop path is identity in eval)."""
 from .resnet_torch import resnet50
 from .vit_torch import vit_base
+from .convnext_torch import convnext_base
 
 _REGISTRY = {'resnet50_official': resnet50, 'resnet50': resnet50, 'vit_base': vit_base, 'vit_b16_224': vit_base,
-             'vit_base_patch16_224': vit_base}
+             'vit_base_patch16_224': vit_base, 'convnext_base': convnext_base}
 
 
 def get_model(config):
@@ -17,5 +18,5 @@ def get_model(config):
     kwargs = dict((config.get('kwargs') if isinstance(config, dict) else getattr(config, 'kwargs', None)) or {})
     kwargs.pop('bn', None)          # {use_sync_bn: False}: BN statistics are local
     if mtype not in _REGISTRY:
-        raise NotImplementedError('model type %r is outside the hot-path scope (ResNet-50 / ViT-B/16 only)' % mtype)
+        raise NotImplementedError('model type %r is outside the hot-path scope (ResNet-50 / ViT-B/16 / ConvNeXt-B only)' % mtype)
     return _REGISTRY[mtype](**kwargs)

@@ -1,0 +1,359 @@
+"""ConvNeXt-B forward and backward-to-input on the hand-written HIP kernels (evaluation of clean / corrupted images; the gradient
+step of every attack, adv/attack.py:21-22, autopgd_base.py:271-289).  Reference module: robustart_amd/model/convnext_torch.py.
+
+Layout: NHWC activations, rows = (image, y, x).  Per launch:
+  stem        rart_cnx_patchify (4x4 patches, K = 48 padded to 64, hi + lo planes) -> GEMM (+ bias) -> LayerNorm
+  downsample  LayerNorm -> the 2x2 stride-2 conv as the GEMM's conv mode (4 taps, k_per_tap = C_in, stride 2)
+  block       rart_cnx_dwconv_ln_* (7x7 depthwise conv + bias + LayerNorm, one launch) -> fc1 GEMM + exact GELU ->
+              fc2 GEMM (gamma folded in) + residual, written in place over the block input
+  head        global average pool (rart_engine_avgpool*) -> LayerNorm -> fc GEMM (fp32 logits)
+Backward: the fc dgrad GEMMs (fc2's with GELU' of the kept pre-activation in its epilogue), rart_layernorm_bwd_* against the kept
+depthwise-conv output, then rart_cnx_dwconv_bwd_* (transposed 7x7 taps) adding into the residual gradient in place; the downsample's
+backward is four GEMM launches, one per input parity (py, px), each scattering its output pixels with destination stride 2; the pool's
+backward is rart_cnx_pool_bwd_*; the stem's is a dgrad GEMM to fp32 patches and rart_vit_unpatchify_from_f32 (patch 4, row stride 64).
+
+precision 'bf16': bf16 storage, fp32 accumulation and statistics, every contraction on rart_conv_igemm_bf16 (the image still enters
+as a hi + lo pair: the stem GEMM runs both planes as two taps).  'bf16x3' (alias 'fp32x'): the reference-precision mode, every
+activation and gradient a pair of bf16 planes, every contraction the three MFMA products of rart_gemm_pair_bf16.
+
+Torch on the forward / backward path: allocation (cached per name and shape) and the fp32 logits / gradient outputs; nothing else,
+no host synchronisation."""
+import ctypes
+
+from .. import _lib
+from .vit_engine import ViTEngine, PRECISIONS, F_OUT_F32, F_GELU, F_GELU_BWD, F_GELU_KEEP, _pair
+
+STEM_K = 64                      # 3 x 4 x 4 = 48 columns, padded to the K granularity of both GEMMs
+DS_TAPS = [(0, 0), (0, 1), (1, 0), (1, 1)]
+
+
+class ConvNeXtEngine:
+    def __init__(self, model, device='cuda', precision='bf16'):
+        """precision: 'bf16' (fast path) or 'bf16x3' / 'fp32x' (reference precision: split-bf16 pairs throughout)."""
+        torch = _lib.require_gpu()
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        if precision not in PRECISIONS:
+            raise ValueError('precision must be one of %s' % sorted(PRECISIONS))
+        self.precision = PRECISIONS[precision]
+        self.x3 = self.precision == 'bf16x3'
+        self.profile = None
+        self.pair_w_interleaved = False          # (the ViT engine's lab switch; the pair tables here are plain planes)
+        self._w_il = {}
+        self._buf = {}
+        self.refold(model)
+
+    _get = ViTEngine._get
+    _gemm = ViTEngine._gemm
+    _gemm_pair = ViTEngine._gemm_pair
+
+    def refold(self, model):
+        """(Re)build every weight table from `model`'s current parameters.  fc2 carries the layer scale: W2' = gamma * W2 and
+        b2' = gamma * b2 (one fp32 product per element).  The bf16 engine then rounds gamma * W2 to bf16 once, where the module
+        multiplies the fp32 fc2 output by gamma; the reference-precision engine splits gamma * W2 into hi + lo, so it represents the
+        fp32 product to 16 significand bits like every other weight -- no rounding beyond what the pair format already carries."""
+        torch = _lib.require_gpu()
+        dev = self.device
+        m = model
+        self.depths, self.dims = tuple(m.depths), tuple(m.dims)
+
+        def f32(t):
+            return t.detach().to(dev, torch.float32).contiguous()
+
+        def pad_rows(w, mult):
+            r = (w.shape[0] + mult - 1) // mult * mult
+            if r != w.shape[0]:
+                w = torch.cat([w, torch.zeros(r - w.shape[0], w.shape[1], dtype=w.dtype, device=w.device)], 0)
+            return w.contiguous()
+
+        def pad_k(w, k):
+            if k > w.shape[1]:
+                w = torch.cat([w, torch.zeros(w.shape[0], k - w.shape[1], dtype=w.dtype, device=w.device)], 1)
+            return w.contiguous()
+
+        if self.x3:
+            def tab(w32):                  # pair planes [2][rows padded to 256][K]
+                return _pair(pad_rows(f32(w32), 256))
+            fwd = bwd = tab
+        else:
+            def fwd(w32):                  # bf16 [rows padded to 128 / 64][K]
+                w = f32(w32).to(torch.bfloat16)
+                return pad_rows(w, 128 if w.shape[0] > 64 else 64)
+            bwd = fwd
+        c0 = self.dims[0]
+        sw = pad_k(f32(m.stem[0].weight).reshape(c0, 48), STEM_K)                       # [c0][c*16 + r*4 + s], zero columns 48..63
+        if self.x3:
+            self.stem_w = fwd(sw)
+        else:
+            swb = sw.to(torch.bfloat16)
+            self.stem_w = pad_rows(torch.cat([swb, swb], 1), 128)                       # hi | lo taps of the image pair
+        self.stem_wd = bwd(sw.t())                                                       # [64][c0]
+        self.stem_b = f32(m.stem[0].bias)
+        self.stem_g, self.stem_nb = f32(m.stem[1].weight), f32(m.stem[1].bias)
+        self.stages = []
+        for si, st in enumerate(m.stages):
+            S = dict(index=si, blocks=[])
+            if si > 0:
+                ln, conv = st.downsample[0], st.downsample[1]
+                w = f32(conv.weight)                                                     # [cout][cin][2][2]
+                cout, cin = w.shape[0], w.shape[1]
+                S.update(ds_g=f32(ln.weight), ds_nb=f32(ln.bias), ds_bias=f32(conv.bias),
+                         ds_w=fwd(w.permute(0, 2, 3, 1).reshape(cout, 4 * cin)),         # k = (ty * 2 + tx) * cin + c
+                         ds_wd=[bwd(w[:, :, py, px].t()) for py, px in DS_TAPS])         # per input parity: [cin][cout]
+            for blk in st.blocks:
+                c = blk.conv_dw.weight.shape[0]
+                g = f32(blk.gamma)
+                w1, w2 = f32(blk.mlp.fc1.weight), g[:, None] * f32(blk.mlp.fc2.weight)
+                S['blocks'].append(dict(
+                    dw_w=f32(blk.conv_dw.weight).reshape(c, 49).t().contiguous(), dw_b=f32(blk.conv_dw.bias),
+                    ng=f32(blk.norm.weight), nb=f32(blk.norm.bias),
+                    fc1_w=fwd(w1), fc1_b=f32(blk.mlp.fc1.bias), fc1_wd=bwd(w1.t()),
+                    fc2_w=fwd(w2), fc2_b=(g * f32(blk.mlp.fc2.bias)).contiguous(), fc2_wd=bwd(w2.t())))
+            self.stages.append(S)
+        self.head_g, self.head_nb = f32(m.head.norm.weight), f32(m.head.norm.bias)
+        self.n_classes = m.head.fc.out_features
+        self.head_kpad = (self.n_classes + 31) // 32 * 32
+        hw = f32(m.head.fc.weight)
+        self.head_w = fwd(hw)
+        self.head_wd = bwd(pad_k(hw.t(), self.head_kpad))
+        self.head_b = f32(m.head.fc.bias)
+
+    # ------------------------------------------------------------------ precision-generic launch helpers
+    def _act(self, name, shape):
+        """activation buffer: bf16 [shape], or the pair [2][shape]"""
+        return self._get(name, ((2,) + tuple(shape)) if self.x3 else tuple(shape))
+
+    def _hl(self, t):
+        return (_lib.ptr(t[0]), _lib.ptr(t[1])) if self.x3 else (_lib.ptr(t), None)
+
+    def _mm(self, a, w, dst, M, N, K, bias=None, res=None, flags=0, aux=None):
+        """dst[M][N] = a[M][K] . w[N][K]^T (+ bias, + res, epilogue flags; aux = the GELU pre-activation kept / read)"""
+        if self.x3:
+            self._gemm_pair(a, w, dst, M, N, K, K, N, bias=bias, res=res, flags=flags, aux=aux)
+        else:
+            self._gemm(a, w, dst, M, K, N, K, N, bias=bias, res=res, flags=flags, mask=aux)
+
+    def _conv(self, src, w, dst, B, grid, src_hw, k_per_tap, taps, n_cols, dst_hw, stride, dst_stride, dst_off, bias=None):
+        """implicit-GEMM convolution on NHWC src (k_per_tap channels per pixel) -> dst (n_cols channels per pixel)"""
+        if self.x3:
+            d = _lib.GemmPairDesc()
+            d.a_hi, d.a_lo = src[0].data_ptr(), src[1].data_ptr()
+            d.w_hi, d.w_lo = w[0].data_ptr(), w[1].data_ptr()
+            d.dst_hi, d.dst_lo = dst[0].data_ptr(), dst[1].data_ptr()
+            d.bias = bias.data_ptr() if bias is not None else None
+            d.M, d.N, d.K = B * grid[0] * grid[1], n_cols, k_per_tap * len(taps)
+            d.lda, d.ldw, d.ldc, d.w_rows = k_per_tap, k_per_tap * len(taps), n_cols, w.shape[1]
+            d.conv, d.batch, d.grid_h, d.grid_w = 1, B, grid[0], grid[1]
+            d.src_h, d.src_w, d.sy, d.sx = src_hw[0], src_hw[1], stride[0], stride[1]
+            d.k_per_tap, d.n_taps = k_per_tap, len(taps)
+            for i, (dy, dx) in enumerate(taps):
+                d.tap_dy[i], d.tap_dx[i] = dy, dx
+            d.dst_h, d.dst_w = dst_hw
+            d.dst_sy, d.dst_sx = dst_stride
+            d.dst_oy, d.dst_ox = dst_off
+            _lib.check(self.lib.rart_gemm_pair_bf16(ctypes.byref(d), _lib.stream_ptr()))
+            return
+        d = _lib.ConvDesc()
+        d.src, d.wgt, d.dst = src.data_ptr(), w.data_ptr(), dst.data_ptr()
+        d.bias = bias.data_ptr() if bias is not None else None
+        d.batch, d.grid_h, d.grid_w = B, grid[0], grid[1]
+        d.src_h, d.src_w, d.src_pix_stride = src_hw[0], src_hw[1], k_per_tap
+        d.k_per_tap, d.n_taps = k_per_tap, len(taps)
+        d.sy, d.sx = stride
+        for i, (dy, dx) in enumerate(taps):
+            d.tap_dy[i], d.tap_dx[i], d.tap_src_off[i] = dy, dx, 0
+        d.n_cols = n_cols
+        d.dst_h, d.dst_w = dst_hw
+        d.dst_sy, d.dst_sx = dst_stride
+        d.dst_oy, d.dst_ox = dst_off
+        d.dst_pix_stride = n_cols
+        d.flags = 0
+        _lib.check(self.lib.rart_conv_igemm_bf16(ctypes.byref(d), _lib.stream_ptr()))
+
+    def _ln(self, x, g, b, out, rows, c):
+        lib, sp = self.lib, _lib.stream_ptr()
+        if self.x3:
+            (xh, xl), (oh, ol) = self._hl(x), self._hl(out)
+            _lib.check(lib.rart_layernorm_pair(xh, xl, _lib.ptr(g), _lib.ptr(b), oh, ol, rows, c, c, c, 1e-6, sp))
+        else:
+            _lib.check(lib.rart_layernorm_bf16(_lib.ptr(x), _lib.ptr(g), _lib.ptr(b), _lib.ptr(out), rows, c, c, c, 1e-6, sp))
+
+    def _ln_bwd(self, dy, x, g, dx, rows, c):
+        lib, sp = self.lib, _lib.stream_ptr()
+        if self.x3:
+            (dh, dl), (xh, xl), (oh, ol) = self._hl(dy), self._hl(x), self._hl(dx)
+            _lib.check(lib.rart_layernorm_bwd_pair(dh, dl, xh, xl, _lib.ptr(g), None, None, oh, ol, rows, c, c, c, 0, c, 1e-6, sp))
+        else:
+            _lib.check(lib.rart_layernorm_bwd_bf16(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(g), None, _lib.ptr(dx), rows, c, c, c, 0, c,
+                                                   1e-6, sp))
+
+    def _dwconv_ln(self, x, L, out, y, B, H, W, C):
+        lib, sp = self.lib, _lib.stream_ptr()
+        if self.x3:
+            (xh, xl), (oh, ol) = self._hl(x), self._hl(out)
+            yh, yl = self._hl(y) if y is not None else (None, None)
+            _lib.check(lib.rart_cnx_dwconv_ln_pair(xh, xl, _lib.ptr(L['dw_w']), _lib.ptr(L['dw_b']), _lib.ptr(L['ng']), _lib.ptr(L['nb']),
+                                                   oh, ol, yh, yl, B, H, W, C, 1e-6, sp))
+        else:
+            _lib.check(lib.rart_cnx_dwconv_ln_bf16(_lib.ptr(x), _lib.ptr(L['dw_w']), _lib.ptr(L['dw_b']), _lib.ptr(L['ng']),
+                                                   _lib.ptr(L['nb']), _lib.ptr(out), _lib.ptr(y), B, H, W, C, 1e-6, sp))
+
+    def _dwconv_bwd(self, dz, L, res, dx, B, H, W, C):
+        lib, sp = self.lib, _lib.stream_ptr()
+        if self.x3:
+            (zh, zl), (oh, ol) = self._hl(dz), self._hl(dx)
+            rh, rl = self._hl(res) if res is not None else (None, None)
+            _lib.check(lib.rart_cnx_dwconv_bwd_pair(zh, zl, _lib.ptr(L['dw_w']), rh, rl, oh, ol, B, H, W, C, sp))
+        else:
+            _lib.check(lib.rart_cnx_dwconv_bwd_bf16(_lib.ptr(dz), _lib.ptr(L['dw_w']), _lib.ptr(res), _lib.ptr(dx), B, H, W, C, sp))
+
+    def _downsample(self, x, S, out, B, H, W):
+        """LayerNorm of the H x W stage output x, then the 2x2 stride-2 conv into out (H/2 x W/2)"""
+        si = S['index']
+        cin, cout = self.dims[si - 1], self.dims[si]
+        ln = self._act('ds_ln%d' % si, (B * H * W, cin))
+        self._ln(x, S['ds_g'], S['ds_nb'], ln, B * H * W, cin)
+        self._conv(ln, S['ds_w'], out, B, (H // 2, W // 2), (H, W), cin, DS_TAPS, cout, (H // 2, W // 2), (2, 2), (1, 1), (0, 0),
+                   bias=S['ds_bias'])
+
+    def _downsample_scatter(self, g, S, out, B, H, W):
+        """backward of the 2x2 stride-2 conv: g [B][H/2][W/2][cout] -> out [B][H][W][cin], one GEMM per input parity (py, px)
+        writing every second pixel of every second row (the taps do not overlap: each input pixel has exactly one)"""
+        si = S['index']
+        cin, cout = self.dims[si - 1], self.dims[si]
+        for p, (py, px) in enumerate(DS_TAPS):
+            self._conv(g, S['ds_wd'][p], out, B, (H // 2, W // 2), (H // 2, W // 2), cout, [(0, 0)], cin, (H, W), (1, 1), (2, 2), (py, px))
+
+    # ------------------------------------------------------------------ forward
+    def _forward(self, src, src_is_u8, mean, std, keep=False):
+        torch = _lib.require_gpu()
+        lib, sp = self.lib, _lib.stream_ptr()
+        if src_is_u8:
+            B, Himg, Wimg = src.shape[0], src.shape[1], src.shape[2]
+        else:
+            B, Himg, Wimg = src.shape[0], src.shape[2], src.shape[3]
+        if Himg % 32 or Wimg % 32:
+            raise ValueError('ConvNeXt needs image sides that are multiples of 32 (got %dx%d)' % (Himg, Wimg))
+        H, W = Himg // 4, Wimg // 4
+        c0 = self.dims[0]
+        patches = self._get('patches', (2, B * H * W, STEM_K))
+        meanf, stdf = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+        _lib.check(lib.rart_cnx_patchify(_lib.ptr(src), 1 if src_is_u8 else 0, _lib.ptr(patches[0]), _lib.ptr(patches[1]), B, Himg, Wimg,
+                                         4, STEM_K, meanf, stdf, sp))
+        xs = self._act('stem', (B * H * W, c0))
+        if self.x3:
+            self._gemm_pair(patches, self.stem_w, xs, B * H * W, c0, STEM_K, STEM_K, c0, bias=self.stem_b)
+        else:
+            lo_off = (patches[1].data_ptr() - patches[0].data_ptr()) // 2
+            self._gemm(patches[0], self.stem_w, xs, B * H * W, STEM_K, c0, STEM_K, c0, bias=self.stem_b, n_taps=2, tap_src_off=[0, lo_off])
+        x = self._act('x0', (B * H * W, c0))
+        self._ln(xs, self.stem_g, self.stem_nb, x, B * H * W, c0)
+        saved, stage_out = [], []
+        for si, S in enumerate(self.stages):
+            C = self.dims[si]
+            if si > 0:
+                xn = self._act('x%d' % si, (B * (H // 2) * (W // 2), C))
+                self._downsample(x, S, xn, B, H, W)
+                stage_out.append(x)
+                x, H, W = xn, H // 2, W // 2
+            rows = B * H * W
+            ln = self._act('ln%d' % si, (rows, C))
+            hid = self._act('hid%d' % si, (rows, 4 * C))
+            for bi, L in enumerate(S['blocks']):
+                y = self._act('y%d_%d' % (si, bi), (rows, C)) if keep else None
+                self._dwconv_ln(x, L, ln, y, B, H, W, C)
+                if keep:
+                    u = self._act('u%d_%d' % (si, bi), (rows, 4 * C))
+                    if self.x3:
+                        self._mm(ln, L['fc1_w'], hid, rows, 4 * C, C, bias=L['fc1_b'], flags=F_GELU_KEEP, aux=u)
+                    else:
+                        # two launches at every batch size: the one-launch form (flag 64) exists only on the 256 x 256 kernel, which
+                        # takes a product above a row threshold, and it applies GELU to the fp32 pre-activation where this form uses
+                        # the bf16 one -- B = 256 and B = 8 would differ
+                        self._mm(ln, L['fc1_w'], u, rows, 4 * C, C, bias=L['fc1_b'])
+                        _lib.check(lib.rart_gelu_bf16(_lib.ptr(u), _lib.ptr(hid), u.numel(), sp))
+                    saved.append((y, u))
+                else:
+                    self._mm(ln, L['fc1_w'], hid, rows, 4 * C, C, bias=L['fc1_b'], flags=F_GELU)
+                self._mm(hid, L['fc2_w'], x, rows, C, 4 * C, bias=L['fc2_b'], res=x)       # in place: x + gamma * fc2(...)
+        cl = self.dims[-1]
+        pooled = self._act('pooled', (B, cl))
+        if self.x3:
+            _lib.check(lib.rart_engine_avgpool_pair(_lib.ptr(x[0]), x[0].numel(), _lib.ptr(pooled[0]), pooled[0].numel(), B, H * W, cl, sp))
+        else:
+            _lib.check(lib.rart_engine_avgpool(_lib.ptr(x), _lib.ptr(pooled), B, H * W, cl, sp))
+        pl = self._act('pooled_ln', (B, cl))
+        self._ln(pooled, self.head_g, self.head_nb, pl, B, cl)
+        logits = torch.empty(B, self.n_classes, dtype=torch.float32, device=self.device)
+        self._mm(pl, self.head_w, logits, B, self.n_classes, cl, bias=self.head_b, flags=F_OUT_F32)
+        if keep:
+            self._saved = (saved, stage_out, xs, pooled, (B, Himg, Wimg))
+        return logits
+
+    # ------------------------------------------------------------------ backward to the input
+    def forward_backward(self, x01, mean, std, y, kind, y_target=None, scale=1.0):
+        """-> (logits fp32, loss_indiv, d(sum_i scale*loss_i)/dx01 fp32 NCHW, pred int32); same contract as
+        ResNet50Engine.forward_backward."""
+        from ..noise.adv import logit_loss
+        torch = _lib.require_gpu()
+        lib, sp = self.lib, _lib.stream_ptr()
+        x01 = x01.detach().float().contiguous()
+        logits = self._forward(x01, False, mean, std, keep=True)
+        saved, stage_out, xs, pooled, (B, Himg, Wimg) = self._saved
+        loss, dl, pred = logit_loss(logits, y, kind, y_target, scale)
+        self.last_dlogits = dl
+        cl, kp = self.dims[-1], self.head_kpad
+        dlb = self._act('g_dl', (B, kp))
+        if self.x3:
+            _lib.check(lib.rart_f32_to_pair_rows(_lib.ptr(dl), _lib.ptr(dlb[0]), dlb[0].numel(), B, self.n_classes, kp, sp))
+        else:
+            _lib.check(lib.rart_f32_to_bf16_rows(_lib.ptr(dl), _lib.ptr(dlb), B, self.n_classes, kp, sp))
+        dpl = self._act('g_pooled_ln', (B, cl))
+        self._mm(dlb, self.head_wd, dpl, B, cl, kp)
+        dpooled = self._act('g_pooled', (B, cl))
+        self._ln_bwd(dpl, pooled, self.head_g, dpooled, B, cl)
+        H, W = Himg // 32, Wimg // 32
+        n_st = len(self.stages)
+        gx = self._act('g_x%d' % (n_st - 1), (B * H * W, cl))
+        if self.x3:
+            _lib.check(lib.rart_cnx_pool_bwd_pair(_lib.ptr(dpooled[0]), _lib.ptr(dpooled[1]), _lib.ptr(gx[0]), _lib.ptr(gx[1]), B, H * W, cl, sp))
+        else:
+            _lib.check(lib.rart_cnx_pool_bwd_bf16(_lib.ptr(dpooled), _lib.ptr(gx), B, H * W, cl, sp))
+        k = len(saved)
+        for si in range(n_st - 1, -1, -1):
+            S, C = self.stages[si], self.dims[si]
+            rows = B * H * W
+            dh = self._act('g_hid%d' % si, (rows, 4 * C))
+            dln = self._act('g_ln%d' % si, (rows, C))
+            dz = self._act('g_dz%d' % si, (rows, C))
+            for bi in range(len(S['blocks']) - 1, -1, -1):
+                L = S['blocks'][bi]
+                k -= 1
+                yk, u = saved[k]
+                self._mm(gx, L['fc2_wd'], dh, rows, 4 * C, C, flags=F_GELU_BWD, aux=u)       # (g W2') * gelu'(u)
+                self._mm(dh, L['fc1_wd'], dln, rows, C, 4 * C)
+                self._ln_bwd(dln, yk, L['ng'], dz, rows, C)
+                self._dwconv_bwd(dz, L, gx, gx, B, H, W, C)                                   # residual + transposed 7x7, in place
+            if si > 0:
+                cin = self.dims[si - 1]
+                gds = self._act('g_ds_ln%d' % si, (B * 4 * H * W, cin))
+                self._downsample_scatter(gx, S, gds, B, 2 * H, 2 * W)
+                H, W = 2 * H, 2 * W
+                gprev = self._act('g_x%d' % (si - 1), (B * H * W, cin))
+                self._ln_bwd(gds, stage_out[si - 1], S['ds_g'], gprev, B * H * W, cin)
+                gx = gprev
+        c0, rows = self.dims[0], B * H * W
+        gs = self._act('g_stem', (rows, c0))
+        self._ln_bwd(gx, xs, self.stem_g, gs, rows, c0)
+        dpatch = self._get('g_patch', (rows, STEM_K), torch.float32)
+        self._mm(gs, self.stem_wd, dpatch, rows, STEM_K, c0, flags=F_OUT_F32)
+        grad = torch.empty(B, 3, Himg, Wimg, dtype=torch.float32, device=self.device)
+        _lib.check(lib.rart_vit_unpatchify_from_f32(_lib.ptr(dpatch), _lib.ptr(grad), B, Himg, Wimg, 4, STEM_K,
+                                                    (ctypes.c_float * 3)(*std), sp))
+        return logits, loss, grad, pred
+
+    def logits(self, x01, mean, std):
+        return self._forward(x01.detach().float().contiguous(), False, mean, std)
+
+    def logits_from_u8(self, batch_u8, mean, std):
+        return self._forward(batch_u8, True, mean, std)

@@ -531,6 +531,11 @@ def train(cfg, args, rank, world, device):
     n = len(ds)
     max_iter, warmup_steps = resolve_schedule(cfg, n, bs, world, getattr(args, 'max_iter', 20))
     model = build_model(cfg, args).to(device)
+    from ..model.convnext_torch import ConvNeXt
+    if isinstance(model, ConvNeXt):
+        raise NotImplementedError('training %r: there is no ConvNeXt train engine (train-mode forward / weight gradients of the '
+                                  'depthwise conv, LayerNorm and layer scale); ConvNeXt-B runs --evaluate [--attack ...] only'
+                                  % cfg['model']['type'])
     resume = getattr(build_model, 'last_checkpoint', None) or {}
     ocfg = cfg.get('optimizer', {'type': 'SGD', 'kwargs': {'nesterov': True, 'momentum': 0.9, 'weight_decay': 1e-4}})
     okw = dict(ocfg.get('kwargs', {}))
