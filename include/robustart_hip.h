@@ -891,6 +891,27 @@ int rart_cnx_pool_bwd_pair(const void* dpool_hi, const void* dpool_lo, void* dz_
 int rart_cnx_patchify(const void* src, int src_is_u8, void* hi, void* lo, int n, int h, int w, int patch, int ld, const float* mean_host,
                       const float* std_host, rart_stream_t stream);
 
+/* ---- ConvNeXt-B training (csrc/convnext_train.hip; robustart_amd/model/convnext_train_engine.py), bf16 storage, fp32 arithmetic -------
+ * rart_cnx_dwconv_wgrad_bf16: the 7x7 pad-3 depthwise convolution's weight and bias gradient, dw[dy * 7 + dx][c] (+)= sum over
+ *   (image, y, x) of x[y + dy - 3][x + dx - 3][c] * dz[y][x][c] and db[c] (+)= sum dz (accumulate != 0 adds).  x: the block input, dz: the
+ *   gradient of the conv output, both NHWC [n][h][w][c] bf16.  dw_layout 0: dw is [49][c] (the w_dw layout of rart_cnx_dwconv_ln_*),
+ *   1: [c][49] (the module's conv_dw.weight [c][1][7][7]).  Deterministic: fp32 per-workgroup partials in `workspace`
+ *   (rart_cnx_dwconv_wgrad_workspace_bytes, 0 for an unsupported shape), folded in a fixed order.  c % 8 == 0, c <= 1024, w <= 128,
+ *   n, h <= 65535; x / dz 8-byte aligned. */
+size_t rart_cnx_dwconv_wgrad_workspace_bytes(int n, int h, int w, int c);
+int rart_cnx_dwconv_wgrad_bf16(const void* x, const void* dz, float* dw, float* db, int n, int h, int w, int c, int dw_layout, int accumulate,
+                               void* workspace, size_t workspace_bytes, rart_stream_t stream);
+/* rart_cnx_layer_scale_fwd_bf16: x_out = x_in + gamma * u2 over bf16 [rows][c] (u2 = the block's unscaled fc2 output, kept for the
+ *   backward; x_out may alias x_in, not u2).
+ * rart_cnx_layer_scale_bwd_bf16: from dx (the gradient of the block output) and u2: dv = gamma * dx (bf16, fc2's output gradient),
+ *   dgamma[c] (+)= sum_rows dx * u2 and, when db2 is non-null, db2[c] (+)= sum_rows gamma * dx (fc2's bias gradient) in the same pass.
+ *   Deterministic like the weight gradient; workspace: rart_cnx_layer_scale_bwd_workspace_bytes.  gamma is never divided out.
+ *   Both: c % 8 == 0, c <= 1024, 0 < rows < 2^31; bf16 pointers 16-byte aligned; dv must not alias dx or u2. */
+int rart_cnx_layer_scale_fwd_bf16(const void* x_in, const void* u2, const float* gamma, void* x_out, long long rows, int c, rart_stream_t stream);
+size_t rart_cnx_layer_scale_bwd_workspace_bytes(long long rows, int c);
+int rart_cnx_layer_scale_bwd_bf16(const void* dx, const void* u2, const float* gamma, void* dv, float* dgamma, float* db2, long long rows,
+                                  int c, int accumulate, void* workspace, size_t workspace_bytes, rart_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

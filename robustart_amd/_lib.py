@@ -152,6 +152,11 @@ SIGNATURES = {
     'rart_cnx_pool_bwd_bf16': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     'rart_cnx_pool_bwd_pair': (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p]),
     'rart_cnx_patchify': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'rart_cnx_dwconv_wgrad_workspace_bytes': (c_size_t, [c_int] * 4),
+    'rart_cnx_dwconv_wgrad_bf16': (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p, c_size_t, c_void_p]),
+    'rart_cnx_layer_scale_fwd_bf16': (c_int, [c_void_p] * 4 + [ctypes.c_longlong, c_int, c_void_p]),
+    'rart_cnx_layer_scale_bwd_workspace_bytes': (c_size_t, [ctypes.c_longlong, c_int]),
+    'rart_cnx_layer_scale_bwd_bf16': (c_int, [c_void_p] * 6 + [ctypes.c_longlong, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     'rart_vit_patchify': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                   c_void_p]),
     'rart_vit_add_pos_cls': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

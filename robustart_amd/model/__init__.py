@@ -2,7 +2,8 @@
 
 Three architectures: `resnet50_official` (forward + backward-to-input HIP engine: engine.py), `vit_base` / `vit_b16_224`
 (forward + backward-to-input HIP engine: vit_engine.py) and `convnext_base` (forward + backward-to-input HIP engine:
-convnext_engine.py; no train engine).  kwargs `num_classes` and `drop_path_rate` are accepted (drop path is identity in eval)."""
+convnext_engine.py; train engine: convnext_train_engine.py, drop_path_rate 0 only).  kwargs `num_classes` and `drop_path_rate` are
+accepted (drop path is identity in eval)."""
 from .resnet_torch import resnet50
 from .vit_torch import vit_base
 from .convnext_torch import convnext_base

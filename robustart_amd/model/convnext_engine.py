@@ -28,6 +28,8 @@ DS_TAPS = [(0, 0), (0, 1), (1, 0), (1, 1)]
 
 
 class ConvNeXtEngine:
+    fold_layer_scale = True          # refold: gamma folded into fc2 (the train engine keeps fc2 unscaled and applies gamma itself)
+
     def __init__(self, model, device='cuda', precision='bf16'):
         """precision: 'bf16' (fast path) or 'bf16x3' / 'fp32x' (reference precision: split-bf16 pairs throughout)."""
         torch = _lib.require_gpu()
@@ -102,13 +104,15 @@ class ConvNeXtEngine:
                          ds_wd=[bwd(w[:, :, py, px].t()) for py, px in DS_TAPS])         # per input parity: [cin][cout]
             for blk in st.blocks:
                 c = blk.conv_dw.weight.shape[0]
-                g = f32(blk.gamma)
-                w1, w2 = f32(blk.mlp.fc1.weight), g[:, None] * f32(blk.mlp.fc2.weight)
+                g = f32(blk.gamma) if self.fold_layer_scale else None
+                w1 = f32(blk.mlp.fc1.weight)
+                w2 = g[:, None] * f32(blk.mlp.fc2.weight) if self.fold_layer_scale else f32(blk.mlp.fc2.weight)
                 S['blocks'].append(dict(
                     dw_w=f32(blk.conv_dw.weight).reshape(c, 49).t().contiguous(), dw_b=f32(blk.conv_dw.bias),
                     ng=f32(blk.norm.weight), nb=f32(blk.norm.bias),
                     fc1_w=fwd(w1), fc1_b=f32(blk.mlp.fc1.bias), fc1_wd=bwd(w1.t()),
-                    fc2_w=fwd(w2), fc2_b=(g * f32(blk.mlp.fc2.bias)).contiguous(), fc2_wd=bwd(w2.t())))
+                    fc2_w=fwd(w2), fc2_b=(g * f32(blk.mlp.fc2.bias)).contiguous() if self.fold_layer_scale else f32(blk.mlp.fc2.bias),
+                    fc2_wd=bwd(w2.t())))
             self.stages.append(S)
         self.head_g, self.head_nb = f32(m.head.norm.weight), f32(m.head.norm.bias)
         self.n_classes = m.head.fc.out_features

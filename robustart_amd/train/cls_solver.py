@@ -532,10 +532,10 @@ def train(cfg, args, rank, world, device):
     max_iter, warmup_steps = resolve_schedule(cfg, n, bs, world, getattr(args, 'max_iter', 20))
     model = build_model(cfg, args).to(device)
     from ..model.convnext_torch import ConvNeXt
-    if isinstance(model, ConvNeXt):
-        raise NotImplementedError('training %r: there is no ConvNeXt train engine (train-mode forward / weight gradients of the '
-                                  'depthwise conv, LayerNorm and layer scale); ConvNeXt-B runs --evaluate [--attack ...] only'
-                                  % cfg['model']['type'])
+    if isinstance(model, ConvNeXt) and not (device.type == 'cuda' and args.engine == 'hip' and getattr(args, 'train_engine', 'hip') == 'hip'):
+        raise NotImplementedError('training %r on %s with --engine %s --train-engine %s: there is no ConvNeXt train engine on this path; '
+                                  'ConvNeXtTrainEngine runs on the GPU with --engine hip --train-engine hip'
+                                  % (cfg['model']['type'], device.type, args.engine, getattr(args, 'train_engine', 'hip')))
     resume = getattr(build_model, 'last_checkpoint', None) or {}
     ocfg = cfg.get('optimizer', {'type': 'SGD', 'kwargs': {'nesterov': True, 'momentum': 0.9, 'weight_decay': 1e-4}})
     okw = dict(ocfg.get('kwargs', {}))
@@ -590,6 +590,9 @@ def train(cfg, args, rank, world, device):
         elif isinstance(model, VisionTransformer):
             from ..model.vit_train_engine import ViTTrainEngine
             train_engine = ViTTrainEngine(model, device, on_grad_ready=arena.grad_ready)
+        elif isinstance(model, ConvNeXt):
+            from ..model.convnext_train_engine import ConvNeXtTrainEngine
+            train_engine = ConvNeXtTrainEngine(model, device, on_grad_ready=arena.grad_ready)
     ls = float(cfg.get('label_smooth', 0.0))
     adv = cfg.get('adv_train', None)                        # {'eps': '4/255', 'steps': 3, 'rel_stepsize': 0.4}
     mean = torch.tensor(IMAGENET_MEAN, device=device).view(1, 3, 1, 1)
@@ -765,7 +768,8 @@ def main(argv=None):
                     help="evaluation engine arithmetic: bf16 (default) or the reference-precision mode 'fp32x' (= 'bf16x3')")
     ap.add_argument('--max-iter', type=int, default=20)
     ap.add_argument('--train-engine', choices=['hip', 'torch'], default='hip', dest='train_engine',
-                    help='train-mode forward/backward: hip = ResNet50TrainEngine, torch = autograd scaffold')
+                    help='train-mode forward/backward: hip = the HIP train engine of the model (ResNet50TrainEngine, ViTTrainEngine, '
+                         'ConvNeXtTrainEngine), torch = autograd scaffold (ResNet-50 / ViT only)')
     ap.add_argument('--recover', default=None, help='checkpoint to start from (overrides saver.pretrain.path)')
     ap.add_argument('--ckpt-dir', default=None, dest='ckpt_dir', help='write <dir>/ckpt.pth.tar at the end of training')
     ap.add_argument('--save-dir', default=None, help='root of <model>/<noise>_<eps>/results.txt.all (robustart_amd.metrics)')
