@@ -912,6 +912,32 @@ size_t rart_cnx_layer_scale_bwd_workspace_bytes(long long rows, int c);
 int rart_cnx_layer_scale_bwd_bf16(const void* dx, const void* u2, const float* gamma, void* dv, float* dgamma, float* db2, long long rows,
                                   int c, int accumulate, void* workspace, size_t workspace_bytes, rart_stream_t stream);
 
+/* ---- ConvNeXt-V2-B Global Response Norm (model `convnextv2_base`, csrc/convnext_v2.hip; robustart_amd/model/convnext_engine.py) ------
+ * y: the GELU output of a block's fc1, per image [p][c] (p = h * w pixels, c = the hidden width); *_bf16 / *_pair as above, fp32
+ *   arithmetic and statistics.  G, a: fp32 [n][c].  w, b: mlp.grn.weight / bias, fp32 [c].  m = mean_c G[n][c].
+ * rart_cnx_grn_stats_*: G[n][c] = sqrt(sum_p y^2).
+ * rart_cnx_grn_apply_*: z = y * (1 + w[c] * G[n][c] / (m + eps)) + b[c]; z may alias y (both planes of it) or be another buffer.
+ * rart_cnx_grn_bwd_reduce_*: a[n][c] = w[c] * sum_p g * y, g = the gradient of z.
+ * rart_cnx_grn_bwd_apply_*: dh = (g * (1 + w[c] G[c] / (m + eps)) + y * beta[c] / G[c]) * gelu'(u), beta[c] = a[c] / (m + eps) -
+ *   s / (c * (m + eps)^2), s = sum_c a[c] G[c] (the y term 0 where G[c] == 0); u = the fc1 pre-activation (exact-erf GELU).  dh may
+ *   alias g (both planes), not y or u.
+ * Deterministic, no atomics: a reduction over pixels is one workgroup per (image, 128 channels), the per-image scalars are fixed-order
+ *   block sums, and no launch geometry depends on n.  c % 8 == 0, c <= 4096, 0 < n <= 65535, p > 0; bf16 pointers 16-byte aligned. */
+int rart_cnx_grn_stats_bf16(const void* y, float* G, int n, int p, int c, rart_stream_t stream);
+int rart_cnx_grn_stats_pair(const void* y_hi, const void* y_lo, float* G, int n, int p, int c, rart_stream_t stream);
+int rart_cnx_grn_apply_bf16(const void* y, const float* G, const float* w, const float* b, void* z, int n, int p, int c, float eps,
+                            rart_stream_t stream);
+int rart_cnx_grn_apply_pair(const void* y_hi, const void* y_lo, const float* G, const float* w, const float* b, void* z_hi, void* z_lo, int n,
+                            int p, int c, float eps, rart_stream_t stream);
+int rart_cnx_grn_bwd_reduce_bf16(const void* g, const void* y, const float* w, float* a, int n, int p, int c, rart_stream_t stream);
+int rart_cnx_grn_bwd_reduce_pair(const void* g_hi, const void* g_lo, const void* y_hi, const void* y_lo, const float* w, float* a, int n, int p,
+                                 int c, rart_stream_t stream);
+int rart_cnx_grn_bwd_apply_bf16(const void* g, const void* y, const void* u, const float* G, const float* a, const float* w, void* dh, int n,
+                                int p, int c, float eps, rart_stream_t stream);
+int rart_cnx_grn_bwd_apply_pair(const void* g_hi, const void* g_lo, const void* y_hi, const void* y_lo, const void* u_hi, const void* u_lo,
+                                const float* G, const float* a, const float* w, void* dh_hi, void* dh_lo, int n, int p, int c, float eps,
+                                rart_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,6 +157,14 @@ SIGNATURES = {
     'rart_cnx_layer_scale_fwd_bf16': (c_int, [c_void_p] * 4 + [ctypes.c_longlong, c_int, c_void_p]),
     'rart_cnx_layer_scale_bwd_workspace_bytes': (c_size_t, [ctypes.c_longlong, c_int]),
     'rart_cnx_layer_scale_bwd_bf16': (c_int, [c_void_p] * 6 + [ctypes.c_longlong, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    'rart_cnx_grn_stats_bf16': (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_void_p]),
+    'rart_cnx_grn_stats_pair': (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
+    'rart_cnx_grn_apply_bf16': (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_float, c_void_p]),
+    'rart_cnx_grn_apply_pair': (c_int, [c_void_p] * 7 + [c_int] * 3 + [c_float, c_void_p]),
+    'rart_cnx_grn_bwd_reduce_bf16': (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p]),
+    'rart_cnx_grn_bwd_reduce_pair': (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p]),
+    'rart_cnx_grn_bwd_apply_bf16': (c_int, [c_void_p] * 7 + [c_int] * 3 + [c_float, c_void_p]),
+    'rart_cnx_grn_bwd_apply_pair': (c_int, [c_void_p] * 11 + [c_int] * 3 + [c_float, c_void_p]),
     'rart_vit_patchify': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                   c_void_p]),
     'rart_vit_add_pos_cls': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

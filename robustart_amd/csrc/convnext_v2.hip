@@ -1,0 +1,309 @@
+// Global Response Norm (GRN) of the ConvNeXt-V2-B engine (model `convnextv2_base`, robustart_amd/model/convnext_engine.py) for gfx950:
+// its statistics, its application and its backward to the input, fused with GELU' of the fc1 pre-activation.  Every kernel exists in
+// two precisions: bf16 storage (the fast engine) and PAIRS of bf16 planes, value = hi + lo (the reference-precision "fp32x" engine).
+// Arithmetic and statistics are fp32.  Activations are NHWC, per image [p][c] with P = H * W pixels and C = the 4x hidden width.
+//
+//   forward    G[n][c] = sqrt(sum_p y^2),  m = mean_c G,  z = y * (1 + w[c] G[c] / (m + eps)) + b[c]
+//   backward   a[n][c] = w[c] * sum_p g y,  s = sum_c a G,  beta[c] = a[c] / (m + eps) - s / (C (m + eps)^2),
+//              dh = (g (1 + w[c] G[c] / (m + eps)) + y beta[c] / G[c]) * gelu'(u)     (the y term is 0 where G[c] == 0)
+//
+// Reductions over pixels (stats, bwd_reduce): one workgroup per (image, 128-channel slice) walks all P pixels.  Lane (l % 16) owns
+// eight consecutive channels (one 16-byte load per plane), row (l / 16) every 16th pixel; the 16 row sums meet in LDS and are added
+// in a fixed order.  The split depends on C alone -- never on the batch -- and there are no atomics, so an image's statistics are
+// bit-identical whatever batch it is in and on every call.  At ConvNeXt-V2-B's four stages (P = 3136 .. 49, C = 512 .. 4096) a
+// batch of 256 gives 1024 .. 8192 workgroups.
+// Per-pixel kernels (apply, bwd_apply): one workgroup per (image, tile of about 32768 / C pixels).  Each workgroup first forms the
+// per-image scalars (m, and s for the backward) with a fixed-order block sum over the C statistics of its image, then the per-channel
+// factors into LDS (2 x C fp32), then streams its tile eight channels per lane.  The output may alias the input it replaces
+// (z over y, dh over g): every element is read and written by the same lane.
+// Reference: timm's GlobalResponseNorm (channels-last) inside GlobalResponseNormMlp, restated in robustart_amd/model/convnext_torch.py.
+#include "rart_gemm_pair_dev.h"
+
+namespace {
+constexpr int kBlock = 256;
+constexpr int kSliceLanes = 16;                         // lanes across channels in the reductions: 16 x 8 = 128 channels
+constexpr int kSlice = kSliceLanes * 8;
+constexpr int kRows = kBlock / kSliceLanes;             // pixel rows per pass
+constexpr int kMaxC = 4096;                             // per-channel factors in LDS: 2 x C x 4 bytes <= 32 KB
+constexpr int kTileElems = 32768;                       // elements per workgroup of the per-pixel kernels
+
+// eight consecutive channels of one pixel: one 16-byte load per plane
+template <bool PAIR>
+__device__ __forceinline__ void ld8(const uint16_t* h, const uint16_t* l, size_t i, float* v) {
+  const uint4 a = *reinterpret_cast<const uint4*>(h + i);
+  const uint32_t aw[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    v[2 * j] = __uint_as_float(aw[j] << 16);
+    v[2 * j + 1] = __uint_as_float(aw[j] & 0xFFFF0000u);
+  }
+  if (PAIR) {
+    const uint4 b = *reinterpret_cast<const uint4*>(l + i);
+    const uint32_t bw[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v[2 * j] += __uint_as_float(bw[j] << 16);
+      v[2 * j + 1] += __uint_as_float(bw[j] & 0xFFFF0000u);
+    }
+  }
+}
+// eight values -> bf16 (round to nearest even), or hi + lo planes
+template <bool PAIR>
+__device__ __forceinline__ void st8(uint16_t* h, uint16_t* l, size_t i, const float* v) {
+  if (PAIR) {
+    uint4 hi, lo;
+    gp_split8(v, hi, lo);
+    *reinterpret_cast<uint4*>(h + i) = hi;
+    *reinterpret_cast<uint4*>(l + i) = lo;
+  } else {
+    *reinterpret_cast<uint4*>(h + i) = make_uint4(gp_pack_bf16x2(v[0], v[1]), gp_pack_bf16x2(v[2], v[3]), gp_pack_bf16x2(v[4], v[5]),
+                                                  gp_pack_bf16x2(v[6], v[7]));
+  }
+}
+
+// sum of one value per thread over the workgroup, the same fixed order in every workgroup; s_red: kBlock / 64 floats
+__device__ __forceinline__ float block_sum(float v, float* s_red) {
+  v = rart_wave_sum(v);
+  __syncthreads();                                      // s_red may still be read by a previous call
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float t = 0.f;
+#pragma unroll
+  for (int k = 0; k < kBlock / 64; ++k) t += s_red[k];
+  return t;
+}
+
+// grid (slices, n): out[n][c] = sqrt(sum_p y^2) (GRAD = false) or w[c] * sum_p g y (GRAD = true)
+template <bool PAIR, bool GRAD>
+__global__ __launch_bounds__(kBlock) void k_grn_reduce(const uint16_t* __restrict__ yh, const uint16_t* __restrict__ yl,
+                                                       const uint16_t* __restrict__ gh, const uint16_t* __restrict__ gl,
+                                                       const float* __restrict__ w, float* __restrict__ out, int P, int C) {
+  __shared__ float s_part[kRows][kSlice];
+  const int lc = threadIdx.x % kSliceLanes, row = threadIdx.x / kSliceLanes;
+  const int c = blockIdx.x * kSlice + lc * 8;
+  const size_t img = (size_t)blockIdx.y * P * C;
+  float acc[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) acc[k] = 0.f;
+  if (c < C) {
+    int p = row;
+    for (; p + 3 * kRows < P; p += 4 * kRows) {        // four independent loads in flight, summed in pixel order
+      float y[4][8], g[4][8];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const size_t o = img + (size_t)(p + q * kRows) * C + c;
+        ld8<PAIR>(yh, yl, o, y[q]);
+        if (GRAD) ld8<PAIR>(gh, gl, o, g[q]);
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[k] = fmaf(GRAD ? g[q][k] : y[q][k], y[q][k], acc[k]);
+    }
+    for (; p < P; p += kRows) {
+      float y[8], g[8];
+      const size_t o = img + (size_t)p * C + c;
+      ld8<PAIR>(yh, yl, o, y);
+      if (GRAD) ld8<PAIR>(gh, gl, o, g);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc[k] = fmaf(GRAD ? g[k] : y[k], y[k], acc[k]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) s_part[row][lc * 8 + k] = acc[k];
+  __syncthreads();
+  if (threadIdx.x < kSlice) {
+    const int cc = blockIdx.x * kSlice + threadIdx.x;
+    if (cc < C) {
+      float t = 0.f;
+#pragma unroll
+      for (int r = 0; r < kRows; ++r) t += s_part[r][threadIdx.x];
+      out[(size_t)blockIdx.y * C + cc] = GRAD ? w[cc] * t : sqrtf(t);
+    }
+  }
+}
+
+// grid (tiles, n): z = y * (1 + w N) + b over pixels [tile * tile_px, + tile_px) of image n.  z may alias y.
+template <bool PAIR>
+__global__ __launch_bounds__(kBlock) void k_grn_apply(const uint16_t* yh, const uint16_t* yl, const float* __restrict__ G,
+                                                      const float* __restrict__ w, const float* __restrict__ b, uint16_t* zh, uint16_t* zl,
+                                                      int P, int C, int tile_px, float eps) {
+  extern __shared__ float s_f[];                        // [C] scale 1 + w N, [C] bias
+  __shared__ float s_red[kBlock / 64];
+  float* s_scale = s_f;
+  float* s_bias = s_f + C;
+  const float* Gn = G + (size_t)blockIdx.y * C;
+  float t = 0.f;
+  for (int c = threadIdx.x; c < C; c += kBlock) t += Gn[c];
+  const float inv = 1.0f / (block_sum(t, s_red) / (float)C + eps);
+  for (int c = threadIdx.x; c < C; c += kBlock) {
+    s_scale[c] = fmaf(w[c], Gn[c] * inv, 1.0f);
+    s_bias[c] = b[c];
+  }
+  __syncthreads();
+  const int c8 = C / 8;
+  const int p0 = blockIdx.x * tile_px, np = min(tile_px, P - p0);
+  const size_t base = ((size_t)blockIdx.y * P + p0) * C;
+  for (int i = threadIdx.x; i < np * c8; i += kBlock) {
+    const int c = (i % c8) * 8;
+    const size_t o = base + (size_t)i * 8;
+    float v[8];
+    ld8<PAIR>(yh, yl, o, v);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = fmaf(v[k], s_scale[c + k], s_bias[c + k]);
+    st8<PAIR>(zh, zl, o, v);
+  }
+}
+
+// grid (tiles, n): dh = (g (1 + w N) + y beta / G) * gelu'(u).  dh may alias g.
+template <bool PAIR>
+__global__ __launch_bounds__(kBlock) void k_grn_bwd_apply(const uint16_t* gh, const uint16_t* gl, const uint16_t* __restrict__ yh,
+                                                          const uint16_t* __restrict__ yl, const uint16_t* __restrict__ uh,
+                                                          const uint16_t* __restrict__ ul, const float* __restrict__ G,
+                                                          const float* __restrict__ a, const float* __restrict__ w, uint16_t* dhh,
+                                                          uint16_t* dhl, int P, int C, int tile_px, float eps) {
+  extern __shared__ float s_f[];                        // [C] 1 + w N, [C] beta / G
+  __shared__ float s_red[kBlock / 64];
+  float* s_k1 = s_f;
+  float* s_k2 = s_f + C;
+  const float* Gn = G + (size_t)blockIdx.y * C;
+  const float* an = a + (size_t)blockIdx.y * C;
+  float tg = 0.f, ts = 0.f;
+  for (int c = threadIdx.x; c < C; c += kBlock) {
+    tg += Gn[c];
+    ts = fmaf(an[c], Gn[c], ts);
+  }
+  const float me = block_sum(tg, s_red) / (float)C + eps;
+  const float s = block_sum(ts, s_red);
+  const float inv = 1.0f / me, corr = s / ((float)C * me * me);
+  for (int c = threadIdx.x; c < C; c += kBlock) {
+    const float gc = Gn[c];
+    s_k1[c] = fmaf(w[c], gc * inv, 1.0f);
+    s_k2[c] = gc > 0.f ? fmaf(an[c], inv, -corr) / gc : 0.f;
+  }
+  __syncthreads();
+  const int c8 = C / 8;
+  const int p0 = blockIdx.x * tile_px, np = min(tile_px, P - p0);
+  const size_t base = ((size_t)blockIdx.y * P + p0) * C;
+  for (int i = threadIdx.x; i < np * c8; i += kBlock) {
+    const int c = (i % c8) * 8;
+    const size_t o = base + (size_t)i * 8;
+    float g[8], y[8], u[8];
+    ld8<PAIR>(gh, gl, o, g);
+    ld8<PAIR>(yh, yl, o, y);
+    ld8<PAIR>(uh, ul, o, u);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) g[k] = fmaf(g[k], s_k1[c + k], y[k] * s_k2[c + k]) * gp_gelu_grad(u[k]);
+    st8<PAIR>(dhh, dhl, o, g);
+  }
+}
+
+bool al16(const void* p) { return ((uintptr_t)p % 16) == 0; }
+
+bool grn_shape_ok(int n, int p, int c) {
+  return n > 0 && n <= 65535 && p > 0 && c > 0 && c % 8 == 0 && c <= kMaxC && (long long)n * p * c < (1ll << 40);
+}
+
+int tile_px(int c) { return kTileElems / c > 1 ? kTileElems / c : 1; }
+
+#define GRN_SHAPE_MSG "c a multiple of 8, at most 4096; 0 < n <= 65535, p > 0"
+
+template <bool PAIR, bool GRAD>
+int launch_reduce(const void* yh, const void* yl, const void* gh, const void* gl, const float* w, float* out, int n, int p, int c,
+                  rart_stream_t stream, const char* what) {
+  hipLaunchKernelGGL((k_grn_reduce<PAIR, GRAD>), dim3((c + kSlice - 1) / kSlice, n), dim3(kBlock), 0, (hipStream_t)stream,
+                     (const uint16_t*)yh, (const uint16_t*)yl, (const uint16_t*)gh, (const uint16_t*)gl, w, out, p, c);
+  RART_CHECK_LAUNCH(what);
+  return RART_OK;
+}
+
+template <bool PAIR>
+int launch_apply(const void* yh, const void* yl, const float* G, const float* w, const float* b, void* zh, void* zl, int n, int p, int c,
+                 float eps, rart_stream_t stream, const char* what) {
+  const int tp = tile_px(c);
+  hipLaunchKernelGGL(k_grn_apply<PAIR>, dim3((p + tp - 1) / tp, n), dim3(kBlock), 2 * c * sizeof(float), (hipStream_t)stream,
+                     (const uint16_t*)yh, (const uint16_t*)yl, G, w, b, (uint16_t*)zh, (uint16_t*)zl, p, c, tp, eps);
+  RART_CHECK_LAUNCH(what);
+  return RART_OK;
+}
+
+template <bool PAIR>
+int launch_bwd_apply(const void* gh, const void* gl, const void* yh, const void* yl, const void* uh, const void* ul, const float* G,
+                     const float* a, const float* w, void* dhh, void* dhl, int n, int p, int c, float eps, rart_stream_t stream,
+                     const char* what) {
+  const int tp = tile_px(c);
+  hipLaunchKernelGGL(k_grn_bwd_apply<PAIR>, dim3((p + tp - 1) / tp, n), dim3(kBlock), 2 * c * sizeof(float), (hipStream_t)stream,
+                     (const uint16_t*)gh, (const uint16_t*)gl, (const uint16_t*)yh, (const uint16_t*)yl, (const uint16_t*)uh,
+                     (const uint16_t*)ul, G, a, w, (uint16_t*)dhh, (uint16_t*)dhl, p, c, tp, eps);
+  RART_CHECK_LAUNCH(what);
+  return RART_OK;
+}
+}  // namespace
+
+int rart_cnx_grn_stats_bf16(const void* y, float* G, int n, int p, int c, rart_stream_t stream) {
+  RART_CHECK_ARG(y && G, "rart_cnx_grn_stats_bf16: bad arguments");
+  RART_CHECK_ARG(al16(y), "rart_cnx_grn_stats_bf16: y 16-byte aligned");
+  RART_CHECK_ARG(grn_shape_ok(n, p, c), "rart_cnx_grn_stats_bf16: " GRN_SHAPE_MSG);
+  return launch_reduce<false, false>(y, y, nullptr, nullptr, nullptr, G, n, p, c, stream, "rart_cnx_grn_stats_bf16");
+}
+
+int rart_cnx_grn_stats_pair(const void* y_hi, const void* y_lo, float* G, int n, int p, int c, rart_stream_t stream) {
+  RART_CHECK_ARG(y_hi && y_lo && G, "rart_cnx_grn_stats_pair: bad arguments");
+  RART_CHECK_ARG(al16(y_hi) && al16(y_lo), "rart_cnx_grn_stats_pair: y planes 16-byte aligned");
+  RART_CHECK_ARG(grn_shape_ok(n, p, c), "rart_cnx_grn_stats_pair: " GRN_SHAPE_MSG);
+  return launch_reduce<true, false>(y_hi, y_lo, nullptr, nullptr, nullptr, G, n, p, c, stream, "rart_cnx_grn_stats_pair");
+}
+
+int rart_cnx_grn_apply_bf16(const void* y, const float* G, const float* w, const float* b, void* z, int n, int p, int c, float eps,
+                            rart_stream_t stream) {
+  RART_CHECK_ARG(y && G && w && b && z, "rart_cnx_grn_apply_bf16: bad arguments");
+  RART_CHECK_ARG(al16(y) && al16(z), "rart_cnx_grn_apply_bf16: y / z 16-byte aligned");
+  RART_CHECK_ARG(grn_shape_ok(n, p, c), "rart_cnx_grn_apply_bf16: " GRN_SHAPE_MSG);
+  return launch_apply<false>(y, y, G, w, b, z, z, n, p, c, eps, stream, "rart_cnx_grn_apply_bf16");
+}
+
+int rart_cnx_grn_apply_pair(const void* y_hi, const void* y_lo, const float* G, const float* w, const float* b, void* z_hi, void* z_lo, int n,
+                            int p, int c, float eps, rart_stream_t stream) {
+  RART_CHECK_ARG(y_hi && y_lo && G && w && b && z_hi && z_lo && (z_hi == y_hi) == (z_lo == y_lo),
+                 "rart_cnx_grn_apply_pair: bad arguments (z aliases both planes of y or neither)");
+  RART_CHECK_ARG(al16(y_hi) && al16(y_lo) && al16(z_hi) && al16(z_lo), "rart_cnx_grn_apply_pair: y / z planes 16-byte aligned");
+  RART_CHECK_ARG(grn_shape_ok(n, p, c), "rart_cnx_grn_apply_pair: " GRN_SHAPE_MSG);
+  return launch_apply<true>(y_hi, y_lo, G, w, b, z_hi, z_lo, n, p, c, eps, stream, "rart_cnx_grn_apply_pair");
+}
+
+int rart_cnx_grn_bwd_reduce_bf16(const void* g, const void* y, const float* w, float* a, int n, int p, int c, rart_stream_t stream) {
+  RART_CHECK_ARG(g && y && w && a, "rart_cnx_grn_bwd_reduce_bf16: bad arguments");
+  RART_CHECK_ARG(al16(g) && al16(y), "rart_cnx_grn_bwd_reduce_bf16: g / y 16-byte aligned");
+  RART_CHECK_ARG(grn_shape_ok(n, p, c), "rart_cnx_grn_bwd_reduce_bf16: " GRN_SHAPE_MSG);
+  return launch_reduce<false, true>(y, y, g, g, w, a, n, p, c, stream, "rart_cnx_grn_bwd_reduce_bf16");
+}
+
+int rart_cnx_grn_bwd_reduce_pair(const void* g_hi, const void* g_lo, const void* y_hi, const void* y_lo, const float* w, float* a, int n, int p,
+                                 int c, rart_stream_t stream) {
+  RART_CHECK_ARG(g_hi && g_lo && y_hi && y_lo && w && a, "rart_cnx_grn_bwd_reduce_pair: bad arguments");
+  RART_CHECK_ARG(al16(g_hi) && al16(g_lo) && al16(y_hi) && al16(y_lo), "rart_cnx_grn_bwd_reduce_pair: g / y planes 16-byte aligned");
+  RART_CHECK_ARG(grn_shape_ok(n, p, c), "rart_cnx_grn_bwd_reduce_pair: " GRN_SHAPE_MSG);
+  return launch_reduce<true, true>(y_hi, y_lo, g_hi, g_lo, w, a, n, p, c, stream, "rart_cnx_grn_bwd_reduce_pair");
+}
+
+int rart_cnx_grn_bwd_apply_bf16(const void* g, const void* y, const void* u, const float* G, const float* a, const float* w, void* dh, int n,
+                                int p, int c, float eps, rart_stream_t stream) {
+  RART_CHECK_ARG(g && y && u && G && a && w && dh && dh != y && dh != u,
+                 "rart_cnx_grn_bwd_apply_bf16: bad arguments (dh may alias g, not y or u)");
+  RART_CHECK_ARG(al16(g) && al16(y) && al16(u) && al16(dh), "rart_cnx_grn_bwd_apply_bf16: g / y / u / dh 16-byte aligned");
+  RART_CHECK_ARG(grn_shape_ok(n, p, c), "rart_cnx_grn_bwd_apply_bf16: " GRN_SHAPE_MSG);
+  return launch_bwd_apply<false>(g, g, y, y, u, u, G, a, w, dh, dh, n, p, c, eps, stream, "rart_cnx_grn_bwd_apply_bf16");
+}
+
+int rart_cnx_grn_bwd_apply_pair(const void* g_hi, const void* g_lo, const void* y_hi, const void* y_lo, const void* u_hi, const void* u_lo,
+                                const float* G, const float* a, const float* w, void* dh_hi, void* dh_lo, int n, int p, int c, float eps,
+                                rart_stream_t stream) {
+  RART_CHECK_ARG(g_hi && g_lo && y_hi && y_lo && u_hi && u_lo && G && a && w && dh_hi && dh_lo && (dh_hi == g_hi) == (dh_lo == g_lo) &&
+                     dh_hi != y_hi && dh_lo != y_lo && dh_hi != u_hi && dh_lo != u_lo,
+                 "rart_cnx_grn_bwd_apply_pair: bad arguments (dh may alias both planes of g, not y or u)");
+  RART_CHECK_ARG(al16(g_hi) && al16(g_lo) && al16(y_hi) && al16(y_lo) && al16(u_hi) && al16(u_lo) && al16(dh_hi) && al16(dh_lo),
+                 "rart_cnx_grn_bwd_apply_pair: planes 16-byte aligned");
+  RART_CHECK_ARG(grn_shape_ok(n, p, c), "rart_cnx_grn_bwd_apply_pair: " GRN_SHAPE_MSG);
+  return launch_bwd_apply<true>(g_hi, g_lo, y_hi, y_lo, u_hi, u_lo, G, a, w, dh_hi, dh_lo, n, p, c, eps, stream,
+                                "rart_cnx_grn_bwd_apply_pair");
+}

@@ -1,15 +1,17 @@
 """Model zoo entry point -- mirrors RobustART/model/__init__.py:1 (`get_model`).
 
-Three architectures: `resnet50_official` (forward + backward-to-input HIP engine: engine.py), `vit_base` / `vit_b16_224`
-(forward + backward-to-input HIP engine: vit_engine.py) and `convnext_base` (forward + backward-to-input HIP engine:
-convnext_engine.py; train engine: convnext_train_engine.py, drop_path_rate 0 only).  kwargs `num_classes` and `drop_path_rate` are
+Four architectures: `resnet50_official` (forward + backward-to-input HIP engine: engine.py), `vit_base` / `vit_b16_224`
+(forward + backward-to-input HIP engine: vit_engine.py), `convnext_base` (forward + backward-to-input HIP engine:
+convnext_engine.py; train engine: convnext_train_engine.py, drop_path_rate 0 only) and `convnextv2_base` (ConvNeXt-V2-B: forward +
+backward-to-input on the same engine with the GRN kernels; no train engine).  kwargs `num_classes` and `drop_path_rate` are
 accepted (drop path is identity in eval)."""
 from .resnet_torch import resnet50
 from .vit_torch import vit_base
-from .convnext_torch import convnext_base
+from .convnext_torch import convnext_base, convnextv2_base
 
 _REGISTRY = {'resnet50_official': resnet50, 'resnet50': resnet50, 'vit_base': vit_base, 'vit_b16_224': vit_base,
-             'vit_base_patch16_224': vit_base, 'convnext_base': convnext_base}
+             'vit_base_patch16_224': vit_base, 'convnext_base': convnext_base,
+             'convnextv2_base': convnextv2_base}
 
 
 def get_model(config):
@@ -19,5 +21,5 @@ def get_model(config):
     kwargs = dict((config.get('kwargs') if isinstance(config, dict) else getattr(config, 'kwargs', None)) or {})
     kwargs.pop('bn', None)          # {use_sync_bn: False}: BN statistics are local
     if mtype not in _REGISTRY:
-        raise NotImplementedError('model type %r is outside the hot-path scope (ResNet-50 / ViT-B/16 / ConvNeXt-B only)' % mtype)
+        raise NotImplementedError('model type %r is outside the hot-path scope (ResNet-50 / ViT-B/16 / ConvNeXt-B / ConvNeXt-V2-B only)' % mtype)
     return _REGISTRY[mtype](**kwargs)

@@ -1,16 +1,20 @@
-"""ConvNeXt-B forward and backward-to-input on the hand-written HIP kernels (evaluation of clean / corrupted images; the gradient
-step of every attack, adv/attack.py:21-22, autopgd_base.py:271-289).  Reference module: robustart_amd/model/convnext_torch.py.
+"""ConvNeXt-B and ConvNeXt-V2-B forward and backward-to-input on the hand-written HIP kernels (evaluation of clean / corrupted images;
+the gradient step of every attack, adv/attack.py:21-22, autopgd_base.py:271-289).  Reference module: robustart_amd/model/convnext_torch.py.
 
 Layout: NHWC activations, rows = (image, y, x).  Per launch:
   stem        rart_cnx_patchify (4x4 patches, K = 48 padded to 64, hi + lo planes) -> GEMM (+ bias) -> LayerNorm
   downsample  LayerNorm -> the 2x2 stride-2 conv as the GEMM's conv mode (4 taps, k_per_tap = C_in, stride 2)
   block       rart_cnx_dwconv_ln_* (7x7 depthwise conv + bias + LayerNorm, one launch) -> fc1 GEMM + exact GELU ->
               fc2 GEMM (gamma folded in) + residual, written in place over the block input
+  V2 block    (ConvNeXt-V2, model.use_grn: no gamma) fc1 GEMM + GELU -> rart_cnx_grn_stats_* -> rart_cnx_grn_apply_* -> fc2 GEMM +
+              residual; with the backward kept, the GELU output and the channel norms G are kept per block
   head        global average pool (rart_engine_avgpool*) -> LayerNorm -> fc GEMM (fp32 logits)
 Backward: the fc dgrad GEMMs (fc2's with GELU' of the kept pre-activation in its epilogue), rart_layernorm_bwd_* against the kept
 depthwise-conv output, then rart_cnx_dwconv_bwd_* (transposed 7x7 taps) adding into the residual gradient in place; the downsample's
 backward is four GEMM launches, one per input parity (py, px), each scattering its output pixels with destination stride 2; the pool's
 backward is rart_cnx_pool_bwd_*; the stem's is a dgrad GEMM to fp32 patches and rart_vit_unpatchify_from_f32 (patch 4, row stride 64).
+A V2 block's fc2 dgrad has no epilogue; rart_cnx_grn_bwd_reduce_* then rart_cnx_grn_bwd_apply_* (GRN backward times GELU'(u), in place)
+turn its output into fc1's pre-activation gradient.
 
 precision 'bf16': bf16 storage, fp32 accumulation and statistics, every contraction on rart_conv_igemm_bf16 (the image still enters
 as a hi + lo pair: the stem GEMM runs both planes as two taps).  'bf16x3' (alias 'fp32x'): the reference-precision mode, every
@@ -58,6 +62,8 @@ class ConvNeXtEngine:
         dev = self.device
         m = model
         self.depths, self.dims = tuple(m.depths), tuple(m.dims)
+        self.grn = bool(getattr(m, 'use_grn', False))          # ConvNeXt-V2: GRN after the GELU, no layer scale
+        fold = self.fold_layer_scale and not self.grn
 
         def f32(t):
             return t.detach().to(dev, torch.float32).contiguous()
@@ -104,15 +110,17 @@ class ConvNeXtEngine:
                          ds_wd=[bwd(w[:, :, py, px].t()) for py, px in DS_TAPS])         # per input parity: [cin][cout]
             for blk in st.blocks:
                 c = blk.conv_dw.weight.shape[0]
-                g = f32(blk.gamma) if self.fold_layer_scale else None
+                g = f32(blk.gamma) if fold else None
                 w1 = f32(blk.mlp.fc1.weight)
-                w2 = g[:, None] * f32(blk.mlp.fc2.weight) if self.fold_layer_scale else f32(blk.mlp.fc2.weight)
+                w2 = g[:, None] * f32(blk.mlp.fc2.weight) if fold else f32(blk.mlp.fc2.weight)
                 S['blocks'].append(dict(
                     dw_w=f32(blk.conv_dw.weight).reshape(c, 49).t().contiguous(), dw_b=f32(blk.conv_dw.bias),
                     ng=f32(blk.norm.weight), nb=f32(blk.norm.bias),
                     fc1_w=fwd(w1), fc1_b=f32(blk.mlp.fc1.bias), fc1_wd=bwd(w1.t()),
-                    fc2_w=fwd(w2), fc2_b=(g * f32(blk.mlp.fc2.bias)).contiguous() if self.fold_layer_scale else f32(blk.mlp.fc2.bias),
+                    fc2_w=fwd(w2), fc2_b=(g * f32(blk.mlp.fc2.bias)).contiguous() if fold else f32(blk.mlp.fc2.bias),
                     fc2_wd=bwd(w2.t())))
+                if self.grn:
+                    S['blocks'][-1].update(grn_w=f32(blk.mlp.grn.weight), grn_b=f32(blk.mlp.grn.bias))
             self.stages.append(S)
         self.head_g, self.head_nb = f32(m.head.norm.weight), f32(m.head.norm.bias)
         self.n_classes = m.head.fc.out_features
@@ -211,6 +219,34 @@ class ConvNeXtEngine:
         else:
             _lib.check(lib.rart_cnx_dwconv_bwd_bf16(_lib.ptr(dz), _lib.ptr(L['dw_w']), _lib.ptr(res), _lib.ptr(dx), B, H, W, C, sp))
 
+    def _grn(self, y, L, G, z, B, P, C):
+        """ConvNeXt-V2: G = the per-image channel norms of the GELU output y [B][P][C], then z = GRN(y) (z may be y)"""
+        lib, sp = self.lib, _lib.stream_ptr()
+        if self.x3:
+            (yh, yl), (zh, zl) = self._hl(y), self._hl(z)
+            _lib.check(lib.rart_cnx_grn_stats_pair(yh, yl, _lib.ptr(G), B, P, C, sp))
+            _lib.check(lib.rart_cnx_grn_apply_pair(yh, yl, _lib.ptr(G), _lib.ptr(L['grn_w']), _lib.ptr(L['grn_b']), zh, zl, B, P, C, 1e-6, sp))
+        else:
+            _lib.check(lib.rart_cnx_grn_stats_bf16(_lib.ptr(y), _lib.ptr(G), B, P, C, sp))
+            _lib.check(lib.rart_cnx_grn_apply_bf16(_lib.ptr(y), _lib.ptr(G), _lib.ptr(L['grn_w']), _lib.ptr(L['grn_b']), _lib.ptr(z), B, P, C,
+                                                   1e-6, sp))
+
+    def _grn_bwd(self, g, y, u, G, L, B, P, C):
+        """ConvNeXt-V2: g = the gradient of the GRN output -> in place, the gradient of fc1's pre-activation u (GRN backward times
+        GELU'(u)); y and G are the forward's GELU output and channel norms"""
+        torch = _lib.require_gpu()
+        lib, sp = self.lib, _lib.stream_ptr()
+        a = self._get('g_grn_a', (B, C), torch.float32)
+        if self.x3:
+            (gh, gl), (yh, yl), (uh, ul) = self._hl(g), self._hl(y), self._hl(u)
+            _lib.check(lib.rart_cnx_grn_bwd_reduce_pair(gh, gl, yh, yl, _lib.ptr(L['grn_w']), _lib.ptr(a), B, P, C, sp))
+            _lib.check(lib.rart_cnx_grn_bwd_apply_pair(gh, gl, yh, yl, uh, ul, _lib.ptr(G), _lib.ptr(a), _lib.ptr(L['grn_w']), gh, gl, B, P, C,
+                                                       1e-6, sp))
+        else:
+            _lib.check(lib.rart_cnx_grn_bwd_reduce_bf16(_lib.ptr(g), _lib.ptr(y), _lib.ptr(L['grn_w']), _lib.ptr(a), B, P, C, sp))
+            _lib.check(lib.rart_cnx_grn_bwd_apply_bf16(_lib.ptr(g), _lib.ptr(y), _lib.ptr(u), _lib.ptr(G), _lib.ptr(a), _lib.ptr(L['grn_w']),
+                                                       _lib.ptr(g), B, P, C, 1e-6, sp))
+
     def _downsample(self, x, S, out, B, H, W):
         """LayerNorm of the H x W stage output x, then the 2x2 stride-2 conv into out (H/2 x W/2)"""
         si = S['index']
@@ -268,17 +304,27 @@ class ConvNeXtEngine:
                 self._dwconv_ln(x, L, ln, y, B, H, W, C)
                 if keep:
                     u = self._act('u%d_%d' % (si, bi), (rows, 4 * C))
+                    # ConvNeXt-V2: the GELU output is the GRN backward's y, kept per block (the pair GEMM forms it from the fp32
+                    # accumulator, so it cannot be recomputed bit-identically from the kept u); GRN writes the shared `hid`
+                    h = self._act('h%d_%d' % (si, bi), (rows, 4 * C)) if self.grn else hid
                     if self.x3:
-                        self._mm(ln, L['fc1_w'], hid, rows, 4 * C, C, bias=L['fc1_b'], flags=F_GELU_KEEP, aux=u)
+                        self._mm(ln, L['fc1_w'], h, rows, 4 * C, C, bias=L['fc1_b'], flags=F_GELU_KEEP, aux=u)
                     else:
                         # two launches at every batch size: the one-launch form (flag 64) exists only on the 256 x 256 kernel, which
                         # takes a product above a row threshold, and it applies GELU to the fp32 pre-activation where this form uses
                         # the bf16 one -- B = 256 and B = 8 would differ
                         self._mm(ln, L['fc1_w'], u, rows, 4 * C, C, bias=L['fc1_b'])
-                        _lib.check(lib.rart_gelu_bf16(_lib.ptr(u), _lib.ptr(hid), u.numel(), sp))
-                    saved.append((y, u))
+                        _lib.check(lib.rart_gelu_bf16(_lib.ptr(u), _lib.ptr(h), u.numel(), sp))
+                    if self.grn:
+                        G = self._get('grn_G%d_%d' % (si, bi), (B, 4 * C), torch.float32)
+                        self._grn(h, L, G, hid, B, H * W, 4 * C)
+                        saved.append((y, u, h, G))
+                    else:
+                        saved.append((y, u))
                 else:
                     self._mm(ln, L['fc1_w'], hid, rows, 4 * C, C, bias=L['fc1_b'], flags=F_GELU)
+                    if self.grn:
+                        self._grn(hid, L, self._get('grn_G', (B, 4 * C), torch.float32), hid, B, H * W, 4 * C)
                 self._mm(hid, L['fc2_w'], x, rows, C, 4 * C, bias=L['fc2_b'], res=x)       # in place: x + gamma * fc2(...)
         cl = self.dims[-1]
         pooled = self._act('pooled', (B, cl))
@@ -333,8 +379,13 @@ class ConvNeXtEngine:
             for bi in range(len(S['blocks']) - 1, -1, -1):
                 L = S['blocks'][bi]
                 k -= 1
-                yk, u = saved[k]
-                self._mm(gx, L['fc2_wd'], dh, rows, 4 * C, C, flags=F_GELU_BWD, aux=u)       # (g W2') * gelu'(u)
+                if self.grn:
+                    yk, u, h, G = saved[k]
+                    self._mm(gx, L['fc2_wd'], dh, rows, 4 * C, C)                              # gradient of the GRN output
+                    self._grn_bwd(dh, h, u, G, L, B, H * W, 4 * C)                             # -> in place, times gelu'(u)
+                else:
+                    yk, u = saved[k]
+                    self._mm(gx, L['fc2_wd'], dh, rows, 4 * C, C, flags=F_GELU_BWD, aux=u)   # (g W2') * gelu'(u)
                 self._mm(dh, L['fc1_wd'], dln, rows, C, 4 * C)
                 self._ln_bwd(dln, yk, L['ng'], dz, rows, C)
                 self._dwconv_bwd(dz, L, gx, gx, B, H, W, C)                                   # residual + transposed 7x7, in place

@@ -34,6 +34,8 @@ class ConvNeXtTrainEngine(ConvNeXtEngine):
     wgrad_target_wgs, wgrad_min_chunk = 1024, 256          # K splits of rart_wgrad_direct_bf16, as ResNet50TrainEngine
 
     def __init__(self, model, device='cuda', on_grad_ready=None):
+        if getattr(model, 'use_grn', False):
+            raise NotImplementedError('ConvNeXtTrainEngine: ConvNeXt-V2 (GRN blocks) has no train engine')
         dp = [b.drop_path for st in model.stages for b in st.blocks if b.drop_path > 0.0]
         if dp:
             raise NotImplementedError('ConvNeXtTrainEngine: drop_path_rate > 0 (stochastic depth) is not implemented; the reference '

@@ -255,7 +255,9 @@ def load_pretrain(model, path, prefer='model', strict=True, ignore_model=()):
     (with or without 'module.') popped from the checkpoint before loading -- fine-tuning with another number of classes; the
     model keeps its own initialisation for them and every OTHER key still has to match when strict.
     A ViT checkpoint in the key layout rounds 1-4 of this repository wrote (`patch_embed.weight`, `blocks.N.fc1.*`) is renamed to
-    timm's layout, which the module tree now carries."""
+    timm's layout, which the module tree now carries.  So is a ConvNeXt-V2 checkpoint in its authors' layout
+    (convnextv2_base_1k_224_ema.pt: `downsample_layers.*`, `pwconv1`, `grn.gamma`, ...); `ignore_model` keys may then be given in
+    either layout."""
     ck = load_checkpoint_file(path)
     sd = ck
     if isinstance(ck, dict):
@@ -268,13 +270,18 @@ def load_pretrain(model, path, prefer='model', strict=True, ignore_model=()):
     strip = lambda k: k[7:] if k.startswith('module.') else k    # noqa: E731
     sd = {strip(k): v for k, v in sd.items()}
     from ..model.vit_torch import VisionTransformer, legacy_vit_keys
+    from ..model.convnext_torch import ConvNeXtV2, official_v2_key, official_v2_state_dict
     if isinstance(model, VisionTransformer):
         sd = legacy_vit_keys(sd)
+    if isinstance(model, ConvNeXtV2):
+        sd = official_v2_state_dict(sd)
     dropped = []
     for k in ignore_model or ():
         k = strip(str(k))
         if isinstance(model, VisionTransformer):
             k = next(iter(legacy_vit_keys({k: None})))
+        if isinstance(model, ConvNeXtV2) and k not in sd:
+            k = official_v2_key(k)
         if k in sd:
             del sd[k]
             dropped.append(k)
@@ -531,7 +538,10 @@ def train(cfg, args, rank, world, device):
     n = len(ds)
     max_iter, warmup_steps = resolve_schedule(cfg, n, bs, world, getattr(args, 'max_iter', 20))
     model = build_model(cfg, args).to(device)
-    from ..model.convnext_torch import ConvNeXt
+    from ..model.convnext_torch import ConvNeXt, ConvNeXtV2
+    if isinstance(model, ConvNeXtV2):
+        raise NotImplementedError('training %r: ConvNeXt-V2 has no train engine (its forward and backward-to-input run on the HIP eval '
+                                  'engine, for evaluation and attacks; GRN parameter gradients are not built)' % cfg['model']['type'])
     if isinstance(model, ConvNeXt) and not (device.type == 'cuda' and args.engine == 'hip' and getattr(args, 'train_engine', 'hip') == 'hip'):
         raise NotImplementedError('training %r on %s with --engine %s --train-engine %s: there is no ConvNeXt train engine on this path; '
                                   'ConvNeXtTrainEngine runs on the GPU with --engine hip --train-engine hip'
