@@ -25,33 +25,21 @@ no host synchronisation."""
 import ctypes
 
 from .. import _lib
-from .vit_engine import ViTEngine, PRECISIONS, F_OUT_F32, F_GELU, F_GELU_BWD, F_GELU_KEEP, _pair
+from .engine_base import (F_GELU, F_GELU_BWD, F_GELU_KEEP, F_OUT_F32, RowEngine, conv_desc, gemm_pair_desc, lo_off, pad_k, pad_rows, pair,
+                          rows_mult)
 
 STEM_K = 64                      # 3 x 4 x 4 = 48 columns, padded to the K granularity of both GEMMs
 DS_TAPS = [(0, 0), (0, 1), (1, 0), (1, 1)]
 
 
-class ConvNeXtEngine:
+class ConvNeXtEngine(RowEngine):
     fold_layer_scale = True          # refold: gamma folded into fc2 (the train engine keeps fc2 unscaled and applies gamma itself)
 
     def __init__(self, model, device='cuda', precision='bf16'):
         """precision: 'bf16' (fast path) or 'bf16x3' / 'fp32x' (reference precision: split-bf16 pairs throughout)."""
-        torch = _lib.require_gpu()
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        if precision not in PRECISIONS:
-            raise ValueError('precision must be one of %s' % sorted(PRECISIONS))
-        self.precision = PRECISIONS[precision]
+        super().__init__(device, precision)
         self.x3 = self.precision == 'bf16x3'
-        self.profile = None
-        self.pair_w_interleaved = False          # (the ViT engine's lab switch; the pair tables here are plain planes)
-        self._w_il = {}
-        self._buf = {}
         self.refold(model)
-
-    _get = ViTEngine._get
-    _gemm = ViTEngine._gemm
-    _gemm_pair = ViTEngine._gemm_pair
 
     def refold(self, model):
         """(Re)build every weight table from `model`'s current parameters.  fc2 carries the layer scale: W2' = gamma * W2 and
@@ -68,25 +56,14 @@ class ConvNeXtEngine:
         def f32(t):
             return t.detach().to(dev, torch.float32).contiguous()
 
-        def pad_rows(w, mult):
-            r = (w.shape[0] + mult - 1) // mult * mult
-            if r != w.shape[0]:
-                w = torch.cat([w, torch.zeros(r - w.shape[0], w.shape[1], dtype=w.dtype, device=w.device)], 0)
-            return w.contiguous()
-
-        def pad_k(w, k):
-            if k > w.shape[1]:
-                w = torch.cat([w, torch.zeros(w.shape[0], k - w.shape[1], dtype=w.dtype, device=w.device)], 1)
-            return w.contiguous()
-
         if self.x3:
             def tab(w32):                  # pair planes [2][rows padded to 256][K]
-                return _pair(pad_rows(f32(w32), 256))
+                return pair(pad_rows(f32(w32), 256))
             fwd = bwd = tab
         else:
             def fwd(w32):                  # bf16 [rows padded to 128 / 64][K]
                 w = f32(w32).to(torch.bfloat16)
-                return pad_rows(w, 128 if w.shape[0] > 64 else 64)
+                return pad_rows(w, rows_mult(w.shape[0]))
             bwd = fwd
         c0 = self.dims[0]
         sw = pad_k(f32(m.stem[0].weight).reshape(c0, 48), STEM_K)                       # [c0][c*16 + r*4 + s], zero columns 48..63
@@ -148,39 +125,12 @@ class ConvNeXtEngine:
     def _conv(self, src, w, dst, B, grid, src_hw, k_per_tap, taps, n_cols, dst_hw, stride, dst_stride, dst_off, bias=None):
         """implicit-GEMM convolution on NHWC src (k_per_tap channels per pixel) -> dst (n_cols channels per pixel)"""
         if self.x3:
-            d = _lib.GemmPairDesc()
-            d.a_hi, d.a_lo = src[0].data_ptr(), src[1].data_ptr()
-            d.w_hi, d.w_lo = w[0].data_ptr(), w[1].data_ptr()
-            d.dst_hi, d.dst_lo = dst[0].data_ptr(), dst[1].data_ptr()
-            d.bias = bias.data_ptr() if bias is not None else None
-            d.M, d.N, d.K = B * grid[0] * grid[1], n_cols, k_per_tap * len(taps)
-            d.lda, d.ldw, d.ldc, d.w_rows = k_per_tap, k_per_tap * len(taps), n_cols, w.shape[1]
-            d.conv, d.batch, d.grid_h, d.grid_w = 1, B, grid[0], grid[1]
-            d.src_h, d.src_w, d.sy, d.sx = src_hw[0], src_hw[1], stride[0], stride[1]
-            d.k_per_tap, d.n_taps = k_per_tap, len(taps)
-            for i, (dy, dx) in enumerate(taps):
-                d.tap_dy[i], d.tap_dx[i] = dy, dx
-            d.dst_h, d.dst_w = dst_hw
-            d.dst_sy, d.dst_sx = dst_stride
-            d.dst_oy, d.dst_ox = dst_off
-            _lib.check(self.lib.rart_gemm_pair_bf16(ctypes.byref(d), _lib.stream_ptr()))
-            return
-        d = _lib.ConvDesc()
-        d.src, d.wgt, d.dst = src.data_ptr(), w.data_ptr(), dst.data_ptr()
-        d.bias = bias.data_ptr() if bias is not None else None
-        d.batch, d.grid_h, d.grid_w = B, grid[0], grid[1]
-        d.src_h, d.src_w, d.src_pix_stride = src_hw[0], src_hw[1], k_per_tap
-        d.k_per_tap, d.n_taps = k_per_tap, len(taps)
-        d.sy, d.sx = stride
-        for i, (dy, dx) in enumerate(taps):
-            d.tap_dy[i], d.tap_dx[i], d.tap_src_off[i] = dy, dx, 0
-        d.n_cols = n_cols
-        d.dst_h, d.dst_w = dst_hw
-        d.dst_sy, d.dst_sx = dst_stride
-        d.dst_oy, d.dst_ox = dst_off
-        d.dst_pix_stride = n_cols
-        d.flags = 0
-        _lib.check(self.lib.rart_conv_igemm_bf16(ctypes.byref(d), _lib.stream_ptr()))
+            self._launch_pair(gemm_pair_desc(src, w, dst, n_cols, k_per_tap, k_per_tap * len(taps), n_cols, w.shape[1], bias=bias, batch=B,
+                                             grid=grid, src_hw=src_hw, stride=stride, k_per_tap=k_per_tap, taps=taps, dst_hw=dst_hw,
+                                             dst_stride=dst_stride, dst_org=dst_off))
+        else:
+            self._launch_conv(conv_desc(src, w, dst, B, grid, src_hw, k_per_tap, k_per_tap, taps, n_cols, dst_hw, n_cols, bias=bias,
+                                        stride=stride, dst_stride=dst_stride, dst_org=dst_off))
 
     def _ln(self, x, g, b, out, rows, c):
         lib, sp = self.lib, _lib.stream_ptr()
@@ -284,8 +234,8 @@ class ConvNeXtEngine:
         if self.x3:
             self._gemm_pair(patches, self.stem_w, xs, B * H * W, c0, STEM_K, STEM_K, c0, bias=self.stem_b)
         else:
-            lo_off = (patches[1].data_ptr() - patches[0].data_ptr()) // 2
-            self._gemm(patches[0], self.stem_w, xs, B * H * W, STEM_K, c0, STEM_K, c0, bias=self.stem_b, n_taps=2, tap_src_off=[0, lo_off])
+            self._gemm(patches[0], self.stem_w, xs, B * H * W, STEM_K, c0, STEM_K, c0, bias=self.stem_b, n_taps=2,
+                       tap_src_off=[0, lo_off(patches)])
         x = self._act('x0', (B * H * W, c0))
         self._ln(xs, self.stem_g, self.stem_nb, x, B * H * W, c0)
         saved, stage_out = [], []
@@ -310,7 +260,7 @@ class ConvNeXtEngine:
                     if self.x3:
                         self._mm(ln, L['fc1_w'], h, rows, 4 * C, C, bias=L['fc1_b'], flags=F_GELU_KEEP, aux=u)
                     else:
-                        # two launches at every batch size: the one-launch form (flag 64) exists only on the 256 x 256 kernel, which
+                        # two launches at every batch size: the one-launch form (F_GELU_KEEP) exists only on the 256 x 256 kernel, which
                         # takes a product above a row threshold, and it applies GELU to the fp32 pre-activation where this form uses
                         # the bf16 one -- B = 256 and B = 8 would differ
                         self._mm(ln, L['fc1_w'], u, rows, 4 * C, C, bias=L['fc1_b'])
@@ -406,9 +356,3 @@ class ConvNeXtEngine:
         _lib.check(lib.rart_vit_unpatchify_from_f32(_lib.ptr(dpatch), _lib.ptr(grad), B, Himg, Wimg, 4, STEM_K,
                                                     (ctypes.c_float * 3)(*std), sp))
         return logits, loss, grad, pred
-
-    def logits(self, x01, mean, std):
-        return self._forward(x01.detach().float().contiguous(), False, mean, std)
-
-    def logits_from_u8(self, batch_u8, mean, std):
-        return self._forward(batch_u8, True, mean, std)

@@ -10,7 +10,7 @@ AdamW, label_smooth 0.1, EMA, drop_path_rate 0.0 -- no stochastic layers) with e
   layer scale                      rart_cnx_layer_scale_bwd_bf16: dgamma, dv = gamma * dx, fc2's bias gradient, one pass
   7x7 depthwise weight and bias    rart_cnx_dwconv_wgrad_bf16
   fc1 / fc2 / downsample weights   rart_wgrad_direct_bf16 straight from the NHWC activations (1 tap; 4 taps stride 2)
-  head and stem weights            ViTTrainEngine._wgrad (split-K GEMM over transposed operands)
+  head and stem weights            RowEngine._wgrad (split-K GEMM over transposed operands)
   Linear and conv biases           rart_colsum_bf16 (fc2's comes with the layer-scale backward)
   LayerNorm gamma / beta           rart_layernorm_bwd_full_bf16, fused with the backward to the input
 
@@ -21,17 +21,11 @@ import ctypes
 
 from .. import _lib
 from .convnext_engine import DS_TAPS, STEM_K, ConvNeXtEngine
-from .vit_engine import F_GELU_BWD, F_OUT_F32
-from .vit_train_engine import ViTTrainEngine
-
-
-def _ints(v):
-    return (ctypes.c_int * len(v))(*v)
+from .engine_base import F_GELU_BWD, F_OUT_F32
 
 
 class ConvNeXtTrainEngine(ConvNeXtEngine):
     fold_layer_scale = False
-    wgrad_target_wgs, wgrad_min_chunk = 1024, 256          # K splits of rart_wgrad_direct_bf16, as ResNet50TrainEngine
 
     def __init__(self, model, device='cuda', on_grad_ready=None):
         if getattr(model, 'use_grn', False):
@@ -56,10 +50,6 @@ class ConvNeXtTrainEngine(ConvNeXtEngine):
         """fp32 master weights -> bf16 tables; call after every optimizer step."""
         self.refold(self.model)
 
-    _scratch = ViTTrainEngine._scratch
-    _wgrad = ViTTrainEngine._wgrad
-    _colsum = ViTTrainEngine._colsum
-
     # ------------------------------------------------------------------ helpers
     def _ready(self, *params):
         for p in params:
@@ -75,26 +65,10 @@ class ConvNeXtTrainEngine(ConvNeXtEngine):
                                                     _lib.stream_ptr()))
         self._ready(norm.weight, norm.bias)
 
-    def _wgrad_direct(self, x, dz, B, x_hw, x_c, grid_hw, n_out, taps, stride, grad):
-        """grad[n_out][x_c][taps] = sum over positions m of dz[m][n] * x[pixel(m) + tap][c] (x: bf16 [B][ih][iw][x_c], dz: bf16
-        [B][gh][gw][n_out]) on rart_wgrad_direct_bf16 + rart_wgrad_reduce_f32"""
-        lib, sp = self.lib, _lib.stream_ptr()
-        M = B * grid_hw[0] * grid_hw[1]
-        row_tiles = len(taps) * (x_c // 128) if x_c >= 128 else (len(taps) + 128 // x_c - 1) // (128 // x_c)
-        tiles = row_tiles * (n_out // (128 if n_out % 128 == 0 else 64))
-        splits = max(1, min(self.wgrad_target_wgs // max(tiles, 1), M // self.wgrad_min_chunk if M >= 2 * self.wgrad_min_chunk else 1, 1024))
-        chunk = ((M + splits - 1) // splits + 31) // 32 * 32
-        splits = (M + chunk - 1) // chunk
-        part = self._scratch('wg_part', splits * len(taps) * x_c * n_out * 4)
-        _lib.check(lib.rart_wgrad_direct_bf16(_lib.ptr(x), _lib.ptr(dz), _lib.ptr(part), B, x_hw[0], x_hw[1], x_c, grid_hw[0], grid_hw[1],
-                                              n_out, stride, stride, len(taps), _ints([t[0] for t in taps]), _ints([t[1] for t in taps]),
-                                              splits, chunk, n_out, sp))
-        _lib.check(lib.rart_wgrad_reduce_f32(_lib.ptr(part), splits, len(taps), x_c, x_c, n_out, n_out, _lib.ptr(grad), 0, sp))
-
     def _linear_wgrad(self, lin, x, dz, rows):
         """Linear weight [n_out][c_in] over NHWC rows: x [rows][c_in], dz [rows][n_out]"""
         n_out, c_in = lin.weight.shape
-        self._wgrad_direct(x, dz, 1, (rows, 1), c_in, (rows, 1), n_out, [(0, 0)], 1, lin.weight.grad)
+        self._wgrad_direct(x, dz, 1, (rows, 1), c_in, (rows, 1), n_out, n_out, [(0, 0)], 1, lin.weight.grad)
         self._ready(lin.weight)
 
     # ------------------------------------------------------------------ forward
@@ -223,7 +197,7 @@ class ConvNeXtTrainEngine(ConvNeXtEngine):
                 cin = self.dims[si - 1]
                 ds_ln, conv = self._buf['ds_ln%d' % si], stage.downsample[1]
                 self._colsum(gx, C, rows, C, conv.bias.grad)
-                self._wgrad_direct(ds_ln, gx, B, (2 * H, 2 * W), cin, (H, W), C, DS_TAPS, 2, conv.weight.grad)
+                self._wgrad_direct(ds_ln, gx, B, (2 * H, 2 * W), cin, (H, W), C, C, DS_TAPS, 2, conv.weight.grad)
                 self._ready(conv.bias, conv.weight)
                 gds = self._get('g_ds_ln%d' % si, (B * 4 * H * W, cin))
                 self._downsample_scatter(gx, S, gds, B, 2 * H, 2 * W)

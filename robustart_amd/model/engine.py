@@ -17,27 +17,13 @@ import ctypes
 import os as _os
 
 from .. import _lib
-
-F_RELU, F_OUT_F32, F_MASK_BITS, F_PAIR = 1, 2, 16, 32
-PRECISIONS = {'bf16': 'bf16', 'bf16x3': 'bf16x3', 'fp32x': 'bf16x3'}
+from .engine_base import (F_MASK_BITS, F_OUT_F32, F_PAIR, F_RELU, EngineBase, cints as _cints, conv_desc, gemm_pair_desc,
+                          interleave_k32, lo_off, pad_rows, rows_mult, pair, split_hi_lo)
 
 
 def _bf16(t):
     import torch
     return t.to(torch.bfloat16).contiguous()
-
-
-def _pad_rows(w2d, mult):
-    import torch
-    rows = w2d.shape[0]
-    pr = (rows + mult - 1) // mult * mult
-    if pr == rows:
-        return w2d
-    return torch.cat([w2d, torch.zeros(pr - rows, w2d.shape[1], dtype=w2d.dtype, device=w2d.device)], 0)
-
-
-def _rows_mult(n_cols):
-    return 128 if n_cols > 64 else 64
 
 
 class _Conv:
@@ -59,15 +45,15 @@ class _Conv:
         self.b_folded = b
         self.bias = b.contiguous().to(device)
         self.fwd_taps = [(r - self.pad, s - self.pad) for r in range(self.r) for s in range(self.s)]
-        wb = w.to(torch.bfloat16).float()    # the values the bf16 kernels see
+        hi, lo = split_hi_lo(w)
+        wb = hi.float()                      # the values the bf16 kernels see
         if not split:
             self.w_fwd, self.bwd = self._tables(wb, device)
         else:
             # reference-precision mode: w = hi + lo (two bf16 pieces, 16 significand bits); a weight row is the
-            # concatenation [hi | lo | hi] matching the products x_hi.w_hi + x_hi.w_lo + x_lo.w_hi (rart_conv_desc flag 32)
-            wl = (w - wb).to(torch.bfloat16).float()
+            # concatenation [hi | lo | hi] matching the products x_hi.w_hi + x_hi.w_lo + x_lo.w_hi (F_PAIR)
             fh, bh = self._tables(wb, device)
-            fl, bl = self._tables(wl, device)
+            fl, bl = self._tables(lo.float(), device)
             self.w_fwd = torch.cat([fh, fl, fh], 1).contiguous()
             self.bwd = [(par, taps, None if th is None else torch.cat([th, tl, th], 1).contiguous())
                         for (par, taps, th), (_, _, tl) in zip(bh, bl)]
@@ -77,7 +63,7 @@ class _Conv:
         fp32 weights wb [cout][cin][r][s]."""
         import torch
         # forward: rows = cout, k = (r*S + s)*Cin + c
-        w_fwd = _bf16(_pad_rows(wb.permute(0, 2, 3, 1).reshape(self.cout, -1), _rows_mult(self.cout))).to(device)
+        w_fwd = _bf16(pad_rows(wb.permute(0, 2, 3, 1).reshape(self.cout, -1), rows_mult(self.cout))).to(device)
         # backward to input: rows = cin, k = tap*Cout + cout
         bwd = []    # list of (parity (ph,pw) or None, taps [(dy,dx)], weight)
         if self.stride == 1:
@@ -87,7 +73,7 @@ class _Conv:
                     taps.append((self.pad - r, self.pad - s))
                     cols.append(wb[:, :, r, s].t())                     # [cin][cout]
             wd = torch.cat(cols, 1)
-            bwd.append((None, taps, _bf16(_pad_rows(wd, _rows_mult(self.cin))).to(device)))
+            bwd.append((None, taps, _bf16(pad_rows(wd, rows_mult(self.cin))).to(device)))
         else:
             assert self.stride == 2
             for ph in range(2):
@@ -105,15 +91,11 @@ class _Conv:
                         bwd.append(((ph, pw), [], None))
                         continue
                     wd = torch.cat(cols, 1)
-                    bwd.append(((ph, pw), taps, _bf16(_pad_rows(wd, _rows_mult(self.cin))).to(device)))
+                    bwd.append(((ph, pw), taps, _bf16(pad_rows(wd, rows_mult(self.cin))).to(device)))
         return w_fwd, bwd
 
 
-def _cints(vals):
-    return (ctypes.c_int * max(len(vals), 1))(*vals)
-
-
-class ResNet50Engine:
+class ResNet50Engine(EngineBase):
     """Hand-written HIP eval engine for robustart_amd.model.resnet_torch.ResNet."""
 
     def __init__(self, model, device='cuda', precision='bf16'):
@@ -122,12 +104,8 @@ class ResNet50Engine:
         autopgd_base.py:271-289) and the north star asks for logits within 1e-4 of it, so every activation, gradient and
         weight is a hi + lo pair of bf16 values (16 significand bits) and every contraction the three MFMA products
         hi.hi + hi.lo + lo.hi with fp32 accumulation (`_forward_x3`): logits within ~1e-5 of the fp32 network's scale."""
+        super().__init__(device, precision)
         torch = _lib.require_gpu()
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        if precision not in PRECISIONS:
-            raise ValueError('precision must be one of %s' % sorted(PRECISIONS))
-        self.precision = PRECISIONS[precision]
         split = self.precision == 'bf16x3'
         m = model
         assert not m.training, 'the attack / eval engine folds BatchNorm: call model.eval() first'
@@ -135,7 +113,8 @@ class ResNet50Engine:
         # ---- stem: 7x7/2 conv on the padded 4-channel hi/lo image; a "tap" = one filter row, 8 px x 4 ch
         st = _Conv(m.conv1, m.bn1, dev, split)
         self.stem = st
-        wb = st.w_folded.to(torch.bfloat16).float()                       # [64][3][7][7]
+        hi, lo = split_hi_lo(st.w_folded)
+        wb = hi.float()                                                   # [64][3][7][7]
         wrow = torch.zeros(64, 7, 8, 4)
         wrow[:, :, :7, :3] = wb.permute(0, 2, 3, 1)                      # [cout][r][s][c]
         wrow = wrow.reshape(64, 7 * 32)
@@ -143,20 +122,19 @@ class ResNet50Engine:
         # stem backward: patches[(r*7+s)*3+c] = sum_k dz[k] * W[k][c][r][s]; 147 rows zero-padded to the tile
         wp = wb.permute(2, 3, 1, 0).reshape(147, 64)
         self.stem_patch_cols = 152                                        # 147 rounded up to 8
-        self.stem_wd = _bf16(_pad_rows(wp, _rows_mult(self.stem_patch_cols))).to(dev)
+        self.stem_wd = _bf16(pad_rows(wp, rows_mult(self.stem_patch_cols))).to(dev)
         self.stem_wt = self._stem_bwd_table(wb).to(dev)                  # fused stem backward (stem_fused.hip)
         if split:
-            wl = (st.w_folded - wb).to(torch.bfloat16).float()
+            wl = lo.float()
             wrow_l = torch.zeros(64, 7, 8, 4)
             wrow_l[:, :, :7, :3] = wl.permute(0, 2, 3, 1)
             wrow_l = wrow_l.reshape(64, 7 * 32)
             self.stem_w = _bf16(torch.cat([wrow, wrow_l, wrow], 1)).to(dev)      # x_hi.w_hi, x_hi.w_lo, x_lo.w_hi row taps
             wpl = wl.permute(2, 3, 1, 0).reshape(147, 64)
-            self.stem_wd = _bf16(_pad_rows(torch.cat([wp, wpl, wp], 1), _rows_mult(self.stem_patch_cols))).to(dev)
+            self.stem_wd = _bf16(pad_rows(torch.cat([wp, wpl, wp], 1), rows_mult(self.stem_patch_cols))).to(dev)
             self.stem_w_pair = _bf16(torch.stack([wrow, wrow_l])).contiguous().to(dev)   # fused pair stem forward (stem_pair.hip): [2][64][224]
             wt32 = self._stem_bwd_table(st.w_folded, dtype=torch.float32)           # fused pair stem backward (stem_pair.hip)
-            wt_hi = wt32.to(torch.bfloat16)
-            self.stem_wt_pair = torch.stack([wt_hi, (wt32 - wt_hi.float()).to(torch.bfloat16)]).contiguous().to(dev)
+            self.stem_wt_pair = pair(wt32).to(dev)
         self.fused_stem_bwd = True       # False: max-pool bwd -> patches GEMM -> col2im (kept as the cross-check)
         self.sign_bit_masks = True       # False: the backward reads the bf16 activations for their ReLU sign (cross-check)
         self.halo_conv3x3 = True         # False: layer1 / layer2 3x3 convs on the generic implicit GEMM (cross-check)
@@ -187,28 +165,26 @@ class ResNet50Engine:
         # ---- classifier
         wfc = m.fc.weight.detach().float()
         self.n_classes, self.fc_in = wfc.shape
-        wfb = wfc.to(torch.bfloat16).float()
-        self.fc_w = _bf16(_pad_rows(wfb, 128)).to(dev)                    # [1024][2048]
+        hi, lo = split_hi_lo(wfc)
+        wfb = hi.float()
+        self.fc_w = _bf16(pad_rows(wfb, 128)).to(dev)                    # [1024][2048]
         self.fc_b = m.fc.bias.detach().float().contiguous().to(dev)
         self.fc_kpad = (self.n_classes + 31) // 32 * 32                   # 1024
         wt = torch.zeros(self.fc_in, self.fc_kpad)
         wt[:, :self.n_classes] = wfb.t()
         self.fc_wd = _bf16(wt).to(dev)                                    # [2048][1024]
         if split:
-            wfl = (wfc - wfb).to(torch.bfloat16).float()
-            fh, fl = _pad_rows(wfb, 128), _pad_rows(wfl, 128)
+            wfl = lo.float()
+            fh, fl = pad_rows(wfb, 128), pad_rows(wfl, 128)
             self.fc_w = _bf16(torch.cat([fh, fl, fh], 1)).to(dev)         # [1024][3 * 2048]
             wtl = torch.zeros(self.fc_in, self.fc_kpad)
             wtl[:, :self.n_classes] = wfl.t()
             self.fc_wd = _bf16(torch.cat([wt, wtl, wt], 1)).to(dev)       # [2048][3 * 1024]
-        self._buf = {}
-        self.profile = None      # set to a list to record (flops, start_event, end_event) per GEMM launch
         # round 5 experiment, OFF by default: the pair GEMM's weight tables with the hi and the lo slice of a 32-deep K step side by side (one
         # 128-byte line per row and step instead of two half lines K apart).  2-5 % per K-deep launch when a shape is replayed back to back
         # (profiles/r05_pair_knockouts.txt), nothing on the whole gradient evaluation (20.61 vs 20.63 ms) and +0.9 % on the forward
         # (scratch/r5/ab_engine_x3.py): the isolated replay keeps the tables hot in L2, the network does not.  RART_PAIR_WIL=1 turns it on.
         self.pair_w_interleaved = _os.environ.get('RART_PAIR_WIL', '0') == '1'
-        self._w_il = {}
         if not split:
             self._pack_frag_tables()
         else:
@@ -472,63 +448,28 @@ class ResNet50Engine:
         host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
         return host.to(self.device)
 
-    # ------------------------------------------------------------------ buffers / launches
-    def _get(self, name, shape, dtype=None):
-        torch = _lib.require_gpu()
-        dtype = dtype or torch.bfloat16
-        t = self._buf.get(name)
-        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
-            t = torch.empty(shape, dtype=dtype, device=self.device)
-            self._buf[name] = t
-        return t
-
+    # ------------------------------------------------------------------ launches
     def _gemm(self, src, wgt, dst, batch, grid, src_hw, src_pix, k_per_tap, taps, n_cols, dst_hw, dst_pix,
               bias=None, res=None, mask=None, flags=0, stride=(1, 1), dst_stride=(1, 1), dst_off=(0, 0),
               tap_src_off=None, sign_out=None, pair=False):
         if pair and self.pair_gemm_kernel and len(taps) <= 16 and k_per_tap >= 32 and (k_per_tap & (k_per_tap - 1)) == 0:
             return self._gemm_pair(src, wgt, dst, batch, grid, src_hw, src_pix, k_per_tap, taps, n_cols, dst_hw, dst_pix, bias, res,
                                    mask, flags, stride, dst_stride, dst_off, sign_out)
-        d = _lib.ConvDesc()
+        dst_pair_off = res_pair_off = 0
         if pair:
             # split-bf16 tensors [2][...] (hi plane, lo plane): the three products as 3x the taps, the lo planes of dst / res
-            # by their element offsets (rart_conv_desc flag 32); an fp32 destination (F_OUT_F32) is a plain tensor
+            # by their element offsets (F_PAIR); an fp32 destination (F_OUT_F32) is a plain tensor
             assert tap_src_off is None and src.shape[0] == 2
-            lo = (src[1].data_ptr() - src[0].data_ptr()) // 2
-            tap_src_off = [0] * (2 * len(taps)) + [lo] * len(taps)
+            tap_src_off = [0] * (2 * len(taps)) + [lo_off(src)] * len(taps)
             taps = list(taps) * 3
             flags |= F_PAIR
             if not (flags & F_OUT_F32):
-                d.dst_pair_off = (dst[1].data_ptr() - dst[0].data_ptr()) // 2
+                dst_pair_off = lo_off(dst)
             if res is not None:
-                d.res_pair_off = (res[1].data_ptr() - res[0].data_ptr()) // 2
-        d.src, d.wgt, d.dst = src.data_ptr(), wgt.data_ptr(), dst.data_ptr()
-        d.bias = bias.data_ptr() if bias is not None else None
-        d.res = res.data_ptr() if res is not None else None
-        d.mask = mask.data_ptr() if mask is not None else None
-        d.sign_out = sign_out.data_ptr() if sign_out is not None else None
-        d.batch, d.grid_h, d.grid_w = batch, grid[0], grid[1]
-        d.src_h, d.src_w, d.src_pix_stride = src_hw[0], src_hw[1], src_pix
-        d.k_per_tap, d.n_taps = k_per_tap, len(taps)
-        d.sy, d.sx = stride
-        for i, (dy, dx) in enumerate(taps):
-            d.tap_dy[i], d.tap_dx[i] = dy, dx
-            d.tap_src_off[i] = tap_src_off[i] if tap_src_off is not None else 0
-        d.n_cols = n_cols
-        d.dst_h, d.dst_w = dst_hw
-        d.dst_sy, d.dst_sx = dst_stride
-        d.dst_oy, d.dst_ox = dst_off
-        d.dst_pix_stride = dst_pix
-        d.flags = flags
-        if self.profile is not None:
-            torch = _lib.require_gpu()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()          # torch's current stream == the stream the kernel is enqueued on (stream_ptr())
-            _lib.check(self.lib.rart_conv_igemm_bf16(ctypes.byref(d), _lib.stream_ptr()))
-            e1.record()
-            flops = 2.0 * batch * grid[0] * grid[1] * k_per_tap * len(taps) * n_cols
-            self.profile.append((flops, e0, e1, 'igemm'))
-            return
-        _lib.check(self.lib.rart_conv_igemm_bf16(ctypes.byref(d), _lib.stream_ptr()))
+                res_pair_off = lo_off(res)
+        self._launch_conv(conv_desc(src, wgt, dst, batch, grid, src_hw, src_pix, k_per_tap, taps, n_cols, dst_hw, dst_pix, bias=bias,
+                                    res=res, mask=mask, sign_out=sign_out, flags=flags, stride=stride, dst_stride=dst_stride,
+                                    dst_org=dst_off, tap_src_off=tap_src_off, dst_pair_off=dst_pair_off, res_pair_off=res_pair_off))
 
     def _gemm_pair(self, src, wgt, dst, batch, grid, src_hw, src_pix, k_per_tap, taps, n_cols, dst_hw, dst_pix, bias, res, mask, flags,
                    stride, dst_stride, dst_off, sign_out):
@@ -540,53 +481,23 @@ class ResNet50Engine:
         assert src.shape[0] == 2
         k_tot = k_per_tap * len(taps)
         assert wgt.shape[1] == 3 * k_tot
-        d = _lib.GemmPairDesc()
-        d.a_hi, d.a_lo = src[0].data_ptr(), src[1].data_ptr()
-        d.w_hi, d.w_lo = wgt.data_ptr(), wgt.data_ptr() + 2 * k_tot
-        ldw, wflag = 3 * k_tot, 0
+        il = None
         if self.pair_w_interleaved:
             # per row and 32-deep K step: the hi slice then the lo slice (one 128-byte line per row and step instead of two half lines)
             il = self._w_il.get(wgt.data_ptr())
             if il is None:
-                import torch
-                rows = wgt.shape[0]
-                il = torch.stack([wgt[:, :k_tot].reshape(rows, k_tot // 32, 32), wgt[:, k_tot:2 * k_tot].reshape(rows, k_tot // 32, 32)], 2)
-                il = self._w_il[wgt.data_ptr()] = il.reshape(rows, 2 * k_tot).contiguous()
-            d.w_hi, d.w_lo, ldw, wflag = il.data_ptr(), il.data_ptr() + 64, 2 * k_tot, 16
-        d.bias = bias.data_ptr() if bias is not None else None
-        if res is not None:
-            d.res_hi, d.res_lo = res[0].data_ptr(), res[1].data_ptr()
-        if flags & F_OUT_F32:
-            d.dst_hi = dst.data_ptr()
-        else:
-            d.dst_hi, d.dst_lo = dst[0].data_ptr(), dst[1].data_ptr()
-        d.N, d.lda, d.ldw, d.ldc, d.w_rows = n_cols, src_pix, ldw, dst_pix, wgt.shape[0]
-        d.flags = (flags & (F_RELU | F_OUT_F32)) | wflag
-        d.conv, d.batch, d.grid_h, d.grid_w = 1, batch, grid[0], grid[1]
-        d.src_h, d.src_w, d.sy, d.sx = src_hw[0], src_hw[1], stride[0], stride[1]
-        d.k_per_tap, d.n_taps = k_per_tap, len(taps)
-        for i, (dy, dx) in enumerate(taps):
-            d.tap_dy[i], d.tap_dx[i] = dy, dx
-        d.dst_h, d.dst_w = dst_hw
-        d.dst_sy, d.dst_sx = dst_stride
-        d.dst_oy, d.dst_ox = dst_off
-        d.mask_bits = mask.data_ptr() if mask is not None else None
-        d.sign_out = sign_out.data_ptr() if sign_out is not None else None
-        d.tile_m, d.tile_n = self.pair_tile          # (0, 0): the library's choice; profiling sweeps force a tile
+                il = self._w_il[wgt.data_ptr()] = interleave_k32(wgt[:, :k_tot], wgt[:, k_tot:2 * k_tot])
+        nbytes = None
         if self.profile is not None:
-            torch = _lib.require_gpu()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            _lib.check(self.lib.rart_gemm_pair_bf16(ctypes.byref(d), _lib.stream_ptr()))
-            e1.record()
-            # MFMA FLOPs issued; algorithmic bytes = every operand once: source pair pixels (4 B per element), destination pair (or fp32),
-            # residual pair, both weight planes, 1 bit per destination element for a mask / sign tensor
+            # algorithmic bytes = every operand once: source pair pixels (4 B per element), destination pair (or fp32), residual pair,
+            # both weight planes, 1 bit per destination element for a mask / sign tensor
             rows = batch * grid[0] * grid[1]
             nbytes = 4.0 * batch * src_hw[0] * src_hw[1] * k_per_tap + 4.0 * rows * n_cols * (2 if res is not None else 1) + 4.0 * k_tot * n_cols \
                 + rows * n_cols / 8.0 * ((mask is not None) + (sign_out is not None))
-            self.profile.append((3 * 2.0 * rows * k_tot * n_cols, e0, e1, 'gemm_pair', nbytes))
-            return
-        _lib.check(self.lib.rart_gemm_pair_bf16(ctypes.byref(d), _lib.stream_ptr()))
+        self._launch_pair(gemm_pair_desc(src, wgt, dst, n_cols, src_pix, 3 * k_tot, dst_pix, wgt.shape[0], bias=bias, res=res, mask_bits=mask,
+                                         sign_out=sign_out, flags=flags & (F_RELU | F_OUT_F32), w_lo_off=k_tot, w_il=il, batch=batch,
+                                         grid=grid, src_hw=src_hw, stride=stride, k_per_tap=k_per_tap, taps=taps, dst_hw=dst_hw,
+                                         dst_stride=dst_stride, dst_org=dst_off, tile=self.pair_tile), nbytes)
 
     def _tail(self, src, wgt, taps, tail, dst, batch, hw, c_mid, bias_mid=None, bias_out=None, res=None, mask_mid=None, mask_out=None,
               sign_mid=None, sign_out=None, relu=False, nxt=None):
@@ -614,49 +525,24 @@ class ResNet50Engine:
             d.dstn_hi, d.dstn_lo = nxt['dst'][0].data_ptr(), nxt['dst'][1].data_ptr()
             d.bias_next, d.mask_next, d.sign_next = _lib.ptr(nxt.get('bias')), _lib.ptr(nxt.get('mask')), _lib.ptr(nxt.get('sign'))
             d.relu_next = 1 if nxt.get('relu') else 0
-        if self.profile is not None:
-            torch = _lib.require_gpu()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            _lib.check(self.lib.rart_conv3x3_tail_pair(ctypes.byref(d), _lib.stream_ptr()))
-            e1.record()
+        ev = self._prof_begin()
+        _lib.check(self.lib.rart_conv3x3_tail_pair(ctypes.byref(d), _lib.stream_ptr()))
+        if ev is not None:
             px = batch * hw[0] * hw[1]
             nbytes = 4.0 * px * c_mid * (1 + 4 + (4 if res is not None else 0) + (1 if nxt is not None else 0)) \
                 + 4.0 * c_mid * c_mid * (9 + 4 + (4 if nxt is not None else 0))
-            self.profile.append((3 * 2.0 * px * (k_tot * c_mid + (8 if nxt is not None else 4) * c_mid * c_mid), e0, e1,
-                                 'conv_tail_pair', nbytes))   # MFMA FLOPs issued, algorithmic bytes (every operand once)
-            return
-        _lib.check(self.lib.rart_conv3x3_tail_pair(ctypes.byref(d), _lib.stream_ptr()))
-
-    def _prof_begin(self):
-        if self.profile is None:
-            return None
-        torch = _lib.require_gpu()
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-        return e0
-
-    def _prof_end(self, e0, flops, kind, nbytes=None):
-        if e0 is None:
-            return
-        e1 = _lib.require_gpu().cuda.Event(enable_timing=True)
-        e1.record()
-        self.profile.append((flops, e0, e1, kind, nbytes))
+            self._prof_end(ev, 3 * 2.0 * px * (k_tot * c_mid + (8 if nxt is not None else 4) * c_mid * c_mid), 'conv_tail_pair',
+                           nbytes)   # MFMA FLOPs issued, algorithmic bytes (every operand once)
 
     def _fc(self, a, w, out, m, n, k, bias=None):
         """The classifier head / its backward: rart_gemm_small_m_bf16 (one workgroup per 32 x 32 tile, waves split K) instead of the
         16-workgroup implicit-GEMM launch; `out` fp32 or bf16."""
         torch = _lib.require_gpu()
-        args = (_lib.ptr(a), a.shape[-1], _lib.ptr(w), w.shape[-1], _lib.ptr(bias) if bias is not None else None, _lib.ptr(out),
-                out.shape[-1], 1 if out.dtype == torch.float32 else 0, m, n, k, _lib.stream_ptr())
-        if self.profile is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            _lib.check(self.lib.rart_gemm_small_m_bf16(*args))
-            e1.record()
-            self.profile.append((2.0 * m * n * k, e0, e1, 'fc_small_m'))
-            return
-        _lib.check(self.lib.rart_gemm_small_m_bf16(*args))
+        ev = self._prof_begin()
+        _lib.check(self.lib.rart_gemm_small_m_bf16(_lib.ptr(a), a.shape[-1], _lib.ptr(w), w.shape[-1], _lib.ptr(bias), _lib.ptr(out),
+                                                   out.shape[-1], 1 if out.dtype == torch.float32 else 0, m, n, k, _lib.stream_ptr()))
+        if ev is not None:
+            self._prof_end(ev, 2.0 * m * n * k, 'fc_small_m')
 
     @staticmethod
     def _fits32(n, hw, channels):
@@ -669,21 +555,12 @@ class ResNet50Engine:
                 and c.cin == c.cout and getattr(c, 'w_fwd_frag', None) is not None and self.lib.rart_conv3x3_halo_supported(c.cin, hw[0], hw[1]))
 
     def _halo(self, src, w, dst, B, hw, ch, taps, bias=None, mask=None, sign=None, relu=False):
-        if self.profile is not None:
-            torch = _lib.require_gpu()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            prof, self.profile = self.profile, None
-            try:
-                self._halo(src, w, dst, B, hw, ch, taps, bias=bias, mask=mask, sign=sign, relu=relu)
-            finally:
-                self.profile = prof
-            e1.record()
-            self.profile.append((2.0 * B * hw[0] * hw[1] * 9 * ch * ch, e0, e1, 'halo3x3'))
-            return
+        ev = self._prof_begin()
         _lib.check(self.lib.rart_conv3x3_halo_bf16(_lib.ptr(src), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(mask), _lib.ptr(sign),
                                                    _lib.ptr(dst), B, hw[0], hw[1], ch, _cints([t[0] for t in taps]),
                                                    _cints([t[1] for t in taps]), 1 if relu else 0, _lib.stream_ptr()))
+        if ev is not None:
+            self._prof_end(ev, 2.0 * B * hw[0] * hw[1] * 9 * ch * ch, 'halo3x3')
 
     def _bneck_ok(self, ca, cb, cc, ds, xhw, n=1):
         return (self._fits32(n, xhw, cc.cout) and self.fused_bottleneck and ds is None and cb.stride == 1 and cb.r == 3 and ca.r == 1 and cc.r == 1
@@ -706,71 +583,45 @@ class ResNet50Engine:
     def _bneck14(self, x, w1, w2, w3, b1, b2, b3, m1, m2, m3, out, B, hw, c_io, c_mid, taps, backward, fn=None):
         """One layer3 / layer2 identity Bottleneck as a single launch (csrc/bottleneck14_fused.hip, bottleneck28_fused.hip)."""
         fn = fn or self.lib.rart_bottleneck14_fused_bf16
-        if self.profile is not None:
-            torch = _lib.require_gpu()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            prof, self.profile = self.profile, None
-            try:
-                self._bneck14(x, w1, w2, w3, b1, b2, b3, m1, m2, m3, out, B, hw, c_io, c_mid, taps, backward, fn)
-            finally:
-                self.profile = prof
-            e1.record()
-            # 5th element: ALGORITHMIC HBM bytes of the launch -- x in, out, the weight tables once, the 1-bit sign tensors
-            m_ = B * hw[0] * hw[1]
-            by = 2 * m_ * c_io * 2 + (2 * c_io * c_mid + 9 * c_mid * c_mid) * 2 + sum(m_ * c // 8 for c, t in ((c_mid, m1), (c_mid, m2), (c_io, m3)) if t is not None)
-            self.profile.append((2.0 * B * hw[0] * hw[1] * c_mid * (2 * c_io + 9 * c_mid), e0, e1,
-                                 {14: 'bottleneck14', 28: 'bottleneck28', 7: 'bottleneck7'}[hw[0]], by))
-            return
+        ev = self._prof_begin()
         _lib.check(fn(
             _lib.ptr(x), _lib.ptr(w1), _lib.ptr(w2), _lib.ptr(w3), _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(b3), _lib.ptr(m1),
             _lib.ptr(m2), _lib.ptr(m3), _lib.ptr(out), B, hw[0], hw[1], c_io, c_mid, _cints([t[0] for t in taps]),
             _cints([t[1] for t in taps]), 1 if backward else 0, _lib.stream_ptr()))
+        if ev is not None:
+            # 5th element: ALGORITHMIC HBM bytes of the launch -- x in, out, the weight tables once, the 1-bit sign tensors
+            m_ = B * hw[0] * hw[1]
+            by = 2 * m_ * c_io * 2 + (2 * c_io * c_mid + 9 * c_mid * c_mid) * 2 + sum(m_ * c // 8 for c, t in ((c_mid, m1), (c_mid, m2), (c_io, m3)) if t is not None)
+            self._prof_end(ev, 2.0 * B * hw[0] * hw[1] * c_mid * (2 * c_io + 9 * c_mid), {14: 'bottleneck14', 28: 'bottleneck28', 7: 'bottleneck7'}[hw[0]],
+                           by)
 
     def _s2_ok(self, ca, cb, cc, ds, xhw, n=1):
         return (self.fused_bottleneck_s2 and ds is not None and getattr(ds, 's2_wd', None) is not None
                 and self._fits32(n, xhw, ca.cin) and self.lib.rart_bottleneck_s2_fwd_supported(ca.cin, ca.cout, cc.cout, xhw[0], xhw[1]))
 
+    @staticmethod
+    def _s2_flops(ca, cb, cc, ds, B, xhw):
+        pin, pout = xhw[0] * xhw[1], xhw[0] * xhw[1] // 4
+        return 2.0 * B * (pin * ca.cin * ca.cout + pout * (9 * cb.cin * cb.cout + cc.cin * cc.cout + ds.cin * ds.cout))
+
     def _bneck_s2(self, x, ca, cb, cc, ds, m1, m2, m3, out, B, xhw):
         """The stride-2 first block of layer2 / layer3, forward, as one launch (csrc/bottleneck_s2_fused.hip)."""
-        if self.profile is not None:
-            torch = _lib.require_gpu()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            prof, self.profile = self.profile, None
-            try:
-                self._bneck_s2(x, ca, cb, cc, ds, m1, m2, m3, out, B, xhw)
-            finally:
-                self.profile = prof
-            e1.record()
-            pin, pout = xhw[0] * xhw[1], xhw[0] * xhw[1] // 4
-            self.profile.append((2.0 * B * (pin * ca.cin * ca.cout + pout * (9 * cb.cin * cb.cout + cc.cin * cc.cout + ds.cin * ds.cout)),
-                                 e0, e1, 'bottleneck_s2'))
-            return
+        ev = self._prof_begin()
         _lib.check(self.lib.rart_bottleneck_s2_fwd_bf16(
             _lib.ptr(x), _lib.ptr(ca.s2_w1), _lib.ptr(cb.s2_w2), _lib.ptr(cc.s2_w3), _lib.ptr(ds.s2_wd), _lib.ptr(ca.bias),
             _lib.ptr(cb.bias), _lib.ptr(ds.bias_sum), _lib.ptr(m1), _lib.ptr(m2), _lib.ptr(m3), _lib.ptr(out), B, xhw[0], xhw[1],
             ca.cin, ca.cout, cc.cout, _lib.stream_ptr()))
+        if ev is not None:
+            self._prof_end(ev, self._s2_flops(ca, cb, cc, ds, B, xhw), 'bottleneck_s2')
 
     def _bneck_s2_bwd(self, g, ca, cb, cc, ds, m2, m1, m0, dx, B, xhw):
         """Backward-to-input of the stride-2 first block of layer2 / layer3 as one launch (csrc/bottleneck_s2_fused.hip)."""
-        if self.profile is not None:
-            torch = _lib.require_gpu()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            prof, self.profile = self.profile, None
-            try:
-                self._bneck_s2_bwd(g, ca, cb, cc, ds, m2, m1, m0, dx, B, xhw)
-            finally:
-                self.profile = prof
-            e1.record()
-            pin, pout = xhw[0] * xhw[1], xhw[0] * xhw[1] // 4
-            self.profile.append((2.0 * B * (pin * ca.cin * ca.cout + pout * (9 * cb.cin * cb.cout + cc.cin * cc.cout + ds.cin * ds.cout)),
-                                 e0, e1, 'bottleneck_s2_bwd'))
-            return
+        ev = self._prof_begin()
         _lib.check(self.lib.rart_bottleneck_s2_bwd_bf16(
             _lib.ptr(g), _lib.ptr(cc.s2_w3t), _lib.ptr(cb.s2_w2t), _lib.ptr(ca.s2_w1t), _lib.ptr(ds.s2_wdt), _lib.ptr(m2), _lib.ptr(m1),
             _lib.ptr(m0), _lib.ptr(dx), B, xhw[0], xhw[1], ca.cin, ca.cout, cc.cout, _lib.stream_ptr()))
+        if ev is not None:
+            self._prof_end(ev, self._s2_flops(ca, cb, cc, ds, B, xhw), 'bottleneck_s2_bwd')
 
     def _first_ok(self, ca, cb, cc, ds, xhw, n=1):
         return (self._fits32(n, xhw, cc.cout) and self.fused_bottleneck and ds is not None and getattr(ds, 'w_fwd_frag', None) is not None
@@ -780,34 +631,25 @@ class ResNet50Engine:
     def _bneck(self, x, w1, w2, w3, b1, b2, b3, m1, m2, m3, out, B, hw, c_io, c_mid, taps, backward, w4=None, c_in=None):
         """One Bottleneck as a single launch (csrc/bottleneck_fused.hip), forward or backward-to-input; w4: the projection
         shortcut's table for the layer's first block (c_in input channels)."""
-        if self.profile is not None:
-            torch = _lib.require_gpu()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            prof, self.profile = self.profile, None
-            try:
-                self._bneck(x, w1, w2, w3, b1, b2, b3, m1, m2, m3, out, B, hw, c_io, c_mid, taps, backward, w4, c_in)
-            finally:
-                self.profile = prof
-            e1.record()
+        ev = self._prof_begin()
+        if w4 is not None:
+            _lib.check(self.lib.rart_bottleneck_first_bf16(
+                _lib.ptr(x), _lib.ptr(w1), _lib.ptr(w2), _lib.ptr(w3), _lib.ptr(w4), _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(b3),
+                _lib.ptr(m1), _lib.ptr(m2), _lib.ptr(m3), _lib.ptr(out), B, hw[0], hw[1], c_in, c_mid, c_io,
+                _cints([t[0] for t in taps]), _cints([t[1] for t in taps]), 1 if backward else 0, _lib.stream_ptr()))
+        else:
+            _lib.check(self.lib.rart_bottleneck_fused_bf16(
+                _lib.ptr(x), _lib.ptr(w1), _lib.ptr(w2), _lib.ptr(w3), _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(b3), _lib.ptr(m1),
+                _lib.ptr(m2), _lib.ptr(m3), _lib.ptr(out), B, hw[0], hw[1], c_io, c_mid, _cints([t[0] for t in taps]),
+                _cints([t[1] for t in taps]), 1 if backward else 0, _lib.stream_ptr()))
+        if ev is not None:
             k_all = (2 * c_io + 9 * c_mid) if w4 is None else (c_in + 9 * c_mid + c_io + c_in * c_io // c_mid)
             # 5th element: ALGORITHMIC HBM bytes of the launch -- x in (read ONCE: the residual re-read and the halo rows are
             # implementation traffic), out, the weight tables once, the 1-bit sign tensors
             m_, cin_ = B * hw[0] * hw[1], (c_io if w4 is None else c_in)
             by = m_ * (c_io + cin_) * 2 + ((c_io + cin_) * c_mid + 9 * c_mid * c_mid + (0 if w4 is None else c_in * c_io)) * 2 + \
                 sum(m_ * c // 8 for c, t in ((c_mid, m1), (c_mid, m2), (c_io if not backward else cin_, m3)) if t is not None)
-            self.profile.append((2.0 * B * hw[0] * hw[1] * c_mid * k_all, e0, e1, 'bottleneck', by))
-            return
-        if w4 is not None:
-            _lib.check(self.lib.rart_bottleneck_first_bf16(
-                _lib.ptr(x), _lib.ptr(w1), _lib.ptr(w2), _lib.ptr(w3), _lib.ptr(w4), _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(b3),
-                _lib.ptr(m1), _lib.ptr(m2), _lib.ptr(m3), _lib.ptr(out), B, hw[0], hw[1], c_in, c_mid, c_io,
-                _cints([t[0] for t in taps]), _cints([t[1] for t in taps]), 1 if backward else 0, _lib.stream_ptr()))
-            return
-        _lib.check(self.lib.rart_bottleneck_fused_bf16(
-            _lib.ptr(x), _lib.ptr(w1), _lib.ptr(w2), _lib.ptr(w3), _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(b3), _lib.ptr(m1),
-            _lib.ptr(m2), _lib.ptr(m3), _lib.ptr(out), B, hw[0], hw[1], c_io, c_mid, _cints([t[0] for t in taps]),
-            _cints([t[1] for t in taps]), 1 if backward else 0, _lib.stream_ptr()))
+            self._prof_end(ev, 2.0 * B * hw[0] * hw[1] * c_mid * k_all, 'bottleneck', by)
 
     def _conv_fwd(self, c, x, xhw, out, relu, res=None, sign=None, pair=False):
         B = x.shape[1] if pair else x.shape[0]
@@ -872,10 +714,8 @@ class ResNet50Engine:
             _lib.check(lib.rart_engine_prep_input(_lib.ptr(src), 1 if src_is_u8 else 0, _lib.ptr(hi[0]), _lib.ptr(hi[1]),
                                                   B, H, W, meanf, stdf, sp))
             y1 = self._get('y1', (B, h1, w1, 64))
-            lo_off = hi[1].data_ptr() - hi[0].data_ptr()
-            assert lo_off % 2 == 0
             taps = [(r, 0) for r in range(7)] * 2
-            offs = [0] * 7 + [lo_off // 2] * 7
+            offs = [0] * 7 + [lo_off(hi)] * 7
             self._gemm(hi[0], self.stem_w, y1, B, (h1, w1), (H + 8, W + 8), 4, 32, taps, 64, (h1, w1), 64,
                        bias=self.stem.bias, flags=F_RELU, stride=(2, 2), tap_src_off=offs)
             _lib.check(lib.rart_engine_maxpool_keep(_lib.ptr(y1), _lib.ptr(p1), _lib.ptr(parg), _lib.ptr(xs), B, h1, w1, 64, sp))
@@ -944,11 +784,6 @@ class ResNet50Engine:
         return logits, acts
 
     # ------------------------------------------------------------------ reference-precision ("bf16x3") mode
-    @staticmethod
-    def _lo(t):
-        """element offset of the lo plane of a pair tensor [2][...]"""
-        return (t[1].data_ptr() - t[0].data_ptr()) // 2
-
     def _forward_x3(self, src, src_is_u8, mean, std, keep):
         """The forward of `_forward` with every tensor a hi + lo pair of bf16 planes and every contraction the three
         products hi.hi + hi.lo + lo.hi (fp32 accumulate) on the implicit-GEMM kernel; one launch per layer."""
@@ -974,8 +809,8 @@ class ResNet50Engine:
             _lib.check(lib.rart_engine_stem_fwd_fused_pair(_lib.ptr(src), 1 if src_is_u8 else 0, _lib.ptr(self.stem_w_pair[0]),
                                                            _lib.ptr(self.stem_w_pair[1]), _lib.ptr(self.stem.bias), _lib.ptr(p1[0]),
                                                            _lib.ptr(p1[1]), _lib.ptr(parg), _lib.ptr(xs), B, H, W, meanf, stdf, sp))
-            # issued: 3 products x (7 row taps x 32 = 224-deep K) x 64 channels per stem output; bytes: the image once + the pooled pair
-            self._prof_end(ev, 3 * 2.0 * B * h1 * w1 * 224 * 64, 'stem_pair', B * H * W * 3 * (1 if src_is_u8 else 4) + 4.0 * B * h2 * w2 * 64)
+            if ev is not None:   # issued: 3 products x (7 row taps x 32 = 224-deep K) x 64 channels per stem output; bytes: the image once + the pooled pair
+                self._prof_end(ev, 3 * 2.0 * B * h1 * w1 * 224 * 64, 'stem_pair', B * H * W * 3 * (1 if src_is_u8 else 4) + 4.0 * B * h2 * w2 * 64)
         else:
             hi = self._get('in_hi', (2, B, H + 8, W + 8, 4))
             _lib.check(lib.rart_engine_prep_input(_lib.ptr(src), 1 if src_is_u8 else 0, _lib.ptr(hi[0]), _lib.ptr(hi[1]),
@@ -983,7 +818,7 @@ class ResNet50Engine:
             y1 = self._get('x3_y1', (2, B, h1, w1, 64))
             self._gemm(hi, self.stem_w, y1, B, (h1, w1), (H + 8, W + 8), 4, 32, [(r, 0) for r in range(7)], 64, (h1, w1), 64,
                        bias=self.stem.bias, flags=F_RELU, stride=(2, 2), pair=True)
-            _lib.check(lib.rart_engine_maxpool_pair(_lib.ptr(y1), self._lo(y1), _lib.ptr(p1), self._lo(p1), _lib.ptr(parg),
+            _lib.check(lib.rart_engine_maxpool_pair(_lib.ptr(y1), lo_off(y1), _lib.ptr(p1), lo_off(p1), _lib.ptr(parg),
                                                     _lib.ptr(xs), B, h1, w1, 64, sp))
         acts['p1_argmax'] = parg
         x, xhw = p1, (h2, w2)
@@ -1023,7 +858,7 @@ class ResNet50Engine:
             acts['b%d_masks' % bi] = (xs, sa, sb)
             x, xhw, xs = yc, ohw, sc
         pooled = self._get('x3_pooled', (2, B, self.fc_in))
-        _lib.check(lib.rart_engine_avgpool_pair(_lib.ptr(x), self._lo(x), _lib.ptr(pooled), self._lo(pooled), B,
+        _lib.check(lib.rart_engine_avgpool_pair(_lib.ptr(x), lo_off(x), _lib.ptr(pooled), lo_off(pooled), B,
                                                 xhw[0] * xhw[1], self.fc_in, sp))
         logits = torch.empty(B, self.n_classes, dtype=torch.float32, device=self.device)
         self._gemm(pooled, self.fc_w, logits, B, (1, 1), (1, 1), self.fc_in, self.fc_in, [(0, 0)], self.n_classes,
@@ -1039,14 +874,14 @@ class ResNet50Engine:
         lib, sp = self.lib, _lib.stream_ptr()
         B, H, W = acts['in_shape']
         dlp = self._get('x3_dl', (2, B, self.fc_kpad))
-        _lib.check(lib.rart_f32_to_pair_rows(_lib.ptr(dl), _lib.ptr(dlp), self._lo(dlp), B, self.n_classes, self.fc_kpad, sp))
+        _lib.check(lib.rart_f32_to_pair_rows(_lib.ptr(dl), _lib.ptr(dlp), lo_off(dlp), B, self.n_classes, self.fc_kpad, sp))
         dpool = self._get('x3_dpool', (2, B, self.fc_in))
         self._gemm(dlp, self.fc_wd, dpool, B, (1, 1), (1, 1), self.fc_kpad, self.fc_kpad, [(0, 0)], self.fc_in, (1, 1),
                    self.fc_in, pair=True)
         xl, xlhw = acts['last']
         dz = self._get('x3_g_out_%d' % (len(self.blocks) - 1), tuple(xl.shape))
-        _lib.check(lib.rart_engine_avgpool_bwd_pair(_lib.ptr(acts['last_sign']), _lib.ptr(dpool), self._lo(dpool), _lib.ptr(dz),
-                                                    self._lo(dz), B, xlhw[0] * xlhw[1], self.fc_in, sp))
+        _lib.check(lib.rart_engine_avgpool_bwd_pair(_lib.ptr(acts['last_sign']), _lib.ptr(dpool), lo_off(dpool), _lib.ptr(dz),
+                                                    lo_off(dz), B, xlhw[0] * xlhw[1], self.fc_in, sp))
         pre_b = False            # this block's conv3^T was already computed by the launch of the block above
         for bi in range(len(self.blocks) - 1, -1, -1):
             ca, cb, cc, ds = self.blocks[bi]
@@ -1088,14 +923,15 @@ class ResNet50Engine:
             _lib.check(lib.rart_engine_stem_bwd_fused_pair(_lib.ptr(dz[0]), _lib.ptr(dz[1]), _lib.ptr(acts['p1_argmax']),
                                                            _lib.ptr(self.stem_wt_pair[0]), _lib.ptr(self.stem_wt_pair[1]),
                                                            _lib.ptr(grad), B, H, W, stdf, sp))
-            # issued: M = stem-output positions, K = 16 taps x 64 channels, N = 16 (4 pixel parities x 3 colours, padded); bytes: pooled
-            # gradient pair + argmax codes + the fp32 image gradient
-            self._prof_end(ev, 3 * 2.0 * B * (H // 2) * (W // 2) * 16 * 64 * 16, 'stem_pair', 4.0 * B * (H // 4) * (W // 4) * 64 * 1.25 + 4.0 * B * H * W * 3)
+            if ev is not None:
+                # issued: M = stem-output positions, K = 16 taps x 64 channels, N = 16 (4 pixel parities x 3 colours, padded); bytes: pooled
+                # gradient pair + argmax codes + the fp32 image gradient
+                self._prof_end(ev, 3 * 2.0 * B * (H // 2) * (W // 2) * 16 * 64 * 16, 'stem_pair', 4.0 * B * (H // 4) * (W // 4) * 64 * 1.25 + 4.0 * B * H * W * 3)
             return grad
         h1, w1 = H // 2, W // 2
         dz1 = self._get('x3_g_y1', (2, B, h1, w1, 64))
-        _lib.check(lib.rart_engine_maxpool_bwd_pair(_lib.ptr(acts['p1_argmax']), _lib.ptr(dz), self._lo(dz), _lib.ptr(dz1),
-                                                    self._lo(dz1), B, h1, w1, 64, sp))
+        _lib.check(lib.rart_engine_maxpool_bwd_pair(_lib.ptr(acts['p1_argmax']), _lib.ptr(dz), lo_off(dz), _lib.ptr(dz1),
+                                                    lo_off(dz1), B, h1, w1, 64, sp))
         pc = self.stem_patch_cols
         patches = self._get('x3_patches', (B, h1, w1, pc), torch.float32)
         self._gemm(dz1, self.stem_wd, patches, B, (h1, w1), (h1, w1), 64, 64, [(0, 0)], pc, (h1, w1), pc, flags=F_OUT_F32,

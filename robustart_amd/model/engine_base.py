@@ -1,0 +1,338 @@
+"""The host launch layer the HIP engines share: the flag tables of the two GEMM descriptors, one builder per descriptor, the weight-table
+helpers, the split-K heuristics of the weight gradient, and `EngineBase` (device, buffers, profiling) that every engine inherits.
+
+The builders take tensors or None and only read `data_ptr()`, so they run on CPU tensors as well.  Every engine keeps the adapter that
+encodes its own convention: ResNet-50's conv form and [hi | lo | hi] weight tables (engine.py), the row form of ViT-B/16 and ConvNeXt
+(`RowEngine` below), ConvNeXt's precision dispatch (convnext_engine.py)."""
+import ctypes
+
+from .. import _lib
+
+# rart_conv_desc flags (csrc/conv_igemm.hip)
+F_RELU, F_OUT_F32, F_GELU, F_GELU_BWD = 1, 2, 4, 8
+F_MASK_BITS = 16         # `mask` is a 1-bit tensor
+F_PAIR = 32              # split-bf16 operands as 3 x the taps, lo planes of dst / res at dst_pair_off / res_pair_off
+F_GELU_KEEP = 64         # dst = gelu(u), `mask` receives the pre-activation u (256 x 256 GEMM only)
+F_MASK_RES = 128         # the 1-bit mask applies to the residual
+# rart_gemm_pair_desc flags (csrc/rart_gemm_pair_dev.h); the epilogue flags have the values of their rart_conv_desc namesakes
+GP_RELU, GP_OUT_F32, GP_GELU, GP_GELU_BWD, GP_W_INTERLEAVED, GP_GELU_KEEP = 1, 2, 4, 8, 16, 64
+
+PRECISIONS = {'bf16': 'bf16', 'bf16x3': 'bf16x3', 'fp32x': 'bf16x3'}
+
+ROW_TAPS = [((0, 0),) * n for n in range(33)]      # ROW_TAPS[n]: n taps at the row itself (row form, per-tap source offsets)
+
+
+def check_precision(precision):
+    """-> the engine's name of `precision` ('fp32x' is 'bf16x3')"""
+    if precision not in PRECISIONS:
+        raise ValueError('precision must be one of %s' % sorted(PRECISIONS))
+    return PRECISIONS[precision]
+
+
+def _addr(t):
+    return None if t is None else t.data_ptr()
+
+
+def cints(vals):
+    return (ctypes.c_int * max(len(vals), 1))(*vals)
+
+
+def lo_off(t):
+    """element offset of the lo plane of a pair tensor [2][...]"""
+    return (t[1].data_ptr() - t[0].data_ptr()) // 2
+
+
+# ---------------------------------------------------------------------- weight tables
+def rows_mult(n_cols):
+    return 128 if n_cols > 64 else 64
+
+
+def pad_rows(w, mult):
+    """[rows][K] -> contiguous [rows rounded up to mult][K], zero rows appended"""
+    import torch
+    r = (w.shape[0] + mult - 1) // mult * mult
+    if r != w.shape[0]:
+        w = torch.cat([w, torch.zeros(r - w.shape[0], w.shape[1], dtype=w.dtype, device=w.device)], 0)
+    return w.contiguous()
+
+
+def pad_k(w, k):
+    """[rows][K] -> [rows][max(K, k)], zero columns appended"""
+    import torch
+    if k is not None and k > w.shape[1]:
+        w = torch.cat([w, torch.zeros(w.shape[0], k - w.shape[1], dtype=w.dtype, device=w.device)], 1)
+    return w
+
+
+def split_hi_lo(t):
+    """fp32 -> (hi, lo) bf16 with hi = bf16(t), lo = bf16(t - hi): the split-bf16 representation"""
+    import torch
+    hi = t.to(torch.bfloat16)
+    return hi, (t - hi.float()).to(torch.bfloat16)
+
+
+def pair(t):
+    """fp32 tensor -> [2][...] bf16 planes (hi, lo)"""
+    import torch
+    return torch.stack(split_hi_lo(t)).contiguous()
+
+
+def interleave_k32(hi, lo):
+    """two bf16 planes [rows][K] -> [rows][2K]: per row and 32-deep K step the hi slice then the lo slice (GP_W_INTERLEAVED)"""
+    import torch
+    rows, k = hi.shape
+    return torch.stack([hi.reshape(rows, k // 32, 32), lo.reshape(rows, k // 32, 32)], 2).reshape(rows, 2 * k).contiguous()
+
+
+# ---------------------------------------------------------------------- descriptors
+def conv_desc(src, wgt, dst, batch, grid, src_hw, src_pix, k_per_tap, taps, n_cols, dst_hw, dst_pix, bias=None, res=None, mask=None,
+              sign_out=None, stats_out=None, flags=0, stride=(1, 1), dst_stride=(1, 1), dst_org=(0, 0), tap_src_off=None, batched=None,
+              dst_pair_off=0, res_pair_off=0):
+    """rart_conv_desc of one implicit GEMM: output pixel (b, y, x) of the batch x grid reads source pixel (y * sy + dy, x * sx + dx)
+    (+ tap_src_off[t] elements) per tap (dy, dx) of `taps`, k_per_tap channels each, and writes n_cols channels at destination pixel
+    (y * dst_sy + oy, x * dst_sx + ox).  batched = dict(n, inner, src=(outer, inner), wgt=(outer, inner), dst=(outer, inner)
+    [, wgt_row_stride]): element strides of problem z = (z / inner, z % inner)."""
+    d = _lib.ConvDesc()
+    d.src, d.wgt, d.dst = src.data_ptr(), wgt.data_ptr(), dst.data_ptr()
+    d.bias, d.res, d.mask, d.sign_out, d.bn_stats_out = _addr(bias), _addr(res), _addr(mask), _addr(sign_out), _addr(stats_out)
+    d.batch, d.grid_h, d.grid_w = batch, grid[0], grid[1]
+    d.src_h, d.src_w, d.src_pix_stride = src_hw[0], src_hw[1], src_pix
+    d.k_per_tap, d.n_taps = k_per_tap, len(taps)
+    d.sy, d.sx = stride
+    for i, (dy, dx) in enumerate(taps):
+        d.tap_dy[i], d.tap_dx[i] = dy, dx
+        if tap_src_off:
+            d.tap_src_off[i] = tap_src_off[i]
+    d.n_cols = n_cols
+    d.dst_h, d.dst_w = dst_hw
+    d.dst_sy, d.dst_sx = dst_stride
+    d.dst_oy, d.dst_ox = dst_org
+    d.dst_pix_stride = dst_pix
+    d.flags = flags
+    d.dst_pair_off, d.res_pair_off = dst_pair_off, res_pair_off
+    if batched:
+        d.n_batched, d.z_inner = batched['n'], batched['inner']
+        d.src_z_outer, d.src_z_inner = batched['src']
+        d.wgt_z_outer, d.wgt_z_inner = batched['wgt']
+        d.dst_z_outer, d.dst_z_inner = batched['dst']
+        d.wgt_row_stride = batched.get('wgt_row_stride', 0)
+    return d
+
+
+def gemm_pair_desc(a, w, dst, N, lda, ldw, ldc, w_rows, M=0, K=0, bias=None, res=None, aux=None, mask_bits=None, sign_out=None, flags=0,
+                   a_off=0, w_off=0, dst_off=0, w_lo_off=None, w_il=None, rows_per_image=0, src_rows_per_image=0, src_row_off=0,
+                   dst_rows_per_image=0, dst_row_off=0, batched=None, batch=0, grid=None, src_hw=(0, 0), stride=(1, 1), k_per_tap=0,
+                   taps=(), dst_hw=(0, 0), dst_stride=(1, 1), dst_org=(0, 0), tile=(0, 0)):
+    """rart_gemm_pair_desc: (a_hi + a_lo)[M][K] . (w_hi + w_lo)[N][K]^T -> dst, three MFMA products per contraction.
+    a / res / aux / dst: pair tensors [2][...] (dst with GP_OUT_F32: a plain fp32 tensor); *_off: element offsets inside a plane.
+    w: a pair tensor, or with w_lo_off one table that holds the lo plane w_lo_off elements after the hi plane; w_il: the
+    interleaved copy of w's planes (`interleave_k32`), which replaces them.  batched = dict(n, inner, a=(outer, inner),
+    w=(outer, inner), c=(outer, inner)).  Row form unless `grid` is given; conv form: output pixel (b, y, x) of batch x grid reads
+    source pixel (y * sy + dy, x * sx + dx) per tap (dy, dx), k_per_tap channels each (M and K follow from the geometry)."""
+    d = _lib.GemmPairDesc()
+    if grid is not None:
+        M, K = batch * grid[0] * grid[1], k_per_tap * len(taps)
+    d.a_hi, d.a_lo = a[0].data_ptr() + 2 * a_off, a[1].data_ptr() + 2 * a_off
+    if w_il is not None:
+        d.w_hi, d.w_lo, ldw = w_il.data_ptr(), w_il.data_ptr() + 64, 2 * K
+        flags |= GP_W_INTERLEAVED
+    elif w_lo_off is not None:
+        w_hi = w.data_ptr() + 2 * w_off
+        d.w_hi, d.w_lo = w_hi, w_hi + 2 * w_lo_off
+    else:
+        d.w_hi, d.w_lo = w[0].data_ptr() + 2 * w_off, w[1].data_ptr() + 2 * w_off
+    d.bias = _addr(bias)
+    if res is not None:
+        d.res_hi, d.res_lo = res[0].data_ptr() + 2 * dst_off, res[1].data_ptr() + 2 * dst_off
+    if flags & GP_OUT_F32:
+        d.dst_hi = dst.data_ptr() + 4 * dst_off
+    else:
+        d.dst_hi, d.dst_lo = dst[0].data_ptr() + 2 * dst_off, dst[1].data_ptr() + 2 * dst_off
+    if aux is not None:
+        d.aux_hi, d.aux_lo = aux[0].data_ptr() + 2 * dst_off, aux[1].data_ptr() + 2 * dst_off
+    d.M, d.N, d.K, d.lda, d.ldw, d.ldc, d.w_rows = M, N, K, lda, ldw, ldc, w_rows
+    d.rows_per_image, d.src_rows_per_image, d.src_row_off = rows_per_image, src_rows_per_image, src_row_off
+    d.dst_rows_per_image, d.dst_row_off = dst_rows_per_image, dst_row_off
+    d.flags = flags
+    if batched:
+        d.n_batched, d.z_inner = batched['n'], batched['inner']
+        d.a_z_outer, d.a_z_inner = batched['a']
+        d.w_z_outer, d.w_z_inner = batched['w']
+        d.c_z_outer, d.c_z_inner = batched['c']
+    if grid is not None:
+        d.conv, d.batch, d.grid_h, d.grid_w = 1, batch, grid[0], grid[1]
+        d.src_h, d.src_w, d.sy, d.sx = src_hw[0], src_hw[1], stride[0], stride[1]
+        d.k_per_tap, d.n_taps = k_per_tap, len(taps)
+        for i, (dy, dx) in enumerate(taps):
+            d.tap_dy[i], d.tap_dx[i] = dy, dx
+        d.dst_h, d.dst_w = dst_hw
+        d.dst_sy, d.dst_sx = dst_stride
+        d.dst_oy, d.dst_ox = dst_org
+    d.mask_bits, d.sign_out = _addr(mask_bits), _addr(sign_out)
+    d.tile_m, d.tile_n = tile
+    return d
+
+
+# ---------------------------------------------------------------------- split-K weight gradients
+def wgrad_split_direct(M, x_c, n_taps, n_cols, target_wgs, min_chunk):
+    """-> (splits, chunk) of rart_wgrad_direct_bf16 over M output positions: about target_wgs workgroups in all, chunks of at least
+    min_chunk positions"""
+    tmr = 128                # the library's tile height (csrc/wgrad_direct.hip: 256-row tiles measured slower)
+    if x_c == 4:             # the ResNet stem's padded hi plane: 32 taps x 4 channels per tile
+        row_tiles = (n_taps + 31) // 32
+    else:
+        row_tiles = n_taps * (x_c // tmr) if x_c >= tmr else (n_taps + tmr // x_c - 1) // (tmr // x_c)
+    tiles = row_tiles * (n_cols // (128 if n_cols % 128 == 0 else 64))
+    splits = max(1, min(target_wgs // max(tiles, 1), M // min_chunk if M >= 2 * min_chunk else 1, 1024))
+    chunk = ((M + splits - 1) // splits + 31) // 32 * 32
+    return (M + chunk - 1) // chunk, chunk
+
+
+def wgrad_split_transposed(M, kp, n_pad):
+    """-> (splits, chunk, n_rows) of the split-K weight-gradient GEMM over transposed copies ([splits][rows][chunk] slabs): kp rows
+    of the transposed im2col, n_pad gradient columns padded to the GEMM's n_rows"""
+    bn_tile = 128 if n_pad > 64 else 64
+    tiles = ((kp + 127) // 128) * ((n_pad + bn_tile - 1) // bn_tile)
+    splits = max(1, min(1024 // max(tiles, 1), M // 512 if M >= 1024 else 1, 256))
+    chunk = ((M + splits - 1) // splits + 63) // 64 * 64
+    return splits, chunk, (n_pad + bn_tile - 1) // bn_tile * bn_tile
+
+
+# ---------------------------------------------------------------------- engines
+class EngineBase:
+    """Device, library, precision, name-keyed buffers and launch profiling of a HIP engine."""
+    # K splits of rart_wgrad_direct_bf16: ~1 024 workgroups in all (measured at B = 256 on ResNet-50: 512 -> 58.1, 1 024 -> 55.1-55.8,
+    # 2 048 -> 56.3, 4 096 -> 57.5 ms per adv_train step: more splits fill the CUs, every split writes and re-reads an fp32 copy of the
+    # weight tensor); up to 1 024 splits of >= 256 positions each (a cap of 256 left layer1's one- and two-tile 1x1 layers at 256-512
+    # workgroups: +0.6 ms)
+    wgrad_target_wgs, wgrad_min_chunk = 1024, 256
+
+    def __init__(self, device='cuda', precision='bf16'):
+        torch = _lib.require_gpu()
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        self.precision = check_precision(precision)
+        self.profile = None      # set to a list to record (flops, start_event, end_event, kind[, algorithmic bytes]) per launch
+        self._buf = {}
+        self._w_il = {}          # interleaved copies of pair weight tables (GP_W_INTERLEAVED), keyed by the table's address
+
+    def _get(self, name, shape, dtype=None, zero=False):
+        torch = _lib.require_gpu()
+        dtype = dtype or torch.bfloat16
+        t = self._buf.get(name)
+        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
+            t = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=self.device)
+            self._buf[name] = t
+        return t
+
+    def _scratch(self, name, nbytes):
+        torch = _lib.require_gpu()
+        t = self._buf.get(name)
+        if t is None or t.numel() < nbytes:
+            t = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+            self._buf[name] = t
+        return t
+
+    def _prof_begin(self):
+        if self.profile is None:
+            return None
+        e0 = _lib.require_gpu().cuda.Event(enable_timing=True)
+        e0.record()          # torch's current stream == the stream the kernel is enqueued on (stream_ptr())
+        return e0
+
+    def _prof_end(self, e0, flops, kind, nbytes=None):
+        e1 = _lib.require_gpu().cuda.Event(enable_timing=True)
+        e1.record()
+        self.profile.append((flops, e0, e1, kind) if nbytes is None else (flops, e0, e1, kind, nbytes))
+
+    def _launch_conv(self, d):
+        """rart_conv_igemm_bf16 on descriptor d; profiled as 'igemm' (FLOPs of the listed taps)"""
+        ev = self._prof_begin()
+        _lib.check(self.lib.rart_conv_igemm_bf16(ctypes.byref(d), _lib.stream_ptr()))
+        if ev is not None:
+            self._prof_end(ev, 2.0 * d.batch * d.grid_h * d.grid_w * d.k_per_tap * d.n_taps * d.n_cols * max(d.n_batched, 1), 'igemm')
+
+    def _launch_pair(self, d, nbytes=None):
+        """rart_gemm_pair_bf16 on descriptor d; profiled as 'gemm_pair' (MFMA FLOPs issued: three products)"""
+        ev = self._prof_begin()
+        _lib.check(self.lib.rart_gemm_pair_bf16(ctypes.byref(d), _lib.stream_ptr()))
+        if ev is not None:
+            self._prof_end(ev, 3 * 2.0 * max(d.n_batched, 1) * d.M * d.N * d.K, 'gemm_pair', nbytes)
+
+    def _wgrad_direct(self, x, dz, B, x_hw, x_c, grid_hw, n_out, n_pad_cols, taps, stride, grad, c_valid=None):
+        """grad[n_out][c][taps] = sum over positions m of dz[m][n] * x[pixel(m) + tap][c] straight from the NHWC activations
+        (x: bf16 [B][ih][iw][x_c], dz: bf16 [B][gh][gw][n_pad_cols], columns >= n_out zero; c_valid: channels of x kept) on
+        rart_wgrad_direct_bf16 + rart_wgrad_reduce_f32"""
+        lib, sp = self.lib, _lib.stream_ptr()
+        splits, chunk = wgrad_split_direct(B * grid_hw[0] * grid_hw[1], x_c, len(taps), n_pad_cols, self.wgrad_target_wgs,
+                                           self.wgrad_min_chunk)
+        part = self._scratch('wg_part', splits * len(taps) * x_c * n_pad_cols * 4)
+        _lib.check(lib.rart_wgrad_direct_bf16(_lib.ptr(x), _lib.ptr(dz), _lib.ptr(part), B, x_hw[0], x_hw[1], x_c, grid_hw[0], grid_hw[1],
+                                              n_pad_cols, stride, stride, len(taps), cints([t[0] for t in taps]), cints([t[1] for t in taps]),
+                                              splits, chunk, n_pad_cols, sp))
+        _lib.check(lib.rart_wgrad_reduce_f32(_lib.ptr(part), splits, len(taps), c_valid if c_valid is not None else x_c, x_c, n_out,
+                                             n_pad_cols, _lib.ptr(grad), 0, sp))
+
+    def _colsum(self, x, ld, rows, cols, out):
+        lib = self.lib
+        need = lib.rart_colsum_workspace_bytes(rows, cols)
+        ws = self._scratch('cs_ws', need)
+        _lib.check(lib.rart_colsum_bf16(_lib.ptr(x), ld, rows, cols, _lib.ptr(out), 0, _lib.ptr(ws), need, _lib.stream_ptr()))
+
+    def logits(self, x01, mean, std):
+        """x01: fp32 NCHW in [0,1]; mean/std: 3-tuples applied inside the input kernel."""
+        return self._forward(x01.detach().float().contiguous(), False, mean, std)
+
+    def logits_from_u8(self, batch_u8, mean, std):
+        """batch_u8: uint8 NHWC (the corruption kernels' output) -> logits, normalisation fused."""
+        return self._forward(batch_u8, True, mean, std)
+
+
+class RowEngine(EngineBase):
+    """The row form of ViT-B/16 and ConvNeXt: activations are dense [rows][features] matrices (tokens, NHWC pixels)."""
+
+    def _gemm(self, src, wgt, dst, rows, k, n_cols, src_ld, dst_ld, bias=None, res=None, flags=0, n_taps=1,
+              tap_src_off=None, rows_per_image=None, dst_rows_per_image=None, dst_row_off=0, batched=None,
+              src_rows_per_image=None, mask=None):
+        """rows x k (x n_taps) times wgt^T -> dst on rart_conv_igemm_bf16.  rows_per_image/dst_rows_per_image/dst_row_off place the
+        output rows of image b at b*dst_rows_per_image + dst_row_off (class-token slot).  batched: as `conv_desc`'s."""
+        rpi = rows_per_image or rows
+        self._launch_conv(conv_desc(src, wgt, dst, rows // rpi, (rpi, 1), (src_rows_per_image or rpi, 1), src_ld, k, ROW_TAPS[n_taps],
+                                    n_cols, (dst_rows_per_image or rpi, 1), dst_ld, bias=bias, res=res, mask=mask, flags=flags,
+                                    dst_org=(dst_row_off, 0), tap_src_off=tap_src_off, batched=batched))
+
+    def _gemm_pair(self, a, w, dst, M, N, K, lda, ldc, ldw=None, bias=None, res=None, flags=0, aux=None, w_rows=None,
+                   rows_per_image=0, src_rows_per_image=0, src_row_off=0, dst_rows_per_image=0, dst_row_off=0, batched=None,
+                   a_off=0, w_off=0, dst_off=0):
+        """(a_hi + a_lo)[M][K] . (w_hi + w_lo)[N][K]^T -> dst on rart_gemm_pair_bf16 (see `gemm_pair_desc`); w: pair planes
+        [2][rows][K], replaced by their interleaved copy in `_w_il` when there is one."""
+        il = self._w_il.get(w.data_ptr()) if (w_off == 0 and ldw is None and not batched) else None
+        self._launch_pair(gemm_pair_desc(a, w, dst, N, lda, ldw or K, ldc, w_rows if w_rows is not None else w.shape[-2], M=M, K=K,
+                                         bias=bias, res=res, aux=aux, flags=flags, a_off=a_off, w_off=w_off, dst_off=dst_off,
+                                         w_il=il if il is not None and il.shape[1] == 2 * K else None, rows_per_image=rows_per_image,
+                                         src_rows_per_image=src_rows_per_image, src_row_off=src_row_off,
+                                         dst_rows_per_image=dst_rows_per_image, dst_row_off=dst_row_off, batched=batched))
+
+    def _wgrad(self, dz, n_out, n_pad, x, c_in, grad, rows, dz_images=None):
+        """grad[n_out][c_in] = dz^T . x (dz: bf16 [rows][n_pad] dense, columns >= n_out zero; x: bf16 [rows][c_in] dense) as a split-K
+        GEMM over transposed copies.  dz_images = (B, rows_per_image_in_memory, rows_used): dz rows are the first `rows_used` of every
+        image block."""
+        lib, sp = self.lib, _lib.stream_ptr()
+        splits, chunk, n_rows = wgrad_split_transposed(rows, c_in, n_pad)
+        m_pad = chunk * splits
+        dzt = self._scratch('wg_dzT', n_rows * m_pad * 2)
+        colt = self._scratch('wg_colT', c_in * m_pad * 2)
+        zero = cints([0])
+        if n_rows > n_pad:
+            dzt[:n_rows * m_pad * 2].zero_()
+        b, sh, gh = dz_images if dz_images is not None else (1, rows, rows)
+        _lib.check(lib.rart_transpose_gather_bf16(_lib.ptr(dz), _lib.ptr(dzt), b, sh, 1, n_pad, gh, 1, 1, 1, 1, zero, zero, m_pad,
+                                                  chunk, n_rows, sp))
+        _lib.check(lib.rart_transpose_gather_bf16(_lib.ptr(x), _lib.ptr(colt), 1, rows, 1, c_in, rows, 1, 1, 1, 1, zero, zero,
+                                                  m_pad, chunk, c_in, sp))
+        ld_n = (n_pad + 7) // 8 * 8
+        part = self._scratch('wg_part', splits * c_in * ld_n * 4)
+        self._gemm(colt, dzt, part, c_in, chunk, ld_n, chunk, ld_n, flags=F_OUT_F32,
+                   batched=dict(n=splits, inner=splits, src=(0, c_in * chunk), wgt=(0, n_rows * chunk), dst=(0, c_in * ld_n),
+                                wgt_row_stride=chunk))
+        _lib.check(lib.rart_wgrad_reduce_f32(_lib.ptr(part), splits, 1, c_in, c_in, n_out, ld_n, _lib.ptr(grad), 0, sp))

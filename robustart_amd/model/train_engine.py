@@ -20,11 +20,8 @@ import ctypes
 import os as _os
 
 from .. import _lib
-from .engine import F_OUT_F32, _rows_mult
-
-
-def _ints(vals):
-    return (ctypes.c_int * max(len(vals), 1))(*vals)
+from .engine_base import (F_MASK_BITS, F_MASK_RES, F_OUT_F32, EngineBase, cints, conv_desc, lo_off, rows_mult,
+                          wgrad_split_transposed)
 
 
 class _TConv:
@@ -37,9 +34,9 @@ class _TConv:
         self.fwd_taps = [(r - self.pad, s - self.pad) for r in range(self.r) for s in range(self.s)]
         self.all_rs = [(r, s) for r in range(self.r) for s in range(self.s)]
         bf = torch.bfloat16
-        self.w_fwd = torch.zeros((self.cout + _rows_mult(self.cout) - 1) // _rows_mult(self.cout) * _rows_mult(self.cout),
+        self.w_fwd = torch.zeros((self.cout + rows_mult(self.cout) - 1) // rows_mult(self.cout) * rows_mult(self.cout),
                                  self.r * self.s * self.cin, dtype=bf, device=device)
-        rm = _rows_mult(self.cin)
+        rm = rows_mult(self.cin)
         rows_b = (self.cin + rm - 1) // rm * rm
         self.bwd = []        # (parity or None, taps [(dy,dx)], rs list, table)
         if self.stride == 1:
@@ -63,22 +60,20 @@ class _TConv:
         wf = w.detach().float() if str(w.dtype) != 'torch.float32' else w.detach()
         rs = self.all_rs
         _lib.check(lib.rart_pack_conv_weight_bf16(wf.data_ptr(), None, self.w_fwd.data_ptr(), self.cout, self.cin, self.r, self.s,
-                                                  len(rs), _ints([a for a, _ in rs]), _ints([b for _, b in rs]), 0,
+                                                  len(rs), cints([a for a, _ in rs]), cints([b for _, b in rs]), 0,
                                                   self.w_fwd.shape[0], sp))
         for parity, taps, prs, tab in self.bwd:
             if tab is None:
                 continue
             _lib.check(lib.rart_pack_conv_weight_bf16(wf.data_ptr(), None, tab.data_ptr(), self.cout, self.cin, self.r, self.s,
-                                                      len(prs), _ints([a for a, _ in prs]), _ints([b for _, b in prs]), 1,
+                                                      len(prs), cints([a for a, _ in prs]), cints([b for _, b in prs]), 1,
                                                       tab.shape[0], sp))
 
 
-class ResNet50TrainEngine:
+class ResNet50TrainEngine(EngineBase):
     def __init__(self, model, device='cuda', on_grad_ready=None, bn_momentum=None):
-        torch = _lib.require_gpu()
-        self.torch = torch
-        self.lib = _lib.load()
-        self.device = torch.device(device)
+        super().__init__(device)
+        torch = self.torch = _lib.require_gpu()
         self.model = model
         self.on_grad_ready = on_grad_ready or (lambda p: None)
         m, dev = model, self.device
@@ -94,12 +89,7 @@ class ResNet50TrainEngine:
         self.fc_kpad = (self.n_classes + 127) // 128 * 128
         self.fc_w = torch.zeros(self.fc_kpad, self.fc_in, dtype=torch.bfloat16, device=dev)      # [1024][2048]
         self.fc_wd = torch.zeros(self.fc_in, self.fc_kpad, dtype=torch.bfloat16, device=dev)     # [2048][1024]
-        self._buf = {}
         _fl = dict(kv.split('=', 1) for kv in _os.environ.get('RART_TRAIN_FLAGS', '').split(',') if '=' in kv)   # A/B switches for profiling
-        # K splits of a weight-gradient launch: ~1 024 workgroups in all (measured at B = 256: 512 -> 58.1, 1 024 -> 55.1-55.8, 2 048 -> 56.3,
-        # 4 096 -> 57.5 ms per adv_train step: more splits fill the CUs, every split writes and re-reads an fp32 copy of the weight tensor);
-        # up to 1 024 splits of >= 256 positions each (a cap of 256 left layer1's one- and two-tile 1x1 layers at 256-512 workgroups: +0.6 ms)
-        self.wgrad_target_wgs, self.wgrad_min_chunk = 1024, 256
         self._nbt_pending = None
         self.masked_skip = _fl.get('skip', '1') == '1'        # False: the BatchNorm backward writes the masked skip gradient as a tensor (cross-check)
         self.conv_bn_stats = _fl.get('stats', '1') == '1'      # False: every BatchNorm takes its own statistics pass over the conv output (rounds 1-3; cross-check)
@@ -142,7 +132,7 @@ class ResNet50TrainEngine:
         wrow = wrow.reshape(64, 224).to(torch.bfloat16)
         self.stem_w[:, :224] = wrow
         self.stem_w[:, 224:] = wrow
-        one = _ints([0])
+        one = cints([0])
         w = self.model.fc.weight.detach()
         _lib.check(self.lib.rart_pack_conv_weight_bf16(w.data_ptr(), None, self.fc_w.data_ptr(), self.n_classes, self.fc_in, 1, 1,
                                                        1, one, one, 0, self.fc_kpad, sp))
@@ -151,51 +141,15 @@ class ResNet50TrainEngine:
 
     # ------------------------------------------------------------------ helpers
     def _get(self, name, shape, dtype=None, zero=False):
+        """keyed by (name, shape, dtype), not by name: one gradient buffer name serves stages of different shapes"""
         torch = self.torch
         dtype = dtype or torch.bfloat16
-        key = (name, tuple(shape), dtype)      # gradient buffers are reused across stages with different shapes
+        key = (name, tuple(shape), dtype)
         t = self._buf.get(key)
         if t is None:
             t = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=self.device)
             self._buf[key] = t
         return t
-
-    def _scratch(self, name, nbytes):
-        t = self._buf.get(name)
-        if t is None or t.numel() < nbytes:
-            t = self.torch.empty(int(nbytes), dtype=self.torch.uint8, device=self.device)
-            self._buf[name] = t
-        return t
-
-    def _gemm(self, src, wgt, dst, batch, grid, src_hw, src_pix, k_per_tap, taps, n_cols, dst_hw, dst_pix, res=None,
-              flags=0, stride=(1, 1), dst_stride=(1, 1), dst_off=(0, 0), tap_src_off=None, bias=None, batched=None, stats_out=None,
-              mask_bits=None):
-        d = _lib.ConvDesc()
-        d.bn_stats_out = stats_out.data_ptr() if stats_out is not None else None
-        d.src, d.wgt, d.dst = src.data_ptr(), wgt.data_ptr(), dst.data_ptr()
-        d.bias = bias.data_ptr() if bias is not None else None
-        d.res = res.data_ptr() if res is not None else None
-        d.mask = mask_bits.data_ptr() if mask_bits is not None else None
-        d.batch, d.grid_h, d.grid_w = batch, grid[0], grid[1]
-        d.src_h, d.src_w, d.src_pix_stride = src_hw[0], src_hw[1], src_pix
-        d.k_per_tap, d.n_taps = k_per_tap, len(taps)
-        d.sy, d.sx = stride
-        for i, (dy, dx) in enumerate(taps):
-            d.tap_dy[i], d.tap_dx[i] = dy, dx
-            d.tap_src_off[i] = tap_src_off[i] if tap_src_off is not None else 0
-        d.n_cols = n_cols
-        d.dst_h, d.dst_w = dst_hw
-        d.dst_sy, d.dst_sx = dst_stride
-        d.dst_oy, d.dst_ox = dst_off
-        d.dst_pix_stride = dst_pix
-        d.flags = flags
-        if batched is not None:
-            d.n_batched, d.z_inner = batched['n'], batched['n']
-            d.src_z_outer, d.src_z_inner = 0, batched['src']
-            d.wgt_z_outer, d.wgt_z_inner = 0, batched['wgt']
-            d.dst_z_outer, d.dst_z_inner = 0, batched['dst']
-            d.wgt_row_stride = batched['wgt_row_stride']
-        _lib.check(self.lib.rart_conv_igemm_bf16(ctypes.byref(d), _lib.stream_ptr()))
 
     def _conv_fwd(self, c, x, xhw, out, stats_name='bn_stats'):
         """-> (partial statistics buffer, row tiles) of the output for the BatchNorm that follows (the igemm's epilogue sums the
@@ -206,8 +160,8 @@ class ResNet50TrainEngine:
         if self.conv_bn_stats:
             tiles = (B * oh * ow + 127) // 128
             stats = (self._scratch(stats_name, tiles * 2 * c.cout * 4), tiles)
-        self._gemm(x, c.w_fwd, out, B, (oh, ow), xhw, c.cin, c.cin, c.fwd_taps, c.cout, (oh, ow), c.cout,
-                   stride=(c.stride, c.stride), stats_out=stats[0] if stats else None)
+        self._launch_conv(conv_desc(x, c.w_fwd, out, B, (oh, ow), xhw, c.cin, c.cin, c.fwd_taps, c.cout, (oh, ow), c.cout,
+                                    stride=(c.stride, c.stride), stats_out=stats[0] if stats else None))
         return stats
 
     def _conv_dgrad(self, c, dz, dz_hw, dx, dx_hw, res=None, res_mask_bits=None):
@@ -216,14 +170,14 @@ class ResNet50TrainEngine:
         B = dz.shape[0]
         for parity, taps, rs, w in c.bwd:
             if parity is None:
-                self._gemm(dz, w, dx, B, dx_hw, dz_hw, c.cout, c.cout, taps, c.cin, dx_hw, c.cin, res=res, mask_bits=res_mask_bits,
-                           flags=(16 | 128) if res_mask_bits is not None else 0)
+                self._launch_conv(conv_desc(dz, w, dx, B, dx_hw, dz_hw, c.cout, c.cout, taps, c.cin, dx_hw, c.cin, res=res, mask=res_mask_bits,
+                                            flags=(F_MASK_BITS | F_MASK_RES) if res_mask_bits is not None else 0))
             else:
                 ph, pw = parity
                 if not taps:
                     continue
-                self._gemm(dz, w, dx, B, (dx_hw[0] // 2, dx_hw[1] // 2), dz_hw, c.cout, c.cout, taps, c.cin, dx_hw,
-                           c.cin, res=res, dst_stride=(2, 2), dst_off=(ph, pw))
+                self._launch_conv(conv_desc(dz, w, dx, B, (dx_hw[0] // 2, dx_hw[1] // 2), dz_hw, c.cout, c.cout, taps, c.cin, dx_hw,
+                                            c.cin, res=res, dst_stride=(2, 2), dst_org=(ph, pw)))
 
     def _bn_fwd(self, c, z, y, rows, relu, res=None, stats=None):
         lib, bn = self.lib, c.bn
@@ -265,52 +219,31 @@ class ResNet50TrainEngine:
     def _wgrad(self, dz, n_out, n_pad_cols, x, x_hw, x_c, grid_hw, taps, stride, grad, c_valid=None):
         """grad[n_out][c][taps] = sum_m dz[m][n] * x[pixel(m) + tap][c] as a split-K GEMM on the igemm kernel.
         dz: bf16 [B, gh, gw, n_pad_cols] (columns >= n_out are zero); x: bf16 [B, ih, iw, x_c]."""
-        torch, lib, sp = self.torch, self.lib, _lib.stream_ptr()
+        lib, sp = self.lib, _lib.stream_ptr()
         B = dz.shape[0]
         gh, gw = grid_hw
-        M = B * gh * gw
-        kp = len(taps) * x_c                                   # rows of the transposed im2col matrix
         if self.direct_wgrad and (c_valid is None or x_c == 4) and lib.rart_wgrad_direct_supported(x_c, n_pad_cols, len(taps)):
             # straight from the NHWC activations (csrc/wgrad_direct.hip): no transposed copies, no materialised im2col
-            tmr = 128                # the library's tile height (csrc/wgrad_direct.hip: 256-row tiles measured slower)
-            if x_c == 4:             # the stem's padded hi plane: 32 taps x 4 channels per tile
-                row_tiles = (len(taps) + 31) // 32
-            else:
-                row_tiles = len(taps) * (x_c // tmr) if x_c >= tmr else (len(taps) + tmr // x_c - 1) // (tmr // x_c)
-            tiles = row_tiles * (n_pad_cols // (128 if n_pad_cols % 128 == 0 else 64))
-            splits = max(1, min(self.wgrad_target_wgs // max(tiles, 1), M // self.wgrad_min_chunk if M >= 2 * self.wgrad_min_chunk else 1,
-                                1024))
-            chunk = ((M + splits - 1) // splits + 31) // 32 * 32
-            splits = (M + chunk - 1) // chunk
-            part = self._scratch('wg_part', splits * kp * n_pad_cols * 4)
-            _lib.check(lib.rart_wgrad_direct_bf16(x.data_ptr(), dz.data_ptr(), part.data_ptr(), B, x_hw[0], x_hw[1], x_c, gh, gw, n_pad_cols,
-                                                  stride, stride, len(taps), _ints([t[0] for t in taps]), _ints([t[1] for t in taps]),
-                                                  splits, chunk, n_pad_cols, sp))
-            _lib.check(lib.rart_wgrad_reduce_f32(part.data_ptr(), splits, len(taps), c_valid if c_valid is not None else x_c, x_c, n_out,
-                                                 n_pad_cols, grad.data_ptr(), 0, sp))
-            return
-        bn_tile = 128 if n_pad_cols > 64 else 64
-        tiles = ((kp + 127) // 128) * ((n_pad_cols + bn_tile - 1) // bn_tile)
-        splits = max(1, min(1024 // max(tiles, 1), M // 512 if M >= 1024 else 1, 256))
-        chunk = ((M + splits - 1) // splits + 63) // 64 * 64
+            return self._wgrad_direct(x, dz, B, x_hw, x_c, grid_hw, n_out, n_pad_cols, taps, stride, grad, c_valid)
+        kp = len(taps) * x_c                                   # rows of the transposed im2col matrix
+        splits, chunk, n_rows = wgrad_split_transposed(B * gh * gw, kp, n_pad_cols)
         m_pad = chunk * splits
-        n_rows = (n_pad_cols + bn_tile - 1) // bn_tile * bn_tile
         # both operands are stored as one compact slab per K split: [splits][rows][chunk]
         dzt = self._scratch('wg_dzT', n_rows * m_pad * 2)
         colt = self._scratch('wg_colT', kp * m_pad * 2)
-        zero = _ints([0])
+        zero = cints([0])
         if n_rows > n_pad_cols:
             dzt[:n_rows * m_pad * 2].zero_()                     # tile-padding rows of every slab stay zero
         _lib.check(lib.rart_transpose_gather_bf16(dz.data_ptr(), dzt.data_ptr(), B, gh, gw, n_pad_cols, gh, gw, 1, 1, 1,
                                                   zero, zero, m_pad, chunk, n_rows, sp))
         _lib.check(lib.rart_transpose_gather_bf16(x.data_ptr(), colt.data_ptr(), B, x_hw[0], x_hw[1], x_c, gh, gw,
-                                                  stride, stride, len(taps), _ints([t[0] for t in taps]),
-                                                  _ints([t[1] for t in taps]), m_pad, chunk, kp, sp))
+                                                  stride, stride, len(taps), cints([t[0] for t in taps]),
+                                                  cints([t[1] for t in taps]), m_pad, chunk, kp, sp))
         ld_n = (n_pad_cols + 7) // 8 * 8
         part = self._scratch('wg_part', splits * kp * ld_n * 4)
-        self._gemm(colt, dzt, part, 1, (1, kp), (1, kp), chunk, chunk, [(0, 0)], ld_n, (1, kp), ld_n, flags=F_OUT_F32,
-                   batched={'n': splits, 'src': kp * chunk, 'wgt': n_rows * chunk, 'dst': kp * ld_n,
-                            'wgt_row_stride': chunk})
+        self._launch_conv(conv_desc(colt, dzt, part, 1, (1, kp), (1, kp), chunk, chunk, [(0, 0)], ld_n, (1, kp), ld_n, flags=F_OUT_F32,
+                                    batched=dict(n=splits, inner=splits, src=(0, kp * chunk), wgt=(0, n_rows * chunk), dst=(0, kp * ld_n),
+                                                 wgt_row_stride=chunk)))
         cv = c_valid if c_valid is not None else x_c
         _lib.check(lib.rart_wgrad_reduce_f32(part.data_ptr(), splits, len(taps), cv, x_c, n_out, ld_n, grad.data_ptr(), 0,
                                              sp))
@@ -336,13 +269,12 @@ class ResNet50TrainEngine:
         h1, w1 = H // 2, W // 2
         z1 = self._get('z1', (B, h1, w1, 64))
         y1 = self._get('y1', (B, h1, w1, 64))
-        lo_off = (hi[1].data_ptr() - hi[0].data_ptr()) // 2
         st = None
         if self.conv_bn_stats:
             tiles = (B * h1 * w1 + 127) // 128
             st = (self._scratch('bn_stats', tiles * 2 * 64 * 4), tiles)
-        self._gemm(hi[0], self.stem_w, z1, B, (h1, w1), (H + 8, W + 8), 4, 32, [(r, 0) for r in range(7)] * 2, 64, (h1, w1),
-                   64, stride=(2, 2), tap_src_off=[0] * 7 + [lo_off] * 7, stats_out=st[0] if st else None)
+        self._launch_conv(conv_desc(hi[0], self.stem_w, z1, B, (h1, w1), (H + 8, W + 8), 4, 32, [(r, 0) for r in range(7)] * 2, 64,
+                                    (h1, w1), 64, stride=(2, 2), tap_src_off=[0] * 7 + [lo_off(hi)] * 7, stats_out=st[0] if st else None))
         self._bn_fwd(self.stem, z1, y1, B * h1 * w1, True, stats=st)
         h2, w2 = h1 // 2, w1 // 2
         p1 = self._get('p1', (B, h2, w2, 64))
@@ -378,8 +310,8 @@ class ResNet50TrainEngine:
         pooled = self._get('pooled', (B, self.fc_in))
         _lib.check(lib.rart_engine_avgpool(_lib.ptr(x), _lib.ptr(pooled), B, xhw[0] * xhw[1], self.fc_in, sp))
         logits = torch.empty(B, self.n_classes, dtype=torch.float32, device=self.device)
-        self._gemm(pooled, self.fc_w, logits, B, (1, 1), (1, 1), self.fc_in, self.fc_in, [(0, 0)], self.n_classes, (1, 1),
-                   self.n_classes, bias=self.model.fc.bias.detach(), flags=F_OUT_F32)
+        self._launch_conv(conv_desc(pooled, self.fc_w, logits, B, (1, 1), (1, 1), self.fc_in, self.fc_in, [(0, 0)], self.n_classes,
+                                    (1, 1), self.n_classes, bias=self.model.fc.bias.detach(), flags=F_OUT_F32))
         acts['last'], acts['pooled'] = (x, xhw), pooled
         self.acts = acts
         pending, self._nbt_pending = self._nbt_pending, None
@@ -404,8 +336,8 @@ class ResNet50TrainEngine:
                     self.fc_in, (1, 1), [(0, 0)], 1, fc.weight.grad)
         self.on_grad_ready(fc.weight)
         dpool = self._get('dpool', (B, self.fc_in))
-        self._gemm(dlb, self.fc_wd, dpool, B, (1, 1), (1, 1), self.fc_kpad, self.fc_kpad, [(0, 0)], self.fc_in, (1, 1),
-                   self.fc_in)
+        self._launch_conv(conv_desc(dlb, self.fc_wd, dpool, B, (1, 1), (1, 1), self.fc_kpad, self.fc_kpad, [(0, 0)], self.fc_in,
+                                    (1, 1), self.fc_in))
         xl, xlhw = acts['last']
         d_out = self._get('g_out_a', tuple(xl.shape))
         _lib.check(lib.rart_engine_avgpool_bwd(_lib.ptr(xl), _lib.ptr(dpool), _lib.ptr(d_out), B, xlhw[0] * xlhw[1],

@@ -11,21 +11,11 @@ csrc/vit_bwd.hip / train_convbn.hip kernels.  Reference module: robustart_amd/mo
 import ctypes
 
 from .. import _lib
-
-F_RELU, F_OUT_F32, F_GELU, F_GELU_BWD = 1, 2, 4, 8
-F_GELU_KEEP = 64          # dst = gelu(u), `mask` receives the pre-activation u (256 x 256 GEMM only)
-PRECISIONS = {'bf16': 'bf16', 'bf16x3': 'bf16x3', 'fp32x': 'bf16x3'}
+from .engine_base import (F_GELU, F_GELU_BWD, F_GELU_KEEP, F_OUT_F32, GP_GELU, GP_GELU_BWD, GP_GELU_KEEP, GP_OUT_F32, RowEngine,
+                          cints, interleave_k32, lo_off, pad_k, pad_rows, pair, rows_mult)
 
 
-def _pair(t):
-    """fp32 tensor -> [2][...] bf16 planes (hi = bf16(v), lo = bf16(v - hi)): the split-bf16 representation"""
-    import torch
-    hi = t.to(torch.bfloat16)
-    lo = (t - hi.float()).to(torch.bfloat16)
-    return torch.stack([hi, lo]).contiguous()
-
-
-class ViTEngine:
+class ViTEngine(RowEngine):
     def __init__(self, model, device='cuda', precision='bf16'):
         """precision: 'bf16' -- bf16 storage, fp32 accumulation (the fast path; logits within ~3e-3 of the fp32 network);
         'bf16x3' (alias 'fp32x') -- the REFERENCE-PRECISION mode (`_forward_x3` / `_backward_x3`): the reference evaluates and
@@ -33,21 +23,13 @@ class ViTEngine:
         autopgd_base.py:271-289) and the north star asks for logits within 1e-4 of it, so every activation, gradient and weight is
         a hi + lo pair of bf16 planes, every contraction the three MFMA products of rart_gemm_pair_bf16, and LayerNorm / soft-max /
         GELU are evaluated in fp32 on hi + lo (csrc/vit_pair.hip)."""
-        torch = _lib.require_gpu()
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        if precision not in PRECISIONS:
-            raise ValueError('precision must be one of %s' % sorted(PRECISIONS))
-        self.precision = PRECISIONS[precision]
-        self.profile = None              # a list collects (flops issued, event0, event1, kind) per GEMM launch (bench.py)
+        super().__init__(device, precision)
         m = model
         self.D, self.H, self.ps = m.embed_dim, m.num_heads, m.patch_size
         self.hd = self.D // self.H
         import os as _os
         self.pair_w_interleaved = _os.environ.get('RART_PAIR_WIL', '0') == '1'     # see engine.py: weight tables interleaved per K step
-        self._w_il = {}
         self.refold(model)
-        self._buf = {}
         self.fused_attention = True
         self.fused_attention_bwd = True      # False: the decomposition into batched igemm products (cross-check)
 
@@ -61,21 +43,13 @@ class ViTEngine:
         def bf(w2d):                                         # fp32 [rows][k] (any device) -> bf16 on the engine's device
             return w2d.detach().to(dev, torch.float32).to(torch.bfloat16)
 
-        def pad_rows(w, mult):
-            r = (w.shape[0] + mult - 1) // mult * mult
-            if r == w.shape[0]:
-                return w.contiguous()
-            return torch.cat([w, torch.zeros(r - w.shape[0], w.shape[1], dtype=w.dtype, device=w.device)], 0).contiguous()
-
         def wt(linear_w, n_cols):
-            return pad_rows(bf(linear_w), 128 if n_cols > 64 else 64)
+            return pad_rows(bf(linear_w), rows_mult(n_cols))
 
         def wd(linear_w, k_pad=None):
             """backward-to-input table: dx[rows][in] = dy[rows][out] . W  ->  rows = in features, K = out features"""
-            w = bf(linear_w).t()
-            if k_pad is not None and k_pad > w.shape[1]:
-                w = torch.cat([w, torch.zeros(w.shape[0], k_pad - w.shape[1], dtype=w.dtype, device=dev)], 1)
-            return pad_rows(w, 128 if w.shape[0] > 64 else 64)
+            w = pad_k(bf(linear_w).t(), k_pad)
+            return pad_rows(w, rows_mult(w.shape[0]))
 
         def f32(t):
             return t.detach().to(dev, torch.float32).contiguous()
@@ -114,18 +88,11 @@ class ViTEngine:
         dev = self.device
 
         def tab(w2d, k_pad=None):
-            w = w2d.detach().to(dev, torch.float32)
-            if k_pad is not None and k_pad > w.shape[1]:
-                w = torch.cat([w, torch.zeros(w.shape[0], k_pad - w.shape[1], device=dev)], 1)
-            r = (w.shape[0] + 255) // 256 * 256
-            if r != w.shape[0]:
-                w = torch.cat([w, torch.zeros(r - w.shape[0], w.shape[1], device=dev)], 0)
-            t = _pair(w.contiguous())
+            t = pair(pad_rows(pad_k(w2d.detach().to(dev, torch.float32), k_pad), 256))
             if self.pair_w_interleaved and t.shape[2] % 32 == 0:
-                # round 5: per row and 32-deep K step the hi slice then the lo slice (rart_gemm_pair_bf16 flag 16: one 128-byte line per
-                # row and step); kept beside the planes, keyed by their address
-                rows, k = t.shape[1], t.shape[2]
-                self._w_il[t.data_ptr()] = torch.stack([t[0].reshape(rows, k // 32, 32), t[1].reshape(rows, k // 32, 32)], 2).reshape(rows, 2 * k).contiguous()
+                # round 5: per row and 32-deep K step the hi slice then the lo slice (GP_W_INTERLEAVED: one 128-byte line per row and
+                # step); kept beside the planes, keyed by their address
+                self._w_il[t.data_ptr()] = interleave_k32(t[0], t[1])
             return t
         self._w_il = {}
         pe = m.patch_embed.weight.detach().reshape(self.D, -1)
@@ -133,47 +100,6 @@ class ViTEngine:
                        layers=[dict(qkv_w=tab(b.attn.qkv.weight), proj_w=tab(b.attn.proj.weight), fc1_w=tab(b.fc1.weight),
                                     fc2_w=tab(b.fc2.weight), qkv_wd=tab(b.attn.qkv.weight.t()), proj_wd=tab(b.attn.proj.weight.t()),
                                     fc1_wd=tab(b.fc1.weight.t()), fc2_wd=tab(b.fc2.weight.t())) for b in m.blocks])
-
-    def _get(self, name, shape, dtype=None, zero=False):
-        torch = _lib.require_gpu()
-        dtype = dtype or torch.bfloat16
-        t = self._buf.get(name)
-        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
-            t = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=self.device)
-            self._buf[name] = t
-        return t
-
-    def _gemm(self, src, wgt, dst, rows, k, n_cols, src_ld, dst_ld, bias=None, res=None, flags=0, n_taps=1,
-              tap_src_off=None, rows_per_image=None, dst_rows_per_image=None, dst_row_off=0, batched=None,
-              src_rows_per_image=None, mask=None):
-        """rows x k (x n_taps) times wgt^T -> dst.  rows_per_image/dst_rows_per_image/dst_row_off place the output
-        rows of image b at b*dst_rows_per_image + dst_row_off (class-token slot).  batched = dict(n, inner,
-        src=(outer, inner), wgt=(outer, inner), dst=(outer, inner), wgt_row_stride)."""
-        d = _lib.ConvDesc()
-        d.src, d.wgt, d.dst = src.data_ptr(), wgt.data_ptr(), dst.data_ptr()
-        d.bias = bias.data_ptr() if bias is not None else None
-        d.res = res.data_ptr() if res is not None else None
-        d.mask = mask.data_ptr() if mask is not None else None
-        rpi = rows_per_image or rows
-        d.batch, d.grid_h, d.grid_w = rows // rpi, rpi, 1
-        d.src_h, d.src_w, d.src_pix_stride = (src_rows_per_image or rpi), 1, src_ld
-        d.k_per_tap, d.n_taps = k, n_taps
-        d.sy, d.sx = 1, 1
-        for i in range(n_taps):
-            d.tap_dy[i], d.tap_dx[i] = 0, 0
-            d.tap_src_off[i] = tap_src_off[i] if tap_src_off else 0
-        d.n_cols = n_cols
-        d.dst_h, d.dst_w = (dst_rows_per_image or rpi), 1
-        d.dst_sy, d.dst_sx, d.dst_oy, d.dst_ox = 1, 1, dst_row_off, 0
-        d.dst_pix_stride = dst_ld
-        d.flags = flags
-        if batched:
-            d.n_batched, d.z_inner = batched['n'], batched['inner']
-            d.src_z_outer, d.src_z_inner = batched['src']
-            d.wgt_z_outer, d.wgt_z_inner = batched['wgt']
-            d.dst_z_outer, d.dst_z_inner = batched['dst']
-            d.wgt_row_stride = batched.get('wgt_row_stride', 0)
-        _lib.check(self.lib.rart_conv_igemm_bf16(ctypes.byref(d), _lib.stream_ptr()))
 
     def _forward(self, src, src_is_u8, mean, std, keep=False):
         if self.precision == 'bf16x3':
@@ -194,8 +120,7 @@ class ViTEngine:
         _lib.check(lib.rart_vit_patchify(_lib.ptr(src), 1 if src_is_u8 else 0, _lib.ptr(patches[0]), _lib.ptr(patches[1]),
                                          B, Himg, Wimg, ps, meanf, stdf, sp))
         x = self._get('x0' if keep else 'x', (B, T, D))
-        lo_off = (patches[1].data_ptr() - patches[0].data_ptr()) // 2
-        self._gemm(patches[0], self.pe_w, x, B * P, kk, D, kk, D, bias=self.pe_b, n_taps=2, tap_src_off=[0, lo_off],
+        self._gemm(patches[0], self.pe_w, x, B * P, kk, D, kk, D, bias=self.pe_b, n_taps=2, tap_src_off=[0, lo_off(patches)],
                    rows_per_image=P, dst_rows_per_image=T, dst_row_off=1)
         _lib.check(lib.rart_vit_add_pos_cls(_lib.ptr(x), _lib.ptr(self.cls_pos0), _lib.ptr(self.pos), B, T, D, sp))
         rows = B * T
@@ -298,7 +223,7 @@ class ViTEngine:
         m_all = BH * t_pad
         dst_t = self._get('ds_t', (t_pad, m_all))
         p_t = self._get('p_t', (t_pad, m_all))
-        zero = (ctypes.c_int * 1)(0)
+        zero = cints([0])
         for src_m, dst_m in ((ds, dst_t), (probs, p_t)):
             _lib.check(lib.rart_transpose_gather_bf16(_lib.ptr(src_m), _lib.ptr(dst_m), BH, T, 1, t_pad, t_pad, 1, 1, 1, 1,
                                                       zero, zero, m_all, 0, 0, sp))
@@ -362,51 +287,6 @@ class ViTEngine:
 
 
     # ------------------------------------------------------------------ reference-precision ("bf16x3" / "fp32x") mode
-    def _gemm_pair(self, a, w, dst, M, N, K, lda, ldc, ldw=None, bias=None, res=None, flags=0, aux=None, w_rows=None,
-                   rows_per_image=0, src_rows_per_image=0, src_row_off=0, dst_rows_per_image=0, dst_row_off=0, batched=None,
-                   a_off=0, w_off=0, dst_off=0):
-        """(a_hi + a_lo)[M][K] . (w_hi + w_lo)[N][K]^T -> dst (pair, or fp32 with F_OUT_F32) on rart_gemm_pair_bf16.  a / w / dst /
-        res / aux are pair tensors [2][...] (dst fp32: a plain tensor); *_off are element offsets inside a plane (head / column
-        slices); batched = dict(n, inner, a=(outer, inner), w=(outer, inner), c=(outer, inner))."""
-        d = _lib.GemmPairDesc()
-        es = 2                                                         # bytes per bf16 element
-        d.a_hi, d.a_lo = a[0].data_ptr() + a_off * es, a[1].data_ptr() + a_off * es
-        d.w_hi, d.w_lo = w[0].data_ptr() + w_off * es, w[1].data_ptr() + w_off * es
-        d.bias = bias.data_ptr() if bias is not None else None
-        if res is not None:
-            d.res_hi, d.res_lo = res[0].data_ptr() + dst_off * es, res[1].data_ptr() + dst_off * es
-        if flags & F_OUT_F32:
-            d.dst_hi, d.dst_lo = dst.data_ptr() + dst_off * 4, None
-        else:
-            d.dst_hi, d.dst_lo = dst[0].data_ptr() + dst_off * es, dst[1].data_ptr() + dst_off * es
-        if aux is not None:
-            d.aux_hi, d.aux_lo = aux[0].data_ptr() + dst_off * es, aux[1].data_ptr() + dst_off * es
-        d.M, d.N, d.K, d.lda, d.ldw, d.ldc = M, N, K, lda, (ldw or K), ldc
-        il = self._w_il.get(w.data_ptr()) if (w_off == 0 and ldw is None and not batched) else None
-        if il is not None and il.shape[1] == 2 * K:
-            d.w_hi, d.w_lo, d.ldw = il.data_ptr(), il.data_ptr() + 64, 2 * K
-            flags |= 16
-        d.w_rows = w_rows if w_rows is not None else w.shape[-2]
-        d.rows_per_image, d.src_rows_per_image, d.src_row_off = rows_per_image, src_rows_per_image, src_row_off
-        d.dst_rows_per_image, d.dst_row_off = dst_rows_per_image, dst_row_off
-        d.flags = flags
-        nz = 1
-        if batched:
-            nz = d.n_batched = batched['n']
-            d.z_inner = batched['inner']
-            d.a_z_outer, d.a_z_inner = batched['a']
-            d.w_z_outer, d.w_z_inner = batched['w']
-            d.c_z_outer, d.c_z_inner = batched['c']
-        if self.profile is not None:
-            torch = _lib.require_gpu()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            _lib.check(self.lib.rart_gemm_pair_bf16(ctypes.byref(d), _lib.stream_ptr()))
-            e1.record()
-            self.profile.append((3 * 2.0 * nz * M * N * K, e0, e1, 'gemm_pair'))       # MFMA FLOPs issued: three products
-            return
-        _lib.check(self.lib.rart_gemm_pair_bf16(ctypes.byref(d), _lib.stream_ptr()))
-
     def _scores_probs_x3(self, qkv, B, T):
         """S = Q K^T (fp32) and P = softmax(S / sqrt(d)) (pair) of one layer, batched over (image, head)"""
         lib, sp = self.lib, _lib.stream_ptr()
@@ -415,7 +295,7 @@ class ViTEngine:
         torch = _lib.require_gpu()
         scores = self._get('x3_scores', (BH, T, s_ld), torch.float32)
         probs = self._get('x3_probs', (2, BH, T, t_pad))
-        self._gemm_pair(qkv, qkv, scores, T, s_ld, hd, 3 * D, s_ld, ldw=3 * D, flags=F_OUT_F32, w_rows=T, w_off=D,
+        self._gemm_pair(qkv, qkv, scores, T, s_ld, hd, 3 * D, s_ld, ldw=3 * D, flags=GP_OUT_F32, w_rows=T, w_off=D,
                         batched=dict(n=BH, inner=H, a=(T * 3 * D, hd), w=(T * 3 * D, hd), c=(H * T * s_ld, T * s_ld)))
         _lib.check(lib.rart_softmax_rows_pair(_lib.ptr(scores), _lib.ptr(probs[0]), _lib.ptr(probs[1]), BH * T, T, s_ld, t_pad,
                                               float(hd) ** -0.5, sp))
@@ -480,10 +360,10 @@ class ViTEngine:
             hid = self._get('x3_hid', (2, B, T, L['hidden']))
             if keep:
                 u = self._get('x3_u%d' % li, (2, B, T, L['hidden']))
-                self._gemm_pair(ln, XL['fc1_w'], hid, rows, L['hidden'], D, D, L['hidden'], bias=L['fc1_b'], flags=F_GELU_KEEP, aux=u)
+                self._gemm_pair(ln, XL['fc1_w'], hid, rows, L['hidden'], D, D, L['hidden'], bias=L['fc1_b'], flags=GP_GELU_KEEP, aux=u)
                 saved.append((x, xm, qkv, u, att))
             else:
-                self._gemm_pair(ln, XL['fc1_w'], hid, rows, L['hidden'], D, D, L['hidden'], bias=L['fc1_b'], flags=F_GELU)
+                self._gemm_pair(ln, XL['fc1_w'], hid, rows, L['hidden'], D, D, L['hidden'], bias=L['fc1_b'], flags=GP_GELU)
             self._gemm_pair(hid, XL['fc2_w'], xo, rows, D, L['hidden'], L['hidden'], D, bias=L['fc2_b'], res=xm)
             x = xo
         if keep:
@@ -492,7 +372,7 @@ class ViTEngine:
         _lib.check(lib.rart_layernorm_pair(_lib.ptr(x[0]), _lib.ptr(x[1]), _lib.ptr(self.ng), _lib.ptr(self.nb), _lib.ptr(cls[0]),
                                            _lib.ptr(cls[1]), B, D, T * D, D, 1e-6, sp))
         logits = torch.empty(B, self.n_classes, dtype=torch.float32, device=self.device)
-        self._gemm_pair(cls, X['head_w'], logits, B, self.n_classes, D, D, self.n_classes, bias=self.head_b, flags=F_OUT_F32)
+        self._gemm_pair(cls, X['head_w'], logits, B, self.n_classes, D, D, self.n_classes, bias=self.head_b, flags=GP_OUT_F32)
         return logits
 
     def _backward_x3(self, dl, std):
@@ -508,7 +388,7 @@ class ViTEngine:
         t_pad, s_ld, BH = (T + 31) // 32 * 32, (T + 7) // 8 * 8, B * H
         scale = float(hd) ** -0.5
         dlp = self._get('x3_dl', (2, B, self.head_kpad))
-        _lib.check(lib.rart_f32_to_pair_rows(_lib.ptr(dl), _lib.ptr(dlp[0]), (dlp[1].data_ptr() - dlp[0].data_ptr()) // 2, B,
+        _lib.check(lib.rart_f32_to_pair_rows(_lib.ptr(dl), _lib.ptr(dlp[0]), lo_off(dlp), B,
                                              self.n_classes, self.head_kpad, sp))
         dcls = self._get('x3_dcls', (2, B, D))
         self._gemm_pair(dlp, X['head_wd'], dcls, B, D, self.head_kpad, self.head_kpad, D)
@@ -518,13 +398,13 @@ class ViTEngine:
                                                _lib.ptr(self.ng), None, None, _lib.ptr(dx[0]), _lib.ptr(dx[1]), B, D, D, T * D, 0, T * D,
                                                1e-6, sp))
         dqkv = self._get('x3_g_qkv', (2, rows, 3 * D))
-        zero = (ctypes.c_int * 1)(0)
+        zero = cints([0])
         m_all = BH * t_pad
         for li in range(len(self.layers) - 1, -1, -1):
             L, XL = self.layers[li], X['layers'][li]
             x_in, xm, qkv, u, att = saved[li]
             dh = self._get('x3_g_hid', (2, rows, L['hidden']))
-            self._gemm_pair(dx, XL['fc2_wd'], dh, rows, L['hidden'], D, D, L['hidden'], flags=F_GELU_BWD, aux=u)    # du = (dx W2) gelu'(u)
+            self._gemm_pair(dx, XL['fc2_wd'], dh, rows, L['hidden'], D, D, L['hidden'], flags=GP_GELU_BWD, aux=u)    # du = (dx W2) gelu'(u)
             dln = self._get('x3_g_ln', (2, rows, D))
             self._gemm_pair(dh, XL['fc1_wd'], dln, rows, D, L['hidden'], L['hidden'], D)
             dxm = self._get('x3_g_xm', (2, B, T, D))
@@ -542,7 +422,7 @@ class ViTEngine:
             else:
                 probs = self._scores_probs_x3(qkv, B, T)
                 dprobs = self._get('x3_dprobs', (BH, T, s_ld), torch.float32)
-                self._gemm_pair(datt, qkv, dprobs, T, s_ld, hd, D, s_ld, ldw=3 * D, flags=F_OUT_F32, w_rows=T, w_off=2 * D,
+                self._gemm_pair(datt, qkv, dprobs, T, s_ld, hd, D, s_ld, ldw=3 * D, flags=GP_OUT_F32, w_rows=T, w_off=2 * D,
                                 batched=dict(n=BH, inner=H, a=(T * D, hd), w=(T * 3 * D, hd), c=(H * T * s_ld, T * s_ld)))       # dP = dO V^T
                 ds = self._get('x3_dscores', (2, BH, T, t_pad))
                 _lib.check(lib.rart_softmax_bwd_rows_pair(_lib.ptr(probs[0]), _lib.ptr(probs[1]), _lib.ptr(dprobs), _lib.ptr(ds[0]),
@@ -569,15 +449,9 @@ class ViTEngine:
         # patch embedding: d(patches)[b][p][:] = dx[b][1 + p][:] . Wpe (fp32) ; class token / position rows drop out
         kk = 3 * self.ps * self.ps
         dpatch = self._get('x3_g_patch', (B * P, kk), torch.float32)
-        self._gemm_pair(dx, X['pe_wd'], dpatch, B * P, kk, D, D, kk, flags=F_OUT_F32, rows_per_image=P, src_rows_per_image=T,
+        self._gemm_pair(dx, X['pe_wd'], dpatch, B * P, kk, D, D, kk, flags=GP_OUT_F32, rows_per_image=P, src_rows_per_image=T,
                         src_row_off=1)
         grad = torch.empty(B, 3, Himg, Wimg, dtype=torch.float32, device=self.device)
         _lib.check(lib.rart_vit_unpatchify_from_f32(_lib.ptr(dpatch), _lib.ptr(grad), B, Himg, Wimg, self.ps, kk,
                                                     (ctypes.c_float * 3)(*std), sp))
         return grad
-
-    def logits(self, x01, mean, std):
-        return self._forward(x01.detach().float().contiguous(), False, mean, std)
-
-    def logits_from_u8(self, batch_u8, mean, std):
-        return self._forward(batch_u8, True, mean, std)

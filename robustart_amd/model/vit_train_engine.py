@@ -12,10 +12,9 @@ AdamW, label_smooth 0.1, drop_path_rate 0.0 -- no stochastic layers) with every 
 Gradients are written into the parameters' `.grad` tensors (views of the flat gradient arena, train/arena.py);
 `on_grad_ready(param)` lets the arena launch a bucket's all-reduce as soon as its last gradient exists.
 """
-import ctypes
-
 from .. import _lib
-from .vit_engine import F_GELU_BWD, F_OUT_F32, ViTEngine
+from .engine_base import F_GELU_BWD
+from .vit_engine import ViTEngine
 
 
 class ViTTrainEngine(ViTEngine):
@@ -34,50 +33,6 @@ class ViTTrainEngine(ViTEngine):
         return self._forward(src, src_is_u8, mean, std, keep=True)
 
     # ------------------------------------------------------------------ helpers
-    def _scratch(self, name, nbytes):
-        torch = _lib.require_gpu()
-        t = self._buf.get(name)
-        if t is None or t.numel() < nbytes:
-            t = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
-            self._buf[name] = t
-        return t
-
-    def _wgrad(self, dz, n_out, n_pad, x, c_in, grad, rows, dz_images=None):
-        """grad[n_out][c_in] = dz^T . x  (dz: bf16 [rows][n_pad] dense, columns >= n_out zero; x: bf16 [rows][c_in] dense).
-        dz_images = (B, rows_per_image_in_memory, rows_used): dz rows are the first `rows_used` of every image block."""
-        lib, sp = self.lib, _lib.stream_ptr()
-        bn_tile = 128 if n_pad > 64 else 64
-        tiles = ((c_in + 127) // 128) * ((n_pad + bn_tile - 1) // bn_tile)
-        splits = max(1, min(1024 // max(tiles, 1), rows // 512 if rows >= 1024 else 1, 256))
-        chunk = ((rows + splits - 1) // splits + 63) // 64 * 64
-        m_pad = chunk * splits
-        n_rows = (n_pad + bn_tile - 1) // bn_tile * bn_tile
-        dzt = self._scratch('wg_dzT', n_rows * m_pad * 2)
-        colt = self._scratch('wg_colT', c_in * m_pad * 2)
-        zero = (ctypes.c_int * 1)(0)
-        if n_rows > n_pad:
-            dzt[:n_rows * m_pad * 2].zero_()
-        if dz_images is None:
-            b, sh, gh = 1, rows, rows
-        else:
-            b, sh, gh = dz_images
-        _lib.check(lib.rart_transpose_gather_bf16(_lib.ptr(dz), _lib.ptr(dzt), b, sh, 1, n_pad, gh, 1, 1, 1, 1, zero, zero, m_pad,
-                                                  chunk, n_rows, sp))
-        _lib.check(lib.rart_transpose_gather_bf16(_lib.ptr(x), _lib.ptr(colt), 1, rows, 1, c_in, rows, 1, 1, 1, 1, zero, zero,
-                                                  m_pad, chunk, c_in, sp))
-        ld_n = (n_pad + 7) // 8 * 8
-        part = self._scratch('wg_part', splits * c_in * ld_n * 4)
-        self._gemm(colt, dzt, part, c_in, chunk, ld_n, chunk, ld_n, flags=F_OUT_F32,
-                   batched=dict(n=splits, inner=splits, src=(0, c_in * chunk), wgt=(0, n_rows * chunk), dst=(0, c_in * ld_n),
-                                wgt_row_stride=chunk))
-        _lib.check(lib.rart_wgrad_reduce_f32(_lib.ptr(part), splits, 1, c_in, c_in, n_out, ld_n, _lib.ptr(grad), 0, sp))
-
-    def _colsum(self, x, ld, rows, cols, out):
-        lib = self.lib
-        need = lib.rart_colsum_workspace_bytes(rows, cols)
-        ws = self._scratch('cs_ws', need)
-        _lib.check(lib.rart_colsum_bf16(_lib.ptr(x), ld, rows, cols, _lib.ptr(out), 0, _lib.ptr(ws), need, _lib.stream_ptr()))
-
     def _ln_bwd(self, dy, x, gamma, res, dx, rows, strides, norm):
         lib, D = self.lib, self.D
         need = lib.rart_layernorm_bwd_workspace_bytes(D)
