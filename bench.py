@@ -13,13 +13,15 @@ images per step = 6*B.  Inputs are resident in HBM before the timed region.  Wea
 rank processes its own B images (global sample indices keep the noise field rank-invariant); the
 only collective is the 3-scalar metric all-reduce after the timed region.
 
-The TOP-LEVEL value / ms_per_step / dtype / roofline are those of the tolerance-meeting path: the reference-precision
-engine (`--precision bf16x3`, the default: logits within 1e-4 of the fp32 network, which is what the reference computes,
-noise/utils/adv/attack.py:20-23).  The bf16 engine's figure for the same step follows as `fast_mode` with its stated
-error; BASELINE configs 4 and 5 (ViT-B/16 x ImageNet-C, ResNet-50 adversarial training) follow as `secondary`, three
-steps each; the oracle on the host cores as `cpu_baseline`.
+The TOP-LEVEL value / ms_per_step / dtype are those of the tolerance-meeting path: the reference-precision engine
+(`--precision bf16x3`, the default: logits within 1e-4 of the fp32 network, which is what the reference computes,
+noise/utils/adv/attack.py:20-23).  A plain run does only what that line needs: set up, warm up, time the steps, write
+--dump-outputs, print.  With --full the line also carries the blocks that take runs of their own: `roofline` of the timed
+engine and `hbm_roofline_gaussian_noise`; the bf16 engine's figure for the same step as `fast_mode` with its stated
+error; BASELINE configs 4 and 5 (ViT-B/16 x ImageNet-C, ResNet-50 adversarial training) as `secondary`, three steps
+each; the oracle on the host cores as `cpu_baseline`.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 """
 import argparse
@@ -48,6 +50,10 @@ def parse():
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--batch', type=int, default=B_DEFAULT)
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: the roofline blocks, the other engine, the secondary '
+                         'workloads and the CPU baseline (headline workload), the reference-precision block (vit_inc); '
+                         'the --no-* options below drop single blocks of a --full run')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--precision', choices=['bf16x3', 'bf16'], default='bf16x3',
                     help="engine of the timed step: 'bf16x3' = the reference-precision engine (hi + lo bf16 pairs, three MFMA products per "
@@ -656,8 +662,8 @@ def run_vit_inc(args, device, rank, world, dist):
     """BASELINE config 4 (secondary mode, not the headline line): per step, one resident batch of 256 uint8 images is corrupted by each of
     the 15 benchmark corruptions at 5 severities (75 corrupted batches; frost blends SYNTHETIC textures -- the reference's six photographs
     are not in its repository, imagenet_c/corruptions.py:251-256 -- drawn and cropped on the device exactly as for real ones) and each is
-    evaluated by ViT-B/16 on the HIP engine.  A `reference_precision` block repeats the step on the 'fp32x' engine (logits within 1e-4 of
-    the fp32 network; the reference evaluates in fp32: exprs/exp/imagenet_c_loop_mini/config_vit_base.yaml:1-9)."""
+    evaluated by ViT-B/16 on the HIP engine.  With --full a `reference_precision` block repeats the step on the 'fp32x' engine (logits within
+    1e-4 of the fp32 network; the reference evaluates in fp32: exprs/exp/imagenet_c_loop_mini/config_vit_base.yaml:1-9)."""
     import numpy as np
     from robustart_amd.model import get_model
     from robustart_amd.model.vit_engine import ViTEngine
@@ -728,7 +734,7 @@ def run_vit_inc(args, device, rank, world, dist):
            'config': {'workload': 'BASELINE config 4 (secondary): 75 corrupted batches of %d per step -> ViT-B/16 eval' % B,
                       'corruptions': len(ids), 'frost_textures': 'synthetic (6 random uint8 photographs, cropped on the device)',
                       'global_batch': B * world, 'parallelism': 'dp%d' % world, 'streams': n_q}}
-    if not args.no_other_engine:
+    if args.full and not args.no_other_engine:
         del engs
         torch.cuda.empty_cache()
         engs = [ViTEngine(model, device, precision='fp32x') for _ in range(n_q)]
@@ -871,7 +877,8 @@ def measure_secondary(args, device, B):
     after one warm-up step): ResNet-50 adversarial training (cls_solver step, PGD-3 inner loop, bf16 as config 5 names it) and the ViT-B/16
     ImageNet-C sweep (15 corruptions x 5 severities generated on the GPU) on the bf16 engine and on the reference-precision engine."""
     import types
-    a = types.SimpleNamespace(steps=max(1, args.secondary_steps), warmup=1, batch=B, one_stream=args.one_stream, no_other_engine=False)
+    a = types.SimpleNamespace(steps=max(1, args.secondary_steps), warmup=1, batch=B, one_stream=args.one_stream, full=True,
+                              no_other_engine=False)
     out = {'note': 'one warm-up + %d timed steps each, batch %d, run after the headline inside the same process' % (a.steps, B)}
     t0 = time.time()
     r = run_adv_train(a, device, 0, 1, None)
@@ -947,7 +954,7 @@ def main():
     B = args.batch
     images, labels, model = build_workload(B, device, rank)
     import copy
-    model_cpu = copy.deepcopy(model) if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    model_cpu = copy.deepcopy(model) if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline) else None
     path = HipEngine(model, device, two_streams=not args.one_stream, precision=args.precision)
 
     for i in range(args.warmup):
@@ -1011,7 +1018,7 @@ def main():
                                            + ('; against the %.1f TFLOP/s fp32 MFMA peak of the arithmetic the reference uses: %.2f x'
                                               % (MFMA_F32_PEAK / 1e12, step_flops * args.steps / dt / MFMA_F32_PEAK / world)
                                               if args.precision != 'bf16' else '')}
-        if world == 1:
+        if world == 1 and args.full:
             out['roofline'] = measure_engine_roofline(path, images, labels)
             out['hbm_roofline_gaussian_noise'] = gaussian_noise_block(B, device)
             other = 'bf16' if args.precision != 'bf16' else 'bf16x3'

@@ -22,7 +22,7 @@ def per_kernel(db):
 def main(fetch_db, write_db, out):
     f, w = per_kernel(fetch_db), per_kernel(write_db)
     res = {'units': 'bytes per launch', 'fetch_correction': 2.0, 'source': 'rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE '
-           '-- python bench.py --steps 1 --warmup 1 --no-cpu-baseline (two passes)', 'kernels': {}}
+           '-- python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline (two passes)', 'kernels': {}}
     for k in sorted(f, key=lambda k: -f[k][1]):
         if k not in w:
             continue

@@ -4,12 +4,12 @@ set -x
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r05; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 # 1. the driver's line: reference-precision headline, fast_mode, secondary (configs 4 and 5), cpu_baseline
-python $R/bench.py --steps 20 --warmup 5 2>$O/r05_bench_line.err | tail -1 > $O/r05_bench_line.json
+python $R/bench.py --full --steps 20 --warmup 5 2>$O/r05_bench_line.err | tail -1 > $O/r05_bench_line.json
 # 2. the same command under the kernel trace (both engines in one process: headline + fast_mode)
-RART_BENCH_NO_4X=1 rocprofv3 --kernel-trace --stats -d /tmp/prof_kt -o b -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 > $O/r05_bench_under_rocprof.json
+RART_BENCH_NO_4X=1 rocprofv3 --kernel-trace --stats -d $TMPDIR/prof_kt -o b -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 > $O/r05_bench_under_rocprof.json
 python $R/profiles/summarize_rocpd.py $(find /tmp/prof_kt -name "*.db" | head -1) $O/r05_bench_kernel_stats.csv > /dev/null
 # 3. HBM traffic: two separate PMC passes of the same command (kernel trace + one counter each)
-for c in FETCH_SIZE WRITE_SIZE; do RART_BENCH_NO_4X=1 rocprofv3 --kernel-trace --pmc $c -d /tmp/prof_$c -o b -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-secondary > /dev/null 2>&1; done
+for c in FETCH_SIZE WRITE_SIZE; do RART_BENCH_NO_4X=1 rocprofv3 --kernel-trace --pmc $c -d $TMPDIR/prof_$c -o b -- python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-secondary > /dev/null 2>&1; done
 python $R/profiles/summarize_pmc.py $(find /tmp/prof_FETCH_SIZE -name "*.db" | head -1) $(find /tmp/prof_WRITE_SIZE -name "*.db" | head -1) $O/r05_pmc_traffic.json > /dev/null
 # 4. per-launch tables of one gradient evaluation, both engines
 python $R/scratch/prof_engine2.py 2>/dev/null > $O/r05_igemm_per_shape.txt

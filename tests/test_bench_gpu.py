@@ -1,8 +1,8 @@
 """The driver's contract for bench.py, checked on the GPU: ONE JSON line on stdout with the metric / timing fields led by the
-tolerance-meeting path (dtype bf16x3: the reference-precision engine), the `roofline` object (the kernel family with the largest share of
-a gradient evaluation of THAT engine, priced against its binding roof) and, on the default run, `fast_mode` (the bf16 engine with its
-stated error), `secondary` (BASELINE configs 4 and 5, driver-timed) and `cpu_baseline`; here short runs.  The secondary workloads also run
-two steps each as stand-alone workloads."""
+tolerance-meeting path (dtype bf16x3: the reference-precision engine); a plain run carries nothing else that needs a run of its own.  With
+--full the line adds the `roofline` object (the kernel family with the largest share of a gradient evaluation of THAT engine, priced against
+its binding roof), `fast_mode` (the bf16 engine with its stated error), `secondary` (BASELINE configs 4 and 5, timed in the same run) and
+`cpu_baseline`; here short runs.  The secondary workloads also run two steps each as stand-alone workloads."""
 import json
 import os
 import subprocess
@@ -34,8 +34,20 @@ def _check_roofline(rf):
         assert rf['algorithmic_bytes_per_launch'] > 0 and 0 < rf['mfma']['frac'] < 1
 
 
+FULL_ONLY = ('roofline', 'hbm_roofline_gaussian_noise', 'fast_mode', 'reference_precision', 'secondary', 'cpu_baseline')
+
+
+def test_plain_bench_prints_the_headline_fields_and_measures_nothing_else():
+    d = _run(['--gpus', '1', '--steps', '2', '--warmup', '1'])
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'n_gpus', 'steps', 'warmup', 'config'):
+        assert k in d, k
+    assert d['dtype'] == 'bf16x3' and d['unit'] == 'images/s' and d['higher_is_better'] is True and d['steps'] == 2 and d['warmup'] == 1
+    assert abs(d['value'] - d['config']['images_per_step'] / (d['ms_per_step'] * 1e-3)) <= 1e-6 * d['value']
+    assert not [k for k in FULL_ONLY if k in d]
+
+
 def test_bench_leads_with_the_reference_precision_engine_and_carries_the_contract_fields():
-    d = _run(['--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-secondary'])
+    d = _run(['--full', '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-secondary'])
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype',
               'data', 'config', 'roofline'):
         assert k in d, k
@@ -67,9 +79,9 @@ def test_bench_leads_with_the_reference_precision_engine_and_carries_the_contrac
 
 
 def test_bench_secondary_block_times_configs_4_and_5():
-    """the default run appends `secondary` -- adv_train (config 5) and vit_inc on both engines (config 4) -- so the
+    """the --full run appends `secondary` -- adv_train (config 5) and vit_inc on both engines (config 4) -- so the
     driver's own BENCH record carries them.  Here at batch 32, two steps."""
-    d = _run(['--steps', '2', '--warmup', '1', '--batch', '32', '--no-cpu-baseline', '--no-fast-mode', '--secondary-steps', '2'])
+    d = _run(['--full', '--steps', '2', '--warmup', '1', '--batch', '32', '--no-cpu-baseline', '--no-fast-mode', '--secondary-steps', '2'])
     sec = d['secondary']
     for k in ('adv_train', 'vit_inc', 'vit_inc_reference_precision'):
         assert sec[k]['value'] > 0 and sec[k]['unit'] == 'images/s' and sec[k]['steps'] == 2, k
@@ -79,7 +91,8 @@ def test_bench_secondary_block_times_configs_4_and_5():
 
 
 def test_bench_fast_engine_can_still_be_the_timed_one():
-    d = _run(['--steps', '2', '--warmup', '1', '--batch', '64', '--precision', 'bf16', '--no-cpu-baseline', '--no-secondary', '--no-reference-precision'])
+    d = _run(['--full', '--steps', '2', '--warmup', '1', '--batch', '64', '--precision', 'bf16', '--no-cpu-baseline', '--no-secondary',
+              '--no-reference-precision'])
     assert d['dtype'] == 'bf16' and 'fast_mode' not in d and 'reference_precision' not in d
     _check_roofline(d['roofline'])
 
