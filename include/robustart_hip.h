@@ -937,6 +937,16 @@ int rart_cnx_grn_bwd_apply_bf16(const void* g, const void* y, const void* u, con
 int rart_cnx_grn_bwd_apply_pair(const void* g_hi, const void* g_lo, const void* y_hi, const void* y_lo, const void* u_hi, const void* u_lo,
                                 const float* G, const float* a, const float* w, void* dh_hi, void* dh_lo, int n, int p, int c, float eps,
                                 rart_stream_t stream);
+/* rart_cnx_grn_bwd_reduce_train_bf16 (ConvNeXt-V2 training, bf16 only): rart_cnx_grn_bwd_reduce_bf16 plus GRN's parameter gradients in
+ *   the same pass over g and y:  a[n][c] = w[c] * sum_p g * y (the same bits as rart_cnx_grn_bwd_reduce_bf16),
+ *   dw[c] (+)= sum_n N[n][c] * sum_p g * y,  db[c] (+)= sum_n sum_p g,  N[n][c] = G[n][c] / (m + eps)  (accumulate != 0 adds).
+ *   G: the forward's rart_cnx_grn_stats_bf16 output; m + eps is formed with rart_cnx_grn_apply_bf16's fixed-order block sum, so N is
+ *   the forward's.  Deterministic, no atomics: per-image fp32 partials in `workspace` (rart_cnx_grn_param_grad_workspace_bytes, 0 for
+ *   an unsupported shape), folded over n in a fixed order.  Shape and alignment rules as above. */
+size_t rart_cnx_grn_param_grad_workspace_bytes(int n, int c);
+int rart_cnx_grn_bwd_reduce_train_bf16(const void* g, const void* y, const float* G, const float* w, float* a, float* dw, float* db, int n,
+                                       int p, int c, float eps, int accumulate, void* workspace, size_t workspace_bytes,
+                                       rart_stream_t stream);
 
 #ifdef __cplusplus
 }

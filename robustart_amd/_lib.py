@@ -165,6 +165,8 @@ SIGNATURES = {
     'rart_cnx_grn_bwd_reduce_pair': (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p]),
     'rart_cnx_grn_bwd_apply_bf16': (c_int, [c_void_p] * 7 + [c_int] * 3 + [c_float, c_void_p]),
     'rart_cnx_grn_bwd_apply_pair': (c_int, [c_void_p] * 11 + [c_int] * 3 + [c_float, c_void_p]),
+    'rart_cnx_grn_param_grad_workspace_bytes': (c_size_t, [c_int] * 2),
+    'rart_cnx_grn_bwd_reduce_train_bf16': (c_int, [c_void_p] * 7 + [c_int] * 3 + [c_float, c_int, c_void_p, c_size_t, c_void_p]),
     'rart_vit_patchify': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                   c_void_p]),
     'rart_vit_add_pos_cls': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

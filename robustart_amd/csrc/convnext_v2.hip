@@ -16,6 +16,11 @@
 // per-image scalars (m, and s for the backward) with a fixed-order block sum over the C statistics of its image, then the per-channel
 // factors into LDS (2 x C fp32), then streams its tile eight channels per lane.  The output may alias the input it replaces
 // (z over y, dh over g): every element is read and written by the same lane.
+// Training (bf16 only; robustart_amd/model/convnext_train_engine.py): rart_cnx_grn_bwd_reduce_train_bf16 adds GRN's parameter gradients,
+//   dw[c] = sum_n N[n][c] sum_p g y,  db[c] = sum_n sum_p g,  N = G / (m + eps),
+// to the bwd_reduce pass: the same workgroup walk also sums g, forms 1 / (m + eps) with k_grn_apply's block sum and writes per-image
+// partials to a workspace ([n][2][c] fp32), and k_grn_param_fold adds them over the images in a fixed order.  `a` keeps the bits of
+// rart_cnx_grn_bwd_reduce_bf16 (same FMAs, same order), so rart_cnx_grn_bwd_apply_bf16 consumes it unchanged.
 // Reference: timm's GlobalResponseNorm (channels-last) inside GlobalResponseNormMlp, restated in robustart_amd/model/convnext_torch.py.
 #include "rart_gemm_pair_dev.h"
 
@@ -73,18 +78,23 @@ __device__ __forceinline__ float block_sum(float v, float* s_red) {
   return t;
 }
 
-// grid (slices, n): out[n][c] = sqrt(sum_p y^2) (GRAD = false) or w[c] * sum_p g y (GRAD = true)
-template <bool PAIR, bool GRAD>
+// grid (slices, n): out[n][c] = sqrt(sum_p y^2) (GRAD = false) or w[c] * sum_p g y (GRAD = true).
+// TRAIN (with GRAD): the same g y sums, the same FMAs in the same order and the same row fold, so `out` keeps its bits; in the same
+// pass sum_p g, and the GRN parameter-gradient partials of image n go to part[n][0][c] = N[n][c] * sum_p g y, part[n][1][c] = sum_p g.
+template <bool PAIR, bool GRAD, bool TRAIN = false>
 __global__ __launch_bounds__(kBlock) void k_grn_reduce(const uint16_t* __restrict__ yh, const uint16_t* __restrict__ yl,
                                                        const uint16_t* __restrict__ gh, const uint16_t* __restrict__ gl,
-                                                       const float* __restrict__ w, float* __restrict__ out, int P, int C) {
+                                                       const float* __restrict__ w, float* __restrict__ out, int P, int C,
+                                                       const float* __restrict__ G, float eps, float* __restrict__ part) {
   __shared__ float s_part[kRows][kSlice];
+  __shared__ float s_partg[TRAIN ? kRows : 1][kSlice];
+  __shared__ float s_red[kBlock / 64];
   const int lc = threadIdx.x % kSliceLanes, row = threadIdx.x / kSliceLanes;
   const int c = blockIdx.x * kSlice + lc * 8;
   const size_t img = (size_t)blockIdx.y * P * C;
-  float acc[8];
+  float acc[8], accg[8];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) acc[k] = 0.f;
+  for (int k = 0; k < 8; ++k) acc[k] = accg[k] = 0.f;
   if (c < C) {
     int p = row;
     for (; p + 3 * kRows < P; p += 4 * kRows) {        // four independent loads in flight, summed in pixel order
@@ -99,6 +109,12 @@ __global__ __launch_bounds__(kBlock) void k_grn_reduce(const uint16_t* __restric
       for (int q = 0; q < 4; ++q)
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc[k] = fmaf(GRAD ? g[q][k] : y[q][k], y[q][k], acc[k]);
+      if (TRAIN) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int k = 0; k < 8; ++k) accg[k] += g[q][k];
+      }
     }
     for (; p < P; p += kRows) {
       float y[8], g[8];
@@ -107,10 +123,25 @@ __global__ __launch_bounds__(kBlock) void k_grn_reduce(const uint16_t* __restric
       if (GRAD) ld8<PAIR>(gh, gl, o, g);
 #pragma unroll
       for (int k = 0; k < 8; ++k) acc[k] = fmaf(GRAD ? g[k] : y[k], y[k], acc[k]);
+      if (TRAIN) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) accg[k] += g[k];
+      }
     }
   }
 #pragma unroll
   for (int k = 0; k < 8; ++k) s_part[row][lc * 8 + k] = acc[k];
+  if (TRAIN) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s_partg[row][lc * 8 + k] = accg[k];
+  }
+  float inv = 0.f;
+  if (TRAIN) {                                          // 1 / (m + eps), formed exactly as k_grn_apply forms it
+    const float* Gn = G + (size_t)blockIdx.y * C;
+    float t = 0.f;
+    for (int cc = threadIdx.x; cc < C; cc += kBlock) t += Gn[cc];
+    inv = 1.0f / (block_sum(t, s_red) / (float)C + eps);
+  }
   __syncthreads();
   if (threadIdx.x < kSlice) {
     const int cc = blockIdx.x * kSlice + threadIdx.x;
@@ -119,7 +150,39 @@ __global__ __launch_bounds__(kBlock) void k_grn_reduce(const uint16_t* __restric
 #pragma unroll
       for (int r = 0; r < kRows; ++r) t += s_part[r][threadIdx.x];
       out[(size_t)blockIdx.y * C + cc] = GRAD ? w[cc] * t : sqrtf(t);
+      if (TRAIN) {
+        float tg = 0.f;
+#pragma unroll
+        for (int r = 0; r < kRows; ++r) tg += s_partg[r][threadIdx.x];
+        float* pn = part + (size_t)blockIdx.y * 2 * C;
+        const float nc = G[(size_t)blockIdx.y * C + cc] * inv;
+        pn[cc] = nc * t;
+        pn[C + cc] = tg;
+      }
     }
+  }
+}
+
+// grid (ceil(C / 32), 2): dw[c] (blockIdx.y 0) or db[c] (1) (+)= sum over images of part[n][blockIdx.y][c].  8 threads per channel
+// each add a contiguous eighth of the images, then one thread adds the eight sums in segment order.
+constexpr int kFoldLanes = 32;
+constexpr int kFoldSeg = kBlock / kFoldLanes;
+__global__ __launch_bounds__(kBlock) void k_grn_param_fold(const float* __restrict__ part, int N, int C, float* __restrict__ dw,
+                                                           float* __restrict__ db, int accumulate) {
+  __shared__ float s_seg[kBlock];
+  const int cl = threadIdx.x % kFoldLanes, seg = threadIdx.x / kFoldLanes, c = blockIdx.x * kFoldLanes + cl, j = blockIdx.y;
+  const int per = (N + kFoldSeg - 1) / kFoldSeg, q0 = seg * per, q1 = min(N, q0 + per);
+  float s = 0.f;
+  if (c < C)
+    for (int q = q0; q < q1; ++q) s += part[((size_t)q * 2 + j) * C + c];
+  s_seg[threadIdx.x] = s;
+  __syncthreads();
+  if (seg == 0 && c < C) {
+    float t = 0.f;
+#pragma unroll
+    for (int k = 0; k < kFoldSeg; ++k) t += s_seg[k * kFoldLanes + cl];
+    float* o = (j ? db : dw) + c;
+    *o = accumulate ? *o + t : t;
   }
 }
 
@@ -212,7 +275,8 @@ template <bool PAIR, bool GRAD>
 int launch_reduce(const void* yh, const void* yl, const void* gh, const void* gl, const float* w, float* out, int n, int p, int c,
                   rart_stream_t stream, const char* what) {
   hipLaunchKernelGGL((k_grn_reduce<PAIR, GRAD>), dim3((c + kSlice - 1) / kSlice, n), dim3(kBlock), 0, (hipStream_t)stream,
-                     (const uint16_t*)yh, (const uint16_t*)yl, (const uint16_t*)gh, (const uint16_t*)gl, w, out, p, c);
+                     (const uint16_t*)yh, (const uint16_t*)yl, (const uint16_t*)gh, (const uint16_t*)gl, w, out, p, c, nullptr, 0.f,
+                     nullptr);
   RART_CHECK_LAUNCH(what);
   return RART_OK;
 }
@@ -306,4 +370,27 @@ int rart_cnx_grn_bwd_apply_pair(const void* g_hi, const void* g_lo, const void* 
   RART_CHECK_ARG(grn_shape_ok(n, p, c), "rart_cnx_grn_bwd_apply_pair: " GRN_SHAPE_MSG);
   return launch_bwd_apply<true>(g_hi, g_lo, y_hi, y_lo, u_hi, u_lo, G, a, w, dh_hi, dh_lo, n, p, c, eps, stream,
                                 "rart_cnx_grn_bwd_apply_pair");
+}
+
+size_t rart_cnx_grn_param_grad_workspace_bytes(int n, int c) {
+  if (!grn_shape_ok(n, 1, c)) return 0;
+  return (size_t)n * 2 * c * sizeof(float);
+}
+
+int rart_cnx_grn_bwd_reduce_train_bf16(const void* g, const void* y, const float* G, const float* w, float* a, float* dw, float* db, int n,
+                                       int p, int c, float eps, int accumulate, void* workspace, size_t workspace_bytes,
+                                       rart_stream_t stream) {
+  RART_CHECK_ARG(g && y && G && w && a && dw && db && workspace, "rart_cnx_grn_bwd_reduce_train_bf16: bad arguments");
+  RART_CHECK_ARG(al16(g) && al16(y), "rart_cnx_grn_bwd_reduce_train_bf16: g / y 16-byte aligned");
+  RART_CHECK_ARG(grn_shape_ok(n, p, c), "rart_cnx_grn_bwd_reduce_train_bf16: " GRN_SHAPE_MSG);
+  RART_CHECK_ARG(workspace_bytes >= rart_cnx_grn_param_grad_workspace_bytes(n, c),
+                 "rart_cnx_grn_bwd_reduce_train_bf16: workspace smaller than rart_cnx_grn_param_grad_workspace_bytes");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL((k_grn_reduce<false, true, true>), dim3((c + kSlice - 1) / kSlice, n), dim3(kBlock), 0, st, (const uint16_t*)y,
+                     (const uint16_t*)y, (const uint16_t*)g, (const uint16_t*)g, w, a, p, c, G, eps, (float*)workspace);
+  RART_CHECK_LAUNCH("rart_cnx_grn_bwd_reduce_train_bf16");
+  hipLaunchKernelGGL(k_grn_param_fold, dim3((c + kFoldLanes - 1) / kFoldLanes, 2), dim3(kBlock), 0, st, (const float*)workspace, n, c, dw,
+                     db, accumulate);
+  RART_CHECK_LAUNCH("rart_cnx_grn_bwd_reduce_train_bf16 (fold)");
+  return RART_OK;
 }

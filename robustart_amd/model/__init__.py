@@ -3,8 +3,8 @@
 Four architectures: `resnet50_official` (forward + backward-to-input HIP engine: engine.py), `vit_base` / `vit_b16_224`
 (forward + backward-to-input HIP engine: vit_engine.py), `convnext_base` (forward + backward-to-input HIP engine:
 convnext_engine.py; train engine: convnext_train_engine.py, drop_path_rate 0 only) and `convnextv2_base` (ConvNeXt-V2-B: forward +
-backward-to-input on the same engine with the GRN kernels; no train engine).  kwargs `num_classes` and `drop_path_rate` are
-accepted (drop path is identity in eval)."""
+backward-to-input on the same engine with the GRN kernels; train engine: the same ConvNeXtTrainEngine, bf16, drop_path_rate 0 only).
+kwargs `num_classes` and `drop_path_rate` are accepted (drop path is identity in eval)."""
 from .resnet_torch import resnet50
 from .vit_torch import vit_base
 from .convnext_torch import convnext_base, convnextv2_base

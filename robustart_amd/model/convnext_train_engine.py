@@ -1,7 +1,8 @@
-"""Train-mode ConvNeXt-B on the HIP kernels: forward, backward to every parameter.
+"""Train-mode ConvNeXt-B and ConvNeXt-V2-B on the HIP kernels: forward, backward to every parameter.
 
-The training step the reference's solver runs for `convnext_base` (exprs/nips_benchmark/{pgd,new}_adv_train/convnext_base/config.yaml:
-AdamW, label_smooth 0.1, EMA, drop_path_rate 0.0 -- no stochastic layers) with every FLOP on HIP kernels:
+The training step the reference's solver runs for `convnext_base` and `convnextv2_base` (exprs/nips_benchmark/{pgd,new}_adv_train/
+{convnext_base,convnextv2}/config.yaml: AdamW, label_smooth 0.1, EMA, drop_path_rate 0.0 -- no stochastic layers) with every FLOP on
+HIP kernels:
 
   forward / backward-to-input      ConvNeXtEngine's bf16 launch helpers (igemm GEMMs, fused dwconv + LayerNorm, transposed dwconv,
                                    downsample parity scatter, pool backward); fc2 runs UNFOLDED into the kept u2 and
@@ -13,6 +14,12 @@ AdamW, label_smooth 0.1, EMA, drop_path_rate 0.0 -- no stochastic layers) with e
   head and stem weights            RowEngine._wgrad (split-K GEMM over transposed operands)
   Linear and conv biases           rart_colsum_bf16 (fc2's comes with the layer-scale backward)
   LayerNorm gamma / beta           rart_layernorm_bwd_full_bf16, fused with the backward to the input
+  ConvNeXt-V2 block (use_grn)      no layer scale: GRN after the GELU (rart_cnx_grn_stats_bf16 into a kept G, rart_cnx_grn_apply_bf16),
+                                   fc2 + bias + residual into the new x_out; kept per block: x_in, the dwconv output, u, G.  Backward:
+                                   fc2's bias by rart_colsum_bf16; gelu(u) and GRN(gelu(u)) recomputed (the same kernels on the same
+                                   operands: the forward's bits) for fc2's weight; fc2's dgrad with no epilogue; GRN's weight and bias
+                                   and the backward's `a` by rart_cnx_grn_bwd_reduce_train_bf16; rart_cnx_grn_bwd_apply_bf16 turns
+                                   fc2's dgrad in place into fc1's pre-activation gradient; the rest as above
 
 Gradients are written into the parameters' `.grad` tensors (views of the flat gradient arena, train/arena.py); `on_grad_ready(param)`
 is called once per parameter, after its gradient is final and nothing reads it again, so the arena may start that bucket's all-reduce.
@@ -28,8 +35,6 @@ class ConvNeXtTrainEngine(ConvNeXtEngine):
     fold_layer_scale = False
 
     def __init__(self, model, device='cuda', on_grad_ready=None):
-        if getattr(model, 'use_grn', False):
-            raise NotImplementedError('ConvNeXtTrainEngine: ConvNeXt-V2 (GRN blocks) has no train engine')
         dp = [b.drop_path for st in model.stages for b in st.blocks if b.drop_path > 0.0]
         if dp:
             raise NotImplementedError('ConvNeXtTrainEngine: drop_path_rate > 0 (stochastic depth) is not implemented; the reference '
@@ -71,6 +76,35 @@ class ConvNeXtTrainEngine(ConvNeXtEngine):
         self._wgrad_direct(x, dz, 1, (rows, 1), c_in, (rows, 1), n_out, n_out, [(0, 0)], 1, lin.weight.grad)
         self._ready(lin.weight)
 
+    def _grn_block_bwd(self, gx, u, G, hid, dh, L, blk, B, P, C):
+        """ConvNeXt-V2 block, fc2 and GRN: from gx (the gradient of x_out = x_in + fc2(GRN(gelu(u)))) -> fc2's and GRN's parameter
+        gradients, and dh = the gradient of fc1's pre-activation u.  y = gelu(u) goes to `hid`, z = GRN(y) to `dh` until fc2's weight
+        gradient has read it; then fc2's dgrad overwrites dh with the gradient of z, which the GRN backward turns in place into dh."""
+        torch = _lib.require_gpu()
+        lib, sp, rows, c4 = self.lib, _lib.stream_ptr(), B * P, 4 * C
+        mlp = blk.mlp
+        # 1. fc2 bias: the column sum of gx
+        self._colsum(gx, C, rows, C, mlp.fc2.bias.grad)
+        self._ready(mlp.fc2.bias)
+        # 2. y = gelu(u), z = GRN(y) (the forward's bits: same kernels, same operands), fc2 weight from z and gx
+        _lib.check(lib.rart_gelu_bf16(_lib.ptr(u), _lib.ptr(hid), u.numel(), sp))
+        _lib.check(lib.rart_cnx_grn_apply_bf16(_lib.ptr(hid), _lib.ptr(G), _lib.ptr(L['grn_w']), _lib.ptr(L['grn_b']), _lib.ptr(dh), B, P, c4,
+                                               1e-6, sp))
+        self._linear_wgrad(mlp.fc2, dh, gx, rows)
+        # 3. fc2 dgrad, no epilogue: g = the gradient of z
+        self._mm(gx, L['fc2_wd'], dh, rows, c4, C)
+        # 4. a = w * sum_p g y for the GRN backward, GRN's weight and bias gradients
+        a = self._get('g_grn_a', (B, c4), torch.float32)
+        need = lib.rart_cnx_grn_param_grad_workspace_bytes(B, c4)
+        ws = self._scratch('grn_ws', need)
+        _lib.check(lib.rart_cnx_grn_bwd_reduce_train_bf16(_lib.ptr(dh), _lib.ptr(hid), _lib.ptr(G), _lib.ptr(L['grn_w']), _lib.ptr(a),
+                                                          _lib.ptr(mlp.grn.weight.grad), _lib.ptr(mlp.grn.bias.grad), B, P, c4, 1e-6, 0,
+                                                          _lib.ptr(ws), need, sp))
+        self._ready(mlp.grn.weight, mlp.grn.bias)
+        # 5. in place: the gradient of u, GELU' included
+        _lib.check(lib.rart_cnx_grn_bwd_apply_bf16(_lib.ptr(dh), _lib.ptr(hid), _lib.ptr(u), _lib.ptr(G), _lib.ptr(a), _lib.ptr(L['grn_w']),
+                                                   _lib.ptr(dh), B, P, c4, 1e-6, sp))
+
     # ------------------------------------------------------------------ forward
     def forward(self, src, src_is_u8, mean, std):
         """train-mode forward -> fp32 logits [B][classes]; keeps what backward() needs"""
@@ -106,17 +140,26 @@ class ConvNeXtTrainEngine(ConvNeXtEngine):
             ln = self._get('t_ln%d' % si, (rows, C))
             hid = self._get('t_hid%d' % si, (rows, 4 * C))
             for bi, L in enumerate(S['blocks']):
-                gamma = self.model.stages[si].blocks[bi].gamma
                 y = self._get('t_y%d_%d' % (si, bi), (rows, C))
                 u = self._get('t_u%d_%d' % (si, bi), (rows, 4 * C))
-                u2 = self._get('t_u2_%d_%d' % (si, bi), (rows, C))
                 xo = self._get('t_x%d_%d' % (si, bi + 1), (rows, C))    # a new buffer: the block input stays for the backward
                 self._dwconv_ln(x, L, ln, y, B, H, W, C)
                 self._mm(ln, L['fc1_w'], u, rows, 4 * C, C, bias=L['fc1_b'])
                 _lib.check(lib.rart_gelu_bf16(_lib.ptr(u), _lib.ptr(hid), u.numel(), sp))
-                self._mm(hid, L['fc2_w'], u2, rows, C, 4 * C, bias=L['fc2_b'])             # unscaled fc2 output, kept
-                _lib.check(lib.rart_cnx_layer_scale_fwd_bf16(_lib.ptr(x), _lib.ptr(u2), _lib.ptr(gamma.detach()), _lib.ptr(xo), rows, C, sp))
-                blocks.append((x, y, u, u2))
+                if self.grn:
+                    # ConvNeXt-V2: GRN in place over the GELU output, fc2 + bias + residual into the new buffer; u and G are kept,
+                    # gelu(u) and GRN are recomputed bit-identically in the backward
+                    G = self._get('t_grn_G%d_%d' % (si, bi), (B, 4 * C), torch.float32)
+                    self._grn(hid, L, G, hid, B, H * W, 4 * C)
+                    self._mm(hid, L['fc2_w'], xo, rows, C, 4 * C, bias=L['fc2_b'], res=x)
+                    blocks.append((x, y, u, G))
+                else:
+                    gamma = self.model.stages[si].blocks[bi].gamma
+                    u2 = self._get('t_u2_%d_%d' % (si, bi), (rows, C))
+                    self._mm(hid, L['fc2_w'], u2, rows, C, 4 * C, bias=L['fc2_b'])             # unscaled fc2 output, kept
+                    _lib.check(lib.rart_cnx_layer_scale_fwd_bf16(_lib.ptr(x), _lib.ptr(u2), _lib.ptr(gamma.detach()), _lib.ptr(xo), rows, C,
+                                                                 sp))
+                    blocks.append((x, y, u, u2))
                 x = xo
         cl = self.dims[-1]
         pooled = self._get('t_pooled', (B, cl))
@@ -154,29 +197,33 @@ class ConvNeXtTrainEngine(ConvNeXtEngine):
         for si in range(n_st - 1, -1, -1):
             S, C, stage = self.stages[si], self.dims[si], m.stages[si]
             rows = B * H * W
-            dv = self._get('g_dv%d' % si, (rows, C))
+            dv = None if self.grn else self._get('g_dv%d' % si, (rows, C))
             hid = self._get('t_hid%d' % si, (rows, 4 * C))
             dh = self._get('g_hid%d' % si, (rows, 4 * C))
             ln = self._get('t_ln%d' % si, (rows, C))
             dln = self._get('g_ln%d' % si, (rows, C))
             dz = self._get('g_dz%d' % si, (rows, C))
-            ls_need = lib.rart_cnx_layer_scale_bwd_workspace_bytes(rows, C)
+            ls_need = 0 if self.grn else lib.rart_cnx_layer_scale_bwd_workspace_bytes(rows, C)
             dw_need = lib.rart_cnx_dwconv_wgrad_workspace_bytes(B, H, W, C)
             for bi in range(len(S['blocks']) - 1, -1, -1):
                 L, blk = S['blocks'][bi], stage.blocks[bi]
                 k -= 1
-                x_in, y, u, u2 = blocks[k]
-                # 1. layer scale: x_out = x_in + gamma * u2 -> dgamma, dv = gamma * dx, fc2's bias gradient
-                ws = self._scratch('ls_ws', ls_need)
-                _lib.check(lib.rart_cnx_layer_scale_bwd_bf16(_lib.ptr(gx), _lib.ptr(u2), _lib.ptr(blk.gamma.detach()), _lib.ptr(dv),
-                                                             _lib.ptr(blk.gamma.grad), _lib.ptr(blk.mlp.fc2.bias.grad), rows, C, 0,
-                                                             _lib.ptr(ws), ls_need, sp))
-                self._ready(blk.gamma, blk.mlp.fc2.bias)
-                # 2. fc2 weight from dv and gelu(u)
-                _lib.check(lib.rart_gelu_bf16(_lib.ptr(u), _lib.ptr(hid), u.numel(), sp))
-                self._linear_wgrad(blk.mlp.fc2, hid, dv, rows)
-                # 3. fc2 dgrad with GELU' of the kept pre-activation
-                self._mm(dv, L['fc2_wd'], dh, rows, 4 * C, C, flags=F_GELU_BWD, aux=u)
+                if self.grn:
+                    x_in, y, u, G = blocks[k]
+                    self._grn_block_bwd(gx, u, G, hid, dh, L, blk, B, H * W, C)
+                else:
+                    x_in, y, u, u2 = blocks[k]
+                    # 1. layer scale: x_out = x_in + gamma * u2 -> dgamma, dv = gamma * dx, fc2's bias gradient
+                    ws = self._scratch('ls_ws', ls_need)
+                    _lib.check(lib.rart_cnx_layer_scale_bwd_bf16(_lib.ptr(gx), _lib.ptr(u2), _lib.ptr(blk.gamma.detach()), _lib.ptr(dv),
+                                                                 _lib.ptr(blk.gamma.grad), _lib.ptr(blk.mlp.fc2.bias.grad), rows, C, 0,
+                                                                 _lib.ptr(ws), ls_need, sp))
+                    self._ready(blk.gamma, blk.mlp.fc2.bias)
+                    # 2. fc2 weight from dv and gelu(u)
+                    _lib.check(lib.rart_gelu_bf16(_lib.ptr(u), _lib.ptr(hid), u.numel(), sp))
+                    self._linear_wgrad(blk.mlp.fc2, hid, dv, rows)
+                    # 3. fc2 dgrad with GELU' of the kept pre-activation
+                    self._mm(dv, L['fc2_wd'], dh, rows, 4 * C, C, flags=F_GELU_BWD, aux=u)
                 # 4. fc1 weight and bias from dh and LN(y), recomputed
                 _lib.check(lib.rart_layernorm_bf16(_lib.ptr(y), _lib.ptr(L['ng']), _lib.ptr(L['nb']), _lib.ptr(ln), rows, C, C, C, 1e-6, sp))
                 self._linear_wgrad(blk.mlp.fc1, ln, dh, rows)

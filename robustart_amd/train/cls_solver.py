@@ -539,10 +539,12 @@ def train(cfg, args, rank, world, device):
     max_iter, warmup_steps = resolve_schedule(cfg, n, bs, world, getattr(args, 'max_iter', 20))
     model = build_model(cfg, args).to(device)
     from ..model.convnext_torch import ConvNeXt, ConvNeXtV2
-    if isinstance(model, ConvNeXtV2):
-        raise NotImplementedError('training %r: ConvNeXt-V2 has no train engine (its forward and backward-to-input run on the HIP eval '
-                                  'engine, for evaluation and attacks; GRN parameter gradients are not built)' % cfg['model']['type'])
-    if isinstance(model, ConvNeXt) and not (device.type == 'cuda' and args.engine == 'hip' and getattr(args, 'train_engine', 'hip') == 'hip'):
+    on_hip = device.type == 'cuda' and args.engine == 'hip' and getattr(args, 'train_engine', 'hip') == 'hip'
+    if isinstance(model, ConvNeXtV2) and not on_hip:
+        raise NotImplementedError('training %r on %s with --engine %s --train-engine %s: ConvNeXt-V2 trains only on ConvNeXtTrainEngine, '
+                                  'on the GPU with --engine hip --train-engine hip (there is no CPU or torch-engine path)'
+                                  % (cfg['model']['type'], device.type, args.engine, getattr(args, 'train_engine', 'hip')))
+    if isinstance(model, ConvNeXt) and not on_hip:
         raise NotImplementedError('training %r on %s with --engine %s --train-engine %s: there is no ConvNeXt train engine on this path; '
                                   'ConvNeXtTrainEngine runs on the GPU with --engine hip --train-engine hip'
                                   % (cfg['model']['type'], device.type, args.engine, getattr(args, 'train_engine', 'hip')))
