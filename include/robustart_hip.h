@@ -948,6 +948,27 @@ int rart_cnx_grn_bwd_reduce_train_bf16(const void* g, const void* y, const float
                                        int p, int c, float eps, int accumulate, void* workspace, size_t workspace_bytes,
                                        rart_stream_t stream);
 
+/* Token-mixing GEMM of MLP-Mixer (csrc/mixer.hip): per image b of `batch`,
+ *   C_b[m][n] = sum_k A[m][k] X_b[k][n]     (m < M, n < N, k < K; fp32 accumulation)
+ * a_*: the weight table [M][lda], K contiguous, shared by every image; lda >= K rounded up to 32 and a multiple of 8, columns K .. lda - 1
+ *   zero.  x_*: image b's activation slab [K][ldx] (n contiguous) at element b * x_stride; rows k >= K are never read (zeros instead).
+ * dst_*: image b's [M][ldc] at element b * c_stride; res_* (indexed like dst, may alias it), aux_* (likewise).  bias: fp32 [M] or null.
+ * The epilogue (fp32): + bias[m]; + res; then flag 4 = GELU (of the value rounded to the output format of u), 64 = the same GELU with u
+ * written to aux, 8 = times gelu'(aux); flag 2 = fp32 output (dst_hi as float*).  rart_tokmix_bf16: bf16 planes (the *_lo are unused);
+ * rart_tokmix_pair: hi + lo bf16 planes of A, X, res, aux and dst, three MFMA products hi.hi + hi.lo + lo.hi per contraction (the
+ * arithmetic of rart_gemm_pair_bf16).  N, ldx, x_stride: multiples of 8; A and X planes 16-byte aligned.  No result depends on the batch. */
+typedef struct rart_tokmix_desc {
+  const void *a_hi, *a_lo, *x_hi, *x_lo;
+  void *dst_hi, *dst_lo;
+  const void *res_hi, *res_lo;
+  void *aux_hi, *aux_lo;
+  const float* bias;
+  int M, N, K, lda, ldx, ldc, batch, flags;
+  int64_t x_stride, c_stride;
+} rart_tokmix_desc;
+int rart_tokmix_bf16(const rart_tokmix_desc* desc, rart_stream_t stream);
+int rart_tokmix_pair(const rart_tokmix_desc* desc, rart_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,6 +167,8 @@ SIGNATURES = {
     'rart_cnx_grn_bwd_apply_pair': (c_int, [c_void_p] * 11 + [c_int] * 3 + [c_float, c_void_p]),
     'rart_cnx_grn_param_grad_workspace_bytes': (c_size_t, [c_int] * 2),
     'rart_cnx_grn_bwd_reduce_train_bf16': (c_int, [c_void_p] * 7 + [c_int] * 3 + [c_float, c_int, c_void_p, c_size_t, c_void_p]),
+    'rart_tokmix_bf16': (c_int, [c_void_p, c_void_p]),
+    'rart_tokmix_pair': (c_int, [c_void_p, c_void_p]),
     'rart_vit_patchify': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                   c_void_p]),
     'rart_vit_add_pos_cls': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
@@ -256,6 +258,13 @@ class GemmPairDesc(ctypes.Structure):
                [('tap_dy', ctypes.c_int32 * 16), ('tap_dx', ctypes.c_int32 * 16)] + \
                [(n, ctypes.c_int32) for n in ('dst_h', 'dst_w', 'dst_sy', 'dst_sx', 'dst_oy', 'dst_ox')] + \
                [('mask_bits', c_void_p), ('sign_out', c_void_p), ('tile_n', ctypes.c_int32), ('tile_m', ctypes.c_int32)]
+
+
+class TokmixDesc(ctypes.Structure):
+    """rart_tokmix_desc (include/robustart_hip.h): MLP-Mixer's token-mixing GEMM, bf16 or pair."""
+    _fields_ = [(n, c_void_p) for n in ('a_hi', 'a_lo', 'x_hi', 'x_lo', 'dst_hi', 'dst_lo', 'res_hi', 'res_lo', 'aux_hi', 'aux_lo', 'bias')] + \
+               [(n, ctypes.c_int32) for n in ('M', 'N', 'K', 'lda', 'ldx', 'ldc', 'batch', 'flags')] + \
+               [(n, ctypes.c_int64) for n in ('x_stride', 'c_stride')]
 
 
 class ConvTailDesc(ctypes.Structure):

@@ -1,17 +1,19 @@
 """Model zoo entry point -- mirrors RobustART/model/__init__.py:1 (`get_model`).
 
-Four architectures: `resnet50_official` (forward + backward-to-input HIP engine: engine.py), `vit_base` / `vit_b16_224`
+Five architectures: `resnet50_official` (forward + backward-to-input HIP engine: engine.py), `vit_base` / `vit_b16_224`
 (forward + backward-to-input HIP engine: vit_engine.py), `convnext_base` (forward + backward-to-input HIP engine:
 convnext_engine.py; train engine: convnext_train_engine.py, drop_path_rate 0 only) and `convnextv2_base` (ConvNeXt-V2-B: forward +
-backward-to-input on the same engine with the GRN kernels; train engine: the same ConvNeXtTrainEngine, bf16, drop_path_rate 0 only).
+backward-to-input on the same engine with the GRN kernels; train engine: the same ConvNeXtTrainEngine, bf16, drop_path_rate 0 only)
+and `mixer_b16_224` (MLP-Mixer-B/16: forward + backward-to-input HIP engine: mixer_engine.py; no train engine).
 kwargs `num_classes` and `drop_path_rate` are accepted (drop path is identity in eval)."""
 from .resnet_torch import resnet50
 from .vit_torch import vit_base
 from .convnext_torch import convnext_base, convnextv2_base
+from .mixer_torch import mixer_b16_224
 
 _REGISTRY = {'resnet50_official': resnet50, 'resnet50': resnet50, 'vit_base': vit_base, 'vit_b16_224': vit_base,
              'vit_base_patch16_224': vit_base, 'convnext_base': convnext_base,
-             'convnextv2_base': convnextv2_base}
+             'convnextv2_base': convnextv2_base, 'mixer_b16_224': mixer_b16_224}
 
 
 def get_model(config):
@@ -21,5 +23,5 @@ def get_model(config):
     kwargs = dict((config.get('kwargs') if isinstance(config, dict) else getattr(config, 'kwargs', None)) or {})
     kwargs.pop('bn', None)          # {use_sync_bn: False}: BN statistics are local
     if mtype not in _REGISTRY:
-        raise NotImplementedError('model type %r is outside the hot-path scope (ResNet-50 / ViT-B/16 / ConvNeXt-B / ConvNeXt-V2-B only)' % mtype)
+        raise NotImplementedError('model type %r is outside the hot-path scope (ResNet-50 / ViT-B/16 / ConvNeXt-B / ConvNeXt-V2-B / MLP-Mixer-B/16 only)' % mtype)
     return _REGISTRY[mtype](**kwargs)

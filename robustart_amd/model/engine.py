@@ -1039,8 +1039,8 @@ class ResNet50Engine(EngineBase):
 
 
 def make_engine(torch_model, device='cuda', precision='bf16'):
-    """HIP engine for a model from robustart_amd.model.get_model: ResNet-50, ViT-B/16, ConvNeXt-B or ConvNeXt-V2-B (a ConvNeXt
-    subclass: ConvNeXtEngine runs its GRN blocks), each with forward and
+    """HIP engine for a model from robustart_amd.model.get_model: ResNet-50, ViT-B/16, ConvNeXt-B, ConvNeXt-V2-B (a ConvNeXt
+    subclass: ConvNeXtEngine runs its GRN blocks) or MLP-Mixer-B/16 (MixerEngine), each with forward and
     backward-to-input (`forward_backward`) on the hand-written kernels.  precision 'bf16x3' / 'fp32x': the
     reference-precision mode (both architectures: split-bf16 pairs, three MFMA products per contraction)."""
     from .resnet_torch import ResNet
@@ -1054,7 +1054,12 @@ def make_engine(torch_model, device='cuda', precision='bf16'):
     if isinstance(torch_model, ConvNeXt):
         from .convnext_engine import ConvNeXtEngine
         return ConvNeXtEngine(torch_model, device, precision)
-    raise NotImplementedError('no HIP engine for %s (ResNet-50 / ViT-B/16 / ConvNeXt-B / ConvNeXt-V2-B only)' % type(torch_model).__name__)
+    from .mixer_torch import MlpMixer
+    if isinstance(torch_model, MlpMixer):
+        from .mixer_engine import MixerEngine
+        return MixerEngine(torch_model, device, precision)
+    raise NotImplementedError('no HIP engine for %s (ResNet-50 / ViT-B/16 / ConvNeXt-B / ConvNeXt-V2-B / MLP-Mixer-B/16 only)'
+                              % type(torch_model).__name__)
 
 
 class EngineModel:

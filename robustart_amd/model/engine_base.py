@@ -173,6 +173,31 @@ def gemm_pair_desc(a, w, dst, N, lda, ldw, ldc, w_rows, M=0, K=0, bias=None, res
     return d
 
 
+def tokmix_desc(a, x, dst, M, N, K, batch, x_stride, c_stride, ldx=None, ldc=None, bias=None, res=None, aux=None, flags=0, pair=False):
+    """rart_tokmix_desc of MLP-Mixer's token-mixing GEMM: C_b[m][n] = sum_k A[m][k] X_b[k][n] for images b < batch.  a: the weight table
+    [M][lda] (K padded with zero columns; a pair [2][M][lda] when `pair`); x / dst / res / aux: per-image slabs x_stride / c_stride
+    elements apart (pairs [2][...] when `pair`, dst a plain fp32 tensor with GP_OUT_F32); ldx / ldc default to N."""
+    d = _lib.TokmixDesc()
+    if pair:
+        d.a_hi, d.a_lo, d.x_hi, d.x_lo = a[0].data_ptr(), a[1].data_ptr(), x[0].data_ptr(), x[1].data_ptr()
+        if flags & GP_OUT_F32:
+            d.dst_hi = dst.data_ptr()
+        else:
+            d.dst_hi, d.dst_lo = dst[0].data_ptr(), dst[1].data_ptr()
+        if res is not None:
+            d.res_hi, d.res_lo = res[0].data_ptr(), res[1].data_ptr()
+        if aux is not None:
+            d.aux_hi, d.aux_lo = aux[0].data_ptr(), aux[1].data_ptr()
+    else:
+        d.a_hi, d.x_hi, d.dst_hi, d.res_hi, d.aux_hi = a.data_ptr(), x.data_ptr(), dst.data_ptr(), _addr(res), _addr(aux)
+    d.bias = _addr(bias)
+    d.M, d.N, d.K, d.lda = M, N, K, a.shape[-1]
+    d.ldx, d.ldc = ldx or N, ldc or N
+    d.batch, d.flags = batch, flags
+    d.x_stride, d.c_stride = x_stride, c_stride
+    return d
+
+
 # ---------------------------------------------------------------------- split-K weight gradients
 def wgrad_split_direct(M, x_c, n_taps, n_cols, target_wgs, min_chunk):
     """-> (splits, chunk) of rart_wgrad_direct_bf16 over M output positions: about target_wgs workgroups in all, chunks of at least
@@ -258,6 +283,13 @@ class EngineBase:
         _lib.check(self.lib.rart_gemm_pair_bf16(ctypes.byref(d), _lib.stream_ptr()))
         if ev is not None:
             self._prof_end(ev, 3 * 2.0 * max(d.n_batched, 1) * d.M * d.N * d.K, 'gemm_pair', nbytes)
+
+    def _launch_tokmix(self, d, pair):
+        """rart_tokmix_{bf16,pair} on descriptor d; profiled as 'tokmix' (MFMA FLOPs issued: three products in pair form)"""
+        ev = self._prof_begin()
+        _lib.check((self.lib.rart_tokmix_pair if pair else self.lib.rart_tokmix_bf16)(ctypes.byref(d), _lib.stream_ptr()))
+        if ev is not None:
+            self._prof_end(ev, (3 if pair else 1) * 2.0 * d.batch * d.M * d.N * d.K, 'tokmix')
 
     def _wgrad_direct(self, x, dz, B, x_hw, x_c, grid_hw, n_out, n_pad_cols, taps, stride, grad, c_valid=None):
         """grad[n_out][c][taps] = sum over positions m of dz[m][n] * x[pixel(m) + tap][c] straight from the NHWC activations

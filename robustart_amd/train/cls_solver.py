@@ -537,7 +537,12 @@ def train(cfg, args, rank, world, device):
     ds = make_dataset(dcfg, n, size, 'train')
     n = len(ds)
     max_iter, warmup_steps = resolve_schedule(cfg, n, bs, world, getattr(args, 'max_iter', 20))
-    model = build_model(cfg, args).to(device)
+    model = build_model(cfg, args)
+    from ..model.mixer_torch import MlpMixer
+    if isinstance(model, MlpMixer):
+        raise NotImplementedError('training %r: MLP-Mixer has no train engine on this path (evaluation and attacks run on MixerEngine; '
+                                  'training is not built on any engine or device)' % (cfg['model']['type'],))
+    model = model.to(device)
     from ..model.convnext_torch import ConvNeXt, ConvNeXtV2
     on_hip = device.type == 'cuda' and args.engine == 'hip' and getattr(args, 'train_engine', 'hip') == 'hip'
     if isinstance(model, ConvNeXtV2) and not on_hip:
