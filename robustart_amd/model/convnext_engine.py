@@ -25,8 +25,8 @@ no host synchronisation."""
 import ctypes
 
 from .. import _lib
-from .engine_base import (F_GELU, F_GELU_BWD, F_GELU_KEEP, F_OUT_F32, RowEngine, conv_desc, gemm_pair_desc, lo_off, pad_k, pad_rows, pair,
-                          rows_mult)
+from .engine_base import (F_GELU, F_GELU_BWD, F_GELU_KEEP, F_OUT_F32, RowEngine, conv_desc, gemm_pair_desc, k32, lo_off, pad_k, pad_rows,
+                          pair, rows_mult)
 
 STEM_K = 64                      # 3 x 4 x 4 = 48 columns, padded to the K granularity of both GEMMs
 DS_TAPS = [(0, 0), (0, 1), (1, 0), (1, 1)]
@@ -38,7 +38,6 @@ class ConvNeXtEngine(RowEngine):
     def __init__(self, model, device='cuda', precision='bf16'):
         """precision: 'bf16' (fast path) or 'bf16x3' / 'fp32x' (reference precision: split-bf16 pairs throughout)."""
         super().__init__(device, precision)
-        self.x3 = self.precision == 'bf16x3'
         self.refold(model)
 
     def refold(self, model):
@@ -101,27 +100,13 @@ class ConvNeXtEngine(RowEngine):
             self.stages.append(S)
         self.head_g, self.head_nb = f32(m.head.norm.weight), f32(m.head.norm.bias)
         self.n_classes = m.head.fc.out_features
-        self.head_kpad = (self.n_classes + 31) // 32 * 32
+        self.head_kpad = k32(self.n_classes)
         hw = f32(m.head.fc.weight)
         self.head_w = fwd(hw)
         self.head_wd = bwd(pad_k(hw.t(), self.head_kpad))
         self.head_b = f32(m.head.fc.bias)
 
-    # ------------------------------------------------------------------ precision-generic launch helpers
-    def _act(self, name, shape):
-        """activation buffer: bf16 [shape], or the pair [2][shape]"""
-        return self._get(name, ((2,) + tuple(shape)) if self.x3 else tuple(shape))
-
-    def _hl(self, t):
-        return (_lib.ptr(t[0]), _lib.ptr(t[1])) if self.x3 else (_lib.ptr(t), None)
-
-    def _mm(self, a, w, dst, M, N, K, bias=None, res=None, flags=0, aux=None):
-        """dst[M][N] = a[M][K] . w[N][K]^T (+ bias, + res, epilogue flags; aux = the GELU pre-activation kept / read)"""
-        if self.x3:
-            self._gemm_pair(a, w, dst, M, N, K, K, N, bias=bias, res=res, flags=flags, aux=aux)
-        else:
-            self._gemm(a, w, dst, M, K, N, K, N, bias=bias, res=res, flags=flags, mask=aux)
-
+    # ------------------------------------------------------------------ ConvNeXt's own precision-generic launches
     def _conv(self, src, w, dst, B, grid, src_hw, k_per_tap, taps, n_cols, dst_hw, stride, dst_stride, dst_off, bias=None):
         """implicit-GEMM convolution on NHWC src (k_per_tap channels per pixel) -> dst (n_cols channels per pixel)"""
         if self.x3:
@@ -131,23 +116,6 @@ class ConvNeXtEngine(RowEngine):
         else:
             self._launch_conv(conv_desc(src, w, dst, B, grid, src_hw, k_per_tap, k_per_tap, taps, n_cols, dst_hw, n_cols, bias=bias,
                                         stride=stride, dst_stride=dst_stride, dst_org=dst_off))
-
-    def _ln(self, x, g, b, out, rows, c):
-        lib, sp = self.lib, _lib.stream_ptr()
-        if self.x3:
-            (xh, xl), (oh, ol) = self._hl(x), self._hl(out)
-            _lib.check(lib.rart_layernorm_pair(xh, xl, _lib.ptr(g), _lib.ptr(b), oh, ol, rows, c, c, c, 1e-6, sp))
-        else:
-            _lib.check(lib.rart_layernorm_bf16(_lib.ptr(x), _lib.ptr(g), _lib.ptr(b), _lib.ptr(out), rows, c, c, c, 1e-6, sp))
-
-    def _ln_bwd(self, dy, x, g, dx, rows, c):
-        lib, sp = self.lib, _lib.stream_ptr()
-        if self.x3:
-            (dh, dl), (xh, xl), (oh, ol) = self._hl(dy), self._hl(x), self._hl(dx)
-            _lib.check(lib.rart_layernorm_bwd_pair(dh, dl, xh, xl, _lib.ptr(g), None, None, oh, ol, rows, c, c, c, 0, c, 1e-6, sp))
-        else:
-            _lib.check(lib.rart_layernorm_bwd_bf16(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(g), None, _lib.ptr(dx), rows, c, c, c, 0, c,
-                                                   1e-6, sp))
 
     def _dwconv_ln(self, x, L, out, y, B, H, W, C):
         lib, sp = self.lib, _lib.stream_ptr()
@@ -303,15 +271,11 @@ class ConvNeXtEngine(RowEngine):
         loss, dl, pred = logit_loss(logits, y, kind, y_target, scale)
         self.last_dlogits = dl
         cl, kp = self.dims[-1], self.head_kpad
-        dlb = self._act('g_dl', (B, kp))
-        if self.x3:
-            _lib.check(lib.rart_f32_to_pair_rows(_lib.ptr(dl), _lib.ptr(dlb[0]), dlb[0].numel(), B, self.n_classes, kp, sp))
-        else:
-            _lib.check(lib.rart_f32_to_bf16_rows(_lib.ptr(dl), _lib.ptr(dlb), B, self.n_classes, kp, sp))
+        dlb = self._dlogits_rows(dl, 'g_dl', B, kp)
         dpl = self._act('g_pooled_ln', (B, cl))
         self._mm(dlb, self.head_wd, dpl, B, cl, kp)
         dpooled = self._act('g_pooled', (B, cl))
-        self._ln_bwd(dpl, pooled, self.head_g, dpooled, B, cl)
+        self._ln_bwd(dpl, pooled, self.head_g, None, dpooled, B, cl)
         H, W = Himg // 32, Wimg // 32
         n_st = len(self.stages)
         gx = self._act('g_x%d' % (n_st - 1), (B * H * W, cl))
@@ -337,7 +301,7 @@ class ConvNeXtEngine(RowEngine):
                     yk, u = saved[k]
                     self._mm(gx, L['fc2_wd'], dh, rows, 4 * C, C, flags=F_GELU_BWD, aux=u)   # (g W2') * gelu'(u)
                 self._mm(dh, L['fc1_wd'], dln, rows, C, 4 * C)
-                self._ln_bwd(dln, yk, L['ng'], dz, rows, C)
+                self._ln_bwd(dln, yk, L['ng'], None, dz, rows, C)
                 self._dwconv_bwd(dz, L, gx, gx, B, H, W, C)                                   # residual + transposed 7x7, in place
             if si > 0:
                 cin = self.dims[si - 1]
@@ -345,11 +309,11 @@ class ConvNeXtEngine(RowEngine):
                 self._downsample_scatter(gx, S, gds, B, 2 * H, 2 * W)
                 H, W = 2 * H, 2 * W
                 gprev = self._act('g_x%d' % (si - 1), (B * H * W, cin))
-                self._ln_bwd(gds, stage_out[si - 1], S['ds_g'], gprev, B * H * W, cin)
+                self._ln_bwd(gds, stage_out[si - 1], S['ds_g'], None, gprev, B * H * W, cin)
                 gx = gprev
         c0, rows = self.dims[0], B * H * W
         gs = self._act('g_stem', (rows, c0))
-        self._ln_bwd(gx, xs, self.stem_g, gs, rows, c0)
+        self._ln_bwd(gx, xs, self.stem_g, None, gs, rows, c0)
         dpatch = self._get('g_patch', (rows, STEM_K), torch.float32)
         self._mm(gs, self.stem_wd, dpatch, rows, STEM_K, c0, flags=F_OUT_F32)
         grad = torch.empty(B, 3, Himg, Wimg, dtype=torch.float32, device=self.device)

@@ -181,8 +181,7 @@ class ConvNeXtTrainEngine(ConvNeXtEngine):
         # ---- head: logits = fc(LN(mean_hw(x)))
         m.head.fc.bias.grad.copy_(dl.sum(0))
         self._ready(m.head.fc.bias)
-        dlb = self._get('g_dl', (B, kp))
-        _lib.check(lib.rart_f32_to_bf16_rows(_lib.ptr(dl), _lib.ptr(dlb), B, self.n_classes, kp, sp))
+        dlb = self._dlogits_rows(dl, 'g_dl', B, kp)
         self._wgrad(dlb, self.n_classes, kp, pl, cl, m.head.fc.weight.grad, B)
         self._ready(m.head.fc.weight)
         dpl = self._get('g_pooled_ln', (B, cl))
@@ -225,7 +224,7 @@ class ConvNeXtTrainEngine(ConvNeXtEngine):
                     # 3. fc2 dgrad with GELU' of the kept pre-activation
                     self._mm(dv, L['fc2_wd'], dh, rows, 4 * C, C, flags=F_GELU_BWD, aux=u)
                 # 4. fc1 weight and bias from dh and LN(y), recomputed
-                _lib.check(lib.rart_layernorm_bf16(_lib.ptr(y), _lib.ptr(L['ng']), _lib.ptr(L['nb']), _lib.ptr(ln), rows, C, C, C, 1e-6, sp))
+                self._ln(y, L['ng'], L['nb'], ln, rows, C)
                 self._linear_wgrad(blk.mlp.fc1, ln, dh, rows)
                 self._colsum(dh, 4 * C, rows, 4 * C, blk.mlp.fc1.bias.grad)
                 self._ready(blk.mlp.fc1.bias)

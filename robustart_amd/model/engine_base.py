@@ -2,8 +2,8 @@
 helpers, the split-K heuristics of the weight gradient, and `EngineBase` (device, buffers, profiling) that every engine inherits.
 
 The builders take tensors or None and only read `data_ptr()`, so they run on CPU tensors as well.  Every engine keeps the adapter that
-encodes its own convention: ResNet-50's conv form and [hi | lo | hi] weight tables (engine.py), the row form of ViT-B/16 and ConvNeXt
-(`RowEngine` below), ConvNeXt's precision dispatch (convnext_engine.py)."""
+encodes its own convention: ResNet-50's conv form and [hi | lo | hi] weight tables (engine.py), the row form of ViT-B/16, MLP-Mixer and
+ConvNeXt with its precision-generic launches (`RowEngine` below)."""
 import ctypes
 
 from .. import _lib
@@ -45,6 +45,11 @@ def lo_off(t):
 # ---------------------------------------------------------------------- weight tables
 def rows_mult(n_cols):
     return 128 if n_cols > 64 else 64
+
+
+def k32(n):
+    """n rounded up to the 32-deep K step of the GEMMs"""
+    return (n + 31) // 32 * 32
 
 
 def pad_rows(w, mult):
@@ -241,6 +246,11 @@ class EngineBase:
         self._buf = {}
         self._w_il = {}          # interleaved copies of pair weight tables (GP_W_INTERLEAVED), keyed by the table's address
 
+    @property
+    def x3(self):
+        """reference precision: every activation, gradient and weight a hi + lo pair of bf16 planes"""
+        return self.precision == 'bf16x3'
+
     def _get(self, name, shape, dtype=None, zero=False):
         torch = _lib.require_gpu()
         dtype = dtype or torch.bfloat16
@@ -321,7 +331,9 @@ class EngineBase:
 
 
 class RowEngine(EngineBase):
-    """The row form of ViT-B/16 and ConvNeXt: activations are dense [rows][features] matrices (tokens, NHWC pixels)."""
+    """The row form of ViT-B/16, MLP-Mixer and ConvNeXt: activations are dense [rows][features] matrices (tokens, NHWC pixels).
+    `_gemm` / `_gemm_pair` are the two GEMM launchers; the helpers after them take either precision: a bf16 tensor or a pair
+    [2][...], the bf16 or the pair library entry."""
 
     def _gemm(self, src, wgt, dst, rows, k, n_cols, src_ld, dst_ld, bias=None, res=None, flags=0, n_taps=1,
               tap_src_off=None, rows_per_image=None, dst_rows_per_image=None, dst_row_off=0, batched=None,
@@ -344,6 +356,80 @@ class RowEngine(EngineBase):
                                          w_il=il if il is not None and il.shape[1] == 2 * K else None, rows_per_image=rows_per_image,
                                          src_rows_per_image=src_rows_per_image, src_row_off=src_row_off,
                                          dst_rows_per_image=dst_rows_per_image, dst_row_off=dst_row_off, batched=batched))
+
+    # ------------------------------------------------------------------ precision-generic launches
+    def _act(self, name, shape):
+        """activation buffer: bf16 [shape], or the pair [2][shape]"""
+        return self._get(name, ((2,) + tuple(shape)) if self.x3 else tuple(shape))
+
+    def _hl(self, t):
+        return (_lib.ptr(t[0]), _lib.ptr(t[1])) if self.x3 else (_lib.ptr(t), None)
+
+    def _mm(self, a, w, dst, M, N, K, lda=None, ldc=None, aux=None, src_row_off=0, **kw):
+        """dst[M][N] = a[M][K] . w[N][K]^T; kw: bias, res, flags (the F_* values, which the GP_* flags share; aux = the GELU
+        pre-activation kept / read) and rows_per_image, src_rows_per_image, dst_rows_per_image, dst_row_off: image b's rows are
+        src_rows_per_image * b + src_row_off + (0 .. rows_per_image) of a and dst_rows_per_image * b + dst_row_off + ... of dst."""
+        lda, ldc = lda or K, ldc or N
+        if self.x3:
+            self._gemm_pair(a, w, dst, M, N, K, lda, ldc, aux=aux, src_row_off=src_row_off, **kw)
+        else:       # rart_conv_desc has no source row offset: start at that row
+            self._gemm(a.view(-1, lda)[src_row_off:] if src_row_off else a, w, dst, M, K, N, lda, ldc, mask=aux, **kw)
+
+    def _ln(self, x, g, b, out, rows, c, ld_in=None, ld_out=None):
+        """out = LayerNorm(x) over the c features of `rows` rows ld_in / ld_out elements apart (default: dense)"""
+        lib, sp = self.lib, _lib.stream_ptr()
+        (xh, xl), (oh, ol) = self._hl(x), self._hl(out)
+        if self.x3:
+            _lib.check(lib.rart_layernorm_pair(xh, xl, _lib.ptr(g), _lib.ptr(b), oh, ol, rows, c, ld_in or c, ld_out or c, 1e-6, sp))
+        else:
+            _lib.check(lib.rart_layernorm_bf16(xh, _lib.ptr(g), _lib.ptr(b), oh, rows, c, ld_in or c, ld_out or c, 1e-6, sp))
+
+    def _ln_bwd(self, dy, x, g, res, dx, rows, c, strides=None):
+        """dx = LayerNorm'(x)^T dy (+ res); strides: the row strides of (dy, x, res, dx), default dense"""
+        lib, sp = self.lib, _lib.stream_ptr()
+        ld = strides or (c, c, c if res is not None else 0, c)
+        (dh, dl), (xh, xl), (oh, ol) = self._hl(dy), self._hl(x), self._hl(dx)
+        rh, rl = self._hl(res) if res is not None else (None, None)
+        if self.x3:
+            _lib.check(lib.rart_layernorm_bwd_pair(dh, dl, xh, xl, _lib.ptr(g), rh, rl, oh, ol, rows, c, *ld, 1e-6, sp))
+        else:
+            _lib.check(lib.rart_layernorm_bwd_bf16(dh, xh, _lib.ptr(g), rh, oh, rows, c, *ld, 1e-6, sp))
+
+    def _fc1_gelu(self, ln, w, b, hid, u, rows, K, N, keep):
+        """hid = gelu(ln . w^T + b), the fc1 of a transformer MLP; keep: u receives the pre-activation (GELU' in the backward)"""
+        if not keep:
+            self._mm(ln, w, hid, rows, N, K, bias=b, flags=F_GELU)
+        elif self.x3 or self.lib.rart_gemm256_supported(rows, K, N, K, N):
+            self._mm(ln, w, hid, rows, N, K, bias=b, flags=F_GELU_KEEP, aux=u)       # one launch writes both
+        else:                        # bf16: only the 256 x 256 GEMM keeps the pre-activation
+            self._mm(ln, w, u, rows, N, K, bias=b)
+            _lib.check(self.lib.rart_gelu_bf16(_lib.ptr(u), _lib.ptr(hid), u.numel(), _lib.stream_ptr()))
+
+    def _dlogits_rows(self, dl, name, B, kpad):
+        """-> the fp32 loss gradient dl [B][n_classes] as rows of kpad columns (zero past n_classes) in the engine's precision"""
+        lib, sp = self.lib, _lib.stream_ptr()
+        dlb = self._act(name, (B, kpad))
+        if self.x3:
+            _lib.check(lib.rart_f32_to_pair_rows(_lib.ptr(dl), _lib.ptr(dlb[0]), lo_off(dlb), B, self.n_classes, kpad, sp))
+        else:
+            _lib.check(lib.rart_f32_to_bf16_rows(_lib.ptr(dl), _lib.ptr(dlb), B, self.n_classes, kpad, sp))
+        return dlb
+
+    def _patchify(self, src, src_is_u8, mean, std, B, H, W, ps):
+        """-> the normalised ps x ps patches of the image batch as the pair [2][B][patches][3 * ps * ps] (in both precisions)"""
+        patches = self._get('patches', (2, B, (H // ps) * (W // ps), 3 * ps * ps))
+        meanf, stdf = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+        _lib.check(self.lib.rart_vit_patchify(_lib.ptr(src), 1 if src_is_u8 else 0, _lib.ptr(patches[0]), _lib.ptr(patches[1]),
+                                              B, H, W, ps, meanf, stdf, _lib.stream_ptr()))
+        return patches
+
+    def _unpatchify(self, dpatch, B, H, W, ps, std):
+        """-> d(loss)/d(x01) fp32 NCHW from the patch gradient [B * patches][3 * ps * ps]: bf16, or fp32 in reference precision"""
+        torch = _lib.require_gpu()
+        grad = torch.empty(B, 3, H, W, dtype=torch.float32, device=self.device)
+        fn = self.lib.rart_vit_unpatchify_from_f32 if self.x3 else self.lib.rart_vit_unpatchify_f32
+        _lib.check(fn(_lib.ptr(dpatch), _lib.ptr(grad), B, H, W, ps, 3 * ps * ps, (ctypes.c_float * 3)(*std), _lib.stream_ptr()))
+        return grad
 
     def _wgrad(self, dz, n_out, n_pad, x, c_in, grad, rows, dz_images=None):
         """grad[n_out][c_in] = dz^T . x (dz: bf16 [rows][n_pad] dense, columns >= n_out zero; x: bf16 [rows][c_in] dense) as a split-K

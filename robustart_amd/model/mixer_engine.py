@@ -12,15 +12,8 @@ mean's backward is rart_cnx_pool_bwd_*, the stem's a dgrad GEMM and rart_vit_unp
 precision 'bf16': bf16 storage, fp32 accumulation; 'bf16x3' (alias 'fp32x'): every activation, gradient and weight a hi + lo pair of
 bf16 planes, three MFMA products per contraction (rart_gemm_pair_bf16, rart_tokmix_pair), as ViTEngine's reference-precision mode.
 Every dimension is read from the module."""
-import ctypes
-
 from .. import _lib
-from .engine_base import (F_GELU, F_GELU_BWD, F_GELU_KEEP, F_OUT_F32, GP_GELU, GP_GELU_BWD, GP_GELU_KEEP, GP_OUT_F32, RowEngine,
-                          lo_off, pad_k, pad_rows, pair, rows_mult, tokmix_desc)
-
-
-def k32(n):
-    return (n + 31) // 32 * 32
+from .engine_base import (F_GELU, F_GELU_BWD, F_GELU_KEEP, F_OUT_F32, RowEngine, k32, lo_off, pad_k, pad_rows, pair, rows_mult, tokmix_desc)
 
 
 class MixerEngine(RowEngine):
@@ -34,7 +27,7 @@ class MixerEngine(RowEngine):
         their transposes, K padded to a multiple of 32 with zero columns, in the engine's precision."""
         torch = _lib.require_gpu()
         m, dev = model, self.device
-        x3 = self.precision == 'bf16x3'
+        x3 = self.x3
 
         def f32(t):
             return t.detach().to(dev, torch.float32).contiguous()
@@ -90,36 +83,12 @@ class MixerEngine(RowEngine):
         """dst_b[M][D] = a[M][K] . x_b[K][D] (+ epilogue) for the B images of dense [B][rows][D] slabs (pairs in reference precision)"""
         D = self.D
         self._launch_tokmix(tokmix_desc(a, x, dst, M, D, K, B, K * D, M * D, bias=bias, res=res, aux=aux, flags=flags,
-                                        pair=self.precision == 'bf16x3'), self.precision == 'bf16x3')
-
-    def _ln(self, x, g, b, out, rows):
-        lib, sp, D = self.lib, _lib.stream_ptr(), self.D
-        if self.precision == 'bf16x3':
-            _lib.check(lib.rart_layernorm_pair(_lib.ptr(x[0]), _lib.ptr(x[1]), _lib.ptr(g), _lib.ptr(b), _lib.ptr(out[0]), _lib.ptr(out[1]),
-                                               rows, D, D, D, 1e-6, sp))
-        else:
-            _lib.check(lib.rart_layernorm_bf16(_lib.ptr(x), _lib.ptr(g), _lib.ptr(b), _lib.ptr(out), rows, D, D, D, 1e-6, sp))
-
-    def _ln_bwd(self, dy, x, g, res, dx, rows):
-        """dx = LayerNorm'(x)^T dy (+ res)"""
-        lib, sp, D = self.lib, _lib.stream_ptr(), self.D
-        ld_res = D if res is not None else 0
-        if self.precision == 'bf16x3':
-            _lib.check(lib.rart_layernorm_bwd_pair(_lib.ptr(dy[0]), _lib.ptr(dy[1]), _lib.ptr(x[0]), _lib.ptr(x[1]), _lib.ptr(g),
-                                                   None if res is None else _lib.ptr(res[0]), None if res is None else _lib.ptr(res[1]),
-                                                   _lib.ptr(dx[0]), _lib.ptr(dx[1]), rows, D, D, D, ld_res, D, 1e-6, sp))
-        else:
-            _lib.check(lib.rart_layernorm_bwd_bf16(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(g), _lib.ptr(res), _lib.ptr(dx), rows, D, D, D,
-                                                   ld_res, D, 1e-6, sp))
-
-    def _act(self, name, shape):
-        return self._get(name, ((2,) if self.precision == 'bf16x3' else ()) + tuple(shape))
+                                        pair=self.x3), self.x3)
 
     # ------------------------------------------------------------------ forward
     def _forward(self, src, src_is_u8, mean, std, keep=False):
         torch = _lib.require_gpu()
         lib, sp = self.lib, _lib.stream_ptr()
-        x3 = self.precision == 'bf16x3'
         if src_is_u8:
             B, Himg, Wimg = src.shape[0], src.shape[1], src.shape[2]
         else:
@@ -128,12 +97,9 @@ class MixerEngine(RowEngine):
         assert (Himg // ps) * (Wimg // ps) == T, 'image size does not match the token-mixing MLP (%d tokens)' % T
         kk = 3 * ps * ps
         rows = B * T
-        patches = self._get('patches', (2, B, T, kk))
-        meanf, stdf = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
-        _lib.check(lib.rart_vit_patchify(_lib.ptr(src), 1 if src_is_u8 else 0, _lib.ptr(patches[0]), _lib.ptr(patches[1]),
-                                         B, Himg, Wimg, ps, meanf, stdf, sp))
+        patches = self._patchify(src, src_is_u8, mean, std, B, Himg, Wimg, ps)
         x = self._act('x0' if keep else 'x', (B, T, D))
-        if x3:
+        if self.x3:
             self._gemm_pair(patches, self.pe_w, x, rows, D, kk, kk, D, bias=self.pe_b)
         else:
             self._gemm(patches[0], self.pe_w, x, rows, kk, D, kk, D, bias=self.pe_b, n_taps=2, tap_src_off=[0, lo_off(patches)],
@@ -145,41 +111,28 @@ class MixerEngine(RowEngine):
             xm = self._act('xm%d' % li, (B, T, D)) if keep else x
             xo = self._act('x%d' % (li + 1), (B, T, D)) if keep else x
             # token mixing: x' = x + W2 gelu(W1 LN1(x) + b1) + b2, per image and channel
-            self._ln(x, L['n1g'], L['n1b'], ln, rows)
+            self._ln(x, L['n1g'], L['n1b'], ln, rows, D)
             ht = self._act('htok', (B, Ht, D))
             u_tok = self._act('utok%d' % li, (B, Ht, D)) if keep else None
             self._tokmix(L['t1'], ln, ht, Ht, T, B, bias=L['t1_b'], aux=u_tok, flags=F_GELU_KEEP if keep else F_GELU)
             self._tokmix(L['t2'], ht, xm, T, Ht, B, bias=L['t2_b'], res=x)
             # channel MLP: x'' = x' + fc2(gelu(fc1(LN2(x'))))
-            self._ln(xm, L['n2g'], L['n2b'], ln, rows)
+            self._ln(xm, L['n2g'], L['n2b'], ln, rows, D)
             hid = self._act('hid', (B, T, Hc))
             u_ch = self._act('uch%d' % li, (B, T, Hc)) if keep else None
-            if x3:
-                self._gemm_pair(ln, L['fc1_w'], hid, rows, Hc, D, D, Hc, bias=L['fc1_b'], flags=GP_GELU_KEEP if keep else GP_GELU, aux=u_ch)
-                self._gemm_pair(hid, L['fc2_w'], xo, rows, D, Hc, Hc, D, bias=L['fc2_b'], res=xm)
-            else:
-                if not keep:
-                    self._gemm(ln, L['fc1_w'], hid, rows, D, Hc, D, Hc, bias=L['fc1_b'], flags=F_GELU)
-                elif lib.rart_gemm256_supported(rows, D, Hc, D, Hc):
-                    self._gemm(ln, L['fc1_w'], hid, rows, D, Hc, D, Hc, bias=L['fc1_b'], mask=u_ch, flags=F_GELU_KEEP)
-                else:
-                    self._gemm(ln, L['fc1_w'], u_ch, rows, D, Hc, D, Hc, bias=L['fc1_b'])
-                    _lib.check(lib.rart_gelu_bf16(_lib.ptr(u_ch), _lib.ptr(hid), u_ch.numel(), sp))
-                self._gemm(hid, L['fc2_w'], xo, rows, Hc, D, Hc, D, bias=L['fc2_b'], res=xm)
+            self._fc1_gelu(ln, L['fc1_w'], L['fc1_b'], hid, u_ch, rows, D, Hc, keep)
+            self._mm(hid, L['fc2_w'], xo, rows, D, Hc, bias=L['fc2_b'], res=xm)
             if keep:
                 saved.append((x, xm, u_tok, u_ch))
             x = xo
-        self._ln(x, self.ng, self.nb, ln, rows)
+        self._ln(x, self.ng, self.nb, ln, rows, D)
         pooled = self._act('pooled', (B, D))
-        if x3:
+        if self.x3:
             _lib.check(lib.rart_engine_avgpool_pair(_lib.ptr(ln[0]), ln[0].numel(), _lib.ptr(pooled[0]), pooled[0].numel(), B, T, D, sp))
         else:
             _lib.check(lib.rart_engine_avgpool(_lib.ptr(ln), _lib.ptr(pooled), B, T, D, sp))
         logits = torch.empty(B, self.n_classes, dtype=torch.float32, device=self.device)
-        if x3:
-            self._gemm_pair(pooled, self.head_w, logits, B, self.n_classes, D, D, self.n_classes, bias=self.head_b, flags=GP_OUT_F32)
-        else:
-            self._gemm(pooled, self.head_w, logits, B, D, self.n_classes, D, self.n_classes, bias=self.head_b, flags=F_OUT_F32)
+        self._mm(pooled, self.head_w, logits, B, self.n_classes, D, bias=self.head_b, flags=F_OUT_F32)
         if keep:
             self._saved = (saved, x, (B, Himg, Wimg))
         return logits
@@ -191,7 +144,6 @@ class MixerEngine(RowEngine):
         from ..noise.adv import logit_loss
         torch = _lib.require_gpu()
         lib, sp = self.lib, _lib.stream_ptr()
-        x3 = self.precision == 'bf16x3'
         x01 = x01.detach().float().contiguous()
         logits = self._forward(x01, False, mean, std, keep=True)
         saved, x_last, (B, Himg, Wimg) = self._saved
@@ -199,21 +151,16 @@ class MixerEngine(RowEngine):
         self.last_dlogits = dl
         D, T, kp = self.D, self.T, self.head_kpad
         rows = B * T
-        dlb = self._act('g_dl', (B, kp))
+        dlb = self._dlogits_rows(dl, 'g_dl', B, kp)
         dpool = self._act('g_pool', (B, D))
-        if x3:
-            _lib.check(lib.rart_f32_to_pair_rows(_lib.ptr(dl), _lib.ptr(dlb[0]), lo_off(dlb), B, self.n_classes, kp, sp))
-            self._gemm_pair(dlb, self.head_wd, dpool, B, D, kp, kp, D)
-        else:
-            _lib.check(lib.rart_f32_to_bf16_rows(_lib.ptr(dl), _lib.ptr(dlb), B, self.n_classes, kp, sp))
-            self._gemm(dlb, self.head_wd, dpool, B, kp, D, kp, D)
+        self._mm(dlb, self.head_wd, dpool, B, D, kp)
         dln = self._act('g_ln', (B, T, D))
-        if x3:
+        if self.x3:
             _lib.check(lib.rart_cnx_pool_bwd_pair(_lib.ptr(dpool[0]), _lib.ptr(dpool[1]), _lib.ptr(dln[0]), _lib.ptr(dln[1]), B, T, D, sp))
         else:
             _lib.check(lib.rart_cnx_pool_bwd_bf16(_lib.ptr(dpool), _lib.ptr(dln), B, T, D, sp))
         dx = self._act('g_x', (B, T, D))
-        self._ln_bwd(dln, x_last, self.ng, None, dx, rows)
+        self._ln_bwd(dln, x_last, self.ng, None, dx, rows, D)
         dxm = self._act('g_xm', (B, T, D))
         for li in range(len(self.layers) - 1, -1, -1):
             L = self.layers[li]
@@ -221,27 +168,19 @@ class MixerEngine(RowEngine):
             Ht, Hc = L['tok_hidden'], L['hidden']
             # channel MLP: dh = (dx W2) gelu'(u_ch), dln = dh W1, dx' = LN2'(dln) + dx
             dh = self._act('g_hid', (B, T, Hc))
-            if x3:
-                self._gemm_pair(dx, L['fc2_wd'], dh, rows, Hc, D, D, Hc, flags=GP_GELU_BWD, aux=u_ch)
-                self._gemm_pair(dh, L['fc1_wd'], dln, rows, D, Hc, Hc, D)
-            else:
-                self._gemm(dx, L['fc2_wd'], dh, rows, D, Hc, D, Hc, mask=u_ch, flags=F_GELU_BWD)
-                self._gemm(dh, L['fc1_wd'], dln, rows, Hc, D, Hc, D)
-            self._ln_bwd(dln, xm, L['n2g'], dx, dxm, rows)
+            self._mm(dx, L['fc2_wd'], dh, rows, Hc, D, flags=F_GELU_BWD, aux=u_ch)
+            self._mm(dh, L['fc1_wd'], dln, rows, D, Hc)
+            self._ln_bwd(dln, xm, L['n2g'], dx, dxm, rows, D)
             # token mixing: dht = (W2^T dx') gelu'(u_tok), dln = W1^T dht, dx = LN1'(dln) + dx'
             dht = self._act('g_htok', (B, Ht, D))
             self._tokmix(L['t2d'], dxm, dht, Ht, T, B, aux=u_tok, flags=F_GELU_BWD)
             self._tokmix(L['t1d'], dht, dln, T, Ht, B)
-            self._ln_bwd(dln, x_in, L['n1g'], dxm, dx, rows)
+            self._ln_bwd(dln, x_in, L['n1g'], dxm, dx, rows, D)
         kk = 3 * self.ps * self.ps
-        grad = torch.empty(B, 3, Himg, Wimg, dtype=torch.float32, device=self.device)
-        stdf = (ctypes.c_float * 3)(*std)
-        if x3:
+        if self.x3:
             dpatch = self._get('g_patch32', (rows, kk), torch.float32)
-            self._gemm_pair(dx, self.pe_wd, dpatch, rows, kk, D, D, kk, flags=GP_OUT_F32)
-            _lib.check(lib.rart_vit_unpatchify_from_f32(_lib.ptr(dpatch), _lib.ptr(grad), B, Himg, Wimg, self.ps, kk, stdf, sp))
+            self._mm(dx, self.pe_wd, dpatch, rows, kk, D, flags=F_OUT_F32)
         else:
             dpatch = self._get('g_patch', (rows, kk))
-            self._gemm(dx, self.pe_wd, dpatch, rows, D, kk, D, kk, rows_per_image=T)
-            _lib.check(lib.rart_vit_unpatchify_f32(_lib.ptr(dpatch), _lib.ptr(grad), B, Himg, Wimg, self.ps, kk, stdf, sp))
-        return logits, loss, grad, pred
+            self._mm(dx, self.pe_wd, dpatch, rows, kk, D, rows_per_image=T)
+        return logits, loss, self._unpatchify(dpatch, B, Himg, Wimg, self.ps, std), pred

@@ -33,7 +33,8 @@ class ViTTrainEngine(ViTEngine):
         return self._forward(src, src_is_u8, mean, std, keep=True)
 
     # ------------------------------------------------------------------ helpers
-    def _ln_bwd(self, dy, x, gamma, res, dx, rows, strides, norm):
+    def _ln_bwd_full(self, dy, x, gamma, res, dx, rows, strides, norm):
+        """the backward of RowEngine._ln_bwd plus the gradients of `norm`'s weight and bias"""
         lib, D = self.lib, self.D
         need = lib.rart_layernorm_bwd_workspace_bytes(D)
         ws = self._scratch('ln_ws', need)
@@ -59,14 +60,13 @@ class ViTTrainEngine(ViTEngine):
         dl = dlogits.detach().float().contiguous()
         m.head.bias.grad.copy_(dl.sum(0))
         self.on_grad_ready(m.head.bias)
-        dlb = self._get('dl_bf16', (B, self.head_kpad))
-        _lib.check(lib.rart_f32_to_bf16_rows(_lib.ptr(dl), _lib.ptr(dlb), B, self.n_classes, self.head_kpad, sp))
+        dlb = self._dlogits_rows(dl, 'g_dl', B, self.head_kpad)
         self._linear_grads(m.head, dlb, self.head_kpad, self._buf['cls'], B)
         dcls = self._get('dcls', (B, D))
         self._gemm(dlb, self.head_wd, dcls, B, self.head_kpad, D, self.head_kpad, D)
         dx = self._get('g_x_a', (B, T, D))
         dx.zero_()
-        self._ln_bwd(dcls, x_last, self.ng, None, dx, B, (D, T * D, 0, T * D), m.norm)
+        self._ln_bwd_full(dcls, x_last, self.ng, None, dx, B, (D, T * D, 0, T * D), m.norm)
         dqkv = self._get('g_qkv', (rows, 3 * D))
         ln = self._get('ln', (B, T, D))
         for li in range(len(self.layers) - 1, -1, -1):
@@ -81,15 +81,14 @@ class ViTTrainEngine(ViTEngine):
             self.on_grad_ready(blk.fc2.bias)
             dh = self._get('g_hid', (rows, hidden))
             self._gemm(dx, L['fc2_wd'], dh, rows, D, hidden, D, hidden, mask=u, flags=F_GELU_BWD)     # du = (dx W2) * gelu'(u)
-            _lib.check(lib.rart_layernorm_bf16(_lib.ptr(xm), _lib.ptr(L['n2g']), _lib.ptr(L['n2b']), _lib.ptr(ln), rows, D, D, D,
-                                               1e-6, sp))
+            self._ln(xm, L['n2g'], L['n2b'], ln, rows, D)
             self._linear_grads(blk.fc1, dh, hidden, ln, rows)
             self._colsum(dh, hidden, rows, hidden, blk.fc1.bias.grad)
             self.on_grad_ready(blk.fc1.bias)
             dln = self._get('g_ln', (rows, D))
             self._gemm(dh, L['fc1_wd'], dln, rows, hidden, D, hidden, D)
             dxm = self._get('g_xm', (B, T, D))
-            self._ln_bwd(dln, xm, L['n2g'], dx, dxm, rows, (D, D, D, D), blk.norm2)
+            self._ln_bwd_full(dln, xm, L['n2g'], dx, dxm, rows, (D, D, D, D), blk.norm2)
             # ---- attention: xm = x_in + proj(attn(LN1(x_in)))
             self._linear_grads(blk.attn.proj, dxm, D, att, rows)
             self._colsum(dxm, D, rows, D, blk.attn.proj.bias.grad)
@@ -98,13 +97,12 @@ class ViTTrainEngine(ViTEngine):
             self._gemm(dxm, L['proj_wd'], datt, rows, D, D, D, D)
             _lib.check(lib.rart_vit_attention_bwd(_lib.ptr(qkv), _lib.ptr(att), _lib.ptr(datt), _lib.ptr(dqkv), B, T, self.H,
                                                   self.hd, sp))
-            _lib.check(lib.rart_layernorm_bf16(_lib.ptr(x_in), _lib.ptr(L['n1g']), _lib.ptr(L['n1b']), _lib.ptr(ln), rows, D, D, D,
-                                               1e-6, sp))
+            self._ln(x_in, L['n1g'], L['n1b'], ln, rows, D)
             self._linear_grads(blk.attn.qkv, dqkv, 3 * D, ln, rows)
             self._colsum(dqkv, 3 * D, rows, 3 * D, blk.attn.qkv.bias.grad)
             self.on_grad_ready(blk.attn.qkv.bias)
             self._gemm(dqkv, L['qkv_wd'], dln, rows, 3 * D, D, 3 * D, D)
-            self._ln_bwd(dln, x_in, L['n1g'], dxm, dx, rows, (D, D, D, D), blk.norm1)
+            self._ln_bwd_full(dln, x_in, L['n1g'], dxm, dx, rows, (D, D, D, D), blk.norm1)
         # ---- embeddings: x0[b][0] = cls + pos[0]; x0[b][1+p] = patch_embed(patch p) + pos[1+p]
         # derive every gradient that READS pos_embed.grad before the first on_grad_ready: with a small dist.bucket_mb the
         # {cls_token, pos_embed} bucket would otherwise start its asynchronous all-reduce (in place, on the RCCL stream)

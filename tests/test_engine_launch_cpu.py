@@ -7,16 +7,25 @@ from robustart_amd.model import engine_base as eb
 
 
 class _Recorder:
+    """stands in for the library: answers every rart_* entry and records (name, arguments); `descs`: the descriptors of the GEMM launches"""
+
     def __init__(self):
-        self.descs = []
+        self.calls, self.gemm256 = [], 0
 
-    def rart_conv_igemm_bf16(self, d, stream):
-        self.descs.append(d._obj)
-        return 0
+    @property
+    def descs(self):
+        return [a[0]._obj for n, a in self.calls if n in ('rart_conv_igemm_bf16', 'rart_gemm_pair_bf16')]
 
-    def rart_gemm_pair_bf16(self, d, stream):
-        self.descs.append(d._obj)
-        return 0
+    def __getattr__(self, name):
+        if not name.startswith('rart_'):
+            raise AttributeError(name)
+        if name == 'rart_gemm256_supported':
+            return lambda *a: self.gemm256
+
+        def call(*args):
+            self.calls.append((name, args))
+            return 0
+        return call
 
 
 def _engine(cls, monkeypatch, **attrs):
@@ -152,3 +161,181 @@ def test_precision_table():
         assert 'precision must be one of' in str(e)
     else:
         raise AssertionError('fp16 accepted')
+
+
+# ---------------------------------------------------------------------- the precision-generic launches of RowEngine, and ViT's one chain
+MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+def _vit(monkeypatch, precision, depth=1):
+    """ViTEngine on the CPU: 32 px, 4 patches + class token, 2 heads of 64, tables built by refold"""
+    from robustart_amd.model.vit_engine import ViTEngine
+    from robustart_amd.model.vit_torch import VisionTransformer
+    torch.manual_seed(0)
+    m = VisionTransformer(img_size=32, num_classes=10, embed_dim=128, depth=depth, num_heads=2).eval()
+    monkeypatch.setattr(_lib, 'require_gpu', lambda: torch)
+    eng = _engine(ViTEngine, monkeypatch, device=torch.device('cpu'), precision=eb.check_precision(precision), D=128, H=2, ps=16, hd=64,
+                  pair_w_interleaved=False, fused_attention=True, fused_attention_bwd=True)
+    eng.refold(m)
+    return eng
+
+
+def _vals(args):
+    return tuple(a.value if hasattr(a, 'value') else a for a in args)
+
+
+def _planes(t, x3):
+    return (t[0].data_ptr(), t[1].data_ptr()) if x3 else (t.data_ptr(),)
+
+
+def _kinds(eng):
+    """entry names with the precision taken out; the per-plane transposes of the pair decomposition count once"""
+    out = []
+    for name, _ in eng.lib.calls:
+        if name in ('rart_conv_igemm_bf16', 'rart_gemm_pair_bf16'):
+            name = 'gemm'
+        else:
+            name = name.replace('_pair', '').replace('_bf16', '').replace('unpatchify_from_f32', 'unpatchify_f32')
+        if not (out and out[-1] == name and name in ('rart_vit_transpose_v', 'rart_transpose_gather')):
+            out.append(name)
+    eng.lib.calls.clear()
+    return out
+
+
+def test_x3_is_a_property_of_the_precision(monkeypatch):
+    eng = _engine(eb.RowEngine, monkeypatch, precision='bf16')
+    assert eng.x3 is False
+    eng.precision = eb.check_precision('fp32x')
+    assert eng.x3 is True
+    assert [eb.k32(n) for n in (1, 32, 33, 197, 1000)] == [32, 32, 64, 224, 1024]
+
+
+def test_vit_chain_launches_the_same_sequence_in_both_precisions(monkeypatch):
+    """forward and forward + backward of a one-block ViT: entry for entry the same chain, up to the per-precision details"""
+    from robustart_amd.noise import adv
+    B, T, D = 2, 5, 128
+    x = torch.rand(B, 3, 32, 32)
+    monkeypatch.setattr(adv, 'logit_loss', lambda logits, *a: (torch.zeros(B), torch.ones(B, 10), torch.zeros(B, dtype=torch.int32)))
+    bf, x3 = _vit(monkeypatch, 'bf16'), _vit(monkeypatch, 'fp32x')
+    bf.lib.gemm256 = 1
+    for fused in (True, False):
+        for e in (bf, x3):
+            e.fused_attention = e.fused_attention_bwd = fused
+        bf.logits(x, MEAN, STD), x3.logits(x, MEAN, STD)
+        fwd = _kinds(bf)
+        assert fwd == _kinds(x3)
+        assert fwd[:3] == ['rart_vit_patchify', 'gemm', 'rart_vit_add_pos_cls'] and fwd[-2:] == ['rart_layernorm', 'gemm']
+        assert ('rart_vit_attention' in fwd) == fused and ('rart_softmax_rows' in fwd) == (not fused)
+        bf.forward_backward(x, MEAN, STD, None, 0), x3.forward_backward(x, MEAN, STD, None, 0)
+        both = _kinds(bf)
+        assert both == _kinds(x3)
+        assert both[:len(fwd)] == fwd and both[-2:] == ['gemm', 'rart_vit_unpatchify_f32']
+        assert ('rart_vit_attention_bwd' in both) == fused and ('rart_softmax_bwd_rows' in both) == (not fused)
+    # bf16 only: where the 256 x 256 GEMM does not take fc1, the pre-activation is kept by a GEMM and rart_gelu_bf16 follows
+    bf.lib.gemm256 = 0
+    bf.forward_backward(x, MEAN, STD, None, 0)
+    two = _kinds(bf)
+    i = two.index('rart_gelu')
+    assert two[:i] + two[i + 1:] == both
+    # the per-precision details
+    assert tuple(bf._buf['qkv0'].shape) == (B * T + 256, 3 * D) and tuple(x3._buf['qkv0'].shape) == (2, B * T, 3 * D)
+    bf.forward_backward(x, MEAN, STD, None, 0), x3.forward_backward(x, MEAN, STD, None, 0)
+    assert 'att_stats' not in bf._buf                                        # the pair fused backward only
+    assert tuple(x3._buf['att_stats'].shape) == (B * 2, 32, 4) and x3._buf['att_stats'].dtype == torch.float32
+    pe_x3, dg_x3 = x3.lib.descs[0], x3.lib.descs[-1]
+    pe_bf, dg_bf = bf.lib.descs[0], bf.lib.descs[-1]
+    # patch GEMM: the image pair as two taps of the [hi | hi] table, or the pair GEMM on the pair; rows 1 .. T-1 of every image
+    assert (pe_bf.n_taps, pe_bf.tap_src_off[1], pe_bf.src) == (2, eb.lo_off(bf._buf['patches']), bf._buf['patches'].data_ptr())
+    assert (pe_bf.batch, pe_bf.grid_h, pe_bf.dst_h, pe_bf.dst_oy) == (B, T - 1, T, 1)
+    assert (pe_x3.a_hi, pe_x3.a_lo) == _planes(x3._buf['patches'], True)
+    assert (pe_x3.rows_per_image, pe_x3.dst_rows_per_image, pe_x3.dst_row_off, pe_x3.src_row_off) == (T - 1, T, 1, 0)
+    # patch dgrad: from token row 1 of every image, into bf16 / fp32 patches
+    dx = bf._buf['g_x_a']
+    assert (dg_bf.src, dg_bf.batch, dg_bf.grid_h, dg_bf.src_h, dg_bf.flags) == (dx.data_ptr() + 2 * D, B, T - 1, T, 0)
+    assert bf._buf['g_patch'].dtype == torch.bfloat16
+    assert (dg_x3.a_hi, dg_x3.a_lo) == _planes(x3._buf['g_x_a'], True) and dg_x3.flags == eb.GP_OUT_F32
+    assert (dg_x3.rows_per_image, dg_x3.src_rows_per_image, dg_x3.src_row_off, dg_x3.dst_rows_per_image) == (T - 1, T, 1, 0)
+    assert x3._buf['g_patch'].dtype == torch.float32
+    assert x3.lib.calls[-1][0] == 'rart_vit_unpatchify_from_f32' and bf.lib.calls[-1][0] == 'rart_vit_unpatchify_f32'
+
+
+def test_layernorm_launches_with_class_token_strides(monkeypatch):
+    """ViT's head reads the class-token row of every image: B rows T * D apart, forward and backward; the default is dense"""
+    B, T, D = 3, 5, 128
+    for prec in ('bf16', 'bf16x3'):
+        eng = _engine(eb.RowEngine, monkeypatch, precision=prec)
+        x3 = eng.x3
+
+        def act(*shape):
+            return _bf(*(((2,) if x3 else ()) + shape))
+        x, cls, dcls, dx, res = act(B, T, D), act(B, D), act(B, D), act(B, T, D), act(B, T, D)
+        g, b = torch.zeros(D), torch.zeros(D)
+        eng._ln(x, g, b, cls, B, D, ld_in=T * D)
+        eng._ln_bwd(dcls, x, g, None, dx, B, D, strides=(D, T * D, 0, T * D))
+        eng._ln(x, g, b, dx, B * T, D)
+        eng._ln_bwd(dx, x, g, res, dx, B * T, D)
+        eng._ln_bwd(dx, x, g, None, dx, B * T, D)
+        (n0, a0), (n1, a1), (n2, a2), (n3, a3), (n4, a4) = eng.lib.calls
+        sfx = 'pair' if x3 else 'bf16'
+        assert [n0, n1, n2, n3, n4] == ['rart_layernorm_' + sfx, 'rart_layernorm_bwd_' + sfx] + ['rart_layernorm_' + sfx] + \
+            ['rart_layernorm_bwd_' + sfx] * 2
+        no_res = (None, None) if x3 else (None,)
+        assert _vals(a0) == _planes(x, x3) + (g.data_ptr(), b.data_ptr()) + _planes(cls, x3) + (B, D, T * D, D, 1e-6, None)
+        assert _vals(a1) == _planes(dcls, x3) + _planes(x, x3) + (g.data_ptr(),) + no_res + _planes(dx, x3) + \
+            (B, D, D, T * D, 0, T * D, 1e-6, None)
+        assert _vals(a2) == _planes(x, x3) + (g.data_ptr(), b.data_ptr()) + _planes(dx, x3) + (B * T, D, D, D, 1e-6, None)
+        assert _vals(a3) == _planes(dx, x3) + _planes(x, x3) + (g.data_ptr(),) + _planes(res, x3) + _planes(dx, x3) + \
+            (B * T, D, D, D, D, D, 1e-6, None)
+        assert _vals(a4) == _planes(dx, x3) + _planes(x, x3) + (g.data_ptr(),) + no_res + _planes(dx, x3) + (B * T, D, D, D, 0, D, 1e-6, None)
+
+
+def test_fc1_gelu_forms(monkeypatch):
+    """bf16: GELU in the epilogue; with the pre-activation kept, one launch where the 256 x 256 GEMM takes the shape, else the GEMM
+    into u and rart_gelu_bf16.  Pair: always one launch."""
+    rows, K, N = 64, 128, 512
+    w, wp, b = _bf(N, K), _bf(2, N, K), torch.zeros(N)
+    ln, hid, u = _bf(rows, K), _bf(rows, N), _bf(rows, N)
+    eng = _engine(eb.RowEngine, monkeypatch, precision='bf16')
+    eng._fc1_gelu(ln, w, b, hid, None, rows, K, N, False)
+    eng.lib.gemm256 = 1
+    eng._fc1_gelu(ln, w, b, hid, u, rows, K, N, True)
+    eng.lib.gemm256 = 0
+    eng._fc1_gelu(ln, w, b, hid, u, rows, K, N, True)
+    assert [n for n, _ in eng.lib.calls] == ['rart_conv_igemm_bf16'] * 3 + ['rart_gelu_bf16']
+    plain, keep, two = eng.lib.descs
+    assert (plain.src, plain.wgt, plain.bias, plain.dst, plain.mask, plain.flags) == \
+        (ln.data_ptr(), w.data_ptr(), b.data_ptr(), hid.data_ptr(), None, eb.F_GELU)
+    assert (plain.batch, plain.grid_h, plain.k_per_tap, plain.n_cols, plain.src_pix_stride, plain.dst_pix_stride) == (1, rows, K, N, K, N)
+    assert (keep.dst, keep.mask, keep.flags) == (hid.data_ptr(), u.data_ptr(), eb.F_GELU_KEEP)
+    assert (two.dst, two.mask, two.bias, two.flags) == (u.data_ptr(), None, b.data_ptr(), 0)
+    assert _vals(eng.lib.calls[-1][1]) == (u.data_ptr(), hid.data_ptr(), rows * N, None)
+    lnp, hidp, up = _bf(2, rows, K), _bf(2, rows, N), _bf(2, rows, N)
+    eng = _engine(eb.RowEngine, monkeypatch, precision='bf16x3')
+    eng._fc1_gelu(lnp, wp, b, hidp, None, rows, K, N, False)
+    eng._fc1_gelu(lnp, wp, b, hidp, up, rows, K, N, True)
+    assert [n for n, _ in eng.lib.calls] == ['rart_gemm_pair_bf16'] * 2
+    plain, keep = eng.lib.descs
+    assert (plain.flags, plain.aux_hi, plain.aux_lo) == (eb.GP_GELU, None, None)
+    assert (keep.flags, keep.aux_hi, keep.aux_lo) == (eb.GP_GELU_KEEP,) + _planes(up, True)
+    for d in (plain, keep):
+        assert (d.a_hi, d.a_lo, d.w_hi, d.w_lo, d.dst_hi, d.dst_lo) == _planes(lnp, True) + _planes(wp, True) + _planes(hidp, True)
+        assert (d.M, d.N, d.K, d.lda, d.ldw, d.ldc, d.bias) == (rows, N, K, K, K, N, b.data_ptr())
+
+
+def test_vit_tables_exist_in_the_engines_precision_only(monkeypatch):
+    """every Linear table (patch embedding, qkv, proj, fc1, fc2, head; forward and backward-to-input) is a pair [2][rows][K] in
+    reference precision and a bf16 [rows][K] matrix in bf16: an engine holds no table of the other precision"""
+    names = ['qkv_w', 'proj_w', 'fc1_w', 'fc2_w', 'qkv_wd', 'proj_wd', 'fc1_wd', 'fc2_wd']
+    for prec, dims in (('bf16', 2), ('fp32x', 3)):
+        eng = _vit(monkeypatch, prec, depth=2)
+        tabs = [eng.pe_w, eng.pe_wd, eng.head_w, eng.head_wd] + [L[n] for L in eng.layers for n in names]
+        assert len(tabs) == 20
+        held = [t for t in vars(eng).values() if torch.is_tensor(t)] + [t for L in eng.layers for t in L.values() if torch.is_tensor(t)]
+        bf16 = [t for t in held if t.dtype == torch.bfloat16]
+        assert len(bf16) == len(tabs) and {t.data_ptr() for t in bf16} == {t.data_ptr() for t in tabs}
+        for t in tabs:
+            assert t.dim() == dims and t.is_contiguous() and (dims == 2 or t.shape[0] == 2)
+            assert t.shape[-2] % (256 if dims == 3 else 64) == 0
+        assert not isinstance(eng.x3, dict)
+        # same keys in both precisions
+        assert sorted(k for k in eng.layers[0] if k.endswith(('_w', '_wd'))) == sorted(names)
