@@ -10,15 +10,17 @@ Host side (this file, PyTorch as plumbing only): fold BatchNorm (eval mode) into
 lay the weights out for the implicit-GEMM kernel (forward: [Cout][tap][Cin]; backward-to-input:
 [Cin][tap][Cout], one table per input-parity class for stride-2 convs), own the activation / gradient
 buffers, and sequence the C-ABI calls.  Device side: rart_conv_igemm_bf16 (every conv, fc, and their
-backward), rart_engine_* (stem input prep, pools, col2im), rart_logit_loss.  bf16 storage, fp32
-accumulation; the fp32 pixels enter the stem as a hi+lo bf16 pair so eps-sized perturbations are kept.
+backward), rart_engine_* (stem input prep, pools, col2im), rart_logit_loss.  Two precisions, one chain (`ResNet50Engine`):
+bf16 storage with fp32 accumulation, where the fp32 pixels enter the stem as a hi+lo bf16 pair so eps-sized perturbations are
+kept; or reference precision, where every tensor is such a pair and rart_gemm_pair_bf16 / the rart_*_pair entries take the
+place of their bf16 namesakes.
 """
 import ctypes
 import os as _os
 
 from .. import _lib
 from .engine_base import (F_MASK_BITS, F_OUT_F32, F_PAIR, F_RELU, EngineBase, cints as _cints, conv_desc, gemm_pair_desc,
-                          interleave_k32, lo_off, pad_rows, rows_mult, pair, split_hi_lo)
+                          interleave_k32, k32, lo_off, pad_k, pad_rows, rows_mult, pair, split_hi_lo)
 
 
 def _bf16(t):
@@ -26,8 +28,31 @@ def _bf16(t):
     return t.to(torch.bfloat16).contiguous()
 
 
+def _planes(w, split):
+    """the bf16-exact fp32 pieces a weight table is built from: (hi,) with hi = bf16(w), the values the bf16 kernels see; in reference
+    precision (hi, lo) with w = hi + lo (two bf16 pieces, 16 significand bits)"""
+    hi, lo = split_hi_lo(w)
+    return (hi.float(), lo.float()) if split else (hi.float(),)
+
+
+def _table(build, planes, device):
+    """the bf16 table build(hi) [rows][K], or in reference precision its rows as [hi | lo | hi]: the concatenation that matches the three
+    products x_hi.w_hi + x_hi.w_lo + x_lo.w_hi (F_PAIR)"""
+    import torch
+    t = [build(p) for p in planes]
+    return _bf16(torch.cat(t + t[:1], 1) if len(t) == 2 else t[0]).to(device)
+
+
+def _stem_rows(w):
+    """stem weights [64][3][7][7] -> the row-tap form [64][224]: one tap = one filter row, 8 px x 4 ch (zero at px 7 and ch 3)"""
+    import torch
+    t = torch.zeros(64, 7, 8, 4, dtype=w.dtype, device=w.device)
+    t[:, :, :7, :3] = w.permute(0, 2, 3, 1)                              # [cout][r][s][c]
+    return t.reshape(64, 7 * 32)
+
+
 class _Conv:
-    """One folded conv layer: forward table + backward-to-input tables."""
+    """One folded conv layer: forward table + backward-to-input tables, in bf16 or (split) as [hi | lo | hi] rows."""
 
     def __init__(self, conv, bn, device, split=False):
         import torch
@@ -40,101 +65,65 @@ class _Conv:
             b = conv.bias.detach().float() if conv.bias is not None else torch.zeros(w.shape[0])
         self.cout, self.cin, self.r, self.s = w.shape
         self.stride = conv.stride[0]
-        self.pad = conv.padding[0]
+        self.pad = pad = conv.padding[0]
         self.w_folded = w                    # fp32, for the reference emulation in tests
         self.b_folded = b
         self.bias = b.contiguous().to(device)
-        self.fwd_taps = [(r - self.pad, s - self.pad) for r in range(self.r) for s in range(self.s)]
-        hi, lo = split_hi_lo(w)
-        wb = hi.float()                      # the values the bf16 kernels see
-        if not split:
-            self.w_fwd, self.bwd = self._tables(wb, device)
-        else:
-            # reference-precision mode: w = hi + lo (two bf16 pieces, 16 significand bits); a weight row is the
-            # concatenation [hi | lo | hi] matching the products x_hi.w_hi + x_hi.w_lo + x_lo.w_hi (F_PAIR)
-            fh, bh = self._tables(wb, device)
-            fl, bl = self._tables(lo.float(), device)
-            self.w_fwd = torch.cat([fh, fl, fh], 1).contiguous()
-            self.bwd = [(par, taps, None if th is None else torch.cat([th, tl, th], 1).contiguous())
-                        for (par, taps, th), (_, _, tl) in zip(bh, bl)]
+        self.fwd_taps = [(r - pad, s - pad) for r in range(self.r) for s in range(self.s)]
+        planes = _planes(w, split)
 
-    def _tables(self, wb, device):
-        """-> (forward table [cout][tap][cin], backward-to-input tables [(parity, taps, [cin][tap][cout])]) of the bf16-exact
-        fp32 weights wb [cout][cin][r][s]."""
-        import torch
-        # forward: rows = cout, k = (r*S + s)*Cin + c
-        w_fwd = _bf16(pad_rows(wb.permute(0, 2, 3, 1).reshape(self.cout, -1), rows_mult(self.cout))).to(device)
-        # backward to input: rows = cin, k = tap*Cout + cout
-        bwd = []    # list of (parity (ph,pw) or None, taps [(dy,dx)], weight)
+        def table(rs, transpose):
+            """filter taps rs of [cout][cin][r][s] side by side.  Forward: rows = cout, k = tap * cin + c; backward to input
+            (transpose): rows = cin, k = tap * cout + cout index"""
+            rows = self.cin if transpose else self.cout
+            return _table(lambda wb: pad_rows(torch.cat([wb[:, :, r, s].t() if transpose else wb[:, :, r, s] for r, s in rs], 1),
+                                              rows_mult(rows)), planes, device)
+        rs_all = [(r, s) for r in range(self.r) for s in range(self.s)]
+        self.w_fwd = table(rs_all, False)
+        # backward to input: list of (input parity (ph, pw) or None, taps [(dy, dx)], table or None); a stride-2 conv has one table
+        # per input-parity class, over the filter taps that reach it
         if self.stride == 1:
-            taps, cols = [], []
-            for r in range(self.r):
-                for s in range(self.s):
-                    taps.append((self.pad - r, self.pad - s))
-                    cols.append(wb[:, :, r, s].t())                     # [cin][cout]
-            wd = torch.cat(cols, 1)
-            bwd.append((None, taps, _bf16(pad_rows(wd, rows_mult(self.cin))).to(device)))
+            self.bwd = [(None, [(pad - r, pad - s) for r, s in rs_all], table(rs_all, True))]
         else:
             assert self.stride == 2
+            self.bwd = []
             for ph in range(2):
                 for pw in range(2):
-                    taps, cols = [], []
-                    for r in range(self.r):
-                        if (ph + self.pad - r) % 2:
-                            continue
-                        for s in range(self.s):
-                            if (pw + self.pad - s) % 2:
-                                continue
-                            taps.append(((ph + self.pad - r) // 2, (pw + self.pad - s) // 2))
-                            cols.append(wb[:, :, r, s].t())
-                    if not taps:
-                        bwd.append(((ph, pw), [], None))
-                        continue
-                    wd = torch.cat(cols, 1)
-                    bwd.append(((ph, pw), taps, _bf16(pad_rows(wd, rows_mult(self.cin))).to(device)))
-        return w_fwd, bwd
+                    rs = [(r, s) for r, s in rs_all if (ph + pad - r) % 2 == 0 and (pw + pad - s) % 2 == 0]
+                    self.bwd.append(((ph, pw), [((ph + pad - r) // 2, (pw + pad - s) // 2) for r, s in rs], table(rs, True) if rs else None))
 
 
 class ResNet50Engine(EngineBase):
-    """Hand-written HIP eval engine for robustart_amd.model.resnet_torch.ResNet."""
+    """Hand-written HIP eval engine for robustart_amd.model.resnet_torch.ResNet, in one of two precisions: one launch chain
+    (stem -> 16 bottlenecks -> average pool -> classifier, and back) that forks on `self.x3` only where the library entry, the
+    tensor form or the fused block kernels of a precision differ.  Tables and buffers exist in the engine's precision only."""
 
     def __init__(self, model, device='cuda', precision='bf16'):
         """precision: 'bf16' -- bf16 storage, fp32 accumulation (the fast path; logits within ~3e-3 of the fp32 network);
-        'bf16x3' (alias 'fp32x') -- the REFERENCE-PRECISION mode: the reference runs fp32 (adv/attack.py:20-23,
+        'bf16x3' (alias 'fp32x') -- REFERENCE PRECISION: the reference runs fp32 (adv/attack.py:20-23,
         autopgd_base.py:271-289) and the north star asks for logits within 1e-4 of it, so every activation, gradient and
         weight is a hi + lo pair of bf16 values (16 significand bits) and every contraction the three MFMA products
-        hi.hi + hi.lo + lo.hi with fp32 accumulation (`_forward_x3`): logits within ~1e-5 of the fp32 network's scale."""
+        hi.hi + hi.lo + lo.hi with fp32 accumulation: logits within ~1e-5 of the fp32 network's scale."""
         super().__init__(device, precision)
         torch = _lib.require_gpu()
-        split = self.precision == 'bf16x3'
+        split = self.x3
         m = model
         assert not m.training, 'the attack / eval engine folds BatchNorm: call model.eval() first'
         dev = self.device
         # ---- stem: 7x7/2 conv on the padded 4-channel hi/lo image; a "tap" = one filter row, 8 px x 4 ch
         st = _Conv(m.conv1, m.bn1, dev, split)
         self.stem = st
-        hi, lo = split_hi_lo(st.w_folded)
-        wb = hi.float()                                                   # [64][3][7][7]
-        wrow = torch.zeros(64, 7, 8, 4)
-        wrow[:, :, :7, :3] = wb.permute(0, 2, 3, 1)                      # [cout][r][s][c]
-        wrow = wrow.reshape(64, 7 * 32)
-        self.stem_w = _bf16(torch.cat([wrow, wrow], 1)).to(dev)          # hi taps then lo taps
+        pl = _planes(st.w_folded, split)                                  # [64][3][7][7]
         # stem backward: patches[(r*7+s)*3+c] = sum_k dz[k] * W[k][c][r][s]; 147 rows zero-padded to the tile
-        wp = wb.permute(2, 3, 1, 0).reshape(147, 64)
         self.stem_patch_cols = 152                                        # 147 rounded up to 8
-        self.stem_wd = _bf16(pad_rows(wp, rows_mult(self.stem_patch_cols))).to(dev)
-        self.stem_wt = self._stem_bwd_table(wb).to(dev)                  # fused stem backward (stem_fused.hip)
-        if split:
-            wl = lo.float()
-            wrow_l = torch.zeros(64, 7, 8, 4)
-            wrow_l[:, :, :7, :3] = wl.permute(0, 2, 3, 1)
-            wrow_l = wrow_l.reshape(64, 7 * 32)
-            self.stem_w = _bf16(torch.cat([wrow, wrow_l, wrow], 1)).to(dev)      # x_hi.w_hi, x_hi.w_lo, x_lo.w_hi row taps
-            wpl = wl.permute(2, 3, 1, 0).reshape(147, 64)
-            self.stem_wd = _bf16(pad_rows(torch.cat([wp, wpl, wp], 1), rows_mult(self.stem_patch_cols))).to(dev)
-            self.stem_w_pair = _bf16(torch.stack([wrow, wrow_l])).contiguous().to(dev)   # fused pair stem forward (stem_pair.hip): [2][64][224]
-            wt32 = self._stem_bwd_table(st.w_folded, dtype=torch.float32)           # fused pair stem backward (stem_pair.hip)
-            self.stem_wt_pair = pair(wt32).to(dev)
+        self.stem_wd = _table(lambda p: pad_rows(p.permute(2, 3, 1, 0).reshape(147, 64), rows_mult(self.stem_patch_cols)), pl, dev)
+        if not split:
+            self.stem_w = _table(lambda p: _stem_rows(p).repeat(1, 2), pl, dev)     # the image's hi taps then its lo taps
+            self.stem_wt = self._stem_bwd_table(pl[0]).to(dev)            # fused stem backward (stem_fused.hip)
+        else:
+            self.stem_w = _table(_stem_rows, pl, dev)                     # x_hi.w_hi, x_hi.w_lo, x_lo.w_hi row taps
+            self.stem_w_pair = _bf16(torch.stack([_stem_rows(p) for p in pl])).to(dev)     # fused pair stem forward (stem_pair.hip): [2][64][224]
+            self.stem_wt_pair = pair(self._stem_bwd_table(st.w_folded, dtype=torch.float32)).to(dev)     # fused pair stem backward
         self.fused_stem_bwd = True       # False: max-pool bwd -> patches GEMM -> col2im (kept as the cross-check)
         self.sign_bit_masks = True       # False: the backward reads the bf16 activations for their ReLU sign (cross-check)
         self.halo_conv3x3 = True         # False: layer1 / layer2 3x3 convs on the generic implicit GEMM (cross-check)
@@ -162,24 +151,14 @@ class ResNet50Engine(EngineBase):
                 ds = _Conv(blk.downsample[0], blk.downsample[1], dev, split) if blk.downsample is not None else None
                 self.blocks.append((_Conv(blk.conv1, blk.bn1, dev, split), _Conv(blk.conv2, blk.bn2, dev, split),
                                     _Conv(blk.conv3, blk.bn3, dev, split), ds))
-        # ---- classifier
+        # ---- classifier: forward table [1024][2048], backward-to-input table [2048][1024] ([hi | lo | hi] rows in reference precision)
         wfc = m.fc.weight.detach().float()
         self.n_classes, self.fc_in = wfc.shape
-        hi, lo = split_hi_lo(wfc)
-        wfb = hi.float()
-        self.fc_w = _bf16(pad_rows(wfb, 128)).to(dev)                    # [1024][2048]
         self.fc_b = m.fc.bias.detach().float().contiguous().to(dev)
-        self.fc_kpad = (self.n_classes + 31) // 32 * 32                   # 1024
-        wt = torch.zeros(self.fc_in, self.fc_kpad)
-        wt[:, :self.n_classes] = wfb.t()
-        self.fc_wd = _bf16(wt).to(dev)                                    # [2048][1024]
-        if split:
-            wfl = lo.float()
-            fh, fl = pad_rows(wfb, 128), pad_rows(wfl, 128)
-            self.fc_w = _bf16(torch.cat([fh, fl, fh], 1)).to(dev)         # [1024][3 * 2048]
-            wtl = torch.zeros(self.fc_in, self.fc_kpad)
-            wtl[:, :self.n_classes] = wfl.t()
-            self.fc_wd = _bf16(torch.cat([wt, wtl, wt], 1)).to(dev)       # [2048][3 * 1024]
+        self.fc_kpad = k32(self.n_classes)                                # 1024
+        pl = _planes(wfc, split)
+        self.fc_w = _table(lambda p: pad_rows(p, 128), pl, dev)
+        self.fc_wd = _table(lambda p: pad_k(p.t(), self.fc_kpad), pl, dev)
         # round 5 experiment, OFF by default: the pair GEMM's weight tables with the hi and the lo slice of a 32-deep K step side by side (one
         # 128-byte line per row and step instead of two half lines K apart).  2-5 % per K-deep launch when a shape is replayed back to back
         # (profiles/r05_pair_knockouts.txt), nothing on the whole gradient evaluation (20.61 vs 20.63 ms) and +0.9 % on the forward
@@ -371,9 +350,7 @@ class ResNet50Engine(EngineBase):
         # stem extras (row-tap table, patches table, fused-backward table) and the classifier
         sc = st['scale'][:64]
         wb = (m.conv1.weight.detach() * sc.view(-1, 1, 1, 1)).to(torch.bfloat16)          # [64][3][7][7]
-        wrow = torch.zeros(64, 7, 8, 4, dtype=torch.bfloat16, device=self.device)
-        wrow[:, :, :7, :3] = wb.permute(0, 2, 3, 1)
-        wrow = wrow.reshape(64, 224)
+        wrow = _stem_rows(wb)
         self.stem_w[:, :224] = wrow
         self.stem_w[:, 224:] = wrow
         self.stem_wd.zero_()
@@ -546,8 +523,9 @@ class ResNet50Engine(EngineBase):
 
     @staticmethod
     def _fits32(n, hw, channels):
-        """the fused / LDS-resident kernels address with 32-bit element offsets (their C entry points check n*H*W*C < 2^31):
-        beyond that the engine falls back to the generic implicit GEMM instead of raising"""
+        """the fused / LDS-resident kernels address with 32-bit element offsets (their C entry points check n*H*W*C < 2^31): beyond
+        that the engine sends the layer to the generic GEMM launches instead -- which refuse tensors above 2^30 elements themselves, so
+        such a batch raises there rather than in the fused kernel's entry point"""
         return n * hw[0] * hw[1] * channels < (1 << 31)
 
     def _halo_ok(self, c, hw, n=1):
@@ -568,7 +546,8 @@ class ResNet50Engine(EngineBase):
                 and self.lib.rart_bottleneck_fused_supported(cc.cout, ca.cout, xhw[0], xhw[1]))
 
     def _image_block_fn(self, ca, cb, cc, ds, xhw, n=1):
-        """-> the C entry point of the image-resident fused kernel for this block (layer3: 14 x 14, layer2: 28 x 28) or None."""
+        """-> the C entry point of the image-resident fused kernel for this identity block (layer3: 14 x 14, then layer2: 28 x 28, then
+        layer4: 7 x 7) or None."""
         if not (self._fits32(n, xhw, cc.cout) and self.fused_bottleneck14 and ds is None and getattr(ca, 'w_fwd_frag', None) is not None
                 and getattr(cb, 'w_fwd_frag', None) is not None and getattr(cc, 'w_fwd_frag', None) is not None):
             return None
@@ -580,9 +559,9 @@ class ResNet50Engine(EngineBase):
             return self.lib.rart_bottleneck7_fused_bf16
         return None
 
-    def _bneck14(self, x, w1, w2, w3, b1, b2, b3, m1, m2, m3, out, B, hw, c_io, c_mid, taps, backward, fn=None):
-        """One layer3 / layer2 identity Bottleneck as a single launch (csrc/bottleneck14_fused.hip, bottleneck28_fused.hip)."""
-        fn = fn or self.lib.rart_bottleneck14_fused_bf16
+    def _bneck_image(self, x, w1, w2, w3, b1, b2, b3, m1, m2, m3, out, B, hw, c_io, c_mid, taps, backward, fn):
+        """One identity Bottleneck of layer2 / layer3 / layer4 as a single launch of the image-resident kernel `fn` of
+        `_image_block_fn` (csrc/bottleneck28_fused.hip, bottleneck14_fused.hip, bottleneck7_fused.hip)."""
         ev = self._prof_begin()
         _lib.check(fn(
             _lib.ptr(x), _lib.ptr(w1), _lib.ptr(w2), _lib.ptr(w3), _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(b3), _lib.ptr(m1),
@@ -682,360 +661,286 @@ class ResNet50Engine(EngineBase):
                 self._gemm(dz, w, dx, B, (dx_hw[0] // 2, dx_hw[1] // 2), dz_hw, c.cout, c.cout, taps, c.cin, dx_hw,
                            c.cin, res=res, mask=mask, flags=fl, dst_stride=(2, 2), dst_off=(ph, pw), pair=pair)
 
-    # ------------------------------------------------------------------ forward
-    def _forward(self, src, src_is_u8, mean, std, keep):
-        if self.precision == 'bf16x3':
-            return self._forward_x3(src, src_is_u8, mean, std, keep)
-        torch = _lib.require_gpu()
-        lib = self.lib
-        if src_is_u8:
-            B, H, W = src.shape[0], src.shape[1], src.shape[2]
-        else:
-            B, H, W = src.shape[0], src.shape[2], src.shape[3]
-        assert H % 32 == 0 and W % 32 == 0, 'input height/width must be multiples of 32'
-        sp = _lib.stream_ptr()
-        meanf = (ctypes.c_float * 3)(*mean)
-        stdf = (ctypes.c_float * 3)(*std)
-        acts = {}
-        h1, w1 = H // 2, W // 2
-        h2, w2 = h1 // 2, w1 // 2
-        p1 = self._get('p1', (B, h2, w2, 64))
-        parg = self._get('p1_argmax', (B, h2, w2, 64), torch.uint8) if keep else None
-        bits = keep and self.sign_bit_masks
-        xs = self._get('p1_sign', (B, h2, w2, 8), torch.uint8) if bits else None
-        if self.fused_stem_fwd:
-            # normalise + hi/lo split + 7x7/2 conv + bias + ReLU + 3x3/2 max pool in one persistent kernel
-            y1 = None
-            _lib.check(lib.rart_engine_stem_fwd_fused(_lib.ptr(src), 1 if src_is_u8 else 0, _lib.ptr(self.stem_w),
-                                                      self.stem_w.shape[1], _lib.ptr(self.stem.bias), _lib.ptr(p1), _lib.ptr(parg),
-                                                      _lib.ptr(xs), B, H, W, meanf, stdf, sp))
-        else:
-            hi = self._get('in_hi', (2, B, H + 8, W + 8, 4))
-            _lib.check(lib.rart_engine_prep_input(_lib.ptr(src), 1 if src_is_u8 else 0, _lib.ptr(hi[0]), _lib.ptr(hi[1]),
-                                                  B, H, W, meanf, stdf, sp))
-            y1 = self._get('y1', (B, h1, w1, 64))
-            taps = [(r, 0) for r in range(7)] * 2
-            offs = [0] * 7 + [lo_off(hi)] * 7
-            self._gemm(hi[0], self.stem_w, y1, B, (h1, w1), (H + 8, W + 8), 4, 32, taps, 64, (h1, w1), 64,
-                       bias=self.stem.bias, flags=F_RELU, stride=(2, 2), tap_src_off=offs)
-            _lib.check(lib.rart_engine_maxpool_keep(_lib.ptr(y1), _lib.ptr(p1), _lib.ptr(parg), _lib.ptr(xs), B, h1, w1, 64, sp))
-        acts['y1'], acts['p1'], acts['p1_argmax'] = y1, p1, parg
-        x, xhw = p1, (h2, w2)
-        for bi, (ca, cb, cc, ds) in enumerate(self.blocks):
-            ohw = (xhw[0] // cb.stride, xhw[1] // cb.stride)
-            ya = yb = None       # the fused kernels keep both intermediates on chip: allocated on the unfused branch only
-            yc = self._get('b%d_c' % bi, (B, ohw[0], ohw[1], cc.cout))
-            sa = self._get('b%d_a_sign' % bi, (B, xhw[0], xhw[1], ca.cout // 8), torch.uint8) if bits else None
-            sb = self._get('b%d_b_sign' % bi, (B, ohw[0], ohw[1], cb.cout // 8), torch.uint8) if bits else None
-            sc = self._get('b%d_c_sign' % bi, (B, ohw[0], ohw[1], cc.cout // 8), torch.uint8) if bits else None
-            if (bits or not keep) and self._bneck_ok(ca, cb, cc, ds, xhw, B):
-                # the two 64-channel intermediates stay on chip; the backward pass gets their sign bits
-                self._bneck(x, ca.w_fwd, cb.w_fwd_frag, cc.w_fwd, ca.bias, cb.bias, cc.bias, sa, sb, sc, yc, B, xhw, cc.cout,
-                            ca.cout, cb.fwd_taps, False)
-                acts['b%d' % bi] = (x, xhw, ya, yb, yc, ohw)
-                acts['b%d_masks' % bi] = (xs, sa, sb)
-                x, xhw, xs = yc, ohw, sc
-                continue
-            fn14 = self._image_block_fn(ca, cb, cc, ds, xhw, B) if (bits or not keep) else None
-            if fn14 is not None:
-                self._bneck14(x, ca.w_fwd_frag, cb.w_fwd_frag, cc.w_fwd_frag, ca.bias, cb.bias, cc.bias, sa, sb, sc, yc, B, xhw,
-                              cc.cout, ca.cout, cb.fwd_taps, False, fn14)
-                acts['b%d' % bi] = (x, xhw, ya, yb, yc, ohw)
-                acts['b%d_masks' % bi] = (xs, sa, sb)
-                x, xhw, xs = yc, ohw, sc
-                continue
-            if (bits or not keep) and self._first_ok(ca, cb, cc, ds, xhw, B):
-                self._bneck(x, ca.w_fwd, cb.w_fwd_frag, cc.w_fwd, ca.bias, cb.bias, ds.bias_sum, sa, sb, sc, yc, B, xhw, cc.cout,
-                            ca.cout, cb.fwd_taps, False, w4=ds.w_fwd_frag, c_in=ca.cin)
-                acts['b%d' % bi] = (x, xhw, ya, yb, yc, ohw)
-                acts['b%d_masks' % bi] = (xs, sa, sb)
-                x, xhw, xs = yc, ohw, sc
-                continue
-            if (bits or not keep) and self._s2_ok(ca, cb, cc, ds, xhw, B):
-                self._bneck_s2(x, ca, cb, cc, ds, sa, sb, sc, yc, B, xhw)
-                acts['b%d' % bi] = (x, xhw, ya, yb, yc, ohw)
-                acts['b%d_masks' % bi] = (xs, sa, sb)
-                x, xhw, xs = yc, ohw, sc
-                continue
-            ya = self._get('b%d_a' % bi, (B, xhw[0], xhw[1], ca.cout))
-            yb = self._get('b%d_b' % bi, (B, ohw[0], ohw[1], cb.cout))
-            self._conv_fwd(ca, x, xhw, ya, True, sign=sa)
-            self._conv_fwd(cb, ya, xhw, yb, True, sign=sb)
-            if ds is not None:
-                sk = self._get('b%d_ds' % bi, (B, ohw[0], ohw[1], cc.cout))
-                self._conv_fwd(ds, x, xhw, sk, False)
-            else:
-                sk = x
-            self._conv_fwd(cc, yb, ohw, yc, True, res=sk, sign=sc)
-            # the backward pass needs the activations only for their ReLU sign: the 1-bit tensors when enabled
-            acts['b%d' % bi] = (x, xhw, ya, yb, yc, ohw)
-            acts['b%d_masks' % bi] = (xs, sa, sb) if bits else (x, ya, yb)
-            x, xhw, xs = yc, ohw, sc
-        pooled = self._get('pooled', (B, self.fc_in))
-        _lib.check(lib.rart_engine_avgpool(_lib.ptr(x), _lib.ptr(pooled), B, xhw[0] * xhw[1], self.fc_in, sp))
-        logits = torch.empty(B, self.n_classes, dtype=torch.float32, device=self.device)
-        if self.small_m_fc:
-            self._fc(pooled, self.fc_w, logits, B, self.n_classes, self.fc_in, bias=self.fc_b)
-        else:
-            self._gemm(pooled, self.fc_w, logits, B, (1, 1), (1, 1), self.fc_in, self.fc_in, [(0, 0)], self.n_classes,
-                       (1, 1), self.n_classes, bias=self.fc_b, flags=F_OUT_F32)
-        acts['last'] = (x, xhw)
-        acts['in_shape'] = (B, H, W)
-        return logits, acts
+    # ------------------------------------------------------------------ the chain: stem -> bottlenecks -> head, and back
+    def _po(self, t):
+        """how an activation goes to a library entry: its pointer, and in reference precision the element offset of the lo plane"""
+        return (_lib.ptr(t), lo_off(t)) if self.x3 else (_lib.ptr(t),)
 
-    # ------------------------------------------------------------------ reference-precision ("bf16x3") mode
-    def _forward_x3(self, src, src_is_u8, mean, std, keep):
-        """The forward of `_forward` with every tensor a hi + lo pair of bf16 planes and every contraction the three
-        products hi.hi + hi.lo + lo.hi (fp32 accumulate) on the implicit-GEMM kernel; one launch per layer."""
-        torch = _lib.require_gpu()
-        lib = self.lib
+    def _logits(self, src, src_is_u8, mean, std):
+        return self._forward(src, src_is_u8, mean, std, False)[0]
+
+    def _forward(self, src, src_is_u8, mean, std, keep):
+        """-> (logits fp32, acts).  keep: also write what the backward reads (pool argmax codes, ReLU signs); acts: per block
+        'b%d' = (x, xhw, ya, yb, yc, ohw) and 'b%d_masks' = (mx, ma, mb), the ReLU masks of block input / conv1 / conv2 output."""
         if src_is_u8:
             B, H, W = src.shape[0], src.shape[1], src.shape[2]
         else:
             B, H, W = src.shape[0], src.shape[2], src.shape[3]
         assert H % 32 == 0 and W % 32 == 0, 'input height/width must be multiples of 32'
-        sp = _lib.stream_ptr()
-        meanf = (ctypes.c_float * 3)(*mean)
-        stdf = (ctypes.c_float * 3)(*std)
-        acts = {}
+        # ReLU signs as 1-bit tensors; the bf16 chain can read the bf16 activations instead (cross-check), the pair chain cannot
+        bits = keep and (self.x3 or self.sign_bit_masks)
+        acts = {'in_shape': (B, H, W)}
+        x, xhw, xs = self._stem_fwd(src, src_is_u8, mean, std, B, H, W, keep, bits, acts)
+        pre_a = False            # this block's conv1 was already computed by the previous block's launch
+        for bi in range(len(self.blocks)):
+            x, xhw, xs, pre_a = self._block_fwd(bi, x, xhw, xs, B, keep, bits, pre_a, acts)
+        acts['last'], acts['last_sign'] = (x, xhw), xs
+        return self._head_fwd(x, xhw, B), acts
+
+    def _backward(self, acts, dl, std):
+        """d(loss)/d(x01) fp32 NCHW from the fp32 loss gradient dl [B][classes] and the `acts` of a keep=True forward."""
+        B = acts['in_shape'][0]
+        dz = self._head_bwd(acts, dl, B)
+        pre_b = False            # this block's conv3^T was already computed by the launch of the block above
+        for bi in range(len(self.blocks) - 1, -1, -1):       # dz = masked gradient at the block output (pre-ReLU)
+            dz, pre_b = self._block_bwd(bi, dz, B, pre_b, acts)
+        return self._stem_bwd(acts, dz, std)
+
+    def _stem_fwd(self, src, src_is_u8, mean, std, B, H, W, keep, bits, acts):
+        """normalise + hi/lo split + 7x7/2 conv + bias + ReLU + 3x3/2 max pool -> (pooled p1, its hw, its sign tensor)"""
+        import torch
+        lib, sp, x3 = self.lib, _lib.stream_ptr(), self.x3
+        meanf, stdf, u8 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std), 1 if src_is_u8 else 0
         h1, w1 = H // 2, W // 2
         h2, w2 = h1 // 2, w1 // 2
-        p1 = self._get('x3_p1', (2, B, h2, w2, 64))
+        p1 = self._act('p1', (B, h2, w2, 64))
         parg = self._get('p1_argmax', (B, h2, w2, 64), torch.uint8) if keep else None
-        xs = self._get('p1_sign', (B, h2, w2, 8), torch.uint8) if keep else None
-        if self.fused_stem_fwd:
-            # stem: normalise + split + 7x7/2 conv + bias + ReLU + max pool on pairs, one persistent kernel (stem_pair.hip)
+        xs = self._get('p1_sign', (B, h2, w2, 8), torch.uint8) if bits else None
+        y1 = None
+        if self.fused_stem_fwd and x3:        # one persistent kernel (stem_pair.hip)
             ev = self._prof_begin()
-            _lib.check(lib.rart_engine_stem_fwd_fused_pair(_lib.ptr(src), 1 if src_is_u8 else 0, _lib.ptr(self.stem_w_pair[0]),
-                                                           _lib.ptr(self.stem_w_pair[1]), _lib.ptr(self.stem.bias), _lib.ptr(p1[0]),
-                                                           _lib.ptr(p1[1]), _lib.ptr(parg), _lib.ptr(xs), B, H, W, meanf, stdf, sp))
+            _lib.check(lib.rart_engine_stem_fwd_fused_pair(_lib.ptr(src), u8, _lib.ptr(self.stem_w_pair[0]), _lib.ptr(self.stem_w_pair[1]),
+                                                           _lib.ptr(self.stem.bias), *self._hl(p1), _lib.ptr(parg), _lib.ptr(xs), B, H, W,
+                                                           meanf, stdf, sp))
             if ev is not None:   # issued: 3 products x (7 row taps x 32 = 224-deep K) x 64 channels per stem output; bytes: the image once + the pooled pair
                 self._prof_end(ev, 3 * 2.0 * B * h1 * w1 * 224 * 64, 'stem_pair', B * H * W * 3 * (1 if src_is_u8 else 4) + 4.0 * B * h2 * w2 * 64)
-        else:
+        elif self.fused_stem_fwd:             # one persistent kernel (stem_fused.hip)
+            _lib.check(lib.rart_engine_stem_fwd_fused(_lib.ptr(src), u8, _lib.ptr(self.stem_w), self.stem_w.shape[1], _lib.ptr(self.stem.bias),
+                                                      _lib.ptr(p1), _lib.ptr(parg), _lib.ptr(xs), B, H, W, meanf, stdf, sp))
+        else:                                 # cross-check: input prep -> row-tap GEMM -> max pool
             hi = self._get('in_hi', (2, B, H + 8, W + 8, 4))
-            _lib.check(lib.rart_engine_prep_input(_lib.ptr(src), 1 if src_is_u8 else 0, _lib.ptr(hi[0]), _lib.ptr(hi[1]),
-                                                  B, H, W, meanf, stdf, sp))
-            y1 = self._get('x3_y1', (2, B, h1, w1, 64))
-            self._gemm(hi, self.stem_w, y1, B, (h1, w1), (H + 8, W + 8), 4, 32, [(r, 0) for r in range(7)], 64, (h1, w1), 64,
-                       bias=self.stem.bias, flags=F_RELU, stride=(2, 2), pair=True)
-            _lib.check(lib.rart_engine_maxpool_pair(_lib.ptr(y1), lo_off(y1), _lib.ptr(p1), lo_off(p1), _lib.ptr(parg),
-                                                    _lib.ptr(xs), B, h1, w1, 64, sp))
-        acts['p1_argmax'] = parg
-        x, xhw = p1, (h2, w2)
-        pre_a = False            # this block's conv1 was already computed by the previous block's launch
-        for bi, (ca, cb, cc, ds) in enumerate(self.blocks):
-            ohw = (xhw[0] // cb.stride, xhw[1] // cb.stride)
-            tail = (self.fused_tail_pair and cb.cout in self.fused_tail_channels and getattr(cc, 'tail_fwd', None) is not None
-                    and self._fits32(B, ohw, cc.cout))
-            ya = self._get('x3_b%d_a' % bi, (2, B, xhw[0], xhw[1], ca.cout))
-            yb = None if tail else self._get('x3_b%d_b' % bi, (2, B, ohw[0], ohw[1], cb.cout))
-            yc = self._get('x3_b%d_c' % bi, (2, B, ohw[0], ohw[1], cc.cout))
-            sa = self._get('b%d_a_sign' % bi, (B, xhw[0], xhw[1], ca.cout // 8), torch.uint8) if keep else None
-            sb = self._get('b%d_b_sign' % bi, (B, ohw[0], ohw[1], cb.cout // 8), torch.uint8) if keep else None
-            sc = self._get('b%d_c_sign' % bi, (B, ohw[0], ohw[1], cc.cout // 8), torch.uint8) if keep else None
+            _lib.check(lib.rart_engine_prep_input(_lib.ptr(src), u8, _lib.ptr(hi[0]), _lib.ptr(hi[1]), B, H, W, meanf, stdf, sp))
+            y1 = self._act('y1', (B, h1, w1, 64))
+            rows = [(r, 0) for r in range(7)]
+            if x3:
+                self._gemm(hi, self.stem_w, y1, B, (h1, w1), (H + 8, W + 8), 4, 32, rows, 64, (h1, w1), 64, bias=self.stem.bias,
+                           flags=F_RELU, stride=(2, 2), pair=True)
+            else:                             # the image pair as two taps per filter row of the [hi | hi] table
+                self._gemm(hi[0], self.stem_w, y1, B, (h1, w1), (H + 8, W + 8), 4, 32, rows * 2, 64, (h1, w1), 64, bias=self.stem.bias,
+                           flags=F_RELU, stride=(2, 2), tap_src_off=[0] * 7 + [lo_off(hi)] * 7)
+            _lib.check((lib.rart_engine_maxpool_pair if x3 else lib.rart_engine_maxpool_keep)(
+                *self._po(y1), *self._po(p1), _lib.ptr(parg), _lib.ptr(xs), B, h1, w1, 64, sp))
+        acts['y1'], acts['p1'], acts['p1_argmax'] = y1, p1, parg
+        return p1, (h2, w2), xs
+
+    def _fused_block(self, ca, cb, cc, ds, xhw, B, backward):
+        """-> the single-launch kernel that takes this Bottleneck in this direction, or None = conv by conv.  Reference precision:
+        'tail' (conv_tail_pair.hip: the 3x3 and the 1x1 after it; the other convs keep their launches).  bf16, in this order:
+        'bneck' (bottleneck_fused.hip), the C entry of an image-resident kernel (14, then 28, then 7), 'first', 's2'."""
+        if self.x3:
+            c = ca if backward else cc       # the 1x1 of the launch; a block with a tail table has a stride-1 C -> C 3x3 (ohw = xhw)
+            return 'tail' if (self.fused_tail_pair and cb.cin in self.fused_tail_channels
+                              and getattr(c, 'tail_bwd' if backward else 'tail_fwd', None) is not None
+                              and self._fits32(B, xhw, c.cin if backward else c.cout)) else None
+        if self._bneck_ok(ca, cb, cc, ds, xhw, B):
+            return 'bneck'
+        fn = self._image_block_fn(ca, cb, cc, ds, xhw, B)
+        if fn is not None:
+            return fn
+        if self._first_ok(ca, cb, cc, ds, xhw, B):
+            return 'first'
+        if (not backward or (self.fused_bottleneck_s2_bwd and getattr(cb, 's2_w2t', None) is not None)) and self._s2_ok(ca, cb, cc, ds, xhw, B):
+            return 's2'
+        return None
+
+    def _block_fwd(self, bi, x, xhw, xs, B, keep, bits, pre_a, acts):
+        """Bottleneck bi -> (output, its hw, its sign tensor, whether the launch also ran conv1 of block bi + 1)"""
+        import torch
+        x3 = self.x3
+        get, lead = self._get, ((2, B) if x3 else (B,))       # an activation: bf16 [B][h][w][c], or the pair [2][B][h][w][c]
+        ca, cb, cc, ds = self.blocks[bi]
+        ohw = (xhw[0] // cb.stride, xhw[1] // cb.stride)
+        sa = get('b%d_a_sign' % bi, (B, xhw[0], xhw[1], ca.cout // 8), torch.uint8) if bits else None
+        sb = get('b%d_b_sign' % bi, (B, ohw[0], ohw[1], cb.cout // 8), torch.uint8) if bits else None
+        sc = get('b%d_c_sign' % bi, (B, ohw[0], ohw[1], cc.cout // 8), torch.uint8) if bits else None
+        yc = get('b%d_c' % bi, lead + (ohw[0], ohw[1], cc.cout))
+        ya = yb = None           # a fused kernel keeps its intermediates on chip: allocated only where a launch writes them
+        nxt = None
+        # the fused kernels emit ReLU signs as 1-bit tensors only
+        kind = self._fused_block(ca, cb, cc, ds, xhw, B, False) if (bits or not keep) else None
+        if kind == 'bneck':
+            self._bneck(x, ca.w_fwd, cb.w_fwd_frag, cc.w_fwd, ca.bias, cb.bias, cc.bias, sa, sb, sc, yc, B, xhw, cc.cout, ca.cout,
+                        cb.fwd_taps, False)
+        elif kind == 'first':
+            self._bneck(x, ca.w_fwd, cb.w_fwd_frag, cc.w_fwd, ca.bias, cb.bias, ds.bias_sum, sa, sb, sc, yc, B, xhw, cc.cout, ca.cout,
+                        cb.fwd_taps, False, w4=ds.w_fwd_frag, c_in=ca.cin)
+        elif kind == 's2':
+            self._bneck_s2(x, ca, cb, cc, ds, sa, sb, sc, yc, B, xhw)
+        elif kind not in (None, 'tail'):
+            self._bneck_image(x, ca.w_fwd_frag, cb.w_fwd_frag, cc.w_fwd_frag, ca.bias, cb.bias, cc.bias, sa, sb, sc, yc, B, xhw, cc.cout,
+                              ca.cout, cb.fwd_taps, False, kind)
+        else:
+            ya = get('b%d_a' % bi, lead + (xhw[0], xhw[1], ca.cout))
             if not pre_a:
-                self._conv_fwd(ca, x, xhw, ya, True, sign=sa, pair=True)
-            pre_a = False
-            if ds is not None:
-                sk = self._get('x3_b%d_ds' % bi, (2, B, ohw[0], ohw[1], cc.cout))
-                self._conv_fwd(ds, x, xhw, sk, False, pair=True)
-            else:
-                sk = x
-            if tail:         # conv2 + relu + conv3 + skip + relu in one launch: the 3x3's output never exists in HBM
-                nxt = None
+                self._conv_fwd(ca, x, xhw, ya, True, sign=sa, pair=x3)
+            if x3:               # (the pair chain launches the projection shortcut before conv2, the bf16 chain after it)
+                sk = x if ds is None else self._shortcut_fwd(bi, ds, x, xhw, ohw, B)
+            if kind == 'tail':   # conv2 + relu + conv3 + skip + relu in one launch: the 3x3's output never exists in HBM
                 na = self.blocks[bi + 1][0] if bi + 1 < len(self.blocks) else None
                 if self.fused_next_pair and na is not None and getattr(na, 'next_fwd', None) is not None and cb.cout in self.fused_next_channels:
                     # ... and the next block's conv1 + relu on the output tile: that block's own read of this output disappears
-                    nxt = dict(tab=na.next_fwd, bias=na.bias, relu=True, dst=self._get('x3_b%d_a' % (bi + 1), (2, B, ohw[0], ohw[1], na.cout)),
-                               sign=self._get('b%d_a_sign' % (bi + 1), (B, ohw[0], ohw[1], na.cout // 8), torch.uint8) if keep else None)
-                    pre_a = True
+                    nxt = dict(tab=na.next_fwd, bias=na.bias, relu=True, dst=get('b%d_a' % (bi + 1), lead + (ohw[0], ohw[1], na.cout)),
+                               sign=get('b%d_a_sign' % (bi + 1), (B, ohw[0], ohw[1], na.cout // 8), torch.uint8) if keep else None)
                 self._tail(ya, cb.w_fwd, cb.fwd_taps, cc.tail_fwd, yc, B, ohw, cb.cout, bias_mid=cb.bias, bias_out=cc.bias, res=sk,
                            sign_mid=sb, sign_out=sc, relu=True, nxt=nxt)
             else:
-                self._conv_fwd(cb, ya, xhw, yb, True, sign=sb, pair=True)
-                self._conv_fwd(cc, yb, ohw, yc, True, res=sk, sign=sc, pair=True)
-            acts['b%d' % bi] = (x, xhw, ya, yb, yc, ohw)
-            acts['b%d_masks' % bi] = (xs, sa, sb)
-            x, xhw, xs = yc, ohw, sc
-        pooled = self._get('x3_pooled', (2, B, self.fc_in))
-        _lib.check(lib.rart_engine_avgpool_pair(_lib.ptr(x), lo_off(x), _lib.ptr(pooled), lo_off(pooled), B,
-                                                xhw[0] * xhw[1], self.fc_in, sp))
-        logits = torch.empty(B, self.n_classes, dtype=torch.float32, device=self.device)
-        self._gemm(pooled, self.fc_w, logits, B, (1, 1), (1, 1), self.fc_in, self.fc_in, [(0, 0)], self.n_classes,
-                   (1, 1), self.n_classes, bias=self.fc_b, flags=F_OUT_F32, pair=True)
-        acts['last'] = (x, xhw)
-        acts['last_sign'] = xs
-        acts['in_shape'] = (B, H, W)
-        return logits, acts
+                yb = get('b%d_b' % bi, lead + (ohw[0], ohw[1], cb.cout))
+                self._conv_fwd(cb, ya, xhw, yb, True, sign=sb, pair=x3)
+                if not x3:
+                    sk = x if ds is None else self._shortcut_fwd(bi, ds, x, xhw, ohw, B)
+                self._conv_fwd(cc, yb, ohw, yc, True, res=sk, sign=sc, pair=x3)
+        acts['b%d' % bi] = (x, xhw, ya, yb, yc, ohw)
+        # the backward pass needs the activations only for their ReLU sign: the 1-bit tensors, or with `sign_bit_masks` off (bf16
+        # cross-check) the activations themselves
+        acts['b%d_masks' % bi] = (xs, sa, sb) if (bits or x3 or kind is not None) else (x, ya, yb)
+        return yc, ohw, sc, nxt is not None
 
-    def _backward_x3(self, acts, dl, std):
-        """d(loss)/d(x01) from the fp32 loss gradient dl [B][classes]: the backward-to-input chain on pairs."""
+    def _shortcut_fwd(self, bi, ds, x, xhw, ohw, B):
+        """-> the projection shortcut ds of Bottleneck bi's input"""
+        sk = self._act('b%d_ds' % bi, (B, ohw[0], ohw[1], ds.cout))
+        self._conv_fwd(ds, x, xhw, sk, False, pair=self.x3)
+        return sk
+
+    def _head_fwd(self, x, xhw, B):
+        """average pool + classifier -> logits fp32"""
         torch = _lib.require_gpu()
-        lib, sp = self.lib, _lib.stream_ptr()
-        B, H, W = acts['in_shape']
-        dlp = self._get('x3_dl', (2, B, self.fc_kpad))
-        _lib.check(lib.rart_f32_to_pair_rows(_lib.ptr(dl), _lib.ptr(dlp), lo_off(dlp), B, self.n_classes, self.fc_kpad, sp))
-        dpool = self._get('x3_dpool', (2, B, self.fc_in))
-        self._gemm(dlp, self.fc_wd, dpool, B, (1, 1), (1, 1), self.fc_kpad, self.fc_kpad, [(0, 0)], self.fc_in, (1, 1),
-                   self.fc_in, pair=True)
+        lib, x3 = self.lib, self.x3
+        pooled = self._act('pooled', (B, self.fc_in))
+        _lib.check((lib.rart_engine_avgpool_pair if x3 else lib.rart_engine_avgpool)(
+            *self._po(x), *self._po(pooled), B, xhw[0] * xhw[1], self.fc_in, _lib.stream_ptr()))
+        logits = torch.empty(B, self.n_classes, dtype=torch.float32, device=self.device)
+        if self.small_m_fc and not x3:
+            self._fc(pooled, self.fc_w, logits, B, self.n_classes, self.fc_in, bias=self.fc_b)
+        else:
+            self._gemm(pooled, self.fc_w, logits, B, (1, 1), (1, 1), self.fc_in, self.fc_in, [(0, 0)], self.n_classes,
+                       (1, 1), self.n_classes, bias=self.fc_b, flags=F_OUT_F32, pair=x3)
+        return logits
+
+    def _head_bwd(self, acts, dl, B):
+        """classifier^T + average-pool backward with the last block's ReLU mask -> gradient at the last block's output"""
+        lib, x3 = self.lib, self.x3
+        # dpool[B][2048] = dlogits[B][1024 padded] . Wfc
+        dlb = self._dlogits_rows(dl, 'g_dl', B, self.fc_kpad)
+        dpool = self._act('dpool', (B, self.fc_in))
+        if self.small_m_fc and not x3:
+            self._fc(dlb, self.fc_wd, dpool, B, self.fc_in, self.fc_kpad)
+        else:
+            self._gemm(dlb, self.fc_wd, dpool, B, (1, 1), (1, 1), self.fc_kpad, self.fc_kpad, [(0, 0)], self.fc_in, (1, 1),
+                       self.fc_in, pair=x3)
         xl, xlhw = acts['last']
-        dz = self._get('x3_g_out_%d' % (len(self.blocks) - 1), tuple(xl.shape))
-        _lib.check(lib.rart_engine_avgpool_bwd_pair(_lib.ptr(acts['last_sign']), _lib.ptr(dpool), lo_off(dpool), _lib.ptr(dz),
-                                                    lo_off(dz), B, xlhw[0] * xlhw[1], self.fc_in, sp))
-        pre_b = False            # this block's conv3^T was already computed by the launch of the block above
-        for bi in range(len(self.blocks) - 1, -1, -1):
-            ca, cb, cc, ds = self.blocks[bi]
-            x, xhw, ya, yb, yc, ohw = acts['b%d' % bi]
-            mx, ma, mb = acts['b%d_masks' % bi]
-            dzb = self._get('x3_g_b%d' % (bi & 1), (2, B, ohw[0], ohw[1], cb.cout))
+        dz = self._get('g_out_%d' % (len(self.blocks) - 1), tuple(xl.shape))
+        # the ReLU mask: the pair entry reads the sign tensor, the bf16 entry the activation itself
+        _lib.check((lib.rart_engine_avgpool_bwd_pair if x3 else lib.rart_engine_avgpool_bwd)(
+            _lib.ptr(acts['last_sign'] if x3 else xl), *self._po(dpool), *self._po(dz), B, xlhw[0] * xlhw[1], self.fc_in, _lib.stream_ptr()))
+        return dz
+
+    def _block_bwd(self, bi, dz, B, pre_b, acts):
+        """backward-to-input of Bottleneck bi -> (gradient at its input, whether the launch also ran conv3^T of block bi - 1)"""
+        import torch
+        x3 = self.x3
+        get, lead = self._get, ((2, B) if x3 else (B,))
+        ca, cb, cc, ds = self.blocks[bi]
+        x, xhw, ya, yb, yc, ohw = acts['b%d' % bi]
+        mx, ma, mb = acts['b%d_masks' % bi]
+        dx = get('g_out_%d' % (bi - 1), tuple(x.shape))
+        # the fused kernels read ReLU masks as 1-bit tensors only
+        if x3:
+            bits = ma is not None and mx is not None
+        else:
+            bits = ma is not None and ma.dtype == torch.uint8 and mb is not None
+        kind = self._fused_block(ca, cb, cc, ds, xhw, B, True) if bits else None
+        if kind == 'bneck':
+            self._bneck(dz, cc.bwd[0][2], cb.w_bwd_frag, ca.bwd[0][2], None, None, None, mb, ma, mx, dx, B, xhw, cc.cout, ca.cout,
+                        cb.bwd[0][1], True)
+        elif kind == 'first':
+            self._bneck(dz, cc.bwd[0][2], cb.w_bwd_frag, ds.bwd[0][2], None, None, None, mb, ma, mx, dx, B, xhw, cc.cout, ca.cout,
+                        cb.bwd[0][1], True, w4=ca.bwd[0][2], c_in=ca.cin)
+        elif kind == 's2':
+            self._bneck_s2_bwd(dz, ca, cb, cc, ds, mb, ma, mx, dx, B, xhw)
+        elif kind not in (None, 'tail'):
+            self._bneck_image(dz, cc.w_bwd_frag, cb.w_bwd_frag, ca.w_bwd_frag, None, None, None, mb, ma, mx, dx, B, xhw, cc.cout, ca.cout,
+                              cb.bwd[0][1], True, kind)
+        else:
+            # (shapes from the layer geometry: a fused forward never materialises ya / yb.)  The pair chain alternates two buffers:
+            # the launch of the block above may have written this block's while its own was live
+            dzb = get('g_b%d' % (bi & 1) if x3 else 'g_b', lead + (ohw[0], ohw[1], cb.cout))
             if not pre_b:
-                self._conv_bwd(cc, dz, ohw, dzb, ohw, mask=mb, pair=True)
-            pre_b = False
-            dx = self._get('x3_g_out_%d' % (bi - 1), tuple(x.shape))
-            if (self.fused_tail_pair and cb.cin in self.fused_tail_channels and getattr(ca, 'tail_bwd', None) is not None and ma is not None
-                    and mx is not None and self._fits32(B, xhw, ca.cin)):
-                # conv2^T + mask + conv1^T + identity-skip gradient + mask in one launch
+                self._conv_bwd(cc, dz, ohw, dzb, ohw, mask=mb, pair=x3)
+            if kind == 'tail':   # conv2^T + mask + conv1^T + identity-skip gradient + mask in one launch
                 nxt = None
                 pc = self.blocks[bi - 1][2] if bi > 0 else None
                 if self.fused_next_pair and pc is not None and getattr(pc, 'next_bwd', None) is not None and cb.cin in self.fused_next_channels:
-                    # ... and the previous block's conv3^T + mask on the input-gradient tile
-                    nxt = dict(tab=pc.next_bwd, mask=acts['b%d_masks' % (bi - 1)][2],
-                               dst=self._get('x3_g_b%d' % ((bi - 1) & 1), (2, B, xhw[0], xhw[1], pc.cin)))
-                    pre_b = nxt['mask'] is not None
-                    if not pre_b:
-                        nxt = None
+                    # ... and the previous block's conv3^T + mask on the input-gradient tile, when that block kept a mask
+                    mask = acts['b%d_masks' % (bi - 1)][2]
+                    if mask is not None:
+                        nxt = dict(tab=pc.next_bwd, mask=mask, dst=get('g_b%d' % ((bi - 1) & 1), lead + (xhw[0], xhw[1], pc.cin)))
                 self._tail(dzb, cb.bwd[0][2], cb.bwd[0][1], ca.tail_bwd, dx, B, xhw, cb.cin, res=dz, mask_mid=ma, mask_out=mx, nxt=nxt)
-                dz = dx
-                continue
-            dza = self._get('x3_g_a', tuple(ya.shape))
-            self._conv_bwd(cb, dzb, ohw, dza, xhw, mask=ma, pair=True)
+                return dx, nxt is not None
+            dza = get('g_a', lead + (xhw[0], xhw[1], ca.cout))
+            self._conv_bwd(cb, dzb, ohw, dza, xhw, mask=ma, pair=x3)
             if ds is None:
-                self._conv_bwd(ca, dza, xhw, dx, xhw, res=dz, mask=mx, pair=True)            # identity skip
+                self._conv_bwd(ca, dza, xhw, dx, xhw, res=dz, mask=mx, pair=x3)            # identity skip
             else:
-                self._conv_bwd(ca, dza, xhw, dx, xhw, mask=mx, pair=True)
-                self._conv_bwd(ds, dz, ohw, dx, xhw, res=dx, mask=mx, pair=True)             # accumulate the projection skip
-            dz = dx
+                self._conv_bwd(ca, dza, xhw, dx, xhw, mask=mx, pair=x3)
+                self._conv_bwd(ds, dz, ohw, dx, xhw, res=dx, mask=mx, pair=x3)             # accumulate the projection skip
+        return dx, False
+
+    def _stem_bwd(self, acts, dz, std):
+        """max-pool backward + ReLU mask + transposed 7x7/2 conv -> d(loss)/d(x01) fp32 NCHW"""
+        torch = _lib.require_gpu()
+        lib, sp, x3 = self.lib, _lib.stream_ptr(), self.x3
+        B, H, W = acts['in_shape']
         grad = torch.empty(B, 3, H, W, dtype=torch.float32, device=self.device)
         stdf = (ctypes.c_float * 3)(*std)
-        if self.fused_stem_bwd:
-            # stem: max-pool backward + ReLU mask + transposed 7x7/2 conv to the fp32 image on pairs, one kernel (stem_pair.hip)
+        parg = acts['p1_argmax']
+        if self.fused_stem_bwd and x3:        # one kernel (stem_pair.hip)
             ev = self._prof_begin()
-            _lib.check(lib.rart_engine_stem_bwd_fused_pair(_lib.ptr(dz[0]), _lib.ptr(dz[1]), _lib.ptr(acts['p1_argmax']),
-                                                           _lib.ptr(self.stem_wt_pair[0]), _lib.ptr(self.stem_wt_pair[1]),
-                                                           _lib.ptr(grad), B, H, W, stdf, sp))
+            _lib.check(lib.rart_engine_stem_bwd_fused_pair(*self._hl(dz), _lib.ptr(parg), *self._hl(self.stem_wt_pair), _lib.ptr(grad),
+                                                           B, H, W, stdf, sp))
             if ev is not None:
                 # issued: M = stem-output positions, K = 16 taps x 64 channels, N = 16 (4 pixel parities x 3 colours, padded); bytes: pooled
                 # gradient pair + argmax codes + the fp32 image gradient
                 self._prof_end(ev, 3 * 2.0 * B * (H // 2) * (W // 2) * 16 * 64 * 16, 'stem_pair', 4.0 * B * (H // 4) * (W // 4) * 64 * 1.25 + 4.0 * B * H * W * 3)
             return grad
+        if self.fused_stem_bwd:               # one kernel (stem_fused.hip)
+            _lib.check(lib.rart_engine_stem_bwd_fused(_lib.ptr(dz), _lib.ptr(parg), _lib.ptr(self.stem_wt), _lib.ptr(grad), B, H, W, stdf, sp))
+            return grad
+        # cross-check: max-pool backward (+ ReLU mask), patches GEMM, col2im to the fp32 image (bf16 patches, fp32 from pairs)
+        y1 = acts['y1']          # the bf16 entry reads the stem output for its ReLU mask, the pair entry the argmax codes alone
+        assert x3 or y1 is not None, 'the unfused stem backward needs the stem output: set fused_stem_fwd = False as well'
         h1, w1 = H // 2, W // 2
-        dz1 = self._get('x3_g_y1', (2, B, h1, w1, 64))
-        _lib.check(lib.rart_engine_maxpool_bwd_pair(_lib.ptr(acts['p1_argmax']), _lib.ptr(dz), lo_off(dz), _lib.ptr(dz1),
-                                                    lo_off(dz1), B, h1, w1, 64, sp))
+        dz1 = self._act('g_y1', (B, h1, w1, 64))
+        if x3:
+            _lib.check(lib.rart_engine_maxpool_bwd_pair(_lib.ptr(parg), *self._po(dz), *self._po(dz1), B, h1, w1, 64, sp))
+        else:
+            _lib.check(lib.rart_engine_maxpool_bwd(_lib.ptr(y1), _lib.ptr(parg), _lib.ptr(dz), _lib.ptr(dz1), B, h1, w1, 64, sp))
         pc = self.stem_patch_cols
-        patches = self._get('x3_patches', (B, h1, w1, pc), torch.float32)
-        self._gemm(dz1, self.stem_wd, patches, B, (h1, w1), (h1, w1), 64, 64, [(0, 0)], pc, (h1, w1), pc, flags=F_OUT_F32,
-                   pair=True)
-        _lib.check(lib.rart_engine_stem_col2im_f32(_lib.ptr(patches), _lib.ptr(grad), B, H, W, pc, stdf, sp))
+        patches = self._get('patches', (B, h1, w1, pc), torch.float32 if x3 else torch.bfloat16)
+        self._gemm(dz1, self.stem_wd, patches, B, (h1, w1), (h1, w1), 64, 64, [(0, 0)], pc, (h1, w1), pc, flags=F_OUT_F32 if x3 else 0,
+                   pair=x3)
+        _lib.check((lib.rart_engine_stem_col2im_f32 if x3 else lib.rart_engine_stem_col2im)(_lib.ptr(patches), _lib.ptr(grad), B, H, W, pc,
+                                                                                             stdf, sp))
         return grad
-
-    def logits(self, x01, mean, std):
-        """x01: fp32 NCHW in [0,1]; mean/std: 3-tuples applied inside the stem's input kernel."""
-        return self._forward(x01.detach().float().contiguous(), False, mean, std, keep=False)[0]
-
-    def logits_from_u8(self, batch_u8, mean, std):
-        """batch_u8: uint8 NHWC (the corruption kernels' output) -> logits, normalisation fused."""
-        return self._forward(batch_u8, True, mean, std, keep=False)[0]
 
     # ------------------------------------------------------------------ forward + backward to the input
     def forward_backward(self, x01, mean, std, y, kind, y_target=None, scale=1.0):
         """-> (logits fp32, loss_indiv, d(sum_i scale*loss_i)/dx01 fp32 NCHW, pred int32)."""
         from ..noise.adv import logit_loss
-        torch = _lib.require_gpu()
-        lib = self.lib
-        sp = _lib.stream_ptr()
-        x01 = x01.detach().float().contiguous()
-        logits, acts = self._forward(x01, False, mean, std, keep=True)
+        logits, acts = self._forward(x01.detach().float().contiguous(), False, mean, std, keep=True)
         self.last_acts = acts            # exposed for the parity tests (ReLU masks of this forward)
         loss, dl, pred = logit_loss(logits, y, kind, y_target, scale)
         self.last_dlogits = dl
-        if self.precision == 'bf16x3':
-            return logits, loss, self._backward_x3(acts, dl, std), pred
-        B, H, W = acts['in_shape']
-        # fc backward: dpool[B][2048] = dlogits[B][1024 padded] . Wfc
-        dlb = self._get('dl_bf16', (B, self.fc_kpad))
-        _lib.check(lib.rart_f32_to_bf16_rows(_lib.ptr(dl), _lib.ptr(dlb), B, self.n_classes, self.fc_kpad, sp))
-        dpool = self._get('dpool', (B, self.fc_in))
-        if self.small_m_fc:
-            self._fc(dlb, self.fc_wd, dpool, B, self.fc_in, self.fc_kpad)
-        else:
-            self._gemm(dlb, self.fc_wd, dpool, B, (1, 1), (1, 1), self.fc_kpad, self.fc_kpad, [(0, 0)], self.fc_in, (1, 1),
-                       self.fc_in)
-        xl, xlhw = acts['last']
-        dz = self._get('g_out_%d' % (len(self.blocks) - 1), tuple(xl.shape))
-        _lib.check(lib.rart_engine_avgpool_bwd(_lib.ptr(xl), _lib.ptr(dpool), _lib.ptr(dz), B, xlhw[0] * xlhw[1],
-                                               self.fc_in, sp))
-        # blocks in reverse; dz = masked gradient at the block output (pre-ReLU)
-        for bi in range(len(self.blocks) - 1, -1, -1):
-            ca, cb, cc, ds = self.blocks[bi]
-            x, xhw, ya, yb, yc, ohw = acts['b%d' % bi]
-            mx, ma, mb = acts['b%d_masks' % bi]
-            if (ma is not None and ma.dtype == torch.uint8 and mb is not None and self._bneck_ok(ca, cb, cc, ds, xhw, B)):
-                dx = self._get('g_out_%d' % (bi - 1), tuple(x.shape))
-                self._bneck(dz, cc.bwd[0][2], cb.w_bwd_frag, ca.bwd[0][2], None, None, None, mb, ma, mx, dx, B, xhw, cc.cout,
-                            ca.cout, cb.bwd[0][1], True)
-                dz = dx
-                continue
-            fn14 = self._image_block_fn(ca, cb, cc, ds, xhw, B) if (ma is not None and ma.dtype == torch.uint8 and mb is not None) else None
-            if fn14 is not None:
-                dx = self._get('g_out_%d' % (bi - 1), tuple(x.shape))
-                self._bneck14(dz, cc.w_bwd_frag, cb.w_bwd_frag, ca.w_bwd_frag, None, None, None, mb, ma, mx, dx, B, xhw,
-                              cc.cout, ca.cout, cb.bwd[0][1], True, fn14)
-                dz = dx
-                continue
-            if (ma is not None and ma.dtype == torch.uint8 and mb is not None and self._first_ok(ca, cb, cc, ds, xhw, B)):
-                dx = self._get('g_out_%d' % (bi - 1), tuple(x.shape))
-                self._bneck(dz, cc.bwd[0][2], cb.w_bwd_frag, ds.bwd[0][2], None, None, None, mb, ma, mx, dx, B, xhw, cc.cout,
-                            ca.cout, cb.bwd[0][1], True, w4=ca.bwd[0][2], c_in=ca.cin)
-                dz = dx
-                continue
-            if (self.fused_bottleneck_s2_bwd and ma is not None and ma.dtype == torch.uint8 and mb is not None
-                    and getattr(cb, 's2_w2t', None) is not None and self._s2_ok(ca, cb, cc, ds, xhw, B)):
-                dx = self._get('g_out_%d' % (bi - 1), tuple(x.shape))
-                self._bneck_s2_bwd(dz, ca, cb, cc, ds, mb, ma, mx, dx, B, xhw)
-                dz = dx
-                continue
-            # (shapes from the layer geometry: a fused forward never materialises ya / yb)
-            dzb = self._get('g_b', (B, ohw[0], ohw[1], cb.cout))
-            self._conv_bwd(cc, dz, ohw, dzb, ohw, mask=mb)
-            dza = self._get('g_a', (B, xhw[0], xhw[1], ca.cout))
-            self._conv_bwd(cb, dzb, ohw, dza, xhw, mask=ma)
-            dx = self._get('g_out_%d' % (bi - 1), tuple(x.shape))
-            if ds is None:
-                self._conv_bwd(ca, dza, xhw, dx, xhw, res=dz, mask=mx)            # identity skip
-            else:
-                self._conv_bwd(ca, dza, xhw, dx, xhw, mask=mx)
-                self._conv_bwd(ds, dz, ohw, dx, xhw, res=dx, mask=mx)             # accumulate the projection skip
-            dz = dx
-        grad = torch.empty(B, 3, H, W, dtype=torch.float32, device=self.device)
-        stdf = (ctypes.c_float * 3)(*std)
-        if self.fused_stem_bwd:
-            # stem: max-pool backward + ReLU mask + transposed 7x7/2 conv to the fp32 image, one kernel
-            _lib.check(lib.rart_engine_stem_bwd_fused(_lib.ptr(dz), _lib.ptr(acts['p1_argmax']), _lib.ptr(self.stem_wt),
-                                                      _lib.ptr(grad), B, H, W, stdf, sp))
-            return logits, loss, grad, pred
-        # cross-check path: max-pool backward (+ReLU mask of y1), patches GEMM, col2im to the fp32 image
-        y1 = acts['y1']
-        assert y1 is not None, 'the unfused stem backward needs the stem output: set fused_stem_fwd = False as well'
-        h1, w1 = H // 2, W // 2
-        dz1 = self._get('g_y1', tuple(y1.shape))
-        _lib.check(lib.rart_engine_maxpool_bwd(_lib.ptr(y1), _lib.ptr(acts['p1_argmax']), _lib.ptr(dz), _lib.ptr(dz1),
-                                               B, h1, w1, 64, sp))
-        pc = self.stem_patch_cols
-        patches = self._get('patches', (B, h1, w1, pc))
-        self._gemm(dz1, self.stem_wd, patches, B, (h1, w1), (h1, w1), 64, 64, [(0, 0)], pc, (h1, w1), pc)
-        _lib.check(lib.rart_engine_stem_col2im(_lib.ptr(patches), _lib.ptr(grad), B, H, W, pc, stdf, sp))
-        return logits, loss, grad, pred
+        return logits, loss, self._backward(acts, dl, std), pred
 
 
 def make_engine(torch_model, device='cuda', precision='bf16'):

@@ -268,6 +268,24 @@ class EngineBase:
             self._buf[name] = t
         return t
 
+    # precision-generic helpers: a bf16 tensor or a pair [2][...], the bf16 or the pair library entry
+    def _act(self, name, shape):
+        """activation buffer: bf16 [shape], or the pair [2][shape]"""
+        return self._get(name, ((2,) + tuple(shape)) if self.x3 else tuple(shape))
+
+    def _hl(self, t):
+        return (_lib.ptr(t[0]), _lib.ptr(t[1])) if self.x3 else (_lib.ptr(t), None)
+
+    def _dlogits_rows(self, dl, name, B, kpad):
+        """-> the fp32 loss gradient dl [B][n_classes] as rows of kpad columns (zero past n_classes) in the engine's precision"""
+        lib, sp = self.lib, _lib.stream_ptr()
+        dlb = self._act(name, (B, kpad))
+        if self.x3:
+            _lib.check(lib.rart_f32_to_pair_rows(_lib.ptr(dl), _lib.ptr(dlb[0]), lo_off(dlb), B, self.n_classes, kpad, sp))
+        else:
+            _lib.check(lib.rart_f32_to_bf16_rows(_lib.ptr(dl), _lib.ptr(dlb), B, self.n_classes, kpad, sp))
+        return dlb
+
     def _prof_begin(self):
         if self.profile is None:
             return None
@@ -323,11 +341,15 @@ class EngineBase:
 
     def logits(self, x01, mean, std):
         """x01: fp32 NCHW in [0,1]; mean/std: 3-tuples applied inside the input kernel."""
-        return self._forward(x01.detach().float().contiguous(), False, mean, std)
+        return self._logits(x01.detach().float().contiguous(), False, mean, std)
 
     def logits_from_u8(self, batch_u8, mean, std):
         """batch_u8: uint8 NHWC (the corruption kernels' output) -> logits, normalisation fused."""
-        return self._forward(batch_u8, True, mean, std)
+        return self._logits(batch_u8, True, mean, std)
+
+    def _logits(self, src, src_is_u8, mean, std):
+        """the inference forward: nothing kept for a backward (ResNet-50's `_forward` also returns its activations)"""
+        return self._forward(src, src_is_u8, mean, std)
 
 
 class RowEngine(EngineBase):
@@ -358,13 +380,6 @@ class RowEngine(EngineBase):
                                          dst_rows_per_image=dst_rows_per_image, dst_row_off=dst_row_off, batched=batched))
 
     # ------------------------------------------------------------------ precision-generic launches
-    def _act(self, name, shape):
-        """activation buffer: bf16 [shape], or the pair [2][shape]"""
-        return self._get(name, ((2,) + tuple(shape)) if self.x3 else tuple(shape))
-
-    def _hl(self, t):
-        return (_lib.ptr(t[0]), _lib.ptr(t[1])) if self.x3 else (_lib.ptr(t), None)
-
     def _mm(self, a, w, dst, M, N, K, lda=None, ldc=None, aux=None, src_row_off=0, **kw):
         """dst[M][N] = a[M][K] . w[N][K]^T; kw: bias, res, flags (the F_* values, which the GP_* flags share; aux = the GELU
         pre-activation kept / read) and rows_per_image, src_rows_per_image, dst_rows_per_image, dst_row_off: image b's rows are
@@ -404,16 +419,6 @@ class RowEngine(EngineBase):
         else:                        # bf16: only the 256 x 256 GEMM keeps the pre-activation
             self._mm(ln, w, u, rows, N, K, bias=b)
             _lib.check(self.lib.rart_gelu_bf16(_lib.ptr(u), _lib.ptr(hid), u.numel(), _lib.stream_ptr()))
-
-    def _dlogits_rows(self, dl, name, B, kpad):
-        """-> the fp32 loss gradient dl [B][n_classes] as rows of kpad columns (zero past n_classes) in the engine's precision"""
-        lib, sp = self.lib, _lib.stream_ptr()
-        dlb = self._act(name, (B, kpad))
-        if self.x3:
-            _lib.check(lib.rart_f32_to_pair_rows(_lib.ptr(dl), _lib.ptr(dlb[0]), lo_off(dlb), B, self.n_classes, kpad, sp))
-        else:
-            _lib.check(lib.rart_f32_to_bf16_rows(_lib.ptr(dl), _lib.ptr(dlb), B, self.n_classes, kpad, sp))
-        return dlb
 
     def _patchify(self, src, src_is_u8, mean, std, B, H, W, ps):
         """-> the normalised ps x ps patches of the image batch as the pair [2][B][patches][3 * ps * ps] (in both precisions)"""

@@ -54,7 +54,7 @@ def wrapped_bneck(x_, w1, w2, w3, b1, b2, b3, m1, m2, m3, out, B_, hw, c_io, c_m
     k_all = (2 * c_io + 9 * c_mid) if w4 is None else (c_in + 9 * c_mid + c_io + c_in * c_io // c_mid)
     rows.append(((M, k_all, c_mid, 98), 2.0 * M * c_mid * k_all, by, e0, e1))   # taps column 98 = fused block
     return r
-orig_b14 = eng._bneck14
+orig_b14 = eng._bneck_image
 def wrapped_b14(x_, w1, w2, w3, b1, b2, b3, m1, m2, m3, out, B_, hw, c_io, c_mid, taps, backward, fn=None):
     M = B_ * hw[0] * hw[1]
     by = 2 * M * c_io * 2 + (2 * c_io * c_mid + 9 * c_mid * c_mid) * 2 + sum(M * c * 0.125 for c, m_ in ((c_mid, m1), (c_mid, m2), (c_io, m3)) if m_ is not None)
@@ -94,7 +94,7 @@ def wrapped_tail(src, wgt, taps, tail, dst, batch, hw, c_mid, **kw):
     return r
 for _ in range(2): eng.forward_backward(x, MEAN, STD, y, 0)
 eng._tail = wrapped_tail
-eng._bneck14 = wrapped_b14
+eng._bneck_image = wrapped_b14
 eng._bneck_s2_bwd = wrapped_s2b
 eng._bneck_s2 = wrapped_s2
 eng._gemm = wrapped
@@ -108,7 +108,7 @@ eng._gemm = orig
 eng._tail = orig_tail
 eng._halo = orig_halo
 eng._bneck = orig_bneck
-eng._bneck14 = orig_b14
+eng._bneck_image = orig_b14
 eng._bneck_s2 = orig_s2
 eng._bneck_s2_bwd = orig_s2b
 agg = {}

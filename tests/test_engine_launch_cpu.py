@@ -10,7 +10,7 @@ class _Recorder:
     """stands in for the library: answers every rart_* entry and records (name, arguments); `descs`: the descriptors of the GEMM launches"""
 
     def __init__(self):
-        self.calls, self.gemm256 = [], 0
+        self.calls, self.gemm256, self.supported = [], 0, None      # supported(name, args): the answer of every rart_*_supported
 
     @property
     def descs(self):
@@ -21,6 +21,8 @@ class _Recorder:
             raise AttributeError(name)
         if name == 'rart_gemm256_supported':
             return lambda *a: self.gemm256
+        if name.endswith('_supported') and self.supported is not None:
+            return lambda *a: self.supported(name, a)
 
         def call(*args):
             self.calls.append((name, args))
@@ -339,3 +341,218 @@ def test_vit_tables_exist_in_the_engines_precision_only(monkeypatch):
         assert not isinstance(eng.x3, dict)
         # same keys in both precisions
         assert sorted(k for k in eng.layers[0] if k.endswith(('_w', '_wd'))) == sorted(names)
+
+
+# ---------------------------------------------------------------------- ResNet-50's one chain
+_RESNET = []
+
+
+def _resnet(monkeypatch, precision, supported=lambda name, args: 0):
+    """ResNet50Engine of the full (3, 4, 6, 3) network on the CPU; supported(name, args) answers every rart_*_supported"""
+    from robustart_amd.model import get_model
+    from robustart_amd.model.engine import ResNet50Engine
+    if not _RESNET:
+        torch.manual_seed(0)
+        _RESNET.append(get_model({'type': 'resnet50_official'}).eval())
+    rec = _Recorder()
+    rec.supported = supported
+    monkeypatch.setattr(_lib, 'require_gpu', lambda: torch)
+    monkeypatch.setattr(_lib, 'stream_ptr', lambda: None)
+    monkeypatch.setattr(_lib, 'load', lambda: rec)
+    eng = ResNet50Engine(_RESNET[0], 'cpu', precision)
+    rec.calls.clear()
+    return eng
+
+
+def _stub_loss(monkeypatch, B, n=1000):
+    from robustart_amd.noise import adv
+    monkeypatch.setattr(adv, 'logit_loss', lambda logits, *a: (torch.zeros(B), torch.ones(B, n), torch.zeros(B, dtype=torch.int32)))
+
+
+def _names(eng):
+    out = [n for n, _ in eng.lib.calls]
+    eng.lib.calls.clear()
+    return out
+
+
+def _resnet_kinds(eng):
+    """entry names with the precision taken out; every GEMM launcher reads as 'gemm'"""
+    out = []
+    for n in _names(eng):
+        n = n.replace('_pair', '').replace('_bf16', '')
+        out.append('gemm' if n in ('rart_conv_igemm', 'rart_gemm', 'rart_gemm_small_m') else n)
+    return out
+
+
+def test_resnet_chain_launches_the_same_sequence_in_both_precisions(monkeypatch):
+    """with no fused block kernel available, forward and forward + backward are entry for entry the same chain in bf16 and in
+    reference precision: stem, 52 convolutions, pool, classifier, and back"""
+    B = 2
+    x = torch.rand(B, 3, 64, 64)
+    _stub_loss(monkeypatch, B)
+    bf, x3 = _resnet(monkeypatch, 'bf16'), _resnet(monkeypatch, 'fp32x')
+    bf.logits(x, MEAN, STD), x3.logits(x, MEAN, STD)
+    fwd = _resnet_kinds(bf)
+    assert fwd == _resnet_kinds(x3)
+    assert len(fwd) == 55 and fwd == ['rart_engine_stem_fwd_fused'] + ['gemm'] * 52 + ['rart_engine_avgpool', 'gemm']
+    u8 = torch.zeros(B, 64, 64, 3, dtype=torch.uint8)
+    bf.logits_from_u8(u8, MEAN, STD), x3.logits_from_u8(u8, MEAN, STD)
+    assert _resnet_kinds(bf) == fwd == _resnet_kinds(x3)
+    bf.forward_backward(x, MEAN, STD, None, 0), x3.forward_backward(x, MEAN, STD, None, 0)
+    both = _resnet_kinds(bf)
+    assert both == _resnet_kinds(x3)
+    assert len(both) == 120 and both.count('gemm') == 115 and both[:55] == fwd
+    # a 1x1 / 2 projection reaches one input-parity class, a 3x3 / 2 all four: 52 + 3 * 3 backward convolutions, one classifier
+    assert both[55:] == ['rart_f32_to_rows', 'gemm', 'rart_engine_avgpool_bwd'] + ['gemm'] * 61 + ['rart_engine_stem_bwd_fused']
+    # the per-precision details: activations and gradients are bf16 tensors or pairs under the same names
+    for name in ('p1', 'b0_a', 'b0_b', 'b0_c', 'b0_ds', 'b15_c', 'pooled', 'g_dl', 'dpool', 'g_a', 'g_out_-1', 'g_out_15'):
+        assert tuple(x3._buf[name].shape) == (2,) + tuple(bf._buf[name].shape), name
+    assert 'g_b' in bf._buf and 'g_b0' not in bf._buf and 'g_b' not in x3._buf and 'g_b0' in x3._buf and 'g_b1' in x3._buf
+    assert not [k for k in list(bf._buf) + list(x3._buf) if k.startswith('x3_')]
+    for e in (bf, x3):
+        acts = e.last_acts
+        assert set(acts) >= {'b0', 'b15', 'b0_masks', 'b15_masks', 'p1', 'y1', 'p1_argmax', 'last', 'in_shape'}
+        assert acts['y1'] is None and acts['p1'] is e._buf['p1'] and acts['in_shape'] == (B, 64, 64) and acts['last'][0] is e._buf['b15_c']
+        assert all(m.dtype == torch.uint8 for m in acts['b7_masks']) and acts['b7_masks'][1] is e._buf['b7_a_sign']
+
+
+def _fused_calls(eng):
+    return [n for n in _names(eng) if 'bottleneck' in n or 'tail' in n]
+
+
+def test_resnet_fused_block_dispatch_order_bf16(monkeypatch):
+    """one ordered dispatch per block and direction: bottleneck_fused, then the image-resident kernels (14, 28, 7), then
+    bottleneck_first, then the stride-2 kernel; the backward takes the same kernels in reverse block order"""
+    B = 1
+    x = torch.rand(B, 3, 64, 64)
+    _stub_loss(monkeypatch, B)
+    off = set()
+    eng = _resnet(monkeypatch, 'bf16', lambda name, args: int(name not in off))
+    fu, fi, s2f, s2b = 'rart_bottleneck_fused_bf16', 'rart_bottleneck_first_bf16', 'rart_bottleneck_s2_fwd_bf16', 'rart_bottleneck_s2_bwd_bf16'
+
+    def image(k):
+        return 'rart_bottleneck%d_fused_bf16' % k
+    # everything available: every identity block on bottleneck_fused (its check comes first); layer4's first block conv by conv
+    fwd = [fi, fu, fu, s2f, fu, fu, fu, s2f] + [fu] * 5 + [fu, fu]
+    eng.logits(x, MEAN, STD)
+    assert _fused_calls(eng) == fwd
+    eng.forward_backward(x, MEAN, STD, None, 0)
+    assert _fused_calls(eng) == fwd + [s2b if n == s2f else n for n in reversed(fwd)]
+    # without bottleneck_fused: layer2 / layer3 / layer4 identity blocks on the first image-resident kernel that takes the geometry
+    for gone, k in ((('rart_bottleneck_fused_supported',), 14), (('rart_bottleneck14_fused_supported',), 28),
+                    (('rart_bottleneck28_fused_supported',), 7)):
+        off.update(gone)
+        fwd = [fi, s2f] + [image(k)] * 3 + [s2f] + [image(k)] * 5 + [image(k)] * 2
+        eng.forward_backward(x, MEAN, STD, None, 0)
+        assert _fused_calls(eng) == fwd + [s2b if n == s2f else n for n in reversed(fwd)]
+    # the switches: 28 and 7 behind their own and behind fused_bottleneck14; the stride-2 backward behind its own
+    eng.fused_bottleneck7 = False
+    eng.fused_bottleneck_s2_bwd = False
+    eng.forward_backward(x, MEAN, STD, None, 0)
+    assert _fused_calls(eng) == [fi, s2f, s2f, fi]
+    eng.fused_bottleneck7, eng.fused_bottleneck14, eng.fused_bottleneck_s2, eng.fused_bottleneck = True, False, False, False
+    eng.forward_backward(x, MEAN, STD, None, 0)
+    assert _fused_calls(eng) == []
+    # the fused kernels emit and read 1-bit masks only: with the bf16 activations as masks (cross-check) they serve the inference forward alone
+    off.clear()
+    eng.fused_bottleneck14 = eng.fused_bottleneck_s2 = eng.fused_bottleneck = True
+    eng.sign_bit_masks = False
+    eng.forward_backward(x, MEAN, STD, None, 0)
+    assert _fused_calls(eng) == []
+    assert all(a is b for a, b in zip(eng.last_acts['b1_masks'], (eng._buf['b0_c'], eng._buf['b1_a'], eng._buf['b1_b'])))
+    eng.logits(x, MEAN, STD)
+    assert len(_fused_calls(eng)) == 15
+
+
+def _tail_descs(eng):
+    return [a[0]._obj for n, a in eng.lib.calls if n == 'rart_conv3x3_tail_pair']
+
+
+def test_resnet_pair_tail_kernel_and_its_hand_over(monkeypatch):
+    """reference precision: layer1's 3x3 + 1x1 as one launch; its rider computes the neighbouring block's 1x1 reduction, and that
+    block then launches none of its own (forward: conv1 of block bi + 1; backward: conv3^T of block bi - 1)"""
+    B = 2
+    x = torch.rand(B, 3, 64, 64)
+    _stub_loss(monkeypatch, B)
+    eng = _resnet(monkeypatch, 'fp32x', lambda name, args: 1)
+    tail = 'rart_conv3x3_tail_pair'
+
+    def writers(buf):
+        """the GEMM launches that write pair buffer `buf`"""
+        return [d for d in eng.lib.descs if d.dst_hi == eng._buf[buf][0].data_ptr()]
+    eng.logits(x, MEAN, STD)
+    t = _tail_descs(eng)
+    assert len(t) == 3 and [d.c_mid for d in t] == [64] * 3 and len(eng.lib.calls) == 55 - 3 - 2
+    # blocks 0 and 1 carry conv1 of blocks 1 and 2; block 2's neighbour (layer2, 128 wide) has no rider table
+    assert [d.dstn_hi for d in t] == [eng._buf['b1_a'][0].data_ptr(), eng._buf['b2_a'][0].data_ptr(), None]
+    assert [d.relu_next for d in t] == [1, 1, 0] and t[0].n_hi == eng.blocks[1][0].next_fwd[0].data_ptr()
+    assert len(writers('b0_a')) == 1 and not writers('b1_a') and not writers('b2_a') and len(writers('b3_a')) == 1
+    assert 'b0_b' not in eng._buf and 'b3_b' in eng._buf          # the 3x3's output never exists in HBM
+    eng.lib.calls.clear()
+    eng.forward_backward(x, MEAN, STD, None, 0)
+    t = _tail_descs(eng)
+    assert len(t) == 5 and [n for n, _ in eng.lib.calls].count(tail) == 5
+    fwd, bwd = t[:3], t[3:]
+    assert [d.sign_next for d in fwd] == [eng._buf['b1_a_sign'].data_ptr(), eng._buf['b2_a_sign'].data_ptr(), None]
+    # backward: blocks 2 and 1 (identity blocks) on the tail kernel, each with conv3^T of the block below into the other g_b buffer
+    assert [d.dst_hi for d in bwd] == [eng._buf['g_out_1'][0].data_ptr(), eng._buf['g_out_0'][0].data_ptr()]
+    assert [d.dstn_hi for d in bwd] == [eng._buf['g_b1'][0].data_ptr(), eng._buf['g_b0'][0].data_ptr()]
+    assert [d.mask_next for d in bwd] == [eng._buf['b1_b_sign'].data_ptr(), eng._buf['b0_b_sign'].data_ptr()]
+
+    def conv3_t(bi):
+        """the GEMM launches of conv3^T of block bi"""
+        return [d for d in eng.lib.descs if d.w_hi == eng.blocks[bi][2].bwd[0][2].data_ptr()]
+    assert not conv3_t(0) and not conv3_t(1) and len(conv3_t(2)) == 1
+    with_rider = len(eng.lib.calls)
+    # without the rider every block launches its own reduction again: two more in the forward, two more in the backward
+    eng.fused_next_pair = False
+    eng.lib.calls.clear()
+    eng.forward_backward(x, MEAN, STD, None, 0)
+    assert len(eng.lib.calls) == with_rider + 4 and all(d.dstn_hi is None and d.n_hi is None for d in _tail_descs(eng))
+    assert len(writers('b1_a')) == 1 and len(writers('b2_a')) == 1 and [len(conv3_t(bi)) for bi in range(3)] == [1, 1, 1]
+    eng.fused_next_pair = True
+    # the backward rider is dropped when the block below kept no mask for it: that block launches its conv3^T itself
+    acts, dl = dict(eng.last_acts), eng.last_dlogits
+    acts['b1_masks'] = acts['b1_masks'][:2] + (None,)
+    eng.lib.calls.clear()
+    eng._backward(acts, dl, STD)
+    b2, b1 = _tail_descs(eng)
+    assert (b2.dstn_hi, b2.n_hi, b2.mask_next) == (None, None, None) and b1.dstn_hi == eng._buf['g_b0'][0].data_ptr()
+    own, = conv3_t(1)
+    assert own.mask_bits is None and own.dst_hi == eng._buf['g_b1'][0].data_ptr() and not conv3_t(0)
+    # the switches of the tail kernel
+    eng.fused_tail_channels = (64, 128)
+    eng.lib.calls.clear()
+    eng.logits(x, MEAN, STD)
+    assert [d.c_mid for d in _tail_descs(eng)] == [64] * 3 + [128] * 3
+    eng.fused_tail_pair = False
+    eng.lib.calls.clear()
+    eng.logits(x, MEAN, STD)
+    assert not _tail_descs(eng) and len(eng.lib.calls) == 55
+
+
+def test_resnet_tables_exist_in_the_engines_precision_only(monkeypatch):
+    convs = lambda e: [e.stem] + [c for blk in e.blocks for c in blk if c is not None]      # noqa: E731
+    bf = _resnet(monkeypatch, 'bf16', lambda name, args: 1)
+    x3 = _resnet(monkeypatch, 'fp32x', lambda name, args: 1)
+    pair_only = ('stem_w_pair', 'stem_wt_pair')
+    assert all(hasattr(x3, n) for n in pair_only) and not any(hasattr(bf, n) for n in pair_only)
+    assert hasattr(bf, 'stem_wt') and not hasattr(x3, 'stem_wt')
+    frag = ('w_fwd_frag', 'w_bwd_frag', 's2_w1', 's2_w2t', 'bias_sum')
+    tails = ('tail_fwd', 'tail_bwd', 'next_fwd', 'next_bwd')
+    for names, has, has_not in ((frag, bf, x3), (tails, x3, bf)):
+        for n in names:
+            assert any(hasattr(c, n) for c in convs(has)) and not any(hasattr(c, n) for c in convs(has_not)), n
+    # one table per use, [rows][K] in bf16 and [rows][hi | lo | hi] in reference precision, the same hi plane in both
+    for a, b in ((bf.stem_wd, x3.stem_wd), (bf.fc_w, x3.fc_w), (bf.fc_wd, x3.fc_wd), (bf.blocks[3][1].w_fwd, x3.blocks[3][1].w_fwd),
+                 (bf.blocks[3][1].bwd[3][2], x3.blocks[3][1].bwd[3][2])):
+        k = a.shape[1]
+        assert b.shape == (a.shape[0], 3 * k) and torch.equal(b[:, :k], a) and torch.equal(b[:, 2 * k:], a) and a.dtype == b.dtype == torch.bfloat16
+    assert bf.stem_w.shape == (64, 448) and torch.equal(bf.stem_w[:, :224], bf.stem_w[:, 224:]) and x3.stem_w.shape == (64, 672)
+    assert torch.equal(x3.stem_w[:, :224], bf.stem_w[:, :224]) and torch.equal(x3.stem_w_pair[0], bf.stem_w[:, :224])
+    assert torch.equal(x3.stem_w_pair[1], x3.stem_w[:, 224:448])
+    w = _RESNET[0].fc.weight.detach()
+    assert torch.equal(bf.fc_w[:bf.n_classes], w.to(torch.bfloat16)) and not bf.fc_w[bf.n_classes:].any()
+    assert torch.equal(x3.fc_wd[:, 1024:2024], (w - w.to(torch.bfloat16).float()).to(torch.bfloat16).t()) and not x3.fc_wd[:, 1000:1024].any()
+    # the precision helpers live on the base class
+    assert 'x3' in vars(eb.EngineBase) and all(n in vars(eb.EngineBase) and n not in vars(eb.RowEngine) for n in ('_act', '_hl', '_dlogits_rows'))

@@ -487,14 +487,14 @@ def test_x3_fused_stem_forward_is_bit_identical_to_the_three_launch_chain(setup,
         run = lambda: eng._forward(x, False, MEAN, STD, True)         # noqa: E731
     assert eng.fused_stem_fwd
     la, _ = run()
-    a = [eng._buf[k].clone() for k in ('x3_p1', 'p1_argmax', 'p1_sign')]
+    a = [eng._buf[k].clone() for k in ('p1', 'p1_argmax', 'p1_sign')]
     la = la.clone()
     eng.fused_stem_fwd = False
     try:
         lb, _ = run()
     finally:
         eng.fused_stem_fwd = True
-    b = [eng._buf[k] for k in ('x3_p1', 'p1_argmax', 'p1_sign')]
+    b = [eng._buf[k] for k in ('p1', 'p1_argmax', 'p1_sign')]
     for name, u, v in zip(('p1 pair', 'argmax codes', 'sign bits'), a, b):
         assert torch.equal(u, v), name
     assert torch.equal(la, lb)
