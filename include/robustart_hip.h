@@ -969,6 +969,28 @@ typedef struct rart_tokmix_desc {
 int rart_tokmix_bf16(const rart_tokmix_desc* desc, rart_stream_t stream);
 int rart_tokmix_pair(const rart_tokmix_desc* desc, rart_stream_t stream);
 
+/* Gradient of a token-mixing weight table (csrc/mixer_train.hip, bf16 training):
+ *   G[m][n] = sum_b sum_d P_b[m][d] Q_b[n][d]     (m < M, n < N, d < D, b < batch; bf16 operands, fp32 accumulation)
+ * p / q: per-image slabs [M][D] / [N][D], D contiguous, image b at element b * p_stride / b * q_stride; 16-byte aligned, D and the
+ *   strides multiples of 8, p_stride >= M D, q_stride >= N D.  Rows past M / N and channels past D are never read (zeros instead).
+ * Split z < splits sums images [z * images_per_split, (z + 1) * images_per_split) (splits * images_per_split >= batch) into
+ * partial[z][n][m], fp32 [splits][N][ld_partial >= M]: the layout rart_wgrad_reduce_f32(partial, splits, 1, N, N, M, ld_partial, grad, ..)
+ * folds into grad[M][N], the torch layout of the table (dW1: P = d(u_tok), Q = LN1(x); dW2: P = dx', Q = gelu(u_tok)).
+ * Fixed summation order, no atomics: the same bits on every run. */
+typedef struct rart_tokmix_wgrad_desc {
+  const void *p, *q;
+  float* partial;
+  int M, N, D, batch, splits, images_per_split, ld_partial, reserved;
+  int64_t p_stride, q_stride;
+} rart_tokmix_wgrad_desc;
+int rart_tokmix_wgrad_bf16(const rart_tokmix_wgrad_desc* desc, rart_stream_t stream);
+/* out[m] (+)= sum_b sum_d x[b][m][d] for bf16 per-image slabs [rows][dim] `stride` elements apart (the token biases' gradients; dim and
+ * stride multiples of 8, stride >= rows dim, x 16-byte aligned); deterministic two-level reduction.
+ * workspace: rart_tok_rowsum_workspace_bytes(rows, batch). */
+size_t rart_tok_rowsum_workspace_bytes(int rows, int batch);
+int rart_tok_rowsum_bf16(const void* x, int rows, int dim, int batch, int64_t stride, float* out, int accumulate, void* workspace,
+                         size_t workspace_bytes, rart_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

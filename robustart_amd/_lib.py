@@ -169,6 +169,9 @@ SIGNATURES = {
     'rart_cnx_grn_bwd_reduce_train_bf16': (c_int, [c_void_p] * 7 + [c_int] * 3 + [c_float, c_int, c_void_p, c_size_t, c_void_p]),
     'rart_tokmix_bf16': (c_int, [c_void_p, c_void_p]),
     'rart_tokmix_pair': (c_int, [c_void_p, c_void_p]),
+    'rart_tokmix_wgrad_bf16': (c_int, [c_void_p, c_void_p]),
+    'rart_tok_rowsum_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'rart_tok_rowsum_bf16': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_int64, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     'rart_vit_patchify': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                   c_void_p]),
     'rart_vit_add_pos_cls': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
@@ -265,6 +268,13 @@ class TokmixDesc(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ('a_hi', 'a_lo', 'x_hi', 'x_lo', 'dst_hi', 'dst_lo', 'res_hi', 'res_lo', 'aux_hi', 'aux_lo', 'bias')] + \
                [(n, ctypes.c_int32) for n in ('M', 'N', 'K', 'lda', 'ldx', 'ldc', 'batch', 'flags')] + \
                [(n, ctypes.c_int64) for n in ('x_stride', 'c_stride')]
+
+
+class TokmixWgradDesc(ctypes.Structure):
+    """rart_tokmix_wgrad_desc (include/robustart_hip.h): the gradient of one of MLP-Mixer's token-mixing weight tables."""
+    _fields_ = [(n, c_void_p) for n in ('p', 'q', 'partial')] + \
+               [(n, ctypes.c_int32) for n in ('M', 'N', 'D', 'batch', 'splits', 'images_per_split', 'ld_partial', 'reserved')] + \
+               [(n, ctypes.c_int64) for n in ('p_stride', 'q_stride')]
 
 
 class ConvTailDesc(ctypes.Structure):

@@ -4,7 +4,8 @@ Five architectures: `resnet50_official` (forward + backward-to-input HIP engine:
 (forward + backward-to-input HIP engine: vit_engine.py), `convnext_base` (forward + backward-to-input HIP engine:
 convnext_engine.py; train engine: convnext_train_engine.py, drop_path_rate 0 only) and `convnextv2_base` (ConvNeXt-V2-B: forward +
 backward-to-input on the same engine with the GRN kernels; train engine: the same ConvNeXtTrainEngine, bf16, drop_path_rate 0 only)
-and `mixer_b16_224` (MLP-Mixer-B/16: forward + backward-to-input HIP engine: mixer_engine.py; no train engine).
+and `mixer_b16_224` (MLP-Mixer-B/16: forward + backward-to-input HIP engine: mixer_engine.py; train engine: MixerTrainEngine,
+mixer_train_engine.py, bf16, drop rates 0 only).
 kwargs `num_classes` and `drop_path_rate` are accepted (drop path is identity in eval)."""
 from .resnet_torch import resnet50
 from .vit_torch import vit_base

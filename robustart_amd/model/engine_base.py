@@ -203,6 +203,18 @@ def tokmix_desc(a, x, dst, M, N, K, batch, x_stride, c_stride, ldx=None, ldc=Non
     return d
 
 
+def tokmix_wgrad_desc(p, q, partial, M, N, D, batch, splits, images_per_split, ld_partial, p_stride=None, q_stride=None):
+    """rart_tokmix_wgrad_desc of a token-mixing weight gradient: partial[z][n][m] = sum over split z's images b and channels d of
+    p_b[m][d] q_b[n][d].  p / q: bf16 per-image slabs [batch][M][D] / [batch][N][D], p_stride / q_stride elements apart (default:
+    dense); partial: fp32 [splits][N][ld_partial]."""
+    d = _lib.TokmixWgradDesc()
+    d.p, d.q, d.partial = p.data_ptr(), q.data_ptr(), partial.data_ptr()
+    d.M, d.N, d.D, d.batch = M, N, D, batch
+    d.splits, d.images_per_split, d.ld_partial = splits, images_per_split, ld_partial
+    d.p_stride, d.q_stride = p_stride or M * D, q_stride or N * D
+    return d
+
+
 # ---------------------------------------------------------------------- split-K weight gradients
 def wgrad_split_direct(M, x_c, n_taps, n_cols, target_wgs, min_chunk):
     """-> (splits, chunk) of rart_wgrad_direct_bf16 over M output positions: about target_wgs workgroups in all, chunks of at least
@@ -226,6 +238,16 @@ def wgrad_split_transposed(M, kp, n_pad):
     splits = max(1, min(1024 // max(tiles, 1), M // 512 if M >= 1024 else 1, 256))
     chunk = ((M + splits - 1) // splits + 63) // 64 * 64
     return splits, chunk, (n_pad + bn_tile - 1) // bn_tile * bn_tile
+
+
+def wgrad_split_tokens(batch, M, N, target_wgs):
+    """-> (splits, images_per_split) of rart_tokmix_wgrad_bf16: its contraction runs over images and channels, so it is split over
+    whole images: split z sums images [z * images_per_split, min(batch, (z + 1) * images_per_split)), about target_wgs workgroups
+    (128 x 128 output tiles x splits) in all, never more splits than images and no empty split"""
+    tiles = ((M + 127) // 128) * ((N + 127) // 128)
+    splits = max(1, min(batch, target_wgs // tiles))
+    per = (batch + splits - 1) // splits
+    return (batch + per - 1) // per, per
 
 
 # ---------------------------------------------------------------------- engines
@@ -435,6 +457,26 @@ class RowEngine(EngineBase):
         fn = self.lib.rart_vit_unpatchify_from_f32 if self.x3 else self.lib.rart_vit_unpatchify_f32
         _lib.check(fn(_lib.ptr(dpatch), _lib.ptr(grad), B, H, W, ps, 3 * ps * ps, (ctypes.c_float * 3)(*std), _lib.stream_ptr()))
         return grad
+
+    # train engines (ViTTrainEngine, MixerTrainEngine): they set `on_grad_ready`, called once per parameter after the last kernel
+    # that writes or reads its gradient has been enqueued
+    def _ln_bwd_full(self, dy, x, gamma, res, dx, rows, strides, norm):
+        """the backward of `_ln_bwd` plus the gradients of `norm`'s weight and bias (bf16)"""
+        lib, D = self.lib, self.D
+        need = lib.rart_layernorm_bwd_workspace_bytes(D)
+        ws = self._scratch('ln_ws', need)
+        _lib.check(lib.rart_layernorm_bwd_full_bf16(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(gamma), _lib.ptr(res), _lib.ptr(dx), rows,
+                                                    D, strides[0], strides[1], strides[2], strides[3], 1e-6,
+                                                    _lib.ptr(norm.weight.grad), _lib.ptr(norm.bias.grad), 0, _lib.ptr(ws), need,
+                                                    _lib.stream_ptr()))
+        self.on_grad_ready(norm.weight)
+        self.on_grad_ready(norm.bias)
+
+    def _linear_grads(self, lin, dz, n_pad, x, rows, dz_images=None):
+        """the weight gradient of the Linear (or patch convolution) `lin` from its output gradient dz and its input x, see `_wgrad`"""
+        n_out, c_in = lin.weight.shape[0], lin.weight[0].numel()
+        self._wgrad(dz, n_out, n_pad, x, c_in, lin.weight.grad, rows, dz_images)
+        self.on_grad_ready(lin.weight)
 
     def _wgrad(self, dz, n_out, n_pad, x, c_in, grad, rows, dz_images=None):
         """grad[n_out][c_in] = dz^T . x (dz: bf16 [rows][n_pad] dense, columns >= n_out zero; x: bf16 [rows][c_in] dense) as a split-K

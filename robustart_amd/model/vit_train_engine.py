@@ -32,24 +32,6 @@ class ViTTrainEngine(ViTEngine):
             src = src.detach().float().contiguous()
         return self._forward(src, src_is_u8, mean, std, keep=True)
 
-    # ------------------------------------------------------------------ helpers
-    def _ln_bwd_full(self, dy, x, gamma, res, dx, rows, strides, norm):
-        """the backward of RowEngine._ln_bwd plus the gradients of `norm`'s weight and bias"""
-        lib, D = self.lib, self.D
-        need = lib.rart_layernorm_bwd_workspace_bytes(D)
-        ws = self._scratch('ln_ws', need)
-        _lib.check(lib.rart_layernorm_bwd_full_bf16(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(gamma), _lib.ptr(res), _lib.ptr(dx), rows,
-                                                    D, strides[0], strides[1], strides[2], strides[3], 1e-6,
-                                                    _lib.ptr(norm.weight.grad), _lib.ptr(norm.bias.grad), 0, _lib.ptr(ws), need,
-                                                    _lib.stream_ptr()))
-        self.on_grad_ready(norm.weight)
-        self.on_grad_ready(norm.bias)
-
-    def _linear_grads(self, lin, dz, n_pad, x, rows, dz_images=None):
-        n_out, c_in = lin.weight.shape[0], lin.weight[0].numel()
-        self._wgrad(dz, n_out, n_pad, x, c_in, lin.weight.grad, rows, dz_images)
-        self.on_grad_ready(lin.weight)
-
     # ------------------------------------------------------------------ backward to every parameter
     def backward(self, dlogits):
         """dlogits: fp32 [B][classes] = d(loss)/dlogits of the last forward().  Fills .grad of every parameter."""

@@ -538,13 +538,14 @@ def train(cfg, args, rank, world, device):
     n = len(ds)
     max_iter, warmup_steps = resolve_schedule(cfg, n, bs, world, getattr(args, 'max_iter', 20))
     model = build_model(cfg, args)
-    from ..model.mixer_torch import MlpMixer
-    if isinstance(model, MlpMixer):
-        raise NotImplementedError('training %r: MLP-Mixer has no train engine on this path (evaluation and attacks run on MixerEngine; '
-                                  'training is not built on any engine or device)' % (cfg['model']['type'],))
     model = model.to(device)
     from ..model.convnext_torch import ConvNeXt, ConvNeXtV2
+    from ..model.mixer_torch import MlpMixer
     on_hip = device.type == 'cuda' and args.engine == 'hip' and getattr(args, 'train_engine', 'hip') == 'hip'
+    if isinstance(model, MlpMixer) and not on_hip:
+        raise NotImplementedError('training %r on %s with --engine %s --train-engine %s: MLP-Mixer trains only on MixerTrainEngine, '
+                                  'on the GPU with --engine hip --train-engine hip (there is no CPU or torch-engine path)'
+                                  % (cfg['model']['type'], device.type, args.engine, getattr(args, 'train_engine', 'hip')))
     if isinstance(model, ConvNeXtV2) and not on_hip:
         raise NotImplementedError('training %r on %s with --engine %s --train-engine %s: ConvNeXt-V2 trains only on ConvNeXtTrainEngine, '
                                   'on the GPU with --engine hip --train-engine hip (there is no CPU or torch-engine path)'
@@ -610,6 +611,9 @@ def train(cfg, args, rank, world, device):
         elif isinstance(model, ConvNeXt):
             from ..model.convnext_train_engine import ConvNeXtTrainEngine
             train_engine = ConvNeXtTrainEngine(model, device, on_grad_ready=arena.grad_ready)
+        elif isinstance(model, MlpMixer):
+            from ..model.mixer_train_engine import MixerTrainEngine
+            train_engine = MixerTrainEngine(model, device, on_grad_ready=arena.grad_ready)
     ls = float(cfg.get('label_smooth', 0.0))
     adv = cfg.get('adv_train', None)                        # {'eps': '4/255', 'steps': 3, 'rel_stepsize': 0.4}
     mean = torch.tensor(IMAGENET_MEAN, device=device).view(1, 3, 1, 1)
@@ -786,7 +790,7 @@ def main(argv=None):
     ap.add_argument('--max-iter', type=int, default=20)
     ap.add_argument('--train-engine', choices=['hip', 'torch'], default='hip', dest='train_engine',
                     help='train-mode forward/backward: hip = the HIP train engine of the model (ResNet50TrainEngine, ViTTrainEngine, '
-                         'ConvNeXtTrainEngine), torch = autograd scaffold (ResNet-50 / ViT only)')
+                         'ConvNeXtTrainEngine, MixerTrainEngine), torch = autograd scaffold (ResNet-50 / ViT only)')
     ap.add_argument('--recover', default=None, help='checkpoint to start from (overrides saver.pretrain.path)')
     ap.add_argument('--ckpt-dir', default=None, dest='ckpt_dir', help='write <dir>/ckpt.pth.tar at the end of training')
     ap.add_argument('--save-dir', default=None, help='root of <model>/<noise>_<eps>/results.txt.all (robustart_amd.metrics)')
