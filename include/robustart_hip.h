@@ -891,6 +891,34 @@ int rart_cnx_pool_bwd_pair(const void* dpool_hi, const void* dpool_lo, void* dz_
 int rart_cnx_patchify(const void* src, int src_is_u8, void* hi, void* lo, int n, int h, int w, int patch, int ld, const float* mean_host,
                       const float* std_host, rart_stream_t stream);
 
+/* ---- ConvStem (csrc/convstem.hip; robustart_amd/model/convstem_engine.py): the overlapping-convolution stem of `convnext_base_cvst`
+ * and `vit_base_cvst`, units of Conv2d(3x3, stride 2, padding 1) -> LayerNorm over channels -> exact GELU.  The convolutions run on
+ * rart_conv_igemm_bf16 / rart_gemm_pair_bf16; these are the kernels between them.
+ * rart_cvst_im2col: src fp32 NCHW in [0,1] (src_is_u8 = 0) or uint8 NHWC (1) -> the 3x3 / stride-2 / padding-1 patch matrix of the
+ *   normalised image (x - mean) / std as bf16 planes hi and lo (lo nullable) [n * (h / 2) * (w / 2)][ld], column c * 9 + ky * 3 + kx
+ *   (the Conv2d weight's order); a tap outside the image is 0 (zero padding of the NORMALISED image) and columns 27 .. ld are zero: every
+ *   byte of the output is written.  ld % 8 == 0, ld >= 32.  RART_ERR_UNSUPPORTED for an odd h or w.
+ * rart_cvst_col2im_f32: the backward: fp32 dpatches [n * (h / 2) * (w / 2)][ld] (27 valid columns) -> grad [n][3][h][w] =
+ *   d(loss)/d(x01) including 1 / std.  Every pixel gathers the one, two or four patch entries that cover it in a fixed order (no
+ *   atomics, deterministic, every pixel written).  RART_ERR_UNSUPPORTED for an odd h or w.
+ * rart_ln_gelu_*: out[r][0 .. dim) = GELU(LayerNorm(x[r][0 .. dim)) * gamma + beta) (exact erf GELU), out[r][dim .. out_row_stride) = 0.
+ *   Rows in_row_stride / out_row_stride elements apart (multiples of 8, >= dim); dim 32 .. 1024 in steps of 16; 16-byte aligned
+ *   pointers; out must not alias x.
+ * rart_ln_gelu_bwd_*: dx[r][0 .. dim) = LayerNorm'(x)^T (dy * GELU'(LayerNorm(x) * gamma + beta)) with the statistics recomputed from
+ *   x (the forward's input, i.e. the kept convolution output); dx[r][dim .. dx_row_stride) = 0.  No parameter gradients. */
+int rart_cvst_im2col(const void* src, int src_is_u8, void* hi, void* lo, int n, int h, int w, int ld, const float* mean_host,
+                     const float* std_host, rart_stream_t stream);
+int rart_cvst_col2im_f32(const float* dpatches, float* grad, int n, int h, int w, int ld, const float* std_host, rart_stream_t stream);
+int rart_ln_gelu_bf16(const void* x, const float* gamma, const float* beta, void* out, int rows, int dim, int64_t in_row_stride,
+                      int64_t out_row_stride, float eps, rart_stream_t stream);
+int rart_ln_gelu_pair(const void* x_hi, const void* x_lo, const float* gamma, const float* beta, void* out_hi, void* out_lo, int rows,
+                      int dim, int64_t in_row_stride, int64_t out_row_stride, float eps, rart_stream_t stream);
+int rart_ln_gelu_bwd_bf16(const void* dy, const void* x, const float* gamma, const float* beta, void* dx, int rows, int dim,
+                          int64_t dy_row_stride, int64_t x_row_stride, int64_t dx_row_stride, float eps, rart_stream_t stream);
+int rart_ln_gelu_bwd_pair(const void* dy_hi, const void* dy_lo, const void* x_hi, const void* x_lo, const float* gamma, const float* beta,
+                          void* dx_hi, void* dx_lo, int rows, int dim, int64_t dy_row_stride, int64_t x_row_stride, int64_t dx_row_stride,
+                          float eps, rart_stream_t stream);
+
 /* ---- ConvNeXt-B training (csrc/convnext_train.hip; robustart_amd/model/convnext_train_engine.py), bf16 storage, fp32 arithmetic -------
  * rart_cnx_dwconv_wgrad_bf16: the 7x7 pad-3 depthwise convolution's weight and bias gradient, dw[dy * 7 + dx][c] (+)= sum over
  *   (image, y, x) of x[y + dy - 3][x + dx - 3][c] * dz[y][x][c] and db[c] (+)= sum dz (accumulate != 0 adds).  x: the block input, dz: the

@@ -152,6 +152,12 @@ SIGNATURES = {
     'rart_cnx_pool_bwd_bf16': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     'rart_cnx_pool_bwd_pair': (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p]),
     'rart_cnx_patchify': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'rart_cvst_im2col': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'rart_cvst_col2im_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'rart_ln_gelu_bf16': (c_int, [c_void_p] * 4 + [c_int, c_int, ctypes.c_int64, ctypes.c_int64, c_float, c_void_p]),
+    'rart_ln_gelu_pair': (c_int, [c_void_p] * 6 + [c_int, c_int, ctypes.c_int64, ctypes.c_int64, c_float, c_void_p]),
+    'rart_ln_gelu_bwd_bf16': (c_int, [c_void_p] * 5 + [c_int, c_int] + [ctypes.c_int64] * 3 + [c_float, c_void_p]),
+    'rart_ln_gelu_bwd_pair': (c_int, [c_void_p] * 8 + [c_int, c_int] + [ctypes.c_int64] * 3 + [c_float, c_void_p]),
     'rart_cnx_dwconv_wgrad_workspace_bytes': (c_size_t, [c_int] * 4),
     'rart_cnx_dwconv_wgrad_bf16': (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p, c_size_t, c_void_p]),
     'rart_cnx_layer_scale_fwd_bf16': (c_int, [c_void_p] * 4 + [ctypes.c_longlong, c_int, c_void_p]),

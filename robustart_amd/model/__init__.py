@@ -1,20 +1,25 @@
 """Model zoo entry point -- mirrors RobustART/model/__init__.py:1 (`get_model`).
 
-Five architectures: `resnet50_official` (forward + backward-to-input HIP engine: engine.py), `vit_base` / `vit_b16_224`
+Five architectures and two stem variants: `resnet50_official` (forward + backward-to-input HIP engine: engine.py), `vit_base` / `vit_b16_224`
 (forward + backward-to-input HIP engine: vit_engine.py), `convnext_base` (forward + backward-to-input HIP engine:
 convnext_engine.py; train engine: convnext_train_engine.py, drop_path_rate 0 only) and `convnextv2_base` (ConvNeXt-V2-B: forward +
 backward-to-input on the same engine with the GRN kernels; train engine: the same ConvNeXtTrainEngine, bf16, drop_path_rate 0 only)
 and `mixer_b16_224` (MLP-Mixer-B/16: forward + backward-to-input HIP engine: mixer_engine.py; train engine: MixerTrainEngine,
 mixer_train_engine.py, bf16, drop rates 0 only).
+`convnext_base_cvst` and `vit_base_cvst` / `vit_b16_224_cvst` are the ConvStem variants of ConvNeXt-B and ViT-B/16 (convstem_torch.py:
+the stem / patch embedding is a chain of 3x3 stride-2 convolutions, each followed by LayerNorm and GELU): forward + backward-to-input on
+the same two engines, the stem on the chain of convstem_engine.py; evaluation only, `cls_solver` refuses to train them.
 kwargs `num_classes` and `drop_path_rate` are accepted (drop path is identity in eval)."""
 from .resnet_torch import resnet50
 from .vit_torch import vit_base
 from .convnext_torch import convnext_base, convnextv2_base
 from .mixer_torch import mixer_b16_224
+from .convstem_torch import convnext_base_cvst, vit_base_cvst
 
 _REGISTRY = {'resnet50_official': resnet50, 'resnet50': resnet50, 'vit_base': vit_base, 'vit_b16_224': vit_base,
              'vit_base_patch16_224': vit_base, 'convnext_base': convnext_base,
-             'convnextv2_base': convnextv2_base, 'mixer_b16_224': mixer_b16_224}
+             'convnextv2_base': convnextv2_base, 'mixer_b16_224': mixer_b16_224, 'convnext_base_cvst': convnext_base_cvst,
+             'vit_base_cvst': vit_base_cvst, 'vit_b16_224_cvst': vit_base_cvst}
 
 
 def get_model(config):

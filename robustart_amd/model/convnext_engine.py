@@ -3,6 +3,8 @@ the gradient step of every attack, adv/attack.py:21-22, autopgd_base.py:271-289)
 
 Layout: NHWC activations, rows = (image, y, x).  Per launch:
   stem        rart_cnx_patchify (4x4 patches, K = 48 padded to 64, hi + lo planes) -> GEMM (+ bias) -> LayerNorm
+              (`convnext_base_cvst`, a module that carries a ConvStem: the chain of convstem_engine.py writes the stage-0 input instead,
+              and its backward takes the stage-0 gradient to the image)
   downsample  LayerNorm -> the 2x2 stride-2 conv as the GEMM's conv mode (4 taps, k_per_tap = C_in, stride 2)
   block       rart_cnx_dwconv_ln_* (7x7 depthwise conv + bias + LayerNorm, one launch) -> fc1 GEMM + exact GELU ->
               fc2 GEMM (gamma folded in) + residual, written in place over the block input
@@ -25,6 +27,8 @@ no host synchronisation."""
 import ctypes
 
 from .. import _lib
+from .convstem_engine import ConvStem
+from .convstem_torch import convstem_of
 from .engine_base import (F_GELU, F_GELU_BWD, F_GELU_KEEP, F_OUT_F32, RowEngine, conv_desc, gemm_pair_desc, k32, lo_off, pad_k, pad_rows,
                           pair, rows_mult)
 
@@ -65,15 +69,18 @@ class ConvNeXtEngine(RowEngine):
                 return pad_rows(w, rows_mult(w.shape[0]))
             bwd = fwd
         c0 = self.dims[0]
-        sw = pad_k(f32(m.stem[0].weight).reshape(c0, 48), STEM_K)                       # [c0][c*16 + r*4 + s], zero columns 48..63
-        if self.x3:
-            self.stem_w = fwd(sw)
-        else:
-            swb = sw.to(torch.bfloat16)
-            self.stem_w = pad_rows(torch.cat([swb, swb], 1), 128)                       # hi | lo taps of the image pair
-        self.stem_wd = bwd(sw.t())                                                       # [64][c0]
-        self.stem_b = f32(m.stem[0].bias)
-        self.stem_g, self.stem_nb = f32(m.stem[1].weight), f32(m.stem[1].bias)
+        cvst = convstem_of(m)
+        self.cvst = ConvStem(self, cvst) if cvst is not None else None                   # `convnext_base_cvst`: the stem is its chain
+        if self.cvst is None:
+            sw = pad_k(f32(m.stem[0].weight).reshape(c0, 48), STEM_K)                   # [c0][c*16 + r*4 + s], zero columns 48..63
+            if self.x3:
+                self.stem_w = fwd(sw)
+            else:
+                swb = sw.to(torch.bfloat16)
+                self.stem_w = pad_rows(torch.cat([swb, swb], 1), 128)                   # hi | lo taps of the image pair
+            self.stem_wd = bwd(sw.t())                                                   # [64][c0]
+            self.stem_b = f32(m.stem[0].bias)
+            self.stem_g, self.stem_nb = f32(m.stem[1].weight), f32(m.stem[1].bias)
         self.stages = []
         for si, st in enumerate(m.stages):
             S = dict(index=si, blocks=[])
@@ -194,18 +201,22 @@ class ConvNeXtEngine(RowEngine):
             raise ValueError('ConvNeXt needs image sides that are multiples of 32 (got %dx%d)' % (Himg, Wimg))
         H, W = Himg // 4, Wimg // 4
         c0 = self.dims[0]
-        patches = self._get('patches', (2, B * H * W, STEM_K))
-        meanf, stdf = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
-        _lib.check(lib.rart_cnx_patchify(_lib.ptr(src), 1 if src_is_u8 else 0, _lib.ptr(patches[0]), _lib.ptr(patches[1]), B, Himg, Wimg,
-                                         4, STEM_K, meanf, stdf, sp))
-        xs = self._act('stem', (B * H * W, c0))
-        if self.x3:
-            self._gemm_pair(patches, self.stem_w, xs, B * H * W, c0, STEM_K, STEM_K, c0, bias=self.stem_b)
-        else:
-            self._gemm(patches[0], self.stem_w, xs, B * H * W, STEM_K, c0, STEM_K, c0, bias=self.stem_b, n_taps=2,
-                       tap_src_off=[0, lo_off(patches)])
         x = self._act('x0', (B * H * W, c0))
-        self._ln(xs, self.stem_g, self.stem_nb, x, B * H * W, c0)
+        if self.cvst is not None:
+            xs = None
+            self.cvst.forward(src, src_is_u8, mean, std, B, Himg, Wimg, x)
+        else:
+            patches = self._get('patches', (2, B * H * W, STEM_K))
+            meanf, stdf = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+            _lib.check(lib.rart_cnx_patchify(_lib.ptr(src), 1 if src_is_u8 else 0, _lib.ptr(patches[0]), _lib.ptr(patches[1]), B, Himg, Wimg,
+                                             4, STEM_K, meanf, stdf, sp))
+            xs = self._act('stem', (B * H * W, c0))
+            if self.x3:
+                self._gemm_pair(patches, self.stem_w, xs, B * H * W, c0, STEM_K, STEM_K, c0, bias=self.stem_b)
+            else:
+                self._gemm(patches[0], self.stem_w, xs, B * H * W, STEM_K, c0, STEM_K, c0, bias=self.stem_b, n_taps=2,
+                           tap_src_off=[0, lo_off(patches)])
+            self._ln(xs, self.stem_g, self.stem_nb, x, B * H * W, c0)
         saved, stage_out = [], []
         for si, S in enumerate(self.stages):
             C = self.dims[si]
@@ -311,6 +322,8 @@ class ConvNeXtEngine(RowEngine):
                 gprev = self._act('g_x%d' % (si - 1), (B * H * W, cin))
                 self._ln_bwd(gds, stage_out[si - 1], S['ds_g'], None, gprev, B * H * W, cin)
                 gx = gprev
+        if self.cvst is not None:
+            return logits, loss, self.cvst.backward(gx, std), pred
         c0, rows = self.dims[0], B * H * W
         gs = self._act('g_stem', (rows, c0))
         self._ln_bwd(gx, xs, self.stem_g, None, gs, rows, c0)

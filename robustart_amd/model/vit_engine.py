@@ -10,10 +10,13 @@ GEMMs carry GELU' in their epilogue, the LayerNorm backward adds the residual gr
 csrc/vit_aux.hip, csrc/vit_bwd.hip.  'bf16x3' (alias 'fp32x'), the reference-precision mode: every activation, gradient and weight a
 hi + lo pair of bf16 planes, rart_gemm_pair_bf16 (three MFMA products per contraction), rart_layernorm[_bwd]_pair,
 rart_vit_attention[_bwd]_pair, soft-max and GELU in fp32 on hi + lo (csrc/vit_pair.hip).
+A module whose patch embedding is a ConvStem (`vit_base_cvst`) runs the chain of convstem_engine.py in place of patch extraction + patch GEMM.
 Reference module: robustart_amd/model/vit_torch.py."""
 import os
 
 from .. import _lib
+from .convstem_engine import ConvStem
+from .convstem_torch import convstem_of
 from .engine_base import (F_GELU_BWD, F_OUT_F32, GP_OUT_F32, RowEngine, cints, interleave_k32, k32, lo_off, pad_k, pad_rows, pair,
                           rows_mult)
 
@@ -64,14 +67,17 @@ class ViTEngine(RowEngine):
                 return tab(w.t(), k_pad)
             t = pad_k(bf(w).t(), k_pad)
             return pad_rows(t, rows_mult(t.shape[0]))
-        pe = m.patch_embed.weight.detach().reshape(self.D, -1)                         # [D][c*ps*ps + r*ps + s]
-        if self.x3:
-            self.pe_w = fwd(pe)
-        else:
-            peb = bf(pe)
-            self.pe_w = pad_rows(torch.cat([peb, peb], 1), 128)                        # [hi | hi] columns: the taps of the image pair
-        self.pe_wd = bwd(pe)
-        self.pe_b = f32(m.patch_embed.bias)
+        cvst = convstem_of(m)
+        self.cvst = ConvStem(self, cvst) if cvst is not None else None                 # `vit_base_cvst`: the patch embedding is its chain
+        if self.cvst is None:
+            pe = m.patch_embed.weight.detach().reshape(self.D, -1)                     # [D][c*ps*ps + r*ps + s]
+            if self.x3:
+                self.pe_w = fwd(pe)
+            else:
+                peb = bf(pe)
+                self.pe_w = pad_rows(torch.cat([peb, peb], 1), 128)                    # [hi | hi] columns: the taps of the image pair
+            self.pe_wd = bwd(pe)
+            self.pe_b = f32(m.patch_embed.bias)
         pos = f32(m.pos_embed)[0]
         self.pos = pos.contiguous()
         self.cls_pos0 = (f32(m.cls_token)[0, 0] + pos[0]).contiguous()
@@ -108,14 +114,19 @@ class ViTEngine(RowEngine):
         assert not self.x3 or T <= 256, 'the pair soft-max rows hold at most 256 keys'
         kk = 3 * ps * ps
         rows = B * T
-        patches = self._patchify(src, src_is_u8, mean, std, B, Himg, Wimg, ps)
         x = self._act('x0' if keep else 'x', (B, T, D))
         (xh, xl), slot = self._hl(x), dict(rows_per_image=P, dst_rows_per_image=T, dst_row_off=1)      # row 0: the class token
+        if self.cvst is not None:
+            self.cvst.forward(src, src_is_u8, mean, std, B, Himg, Wimg, x, **slot)
+        else:
+            patches = self._patchify(src, src_is_u8, mean, std, B, Himg, Wimg, ps)
+            if self.x3:
+                self._mm(patches, self.pe_w, x, B * P, D, kk, bias=self.pe_b, **slot)
+            else:       # the image pair as two taps of the [hi | hi]-column table
+                self._gemm(patches[0], self.pe_w, x, B * P, kk, D, kk, D, bias=self.pe_b, n_taps=2, tap_src_off=[0, lo_off(patches)], **slot)
         if self.x3:
-            self._mm(patches, self.pe_w, x, B * P, D, kk, bias=self.pe_b, **slot)
             _lib.check(lib.rart_vit_add_pos_cls_pair(xh, xl, _lib.ptr(self.cls_pos0), _lib.ptr(self.pos), B, T, D, sp))
-        else:       # the image pair as two taps of the [hi | hi]-column table
-            self._gemm(patches[0], self.pe_w, x, B * P, kk, D, kk, D, bias=self.pe_b, n_taps=2, tap_src_off=[0, lo_off(patches)], **slot)
+        else:
             _lib.check(lib.rart_vit_add_pos_cls(xh, _lib.ptr(self.cls_pos0), _lib.ptr(self.pos), B, T, D, sp))
         ln = self._act('ln', (B, T, D))
         saved = []
@@ -343,6 +354,8 @@ class ViTEngine(RowEngine):
             self._ln_bwd(dln, x_in, L['n1g'], dxm, dx, rows, D)
         # patch embedding: d(patches)[b][p][c*ps*ps + r*ps + s] = dx[b][1 + p][:] . Wpe ; class token / position rows drop out.
         # bf16 patches, fp32 ones in reference precision
+        if self.cvst is not None:      # the stem chain's backward, from the patch rows of dx
+            return logits, loss, self.cvst.backward(dx, std, rows_per_image=P, src_rows_per_image=T, src_row_off=1), pred
         kk = 3 * self.ps * self.ps
         dpatch = self._get('g_patch', (B * P, kk), torch.float32 if self.x3 else torch.bfloat16)
         self._mm(dx, self.pe_wd, dpatch, B * P, kk, D, flags=F_OUT_F32 if self.x3 else 0, rows_per_image=P, src_rows_per_image=T,

@@ -257,7 +257,9 @@ def load_pretrain(model, path, prefer='model', strict=True, ignore_model=()):
     A ViT checkpoint in the key layout rounds 1-4 of this repository wrote (`patch_embed.weight`, `blocks.N.fc1.*`) is renamed to
     timm's layout, which the module tree now carries.  So is a ConvNeXt-V2 checkpoint in its authors' layout
     (convnextv2_base_1k_224_ema.pt: `downsample_layers.*`, `pwconv1`, `grn.gamma`, ...); `ignore_model` keys may then be given in
-    either layout."""
+    either layout.  For EVERY model type, a leading `module.`, `model.` or `base_model.` that every key of the file carries is
+    stripped, repeatedly (wrappers nest); no module of this package has a top-level attribute of those names.  That is what lets the
+    ConvStem checkpoints convnext_b_cvst_robust.pt / vit_b_cvst_robust.pt load strictly into `convnext_base_cvst` / `vit_base_cvst`."""
     ck = load_checkpoint_file(path)
     sd = ck
     if isinstance(ck, dict):
@@ -269,6 +271,13 @@ def load_pretrain(model, path, prefer='model', strict=True, ignore_model=()):
         sd = sd['ema_state_dict']
     strip = lambda k: k[7:] if k.startswith('module.') else k    # noqa: E731
     sd = {strip(k): v for k, v in sd.items()}
+    # a wrapper's prefix that EVERY key carries (any model type; the published ConvStem checkpoints: `module.`, `model.`, `base_model.`)
+    wrapped = True
+    while wrapped and sd:
+        wrapped = False
+        for pre in ('module.', 'model.', 'base_model.'):
+            if all(k.startswith(pre) for k in sd):
+                sd, wrapped = {k[len(pre):]: v for k, v in sd.items()}, True
     from ..model.vit_torch import VisionTransformer, legacy_vit_keys
     from ..model.convnext_torch import ConvNeXtV2, official_v2_key, official_v2_state_dict
     if isinstance(model, VisionTransformer):
@@ -538,6 +547,10 @@ def train(cfg, args, rank, world, device):
     n = len(ds)
     max_iter, warmup_steps = resolve_schedule(cfg, n, bs, world, getattr(args, 'max_iter', 20))
     model = build_model(cfg, args)
+    from ..model.convstem_torch import convstem_of
+    if convstem_of(model) is not None:         # before the model reaches the device: every reference config of these types evaluates
+        raise NotImplementedError('training %r: the ConvStem models are evaluation only (forward and backward-to-input on the HIP '
+                                  'engines; there is no train engine for the stem)' % (cfg['model']['type'],))
     model = model.to(device)
     from ..model.convnext_torch import ConvNeXt, ConvNeXtV2
     from ..model.mixer_torch import MlpMixer
