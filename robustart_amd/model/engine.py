@@ -19,8 +19,8 @@ import ctypes
 import os as _os
 
 from .. import _lib
-from .engine_base import (F_MASK_BITS, F_OUT_F32, F_PAIR, F_RELU, EngineBase, cints as _cints, conv_desc, gemm_pair_desc,
-                          interleave_k32, k32, lo_off, pad_k, pad_rows, rows_mult, pair, split_hi_lo)
+from .engine_base import (F_MASK_BITS, F_OUT_F32, F_PAIR, F_RELU, EngineBase, cints as _cints, conv_desc, conv_tap_classes,
+                          gemm_pair_desc, interleave_k32, k32, lo_off, pad_k, pad_rows, rows_mult, pair, split_hi_lo, stem_rows)
 
 
 def _bf16(t):
@@ -43,14 +43,6 @@ def _table(build, planes, device):
     return _bf16(torch.cat(t + t[:1], 1) if len(t) == 2 else t[0]).to(device)
 
 
-def _stem_rows(w):
-    """stem weights [64][3][7][7] -> the row-tap form [64][224]: one tap = one filter row, 8 px x 4 ch (zero at px 7 and ch 3)"""
-    import torch
-    t = torch.zeros(64, 7, 8, 4, dtype=w.dtype, device=w.device)
-    t[:, :, :7, :3] = w.permute(0, 2, 3, 1)                              # [cout][r][s][c]
-    return t.reshape(64, 7 * 32)
-
-
 class _Conv:
     """One folded conv layer: forward table + backward-to-input tables, in bf16 or (split) as [hi | lo | hi] rows."""
 
@@ -69,7 +61,7 @@ class _Conv:
         self.w_folded = w                    # fp32, for the reference emulation in tests
         self.b_folded = b
         self.bias = b.contiguous().to(device)
-        self.fwd_taps = [(r - pad, s - pad) for r in range(self.r) for s in range(self.s)]
+        self.fwd_taps, rs_all, classes = conv_tap_classes(self.r, self.s, self.stride, pad)
         planes = _planes(w, split)
 
         def table(rs, transpose):
@@ -78,19 +70,10 @@ class _Conv:
             rows = self.cin if transpose else self.cout
             return _table(lambda wb: pad_rows(torch.cat([wb[:, :, r, s].t() if transpose else wb[:, :, r, s] for r, s in rs], 1),
                                               rows_mult(rows)), planes, device)
-        rs_all = [(r, s) for r in range(self.r) for s in range(self.s)]
         self.w_fwd = table(rs_all, False)
         # backward to input: list of (input parity (ph, pw) or None, taps [(dy, dx)], table or None); a stride-2 conv has one table
         # per input-parity class, over the filter taps that reach it
-        if self.stride == 1:
-            self.bwd = [(None, [(pad - r, pad - s) for r, s in rs_all], table(rs_all, True))]
-        else:
-            assert self.stride == 2
-            self.bwd = []
-            for ph in range(2):
-                for pw in range(2):
-                    rs = [(r, s) for r, s in rs_all if (ph + pad - r) % 2 == 0 and (pw + pad - s) % 2 == 0]
-                    self.bwd.append(((ph, pw), [((ph + pad - r) // 2, (pw + pad - s) // 2) for r, s in rs], table(rs, True) if rs else None))
+        self.bwd = [(parity, taps, table(rs, True) if rs else None) for parity, taps, rs in classes]
 
 
 class ResNet50Engine(EngineBase):
@@ -118,11 +101,11 @@ class ResNet50Engine(EngineBase):
         self.stem_patch_cols = 152                                        # 147 rounded up to 8
         self.stem_wd = _table(lambda p: pad_rows(p.permute(2, 3, 1, 0).reshape(147, 64), rows_mult(self.stem_patch_cols)), pl, dev)
         if not split:
-            self.stem_w = _table(lambda p: _stem_rows(p).repeat(1, 2), pl, dev)     # the image's hi taps then its lo taps
+            self.stem_w = _table(lambda p: stem_rows(p).repeat(1, 2), pl, dev)     # the image's hi taps then its lo taps
             self.stem_wt = self._stem_bwd_table(pl[0]).to(dev)            # fused stem backward (stem_fused.hip)
         else:
-            self.stem_w = _table(_stem_rows, pl, dev)                     # x_hi.w_hi, x_hi.w_lo, x_lo.w_hi row taps
-            self.stem_w_pair = _bf16(torch.stack([_stem_rows(p) for p in pl])).to(dev)     # fused pair stem forward (stem_pair.hip): [2][64][224]
+            self.stem_w = _table(stem_rows, pl, dev)                     # x_hi.w_hi, x_hi.w_lo, x_lo.w_hi row taps
+            self.stem_w_pair = _bf16(torch.stack([stem_rows(p) for p in pl])).to(dev)     # fused pair stem forward (stem_pair.hip): [2][64][224]
             self.stem_wt_pair = pair(self._stem_bwd_table(st.w_folded, dtype=torch.float32)).to(dev)     # fused pair stem backward
         self.fused_stem_bwd = True       # False: max-pool bwd -> patches GEMM -> col2im (kept as the cross-check)
         self.sign_bit_masks = True       # False: the backward reads the bf16 activations for their ReLU sign (cross-check)
@@ -350,7 +333,7 @@ class ResNet50Engine(EngineBase):
         # stem extras (row-tap table, patches table, fused-backward table) and the classifier
         sc = st['scale'][:64]
         wb = (m.conv1.weight.detach() * sc.view(-1, 1, 1, 1)).to(torch.bfloat16)          # [64][3][7][7]
-        wrow = _stem_rows(wb)
+        wrow = stem_rows(wb)
         self.stem_w[:, :224] = wrow
         self.stem_w[:, 224:] = wrow
         self.stem_wd.zero_()

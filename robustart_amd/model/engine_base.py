@@ -1,5 +1,6 @@
 """The host launch layer the HIP engines share: the flag tables of the two GEMM descriptors, one builder per descriptor, the weight-table
-helpers, the split-K heuristics of the weight gradient, and `EngineBase` (device, buffers, profiling) that every engine inherits.
+helpers, the tap geometry of a convolution, the split-K heuristics of the weight gradient, and `EngineBase` (device, buffers,
+profiling, both weight-gradient paths) that every engine inherits.
 
 The builders take tensors or None and only read `data_ptr()`, so they run on CPU tensors as well.  Every engine keeps the adapter that
 encodes its own convention: ResNet-50's conv form and [hi | lo | hi] weight tables (engine.py), the row form of ViT-B/16, MLP-Mixer and
@@ -87,6 +88,32 @@ def interleave_k32(hi, lo):
     import torch
     rows, k = hi.shape
     return torch.stack([hi.reshape(rows, k // 32, 32), lo.reshape(rows, k // 32, 32)], 2).reshape(rows, 2 * k).contiguous()
+
+
+def stem_rows(w):
+    """stem weights [64][3][7][7] -> the row-tap form [64][224]: one tap = one filter row, 8 px x 4 ch (zero at px 7 and ch 3)"""
+    import torch
+    t = torch.zeros(64, 7, 8, 4, dtype=w.dtype, device=w.device)
+    t[:, :, :7, :3] = w.permute(0, 2, 3, 1)                              # [cout][r][s][c]
+    return t.reshape(64, 7 * 32)
+
+
+def conv_tap_classes(r, s, stride, pad):
+    """the geometry of an r x s convolution of stride 1 or 2 -> (fwd_taps, all_rs, bwd).  fwd_taps: the (dy, dx) an output pixel reads per
+    filter tap of all_rs = [(r, s)]; bwd: the classes of the backward to the input as [(parity, taps, rs)]: the (dy, dx) an input pixel
+    reads from the output gradient and the filter taps rs that reach it.  Stride 1: one class, parity None; stride 2: one class per
+    input parity (ph, pw), over the filter taps that reach it (none for some classes of a 1 x 1)"""
+    all_rs = [(a, b) for a in range(r) for b in range(s)]
+    fwd_taps = [(a - pad, b - pad) for a, b in all_rs]
+    if stride == 1:
+        return fwd_taps, all_rs, [(None, [(pad - a, pad - b) for a, b in all_rs], all_rs)]
+    assert stride == 2
+    bwd = []
+    for ph in range(2):
+        for pw in range(2):
+            rs = [(a, b) for a, b in all_rs if (ph + pad - a) % 2 == 0 and (pw + pad - b) % 2 == 0]
+            bwd.append(((ph, pw), [((ph + pad - a) // 2, (pw + pad - b) // 2) for a, b in rs], rs))
+    return fwd_taps, all_rs, bwd
 
 
 # ---------------------------------------------------------------------- descriptors
@@ -355,6 +382,36 @@ class EngineBase:
         _lib.check(lib.rart_wgrad_reduce_f32(_lib.ptr(part), splits, len(taps), c_valid if c_valid is not None else x_c, x_c, n_out,
                                              n_pad_cols, _lib.ptr(grad), 0, sp))
 
+    def _wgrad_transposed(self, dz, dz_geom, x, x_geom, n_out, grad, reduce, row_grid=False):
+        """grad[n_out][c][taps] = sum_m dz[m][n] * x[pixel(m) + tap][c] as a split-K GEMM on the igemm kernel over transposed copies
+        of both operands, one compact slab per K split: [splits][rows][chunk].  dz_geom = (images, src_h, src_w, channels, grid_h,
+        grid_w): position m is pixel (y, x) of the grid_h x grid_w grid of an image of src_h x src_w pixels, `channels` bf16 values
+        each (columns >= n_out zero); x_geom: the same for x, then (stride, taps): the pixel a position reads per tap.  reduce =
+        (n_taps, c_valid, x_c) of rart_wgrad_reduce_f32.  row_grid: the GEMM's rows as a (rows, 1) grid, the row form's
+        descriptor, instead of (1, rows): the 256 x 256 kernel's eligibility test reads the grid's width."""
+        lib, sp = self.lib, _lib.stream_ptr()
+        n_pad = dz_geom[3]
+        images, x_h, x_w, x_c, grid_h, grid_w, stride, taps = x_geom
+        kp = len(taps) * x_c                                   # rows of the transposed im2col matrix
+        splits, chunk, n_rows = wgrad_split_transposed(images * grid_h * grid_w, kp, n_pad)
+        m_pad = chunk * splits
+        dzt = self._scratch('wg_dzT', n_rows * m_pad * 2)
+        colt = self._scratch('wg_colT', kp * m_pad * 2)
+        zero = cints([0])
+        if n_rows > n_pad:
+            dzt[:n_rows * m_pad * 2].zero_()                     # tile-padding rows of every slab stay zero
+        _lib.check(lib.rart_transpose_gather_bf16(_lib.ptr(dz), _lib.ptr(dzt), *dz_geom, 1, 1, 1, zero, zero, m_pad, chunk, n_rows, sp))
+        _lib.check(lib.rart_transpose_gather_bf16(_lib.ptr(x), _lib.ptr(colt), images, x_h, x_w, x_c, grid_h, grid_w, stride, stride,
+                                                  len(taps), cints([t[0] for t in taps]), cints([t[1] for t in taps]), m_pad, chunk,
+                                                  kp, sp))
+        ld_n = (n_pad + 7) // 8 * 8
+        part = self._scratch('wg_part', splits * kp * ld_n * 4)
+        grid = (kp, 1) if row_grid else (1, kp)
+        self._launch_conv(conv_desc(colt, dzt, part, 1, grid, grid, chunk, chunk, ROW_TAPS[1], ld_n, grid, ld_n, flags=F_OUT_F32,
+                                    batched=dict(n=splits, inner=splits, src=(0, kp * chunk), wgt=(0, n_rows * chunk), dst=(0, kp * ld_n),
+                                                 wgt_row_stride=chunk)))
+        _lib.check(lib.rart_wgrad_reduce_f32(_lib.ptr(part), splits, *reduce, n_out, ld_n, _lib.ptr(grad), 0, sp))
+
     def _colsum(self, x, ld, rows, cols, out):
         lib = self.lib
         need = lib.rart_colsum_workspace_bytes(rows, cols)
@@ -480,24 +537,8 @@ class RowEngine(EngineBase):
 
     def _wgrad(self, dz, n_out, n_pad, x, c_in, grad, rows, dz_images=None):
         """grad[n_out][c_in] = dz^T . x (dz: bf16 [rows][n_pad] dense, columns >= n_out zero; x: bf16 [rows][c_in] dense) as a split-K
-        GEMM over transposed copies.  dz_images = (B, rows_per_image_in_memory, rows_used): dz rows are the first `rows_used` of every
-        image block."""
-        lib, sp = self.lib, _lib.stream_ptr()
-        splits, chunk, n_rows = wgrad_split_transposed(rows, c_in, n_pad)
-        m_pad = chunk * splits
-        dzt = self._scratch('wg_dzT', n_rows * m_pad * 2)
-        colt = self._scratch('wg_colT', c_in * m_pad * 2)
-        zero = cints([0])
-        if n_rows > n_pad:
-            dzt[:n_rows * m_pad * 2].zero_()
+        GEMM over transposed copies (`_wgrad_transposed`).  dz_images = (B, rows_per_image_in_memory, rows_used): dz rows are the first
+        `rows_used` of every image block."""
         b, sh, gh = dz_images if dz_images is not None else (1, rows, rows)
-        _lib.check(lib.rart_transpose_gather_bf16(_lib.ptr(dz), _lib.ptr(dzt), b, sh, 1, n_pad, gh, 1, 1, 1, 1, zero, zero, m_pad,
-                                                  chunk, n_rows, sp))
-        _lib.check(lib.rart_transpose_gather_bf16(_lib.ptr(x), _lib.ptr(colt), 1, rows, 1, c_in, rows, 1, 1, 1, 1, zero, zero,
-                                                  m_pad, chunk, c_in, sp))
-        ld_n = (n_pad + 7) // 8 * 8
-        part = self._scratch('wg_part', splits * c_in * ld_n * 4)
-        self._gemm(colt, dzt, part, c_in, chunk, ld_n, chunk, ld_n, flags=F_OUT_F32,
-                   batched=dict(n=splits, inner=splits, src=(0, c_in * chunk), wgt=(0, n_rows * chunk), dst=(0, c_in * ld_n),
-                                wgt_row_stride=chunk))
-        _lib.check(lib.rart_wgrad_reduce_f32(_lib.ptr(part), splits, 1, c_in, c_in, n_out, ld_n, _lib.ptr(grad), 0, sp))
+        self._wgrad_transposed(dz, (b, sh, 1, n_pad, gh, 1), x, (1, rows, 1, c_in, rows, 1, 1, ROW_TAPS[1]), n_out, grad,
+                               (1, c_in, c_in), row_grid=True)

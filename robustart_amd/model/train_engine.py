@@ -8,7 +8,9 @@ an activation is a HIP kernel:
 
   contraction (forward conv, backward-to-input, weight gradient, fc)   rart_conv_igemm_bf16
   batch statistics / normalise+ReLU+residual / BatchNorm backward        rart_bn_train_forward_bf16 / _backward_bf16
-  K-contiguous operands of the weight-gradient GEMM                      rart_transpose_gather_bf16
+  weight gradient straight from the NHWC activations                     rart_wgrad_direct_bf16
+  ... for a shape that kernel does not take, or with `direct_wgrad`      EngineBase._wgrad_transposed: transposed copies of both
+  off (cross-check)                                                      operands, the split-K GEMM on rart_conv_igemm_bf16
   split-K partial sums -> torch weight layout                            rart_wgrad_reduce_f32
   fp32 master weights -> bf16 igemm tables (after every optimizer step)  rart_pack_conv_weight_bf16
 
@@ -17,11 +19,10 @@ train/arena.py); `on_grad_ready(param)` lets the arena launch a bucket's all-red
 exists, so the exchange overlaps the rest of the backward pass.
 """
 import ctypes
-import os as _os
 
 from .. import _lib
-from .engine_base import (F_MASK_BITS, F_MASK_RES, F_OUT_F32, EngineBase, cints, conv_desc, lo_off, rows_mult,
-                          wgrad_split_transposed)
+from .engine_base import (F_MASK_BITS, F_MASK_RES, F_OUT_F32, EngineBase, cints, conv_desc, conv_tap_classes, lo_off, rows_mult,
+                          stem_rows)
 
 
 class _TConv:
@@ -31,24 +32,15 @@ class _TConv:
         self.conv, self.bn = conv, bn
         self.cout, self.cin, self.r, self.s = conv.weight.shape
         self.stride, self.pad = conv.stride[0], conv.padding[0]
-        self.fwd_taps = [(r - self.pad, s - self.pad) for r in range(self.r) for s in range(self.s)]
-        self.all_rs = [(r, s) for r in range(self.r) for s in range(self.s)]
+        self.fwd_taps, self.all_rs, classes = conv_tap_classes(self.r, self.s, self.stride, self.pad)
         bf = torch.bfloat16
         self.w_fwd = torch.zeros((self.cout + rows_mult(self.cout) - 1) // rows_mult(self.cout) * rows_mult(self.cout),
                                  self.r * self.s * self.cin, dtype=bf, device=device)
         rm = rows_mult(self.cin)
         rows_b = (self.cin + rm - 1) // rm * rm
-        self.bwd = []        # (parity or None, taps [(dy,dx)], rs list, table)
-        if self.stride == 1:
-            taps = [(self.pad - r, self.pad - s) for r, s in self.all_rs]
-            self.bwd.append((None, taps, self.all_rs, torch.zeros(rows_b, len(taps) * self.cout, dtype=bf, device=device)))
-        else:
-            for ph in range(2):
-                for pw in range(2):
-                    rs = [(r, s) for r, s in self.all_rs if (ph + self.pad - r) % 2 == 0 and (pw + self.pad - s) % 2 == 0]
-                    taps = [((ph + self.pad - r) // 2, (pw + self.pad - s) // 2) for r, s in rs]
-                    tab = torch.zeros(rows_b, len(taps) * self.cout, dtype=bf, device=device) if rs else None
-                    self.bwd.append(((ph, pw), taps, rs, tab))
+        # (parity or None, taps [(dy,dx)], rs list, table or None)
+        self.bwd = [(parity, taps, rs, torch.zeros(rows_b, len(taps) * self.cout, dtype=bf, device=device) if rs else None)
+                    for parity, taps, rs in classes]
         if bn is not None:
             self.mean = torch.empty(self.cout, dtype=torch.float32, device=device)
             self.invstd = torch.empty(self.cout, dtype=torch.float32, device=device)
@@ -89,13 +81,9 @@ class ResNet50TrainEngine(EngineBase):
         self.fc_kpad = (self.n_classes + 127) // 128 * 128
         self.fc_w = torch.zeros(self.fc_kpad, self.fc_in, dtype=torch.bfloat16, device=dev)      # [1024][2048]
         self.fc_wd = torch.zeros(self.fc_in, self.fc_kpad, dtype=torch.bfloat16, device=dev)     # [2048][1024]
-        _fl = dict(kv.split('=', 1) for kv in _os.environ.get('RART_TRAIN_FLAGS', '').split(',') if '=' in kv)   # A/B switches for profiling
         self._nbt_pending = None
-        self.masked_skip = _fl.get('skip', '1') == '1'        # False: the BatchNorm backward writes the masked skip gradient as a tensor (cross-check)
-        self.conv_bn_stats = _fl.get('stats', '1') == '1'      # False: every BatchNorm takes its own statistics pass over the conv output (rounds 1-3; cross-check)
-        self.bit_masks = _fl.get('bits', '1') == '1'          # False: the BatchNorm backward reads the bf16 activation for its ReLU mask (rounds 1-3; cross-check)
         self._ysign = {}
-        self.direct_wgrad = _fl.get('direct', '1') == '1'       # False: transpose_gather (dz^T, im2col^T) + implicit GEMM on the copies (rounds 1-3; cross-check)
+        self.direct_wgrad = True       # False: every weight gradient on `_wgrad_transposed` (rounds 1-3; cross-check)
         self.repack()
 
     # ------------------------------------------------------------------ tables
@@ -126,10 +114,7 @@ class ResNet50TrainEngine(EngineBase):
             for c in convs:
                 c.repack(self.lib, sp)
         # stem forward table: a "tap" = one filter row of 8 px x 4 ch on the padded hi/lo planes (engine.py)
-        wb = self.model.conv1.weight.detach().float()
-        wrow = torch.zeros(64, 7, 8, 4, device=self.device)
-        wrow[:, :, :7, :3] = wb.permute(0, 2, 3, 1)
-        wrow = wrow.reshape(64, 224).to(torch.bfloat16)
+        wrow = stem_rows(self.model.conv1.weight.detach().float()).to(torch.bfloat16)
         self.stem_w[:, :224] = wrow
         self.stem_w[:, 224:] = wrow
         one = cints([0])
@@ -152,16 +137,14 @@ class ResNet50TrainEngine(EngineBase):
         return t
 
     def _conv_fwd(self, c, x, xhw, out, stats_name='bn_stats'):
-        """-> (partial statistics buffer, row tiles) of the output for the BatchNorm that follows (the igemm's epilogue sums the
-        columns of its 128-row tiles), or None with `conv_bn_stats` off (the BatchNorm then takes its own pass over the output)."""
+        """-> (partial statistics buffer, row tiles) of the output for the BatchNorm that follows: the igemm's epilogue sums the
+        columns of its 128-row tiles."""
         B = x.shape[0]
         oh, ow = xhw[0] // c.stride, xhw[1] // c.stride
-        stats = None
-        if self.conv_bn_stats:
-            tiles = (B * oh * ow + 127) // 128
-            stats = (self._scratch(stats_name, tiles * 2 * c.cout * 4), tiles)
+        tiles = (B * oh * ow + 127) // 128
+        stats = (self._scratch(stats_name, tiles * 2 * c.cout * 4), tiles)
         self._launch_conv(conv_desc(x, c.w_fwd, out, B, (oh, ow), xhw, c.cin, c.cin, c.fwd_taps, c.cout, (oh, ow), c.cout,
-                                    stride=(c.stride, c.stride), stats_out=stats[0] if stats else None))
+                                    stride=(c.stride, c.stride), stats_out=stats[0]))
         return stats
 
     def _conv_dgrad(self, c, dz, dz_hw, dx, dx_hw, res=None, res_mask_bits=None):
@@ -180,12 +163,13 @@ class ResNet50TrainEngine(EngineBase):
                                             c.cin, res=res, dst_stride=(2, 2), dst_org=(ph, pw)))
 
     def _bn_fwd(self, c, z, y, rows, relu, res=None, stats=None):
+        """stats: what `_conv_fwd` returned for z; None: the BatchNorm takes its own statistics pass over z"""
         lib, bn = self.lib, c.bn
         need = lib.rart_bn_workspace_bytes(rows, c.cout)
         ws = self._scratch('bn_ws', need)
         mom = bn.momentum if bn.momentum is not None else 0.1
         sign = None
-        if relu and self.bit_masks:      # 1 bit per element of (y > 0): what the backward reads instead of y (1/16 of its bytes)
+        if relu:                         # 1 bit per element of (y > 0): what the backward reads instead of y (1/16 of its bytes)
             sign = self._get('sgn_%x' % id(c), (rows, c.cout // 8), self.torch.uint8)      # one per conv + BatchNorm (stable name: no growth when batch sizes alternate)
             self._ysign[y.data_ptr()] = sign
         _lib.check(lib.rart_bn_train_forward_bf16(
@@ -205,7 +189,7 @@ class ResNet50TrainEngine(EngineBase):
         need = lib.rart_bn_workspace_bytes(rows, c.cout)
         ws = self._scratch('bn_ws', need)
         coef = self._get('bn_coef', (3, 2048), self.torch.float32)
-        bits = self._ysign.get(ymask.data_ptr()) if (ymask is not None and self.bit_masks) else None
+        bits = self._ysign.get(ymask.data_ptr()) if ymask is not None else None      # a y of this forward: its sign bits
         _lib.check(lib.rart_bn_train_backward_bf16(
             dy.data_ptr(),
             bits.data_ptr() if bits is not None else (ymask.data_ptr() if ymask is not None else None), 1 if bits is not None else 0,
@@ -217,36 +201,15 @@ class ResNet50TrainEngine(EngineBase):
         self.on_grad_ready(bn.bias)
 
     def _wgrad(self, dz, n_out, n_pad_cols, x, x_hw, x_c, grid_hw, taps, stride, grad, c_valid=None):
-        """grad[n_out][c][taps] = sum_m dz[m][n] * x[pixel(m) + tap][c] as a split-K GEMM on the igemm kernel.
+        """grad[n_out][c][taps] = sum_m dz[m][n] * x[pixel(m) + tap][c].
         dz: bf16 [B, gh, gw, n_pad_cols] (columns >= n_out are zero); x: bf16 [B, ih, iw, x_c]."""
-        lib, sp = self.lib, _lib.stream_ptr()
-        B = dz.shape[0]
+        lib, B = self.lib, dz.shape[0]
         gh, gw = grid_hw
         if self.direct_wgrad and (c_valid is None or x_c == 4) and lib.rart_wgrad_direct_supported(x_c, n_pad_cols, len(taps)):
             # straight from the NHWC activations (csrc/wgrad_direct.hip): no transposed copies, no materialised im2col
             return self._wgrad_direct(x, dz, B, x_hw, x_c, grid_hw, n_out, n_pad_cols, taps, stride, grad, c_valid)
-        kp = len(taps) * x_c                                   # rows of the transposed im2col matrix
-        splits, chunk, n_rows = wgrad_split_transposed(B * gh * gw, kp, n_pad_cols)
-        m_pad = chunk * splits
-        # both operands are stored as one compact slab per K split: [splits][rows][chunk]
-        dzt = self._scratch('wg_dzT', n_rows * m_pad * 2)
-        colt = self._scratch('wg_colT', kp * m_pad * 2)
-        zero = cints([0])
-        if n_rows > n_pad_cols:
-            dzt[:n_rows * m_pad * 2].zero_()                     # tile-padding rows of every slab stay zero
-        _lib.check(lib.rart_transpose_gather_bf16(dz.data_ptr(), dzt.data_ptr(), B, gh, gw, n_pad_cols, gh, gw, 1, 1, 1,
-                                                  zero, zero, m_pad, chunk, n_rows, sp))
-        _lib.check(lib.rart_transpose_gather_bf16(x.data_ptr(), colt.data_ptr(), B, x_hw[0], x_hw[1], x_c, gh, gw,
-                                                  stride, stride, len(taps), cints([t[0] for t in taps]),
-                                                  cints([t[1] for t in taps]), m_pad, chunk, kp, sp))
-        ld_n = (n_pad_cols + 7) // 8 * 8
-        part = self._scratch('wg_part', splits * kp * ld_n * 4)
-        self._launch_conv(conv_desc(colt, dzt, part, 1, (1, kp), (1, kp), chunk, chunk, [(0, 0)], ld_n, (1, kp), ld_n, flags=F_OUT_F32,
-                                    batched=dict(n=splits, inner=splits, src=(0, kp * chunk), wgt=(0, n_rows * chunk), dst=(0, kp * ld_n),
-                                                 wgt_row_stride=chunk)))
-        cv = c_valid if c_valid is not None else x_c
-        _lib.check(lib.rart_wgrad_reduce_f32(part.data_ptr(), splits, len(taps), cv, x_c, n_out, ld_n, grad.data_ptr(), 0,
-                                             sp))
+        self._wgrad_transposed(dz, (B, gh, gw, n_pad_cols, gh, gw), x, (B, x_hw[0], x_hw[1], x_c, gh, gw, stride, taps), n_out, grad,
+                               (len(taps), c_valid if c_valid is not None else x_c, x_c))
 
     def _conv_wgrad(self, c, dz, dz_hw, x, x_hw):
         self._wgrad(dz, c.cout, c.cout, x, x_hw, c.cin, dz_hw, c.fwd_taps, c.stride, c.conv.weight.grad)
@@ -269,12 +232,10 @@ class ResNet50TrainEngine(EngineBase):
         h1, w1 = H // 2, W // 2
         z1 = self._get('z1', (B, h1, w1, 64))
         y1 = self._get('y1', (B, h1, w1, 64))
-        st = None
-        if self.conv_bn_stats:
-            tiles = (B * h1 * w1 + 127) // 128
-            st = (self._scratch('bn_stats', tiles * 2 * 64 * 4), tiles)
+        tiles = (B * h1 * w1 + 127) // 128
+        st = (self._scratch('bn_stats', tiles * 2 * 64 * 4), tiles)
         self._launch_conv(conv_desc(hi[0], self.stem_w, z1, B, (h1, w1), (H + 8, W + 8), 4, 32, [(r, 0) for r in range(7)] * 2, 64,
-                                    (h1, w1), 64, stride=(2, 2), tap_src_off=[0] * 7 + [lo_off(hi)] * 7, stats_out=st[0] if st else None))
+                                    (h1, w1), 64, stride=(2, 2), tap_src_off=[0] * 7 + [lo_off(hi)] * 7, stats_out=st[0]))
         self._bn_fwd(self.stem, z1, y1, B * h1 * w1, True, stats=st)
         h2, w2 = h1 // 2, w1 // 2
         p1 = self._get('p1', (B, h2, w2, 64))
@@ -328,8 +289,7 @@ class ResNet50TrainEngine(EngineBase):
         dl = dlogits.detach().float().contiguous()
         fc.bias.grad.copy_(dl.sum(0))
         self.on_grad_ready(fc.bias)
-        dlb = self._get('dl_bf16', (B, self.fc_kpad))
-        _lib.check(lib.rart_f32_to_bf16_rows(_lib.ptr(dl), _lib.ptr(dlb), B, self.n_classes, self.fc_kpad, sp))
+        dlb = self._dlogits_rows(dl, 'dl_bf16', B, self.fc_kpad)
         pooled = acts['pooled']
         # classifier weight gradient: [classes][features] = dl^T . pooled  (1x1 "conv" over B pixels)
         self._wgrad(dlb.view(B, 1, 1, self.fc_kpad), self.n_classes, self.fc_kpad, pooled.view(B, 1, 1, self.fc_in), (1, 1),
@@ -347,8 +307,7 @@ class ResNet50TrainEngine(EngineBase):
             x, xhw, za, ya, zb, yb, zc, zd, out, ohw = acts['b%d' % bi]
             rows_o, rows_i = B * ohw[0] * ohw[1], B * xhw[0] * xhw[1]
             dzc = self._get('g_zc', tuple(zc.shape))
-            skip_bits = self._ysign.get(out.data_ptr()) if (self.bit_masks and self.masked_skip and ds is None) else None
-            g = None if skip_bits is not None else self._get('g_skip', tuple(zc.shape))
+            g = self._get('g_skip', tuple(zc.shape)) if ds is not None else None      # the skip gradient a projection reads
             self._bn_bwd(cc, d_out, out, zc, dzc, rows_o, g_out=g)
             self._conv_wgrad(cc, dzc, ohw, yb, ohw)
             dyb = self._get('g_yb', tuple(yb.shape))
@@ -364,11 +323,9 @@ class ResNet50TrainEngine(EngineBase):
             self._bn_bwd(ca, dya, ya, za, dza, rows_i)
             self._conv_wgrad(ca, dza, xhw, x, xhw)
             dx = self._get('g_x_%d' % (bi % 2), tuple(x.shape))
-            if ds is None and skip_bits is not None:
+            if ds is None:
                 # the identity skip's gradient d_out . [out > 0] is formed in the dgrad epilogue from d_out and the sign bits of `out`
-                self._conv_dgrad(ca, dza, xhw, dx, xhw, res=d_out, res_mask_bits=skip_bits)
-            elif ds is None:
-                self._conv_dgrad(ca, dza, xhw, dx, xhw, res=g)
+                self._conv_dgrad(ca, dza, xhw, dx, xhw, res=d_out, res_mask_bits=self._ysign[out.data_ptr()])
             else:
                 self._conv_dgrad(ca, dza, xhw, dx, xhw)
                 dzd = self._get('g_zd', tuple(zd.shape))

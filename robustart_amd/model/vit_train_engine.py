@@ -4,8 +4,9 @@ The training step the reference's solver runs for `vit_base` (exprs/nips_benchma
 AdamW, label_smooth 0.1, drop_path_rate 0.0 -- no stochastic layers) with every FLOP on HIP kernels:
 
   forward / backward-to-input       ViTEngine (igemm GEMMs, fused attention forward / backward, row kernels)
-  Linear weight gradients           split-K GEMM on rart_conv_igemm_bf16 over transposed operands
-                                    (rart_transpose_gather_bf16, rart_wgrad_reduce_f32) -- the ResNet train engine's path
+  Linear weight gradients           split-K GEMM on rart_conv_igemm_bf16 over transposed operands (rart_transpose_gather_bf16,
+                                    rart_wgrad_reduce_f32): EngineBase._wgrad_transposed through RowEngine._wgrad, the method behind
+                                    the ResNet train engine's cross-check path as well
   Linear biases, position embedding rart_colsum_bf16
   LayerNorm gamma / beta            rart_layernorm_bwd_full_bf16 (fused with the backward to the input)
 

@@ -347,19 +347,29 @@ def test_vit_tables_exist_in_the_engines_precision_only(monkeypatch):
 _RESNET = []
 
 
-def _resnet(monkeypatch, precision, supported=lambda name, args: 0):
-    """ResNet50Engine of the full (3, 4, 6, 3) network on the CPU; supported(name, args) answers every rart_*_supported"""
+def _resnet_model():
     from robustart_amd.model import get_model
-    from robustart_amd.model.engine import ResNet50Engine
     if not _RESNET:
         torch.manual_seed(0)
         _RESNET.append(get_model({'type': 'resnet50_official'}).eval())
+    return _RESNET[0]
+
+
+def _cpu_library(monkeypatch, supported):
+    """the recorder as the library of engines built on the CPU by their own constructors"""
     rec = _Recorder()
     rec.supported = supported
     monkeypatch.setattr(_lib, 'require_gpu', lambda: torch)
     monkeypatch.setattr(_lib, 'stream_ptr', lambda: None)
     monkeypatch.setattr(_lib, 'load', lambda: rec)
-    eng = ResNet50Engine(_RESNET[0], 'cpu', precision)
+    return rec
+
+
+def _resnet(monkeypatch, precision, supported=lambda name, args: 0):
+    """ResNet50Engine of the full (3, 4, 6, 3) network on the CPU; supported(name, args) answers every rart_*_supported"""
+    from robustart_amd.model.engine import ResNet50Engine
+    rec = _cpu_library(monkeypatch, supported)
+    eng = ResNet50Engine(_resnet_model(), 'cpu', precision)
     rec.calls.clear()
     return eng
 
@@ -556,3 +566,235 @@ def test_resnet_tables_exist_in_the_engines_precision_only(monkeypatch):
     assert torch.equal(x3.fc_wd[:, 1024:2024], (w - w.to(torch.bfloat16).float()).to(torch.bfloat16).t()) and not x3.fc_wd[:, 1000:1024].any()
     # the precision helpers live on the base class
     assert 'x3' in vars(eb.EngineBase) and all(n in vars(eb.EngineBase) and n not in vars(eb.RowEngine) for n in ('_act', '_hl', '_dlogits_rows'))
+
+
+# ---------------------------------------------------------------------- the train engine of ResNet-50 and the shared weight gradient
+def _resnet_train(monkeypatch, supported=lambda name, args: 1):
+    """ResNet50TrainEngine of the full (3, 4, 6, 3) network on the CPU, its constructor's calls still recorded"""
+    from robustart_amd.model.train_engine import ResNet50TrainEngine
+    m = _resnet_model()
+    for p in m.parameters():
+        if p.grad is None:
+            p.grad = torch.zeros_like(p)
+    _cpu_library(monkeypatch, supported)
+    return ResNet50TrainEngine(m, 'cpu')
+
+
+def _counts(eng):
+    """recorded launches by entry name (the workspace-size queries are no launches)"""
+    out = {}
+    for n in _names(eng):
+        if not n.endswith('_workspace_bytes'):
+            out[n] = out.get(n, 0) + 1
+    return out
+
+
+def test_resnet_train_chain_launch_counts(monkeypatch):
+    """constructor, forward and backward of the train engine at 2 x 3 x 64 x 64 with every kernel available: 53 conv + BatchNorm pairs
+    and the classifier forward; backward 52 + 9 dgrad launches (a 3x3 / 2 reaches four input parities, a 1x1 / 2 one) + the
+    classifier's, and one weight gradient per conv, stem and classifier included, on either weight-gradient path"""
+    B = 2
+    eng = _resnet_train(monkeypatch)
+    assert _counts(eng) == {'rart_pack_jobs_bf16': 1, 'rart_pack_conv_weight_bf16': 1}
+    # the stem's row-tap table comes from the eval engine's builder: the image's hi taps, then the same rows for its lo taps
+    rows = eb.stem_rows(eng.model.conv1.weight.detach().float()).to(torch.bfloat16)
+    assert rows.shape == (64, 224) and torch.equal(eng.stem_w[:, :224], rows) and torch.equal(eng.stem_w[:, 224:], rows)
+    x, dl = torch.rand(B, 3, 64, 64), torch.ones(B, 1000)
+    fwd = {'rart_engine_prep_input': 1, 'rart_conv_igemm_bf16': 54, 'rart_bn_train_forward_bf16': 53, 'rart_engine_maxpool': 1,
+           'rart_engine_avgpool': 1}
+    rest = {'rart_f32_to_bf16_rows': 1, 'rart_wgrad_reduce_f32': 54, 'rart_bn_train_backward_bf16': 53, 'rart_engine_avgpool_bwd': 1,
+            'rart_engine_maxpool_bwd': 1}
+    assert eng.direct_wgrad is True
+    eng.forward(x, False, MEAN, STD)
+    assert _counts(eng) == fwd
+    eng.backward(dl)
+    assert _counts(eng) == dict(rest, rart_conv_igemm_bf16=62, rart_wgrad_direct_bf16=54)
+    eng.direct_wgrad = False
+    eng.forward(x, False, MEAN, STD)
+    assert _counts(eng) == fwd
+    eng.backward(dl)
+    assert _counts(eng) == dict(rest, rart_conv_igemm_bf16=116, rart_transpose_gather_bf16=108)
+
+
+def test_resnet_train_backward_order_around_an_identity_and_a_projection_block(monkeypatch):
+    """per conv: BatchNorm backward, then the weight gradient, then the backward to the input.  Block 15 (identity): the skip gradient
+    is formed in conv1's dgrad epilogue from d_out and the sign bits of the block's output; block 13 (layer4's projection block): the
+    BatchNorm backward of conv3 writes the masked skip gradient, which the downsample's BatchNorm backward reads"""
+    B = 2
+    eng = _resnet_train(monkeypatch)
+    eng.forward(torch.rand(B, 3, 64, 64), False, MEAN, STD)
+    acts = eng.acts
+    eng.lib.calls.clear()
+    eng.backward(torch.ones(B, 1000))
+    calls = eng.lib.calls
+    short = {'rart_bn_train_backward_bf16': 'bn', 'rart_wgrad_direct_bf16': 'wgrad', 'rart_wgrad_reduce_f32': 'reduce',
+             'rart_conv_igemm_bf16': 'gemm', 'rart_transpose_gather_bf16': 'gather'}
+    calls = [(short.get(n, n), a) for n, a in calls if not n.endswith('_workspace_bytes')]
+    kinds = [n for n, _ in calls]
+    assert kinds[:5] == ['rart_f32_to_bf16_rows', 'wgrad', 'reduce', 'gemm', 'rart_engine_avgpool_bwd']
+    conv = ['bn', 'wgrad', 'reduce', 'gemm']
+    # blocks 15 and 14: three convs each, one dgrad launch per conv
+    assert kinds[5:29] == conv * 6
+    b15 = calls[5:17]
+    x, xhw, za, ya, zb, yb, zc, zd, out, ohw = acts['b15']
+    assert [_vals(a)[3] for n, a in b15 if n == 'bn'] == [zc.data_ptr(), zb.data_ptr(), za.data_ptr()]
+    assert _vals(b15[0][1])[5] is None                                   # no skip-gradient tensor
+    d_out = _vals(b15[0][1])[0]
+    d = b15[-1][1][0]._obj
+    assert (d.res, d.mask, d.flags) == (d_out, eng._ysign[out.data_ptr()].data_ptr(), eb.F_MASK_BITS | eb.F_MASK_RES)
+    # block 13: conv3, conv2 (3x3 / 2: four parity classes), conv1, then the projection (1x1 / 2: one class)
+    assert kinds[29:48] == conv + ['bn', 'wgrad', 'reduce'] + ['gemm'] * 4 + conv + conv
+    b13 = calls[29:48]
+    x, xhw, za, ya, zb, yb, zc, zd, out, ohw = acts['b13']
+    bns = [_vals(a) for n, a in b13 if n == 'bn']
+    assert [a[3] for a in bns] == [zc.data_ptr(), zb.data_ptr(), za.data_ptr(), zd.data_ptr()]
+    g_skip = bns[0][5]
+    assert g_skip is not None and bns[3][:3] == (g_skip, None, 0) and bns[1][5] is None and bns[2][5] is None
+    ca_dgrad, ds_dgrad = b13[14][1][0]._obj, b13[18][1][0]._obj
+    assert (ca_dgrad.res, ca_dgrad.mask, ca_dgrad.flags) == (None, None, 0)
+    assert ds_dgrad.res == ds_dgrad.dst == ca_dgrad.dst and (ds_dgrad.dst_sy, ds_dgrad.dst_sx, ds_dgrad.dst_oy, ds_dgrad.dst_ox) == (2, 2, 0, 0)
+    assert [(c[1][0]._obj.dst_oy, c[1][0]._obj.dst_ox) for c in b13[7:11]] == [(0, 0), (0, 1), (1, 0), (1, 1)]
+    # the transposing path keeps the order: BatchNorm backward, both transposes, the GEMM, the reduce, then the dgrad
+    eng.direct_wgrad = False
+    eng.lib.calls.clear()
+    eng.backward(torch.ones(B, 1000))
+    kinds = [short.get(n, n) for n, _ in eng.lib.calls if not n.endswith('_workspace_bytes')]
+    assert kinds[:6] == ['rart_f32_to_bf16_rows', 'gather', 'gather', 'gemm', 'reduce', 'gemm']
+    assert kinds[7:7 + 36] == ['bn', 'gather', 'gather', 'gemm', 'reduce', 'gemm'] * 6
+
+
+def test_train_engine_does_not_read_the_environment(monkeypatch):
+    monkeypatch.setenv('RART_TRAIN_FLAGS', 'direct=0')
+    assert _resnet_train(monkeypatch).direct_wgrad is True
+
+
+def _wgrad_calls(eng):
+    """(gather of dz, gather of x, GEMM descriptor, reduce) of one weight gradient on the transposing path"""
+    (n0, g0), (n1, g1), (n2, mm), (n3, red) = eng.lib.calls
+    assert [n0, n1, n2, n3] == ['rart_transpose_gather_bf16'] * 2 + ['rart_conv_igemm_bf16', 'rart_wgrad_reduce_f32']
+    taps = [tuple(list(g[i]) for i in (11, 12)) for g in (g0, g1)]
+    return [_vals(g[:11] + g[13:]) for g in (g0, g1)], taps, mm[0]._obj, _vals(red)
+
+
+def _check_wgrad_gemm(eng, d, kp, grid, splits, chunk, n_rows, ld_n):
+    dzt, colt, part = (eng._buf[n].data_ptr() for n in ('wg_dzT', 'wg_colT', 'wg_part'))
+    assert (d.src, d.wgt, d.dst, d.bias, d.res, d.mask) == (colt, dzt, part, None, None, None)
+    assert (d.batch, d.grid_h, d.grid_w) == (1,) + grid and (d.src_h, d.src_w) == grid == (d.dst_h, d.dst_w)
+    assert (d.k_per_tap, d.src_pix_stride, d.n_taps, d.tap_dy[0], d.tap_dx[0]) == (chunk, chunk, 1, 0, 0)
+    assert (d.n_cols, d.dst_pix_stride, d.flags) == (ld_n, ld_n, eb.F_OUT_F32)
+    assert (d.n_batched, d.z_inner, d.wgt_row_stride) == (splits, splits, chunk)
+    assert (d.src_z_outer, d.src_z_inner, d.wgt_z_outer, d.wgt_z_inner, d.dst_z_outer, d.dst_z_inner) == \
+        (0, kp * chunk, 0, n_rows * chunk, 0, kp * ld_n)
+    return dzt, colt, part
+
+
+def test_shared_weight_gradient_conv_form(monkeypatch):
+    """ResNet50TrainEngine._wgrad's transposing path, a 3x3 / 2 conv 64 -> 64 on 2 x 8 x 8: both gathers, the GEMM over the
+    [splits][rows][chunk] slabs as a (1, kp) grid, the reduce"""
+    from robustart_amd.model.train_engine import ResNet50TrainEngine, _TConv
+    monkeypatch.setattr(_lib, 'require_gpu', lambda: torch)
+    ready = []
+    eng = _engine(ResNet50TrainEngine, monkeypatch, device=torch.device('cpu'), direct_wgrad=False, on_grad_ready=ready.append)
+    conv = torch.nn.Conv2d(64, 64, 3, stride=2, padding=1, bias=False)
+    conv.weight.grad = torch.zeros_like(conv.weight)
+    tc = _TConv(conv, None, eng.device, torch)
+    B, H, G = 2, 8, 4
+    x, dz = _bf(B, H, H, 64), _bf(B, G, G, 64)
+    kp = 9 * 64
+    splits, chunk, n_rows = eb.wgrad_split_transposed(B * G * G, kp, 64)
+    assert (splits, chunk, n_rows) == (1, 64, 64)
+    eng._buf['wg_dzT'] = torch.ones(2 * n_rows * chunk * splits, dtype=torch.uint8)
+    eng._conv_wgrad(tc, dz, (G, G), x, (H, H))
+    (g_dz, g_x), (t_dz, t_x), d, red = _wgrad_calls(eng)
+    dzt, colt, part = _check_wgrad_gemm(eng, d, kp, (1, kp), splits, chunk, n_rows, 64)
+    assert g_dz == (dz.data_ptr(), dzt, B, G, G, 64, G, G, 1, 1, 1, splits * chunk, chunk, n_rows, None) and t_dz == ([0], [0])
+    assert g_x == (x.data_ptr(), colt, B, H, H, 64, G, G, 2, 2, 9, splits * chunk, chunk, kp, None)
+    assert list(zip(*t_x)) == tc.fwd_taps == [(r - 1, s - 1) for r in range(3) for s in range(3)]
+    assert red == (part, splits, 9, 64, 64, 64, 64, conv.weight.grad.data_ptr(), 0, None)
+    assert ready == [conv.weight]
+    assert bool(eng._buf['wg_dzT'].all())                                # n_rows == n_pad: no tile-padding rows, nothing zeroed
+    # the stem's form: 3 of the 4 channels of the padded plane kept by the reduce
+    eng.lib.calls.clear()
+    hi, dz1, w1 = _bf(B, 24, 24, 4), _bf(B, 8, 8, 64), torch.zeros(64, 3, 7, 7)
+    taps = [(r, s) for r in range(7) for s in range(7)]
+    eng._wgrad(dz1, 64, 64, hi, (24, 24), 4, (8, 8), taps, 2, w1, c_valid=3)
+    (g_dz, g_x), (t_dz, t_x), d, red = _wgrad_calls(eng)
+    assert g_x[2:11] == (B, 24, 24, 4, 8, 8, 2, 2, 49) and g_x[-2] == 196 and list(zip(*t_x)) == taps
+    assert (d.grid_h, d.grid_w) == (1, 196) and red[1:7] == (1, 49, 3, 4, 64, 64)
+
+
+def test_shared_weight_gradient_row_form(monkeypatch):
+    """RowEngine._wgrad: 5 of the 6 rows of each of 2 images, 48 input features, 10 outputs in 64 columns; the GEMM as a (c_in, 1) grid"""
+    monkeypatch.setattr(_lib, 'require_gpu', lambda: torch)
+    eng = _engine(eb.RowEngine, monkeypatch, device=torch.device('cpu'))
+    rows, c_in, n_out, n_pad = 2 * 5, 48, 10, 64
+    dz, x, grad = _bf(2 * 6, n_pad), _bf(rows, c_in), torch.zeros(n_out, c_in)
+    splits, chunk, n_rows = eb.wgrad_split_transposed(rows, c_in, n_pad)
+    assert (splits, chunk, n_rows) == (1, 64, 64)
+    eng._wgrad(dz, n_out, n_pad, x, c_in, grad, rows, dz_images=(2, 6, 5))
+    (g_dz, g_x), (t_dz, t_x), d, red = _wgrad_calls(eng)
+    dzt, colt, part = _check_wgrad_gemm(eng, d, c_in, (c_in, 1), splits, chunk, n_rows, 64)
+    assert g_dz == (dz.data_ptr(), dzt, 2, 6, 1, n_pad, 5, 1, 1, 1, 1, splits * chunk, chunk, n_rows, None)
+    assert g_x == (x.data_ptr(), colt, 1, rows, 1, c_in, rows, 1, 1, 1, 1, splits * chunk, chunk, c_in, None)
+    assert t_dz == t_x == ([0], [0])
+    assert red == (part, splits, 1, c_in, c_in, n_out, 64, grad.data_ptr(), 0, None)
+    # without dz_images: one image of `rows` rows
+    eng.lib.calls.clear()
+    eng._wgrad(dz, n_out, n_pad, x, c_in, grad, rows)
+    assert _wgrad_calls(eng)[0][0][2:8] == (1, rows, 1, n_pad, rows, 1)
+
+
+def test_shared_weight_gradient_zeroes_the_tile_padding_rows_only_when_there_are_some(monkeypatch):
+    """the transposed dz has n_rows = n_pad rounded up to the GEMM's column tile; rows n_pad .. n_rows are written by nobody, so the
+    slabs are zeroed first when and only when n_rows > n_pad"""
+    monkeypatch.setattr(_lib, 'require_gpu', lambda: torch)
+    rows, c_in = 10, 48
+    for n_pad, n_rows in ((64, 64), (128, 128), (40, 64), (200, 256), (72, 128)):
+        eng = _engine(eb.RowEngine, monkeypatch, device=torch.device('cpu'))
+        splits, chunk, got_rows = eb.wgrad_split_transposed(rows, c_in, n_pad)
+        assert got_rows == n_rows
+        used = n_rows * chunk * splits * 2
+        buf = eng._buf['wg_dzT'] = torch.ones(used + 64, dtype=torch.uint8)
+        eng._wgrad(_bf(rows, n_pad), n_pad, n_pad, _bf(rows, c_in), c_in, torch.zeros(n_pad, c_in), rows)
+        assert eng._buf['wg_dzT'] is buf and bool(buf[used:].all())
+        assert bool(buf[:used].all()) if n_rows == n_pad else not buf[:used].any()
+
+
+def test_conv_tap_classes():
+    """one geometry for the eval and the train engine: forward taps, filter taps, and per input-parity class of the backward to the
+    input the (dy, dx) read from the output gradient and the filter taps that reach it"""
+    for r, stride, pad in ((1, 1, 0), (3, 1, 1), (3, 2, 1), (1, 2, 0), (7, 2, 3)):
+        fwd, all_rs, bwd = eb.conv_tap_classes(r, r, stride, pad)
+        assert all_rs == [(a, b) for a in range(r) for b in range(r)]
+        assert fwd == [(a - pad, b - pad) for a in range(r) for b in range(r)]
+        if stride == 1:
+            assert bwd == [(None, [(pad - a, pad - b) for a, b in all_rs], all_rs)]
+            continue
+        assert [p for p, _, _ in bwd] == [(0, 0), (0, 1), (1, 0), (1, 1)]
+        for (ph, pw), taps, rs in bwd:
+            assert rs == [(a, b) for a, b in all_rs if (ph + pad - a) % 2 == 0 and (pw + pad - b) % 2 == 0]
+            assert taps == [((ph + pad - a) // 2, (pw + pad - b) // 2) for a, b in rs]
+        assert sorted(t for _, _, rs in bwd for t in rs) == all_rs      # every filter tap reaches exactly one class
+    assert [len(taps) for _, taps, _ in eb.conv_tap_classes(1, 1, 2, 0)[2]] == [1, 0, 0, 0]
+    assert [len(taps) for _, taps, _ in eb.conv_tap_classes(3, 3, 2, 1)[2]] == [1, 2, 2, 4]
+    assert [len(taps) for _, taps, _ in eb.conv_tap_classes(7, 7, 2, 3)[2]] == [9, 12, 12, 16]
+    assert eb.conv_tap_classes(3, 3, 2, 1)[2][0] == ((0, 0), [(0, 0)], [(1, 1)])
+    assert eb.conv_tap_classes(3, 3, 2, 1)[2][3][1] == [(1, 1), (1, 0), (0, 1), (0, 0)]
+
+
+def test_both_resnet_engines_build_from_the_one_geometry():
+    from robustart_amd.model.engine import _Conv
+    from robustart_amd.model.train_engine import _TConv
+    for cin, cout, r, stride in ((8, 16, 3, 1), (8, 16, 3, 2), (16, 8, 1, 2)):
+        conv = torch.nn.Conv2d(cin, cout, r, stride=stride, padding=r // 2, bias=False)
+        ev, tr = _Conv(conv, None, 'cpu'), _TConv(conv, None, torch.device('cpu'), torch)
+        fwd, all_rs, classes = eb.conv_tap_classes(r, r, stride, r // 2)
+        assert ev.fwd_taps == tr.fwd_taps == fwd and tr.all_rs == all_rs
+        assert [(p, t) for p, t, _ in ev.bwd] == [(p, t) for p, t, _, _ in tr.bwd] == [(p, t) for p, t, _ in classes]
+        assert [rs for _, _, rs, _ in tr.bwd] == [rs for _, _, rs in classes]
+        for (_, taps, a), (_, _, _, b) in zip(ev.bwd, tr.bwd):
+            assert (a is None and b is None and not taps) or a.shape == b.shape == (64, len(taps) * cout)
+        assert ev.w_fwd.shape == tr.w_fwd.shape == (64, r * r * cin)
+    w = torch.randn(64, 3, 7, 7)
+    rows = eb.stem_rows(w).view(64, 7, 8, 4)
+    assert torch.equal(rows[:, :, :7, :3], w.permute(0, 2, 3, 1)) and not rows[:, :, 7].any() and not rows[..., 3].any()
