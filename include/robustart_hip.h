@@ -793,6 +793,26 @@ int rart_ema_update_f32(float* ema, const float* param, size_t n, double decay, 
  * dlogits_out[batch][classes] (nullable) = scale * (softmax - (1-s)*onehot - s/classes). */
 int rart_label_smooth_ce_f32(const float* logits, const int64_t* labels, int batch, int classes, double smoothing,
                              double scale, float* loss_out, float* dlogits_out, rart_stream_t stream);
+/* The two-label loss of Mixup / CutMix (`mixup`, `cutmix` of the solver's config; robustart_amd/train/mixing.py), L = the loss above:
+ *   loss_out[b] = lam * L(z_b, labels_a[b]) + (1 - lam) * L(z_b, labels_b[b])   (two fp32 products, one fp32 sum)
+ *   dlogits_out = scale * (softmax - s/classes - (1-s)*lam*onehot(labels_a) - (1-s)*(1-lam)*onehot(labels_b)), both terms subtracted
+ *   where the labels agree.  lam in [0, 1]; lam and 1 - lam are formed in double and rounded to fp32 once.  lam = 1 (0) reproduces
+ *   rart_label_smooth_ce_f32 on labels_a (labels_b) bit for bit.  As there, every label must lie in [0, classes): the labels index the
+ *   row of logits and are not range-checked on the device (the caller's contract). */
+int rart_label_smooth_ce_mix_f32(const float* logits, const int64_t* labels_a, const int64_t* labels_b, int batch, int classes,
+                                 double smoothing, double lam, double scale, float* loss_out, float* dlogits_out, rart_stream_t stream);
+
+/* ---- Mixup / CutMix of a batch (csrc/batch_mix.hip; robustart_amd/train/mixing.py) ------------------------------------------------
+ * src: uint8 NHWC [n][h][w][3] (src_is_u8 = 1; x01 = u8 * (1 / 255), the arithmetic of rart_u8_to_unit_f32_nchw) or fp32 NCHW
+ * [n][3][h][w] in [0, 1] (0).  perm: int32 [n] on the device, every entry in [0, n) (the caller's contract).  dst: fp32 NCHW, out of
+ * place (image i is also read as the partner of another image): dst must not overlap src.
+ *   mode 1 (Mixup):  dst[i] = lam * x01[i] + (1 - lam) * x01[perm[i]]  (two fp32 products and one fp32 sum, no contraction; lam and
+ *                    1 - lam formed in double, rounded to fp32 once)
+ *   mode 2 (CutMix): dst[i] = x01[perm[i]] for y0 <= y < y1 and x0 <= x < x1, x01[i] elsewhere; lam is not used.
+ * 0 <= y0 <= y1 <= h, 0 <= x0 <= x1 <= w, 0 <= lam <= 1, n * 3 * h * w < 2^32.  16 bytes per store when w % 4 == 0 and the pointers
+ * allow it (dst 16-byte aligned, src 4-byte (u8) / 16-byte (fp32) aligned), one element per thread otherwise, with identical results. */
+int rart_mix_batch_f32(const void* src, int src_is_u8, const int32_t* perm, float* dst, int n, int h, int w, int mode, double lam,
+                       int y0, int y1, int x0, int x1, rart_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Train-mode conv + BatchNorm support (cls_solver training step): the contractions run on

@@ -139,6 +139,50 @@ __global__ __launch_bounds__(kBlock) void k_label_smooth_ce(const float* __restr
   }
 }
 
+// The two-label loss of Mixup / CutMix, one wave per row with the reductions of k_label_smooth_ce: L_a and L_b are that kernel's
+// expressions at y_a and y_b,
+//   loss = lam * L_a + (1 - lam) * L_b                                                         (two products, one sum, no contraction)
+//   dlogits[c] = scale * (softmax[c] - s / C - (1 - s) * lam * [c == y_a] - (1 - s) * (1 - lam) * [c == y_b])
+// lam = 1 (0) is k_label_smooth_ce on y_a (y_b) bit for bit: the other label's weight is an exact zero.
+__global__ __launch_bounds__(kBlock) void k_label_smooth_ce_mix(const float* __restrict__ logits, const int64_t* __restrict__ ya,
+                                                                const int64_t* __restrict__ yb, int batch, int classes, float smoothing,
+                                                                float lam, float one_minus_lam, float scale,
+                                                                float* __restrict__ loss_out, float* __restrict__ dlogits) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  if (row >= batch) return;
+  const float* z = logits + (size_t)row * classes;
+  float mx = -3.402823466e38f;
+  for (int c = lane; c < classes; c += 64) mx = fmaxf(mx, z[c]);
+  mx = rart_wave_max(mx);
+  float se = 0.f, sz = 0.f;
+  for (int c = lane; c < classes; c += 64) {
+    se += expf(z[c] - mx);
+    sz += z[c] - mx;
+  }
+  se = rart_wave_sum(se);
+  sz = rart_wave_sum(sz);
+  const float lse = logf(se);
+  const int a = (int)ya[row], b = (int)yb[row];
+  if (loss_out && lane == 0) {
+    const float mean_nlp = lse - sz / (float)classes;           // mean_c(-logp[c])
+    const float la = (1.0f - smoothing) * (lse - (z[a] - mx)) + smoothing * mean_nlp;
+    const float lb = (1.0f - smoothing) * (lse - (z[b] - mx)) + smoothing * mean_nlp;
+    loss_out[row] = lam * la + one_minus_lam * lb;               // contraction is off in this file: two products, one sum
+  }
+  if (dlogits) {
+    float* d = dlogits + (size_t)row * classes;
+    const float inv = 1.0f / se, off = smoothing / (float)classes;
+    const float wa = (1.0f - smoothing) * lam, wb = (1.0f - smoothing) * one_minus_lam;
+    for (int c = lane; c < classes; c += 64) {
+      float t = expf(z[c] - mx) * inv - off;
+      if (c == a) t -= wa;
+      if (c == b) t -= wb;
+      d[c] = scale * t;
+    }
+  }
+}
+
 inline unsigned grid_for(size_t n4) {
   size_t b = (n4 + kBlock - 1) / kBlock;
   if (b < 1) b = 1;
@@ -203,5 +247,20 @@ extern "C" int rart_label_smooth_ce_f32(const float* logits, const int64_t* labe
   hipLaunchKernelGGL(k_label_smooth_ce, dim3((batch + rows_per_block - 1) / rows_per_block), dim3(kBlock), 0,
                      (hipStream_t)stream, logits, labels, batch, classes, (float)smoothing, (float)scale, loss_out, dlogits_out);
   RART_CHECK_LAUNCH("rart_label_smooth_ce_f32");
+  return RART_OK;
+}
+
+extern "C" int rart_label_smooth_ce_mix_f32(const float* logits, const int64_t* labels_a, const int64_t* labels_b, int batch, int classes,
+                                            double smoothing, double lam, double scale, float* loss_out, float* dlogits_out,
+                                            rart_stream_t stream) {
+  RART_CHECK_ARG(logits && labels_a && labels_b && batch > 0 && classes > 0, "rart_label_smooth_ce_mix_f32: bad arguments");
+  RART_CHECK_ARG(smoothing >= 0.0 && smoothing <= 1.0, "rart_label_smooth_ce_mix_f32: label_smoothing must be in [0, 1]");
+  RART_CHECK_ARG(lam >= 0.0 && lam <= 1.0, "rart_label_smooth_ce_mix_f32: lam must be in [0, 1]");
+  RART_CHECK_ARG(loss_out || dlogits_out, "rart_label_smooth_ce_mix_f32: nothing to compute");
+  const int rows_per_block = kBlock / 64;
+  hipLaunchKernelGGL(k_label_smooth_ce_mix, dim3((batch + rows_per_block - 1) / rows_per_block), dim3(kBlock), 0, (hipStream_t)stream,
+                     logits, labels_a, labels_b, batch, classes, (float)smoothing, (float)lam, (float)(1.0 - lam), (float)scale, loss_out,
+                     dlogits_out);
+  RART_CHECK_LAUNCH("rart_label_smooth_ce_mix_f32");
   return RART_OK;
 }

@@ -228,3 +228,17 @@ def label_smooth_ce(logits, labels, smoothing, scale):
     _lib.check(lib.rart_label_smooth_ce_f32(logits.data_ptr(), labels.contiguous().data_ptr(), b, c, smoothing, scale,
                                             loss.data_ptr(), dl.data_ptr(), _lib.stream_ptr()))
     return loss, dl
+
+
+def label_smooth_ce_mix(logits, y_a, y_b, lam, smoothing, scale):
+    """(loss_rows, dlogits) of lam * CE(logits, y_a) + (1 - lam) * CE(logits, y_b), CE = F.cross_entropy(label_smoothing): the two-label
+    loss of Mixup / CutMix (train/mixing.py) through rart_label_smooth_ce_mix_f32."""
+    from .. import _lib
+    lib = _lib.load()
+    logits = logits.float().contiguous()
+    b, c = logits.shape
+    loss = torch.empty(b, dtype=torch.float32, device=logits.device)
+    dl = torch.empty_like(logits)
+    _lib.check(lib.rart_label_smooth_ce_mix_f32(logits.data_ptr(), y_a.contiguous().data_ptr(), y_b.contiguous().data_ptr(), b, c,
+                                                smoothing, float(lam), scale, loss.data_ptr(), dl.data_ptr(), _lib.stream_ptr()))
+    return loss, dl

@@ -543,6 +543,13 @@ def train(cfg, args, rank, world, device):
     n = int(dcfg.get('fake_size', 512))
     bs = int(dcfg.get('batch_size', 32))
     size = int(dcfg.get('input_size', 224))
+    # `mixup` / `cutmix` (augmentation/resnet50/config.yaml:30-31): the Beta parameters of the batch mixing, None = off (train/mixing.py)
+    from . import mixing
+    mixup_alpha, cutmix_alpha = mixing.mix_alphas(cfg)
+    mix_on = mixup_alpha is not None or cutmix_alpha is not None
+    if mix_on and cfg.get('adv_train', None):  # before the model is built or reaches the device: no reference config combines the two
+        raise ValueError('adv_train together with an active %s key: mixing under adversarial training is not defined here (no reference '
+                         'config combines them); drop one of the two' % ' / '.join(k for k, v in (('mixup', mixup_alpha), ('cutmix', cutmix_alpha)) if v is not None))
     ds = make_dataset(dcfg, n, size, 'train')
     n = len(ds)
     max_iter, warmup_steps = resolve_schedule(cfg, n, bs, world, getattr(args, 'max_iter', 20))
@@ -576,7 +583,7 @@ def train(cfg, args, rank, world, device):
     kind = ocfg.get('type', 'SGD')
     # flat arenas: parameters / gradients are views; the exchange is a few large all-reduces on arena slices,
     # overlapped with backward unless the config asks for `dist.sync: True`
-    from .arena import HipOptimizer, ParamArena, label_smooth_ce
+    from .arena import HipOptimizer, ParamArena, label_smooth_ce, label_smooth_ce_mix
     no_wd = ocfg.get('no_wd', {}) or {}
     norm_names, fc_bias_names = set(), set()
     for mn, mod in model.named_modules():
@@ -711,7 +718,17 @@ def train(cfg, args, rank, world, device):
         sel, epoch = sampler.batch(it)
         items = sel
         imgs, labels = ds.batch(sel, device, epoch) if isinstance(ds, FileImageNet) else ds.batch(sel, device)
-        x01 = imgs.permute(0, 3, 1, 2).float().div(255.0)
+        plan = mixing.draw_mix(mixup_alpha, cutmix_alpha, int(dcfg.get('seed', 0)), it, rank, len(sel), imgs.shape[1], imgs.shape[2]) \
+            if mix_on else None
+        if plan is None:
+            x01 = imgs.permute(0, 3, 1, 2).float().div(255.0)
+        else:
+            # Mixup or CutMix of the batch with its permuted self (one of the two per iteration): on the HIP path one launch that fuses the
+            # u8 -> [0, 1] hand-over, in torch on the scaffold; the partner labels follow the same permutation, uploaded once
+            mix_lam = plan[1]
+            perm_dev = mixing.upload_perm(plan, len(sel), device)
+            x01 = mixing.apply_mix(imgs, plan, device, perm_dev=perm_dev) if use_hip_opt else mixing.apply_mix_torch(imgs, plan)
+            labels_b = labels[perm_dev.long()]
         if adv and device.type == 'cuda':
             # inner maximisation on the HIP eval engine with the CURRENT weights, BN in inference mode: the engine is
             # built once and re-folded on the GPU from the live parameters / running statistics every iteration
@@ -732,7 +749,10 @@ def train(cfg, args, rank, world, device):
         if train_engine is not None:
             # train-mode forward (batch statistics), label-smoothed CE, backward to every parameter: all HIP
             logits = train_engine.forward(x01.contiguous(), False, IMAGENET_MEAN, IMAGENET_STD)
-            loss_rows, dlogits = label_smooth_ce(logits, labels, ls, 1.0 / len(items))
+            if plan is None:
+                loss_rows, dlogits = label_smooth_ce(logits, labels, ls, 1.0 / len(items))
+            else:
+                loss_rows, dlogits = label_smooth_ce_mix(logits, labels, labels_b, mix_lam, ls, 1.0 / len(items))
             train_engine.backward(dlogits)                  # gradients land in the arena; buckets reduce as they fill
             loss = loss_rows.mean()
         else:
@@ -741,11 +761,18 @@ def train(cfg, args, rank, world, device):
                 out = model(xin)
             if use_hip_opt:
                 # label-smoothed CE and its gradient in one HIP kernel; autograd continues from dlogits
-                loss_rows, dlogits = label_smooth_ce(out, labels, ls, 1.0 / len(items))
+                if plan is None:
+                    loss_rows, dlogits = label_smooth_ce(out, labels, ls, 1.0 / len(items))
+                else:
+                    loss_rows, dlogits = label_smooth_ce_mix(out, labels, labels_b, mix_lam, ls, 1.0 / len(items))
                 out.backward(dlogits.to(out.dtype))         # bucket all-reduces start from the grad hooks
                 loss = loss_rows.mean()
-            else:
+            elif plan is None:
                 loss = F.cross_entropy(out.float(), labels, label_smoothing=ls)
+                loss.backward()
+            else:
+                loss = mix_lam * F.cross_entropy(out.float(), labels, label_smoothing=ls) + \
+                    (1.0 - mix_lam) * F.cross_entropy(out.float(), labels_b, label_smoothing=ls)
                 loss.backward()
         scale = arena.finish_grad_exchange()                # waits for the buckets; returns 1 / world_size
         if use_hip_opt:
@@ -776,6 +803,8 @@ def train(cfg, args, rank, world, device):
                 print('[cls_solver rank %d] %s' % (rank, json.dumps(dict(iter=it, grad_exchange=xs))), file=sys.stderr, flush=True)
             if rank == 0:
                 rec = {'iter': it, 'loss': loss_v, 'lr': lr}
+                if plan is not None:
+                    rec['mix'] = {'kind': plan[0], 'lam': mix_lam}
                 if xs is not None:
                     rec['grad_exchange'] = {k: xs[k] for k in ('buckets', 'bytes', 'launched_during_backward', 'stream_wait_s', 'host_wait_s') if k in xs}
                 print(json.dumps(rec))
