@@ -9,29 +9,58 @@
 // LDS from the pooled gradient pair and the argmax codes (code 15 = window maximum <= 0 = ReLU dead), walks the 16 taps as an implicit
 // GEMM (M = positions, K = 16 taps x 64 channels, N = 12 = 4 pixel parities x 3 colours) on v_mfma_f32_16x16x32_bf16 and writes a
 // 32 x 32 x 3 fp32 tile.  The pair doubles every LDS image, so the K dimension is walked in two channel halves (32 channels = one MFMA K
-// step per tap): stage -> pool backward -> 16 taps, twice, into the same accumulators -- 66 KB of LDS, two workgroups per CU whose
-// phases overlap, as in the bf16 kernel.
+// step per tap): stage -> pool backward -> weights -> 16 taps, twice, into the same accumulators.  The weight fragments of a half (32 KB)
+// go through LDS once per workgroup, in the region the raw pooled tile has left by then: fetched per wave from global memory they were
+// 256 KB per tile against 39 KB of pooled gradient and codes, and the texture-address unit they went through paced the kernel.  78 KB of
+// LDS, two workgroups per CU whose phases overlap, as in the bf16 kernel.
 //
 // Reference step: the autograd pass of every attack iteration (RobustART/noise/utils/adv/attack.py:21-22 via foolbox;
 // Attacks/autoattack/autopgd_base.py:271-289, fp32) through conv1 / bn1 / relu / maxpool of the public ResNet-50
 // (RobustART/model/__init__.py:1 -> absent submodule; robustart_amd/model/resnet_torch.py states it).
 #include "rart_common.h"
 
+#include <type_traits>
+
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
+
+// Lab builds only: -DRART_STEM_STAMPS sums s_memtime intervals per phase and wave into g_sp_stamps ([0] backward: stage, pool backward,
+// weights + taps, epilogue, whole kernel, waves; [1] forward: stage, row taps, barrier after them, ReLU + tile store, pool + global store,
+// tiles x waves, whole loop, waves), read and reset by rart_debug_stem_stamps, an export of that build alone (profiles/stem_pair_stamps.py).
+// A stamp does not wait for outstanding loads or MFMAs.  -DRART_STEM_U8_PREFETCH=1 gives the uint8 forward the fp32 one's source prefetch.
+#ifdef RART_STEM_STAMPS
+__device__ unsigned long long g_sp_stamps[2][8];
+#define SP_T(V) const unsigned long long V = __builtin_amdgcn_s_memtime();
+#define SP_ST(...) __VA_ARGS__
+#else
+#define SP_T(V)
+#define SP_ST(...)
+#endif
+#ifndef RART_STEM_U8_PREFETCH
+#define RART_STEM_U8_PREFETCH 0
+#endif
 
 namespace {
 constexpr int T = 16;                     // positions per tile side
 constexpr int HT = T + 3;                 // halo tile side (dp, dq in -1..2)
 constexpr int NPOS_PAD = 368;             // 361 rounded up to a multiple of 16: chunk planes start on a 256-byte bank row
 constexpr int PT = T / 2 + 3;             // pooled positions per side that reach the halo tile (11)
+constexpr int PTS = 12;                   // pooled row stride in LDS: the pool backward walks PTS windows per row, so a window's slot is
+                                          // its walk index + a constant and every read below is conflict free
 constexpr int NPOOL = PT * PT;            // 121
+constexpr int NPOOL_PAD = PT * PTS;       // 132
 constexpr int OT = 2 * T;                 // image pixels per tile side (32)
 constexpr int OLD = OT + 1;               // padded fp32 output row in LDS
+constexpr int OPL = OT * OLD + 3;         // colour plane stride: = 3 mod 32, so the 24 lanes of an epilogue store meet at most two per bank
+// (PTS, NPOS_PAD, HT and the lane -> window walks of pool_bwd_class_pair are mirrored in tests/test_stem_pair_bank_model.py, which
+// holds the modelled LDS cycles of the reads below at the conflict-free count)
 constexpr int DZ_BYTES = 2 * 4 * NPOS_PAD * 16;       // [hi | lo][4 chunks of a channel half][NPOS_PAD] x 16 B
-constexpr int DP_BYTES = 2 * NPOOL * 4 * 16;          // [hi | lo][NPOOL][4 chunks]
-constexpr int ARG_BYTES = NPOOL * 4 * 8;              // [NPOOL][4 chunks] x 8 codes
-static_assert(3 * OT * OLD * 4 <= DP_BYTES + ARG_BYTES, "output tile must fit the raw pooled tile");
+constexpr int DP_BYTES = 2 * NPOOL_PAD * 4 * 16;      // [hi | lo][NPOOL_PAD][4 chunks]
+constexpr int ARG_BYTES = NPOOL_PAD * 4 * 8;          // [NPOOL_PAD][4 chunks] x 8 codes
+constexpr int W_BYTES = 2 * 16 * 64 * 16;             // the weight fragments of a channel half: [hi | lo][16 taps][64 lanes] x 16 B (32 KB)
+constexpr int RW_BYTES = W_BYTES;                     // one region: raw pooled tile, then the half's weights, at the end the output tile
+static_assert(DP_BYTES + ARG_BYTES <= RW_BYTES && 3 * OPL * 4 <= RW_BYTES, "raw pooled tile and output tile must fit the weight region");
+static_assert(2 * (DZ_BYTES + RW_BYTES) <= 160 * 1024, "two workgroups per CU");
 
 __device__ __forceinline__ uint32_t sp_pack2(float lo, float hi) {
   typedef __attribute__((ext_vector_type(2))) float f2;
@@ -47,9 +76,12 @@ __device__ __forceinline__ void pool_bwd_class_pair(uint4* sDz1, const uint4* sD
                                                     int qx0, int oh, int ow) {
   constexpr int NY = EY ? (HT + 1) / 2 : HT / 2, NX = EX ? (HT + 1) / 2 : HT / 2;
   constexpr int NYS = EY ? 2 : 1, NXS = EX ? 2 : 1;
-  for (int i = tid; i < 4 * NY * NX; i += 256) {
-    const int c = i / (NY * NX), j = i - c * (NY * NX);
-    const int iy = j / NX, ix = j - iy * NX;
+  // 32 lanes = 8 consecutive windows of the PTS-wide walk x 4 chunks, window in the low bits: a 16-lane group of a 16-byte read then
+  // holds four windows with distinct slot mod 4 per chunk, the 32 lanes of an 8-byte read eight consecutive windows
+  for (int i = tid; i < ((4 * NY * PTS + 31) & ~31); i += 256) {
+    const int c = (i >> 3) & 3, j = (i & 7) + ((i >> 5) << 3);
+    const int iy = j / PTS, ix = j - iy * PTS;
+    if (iy >= NY || ix >= NX) continue;
     const int hy = 2 * iy + (EY ? 0 : 1), hx = 2 * ix + (EX ? 0 : 1);
     const int py = a0 - 1 + hy, px = b0 - 1 + hx;           // stem-output coordinates
     float g[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -62,9 +94,9 @@ __device__ __forceinline__ void pool_bwd_class_pair(uint4* sDz1, const uint4* sD
         for (int ib = 0; ib < NXS; ++ib) {
           const int qx = (px >> 1) + ib;
           const uint32_t mine = (ky * 3 + (uint32_t)(px - (2 * qx - 1))) * 0x01010101u;
-          const int lp = (qy - qy0) * PT + (qx - qx0);      // out-of-grid windows hold code 15 / zeros
-          const uint2 cd = sArg[c * NPOOL + lp];            // chunk-major: the lanes of a wave walk consecutive windows
-          const uint4 dh = sDp[c * NPOOL + lp], dl = sDp[(4 + c) * NPOOL + lp];
+          const int lp = (qy - qy0) * PTS + (qx - qx0);     // out-of-grid windows hold code 15 / zeros
+          const uint2 cd = sArg[lp * 4 + c];
+          const uint4 dh = sDp[lp * 4 + c], dl = sDp[(NPOOL_PAD + lp) * 4 + c];
           const uint32_t cw[2] = {cd.x, cd.y};
           const uint32_t hw_[4] = {dh.x, dh.y, dh.z, dh.w}, lw_[4] = {dl.x, dl.y, dl.z, dl.w};
 #pragma unroll
@@ -103,11 +135,12 @@ __global__ __launch_bounds__(256, 2) void k_stem_bwd_pair(const uint4* __restric
                                                           const uint16_t* __restrict__ wt_l,    // lo
                                                           float* __restrict__ grad,             // [n][3][h][w]
                                                           int h, int w, Istd3p istd) {
-  __shared__ __attribute__((aligned(16))) uint8_t lds[DZ_BYTES + DP_BYTES + ARG_BYTES];
+  __shared__ __attribute__((aligned(16))) uint8_t lds[DZ_BYTES + RW_BYTES];
   uint4* sDz1 = reinterpret_cast<uint4*>(lds);                                     // [2][4][NPOS_PAD]
-  uint4* sDp = reinterpret_cast<uint4*>(lds + DZ_BYTES);                           // [2][4][NPOOL] (chunk-major)
-  uint2* sArg = reinterpret_cast<uint2*>(lds + DZ_BYTES + DP_BYTES);               // [4][NPOOL]
-  float* sOut = reinterpret_cast<float*>(lds + DZ_BYTES);                          // [3][OT][OLD] (aliases the raw tile)
+  uint4* sDp = reinterpret_cast<uint4*>(lds + DZ_BYTES);                           // [2][NPOOL_PAD][4] (window-major)
+  uint2* sArg = reinterpret_cast<uint2*>(lds + DZ_BYTES + DP_BYTES);               // [NPOOL_PAD][4]
+  uint4* sW = reinterpret_cast<uint4*>(lds + DZ_BYTES);                            // [2][16][64] (aliases the raw tile, dead by then)
+  float* sOut = reinterpret_cast<float*>(lds + DZ_BYTES);                          // [3][OPL] rows of OLD (aliases the weights, dead by then)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int oh = h >> 1, ow = w >> 1;            // stem-output grid
@@ -118,49 +151,81 @@ __global__ __launch_bounds__(256, 2) void k_stem_bwd_pair(const uint4* __restric
   f32x4 acc[4];
 #pragma unroll
   for (int m = 0; m < 4; ++m) acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const uint4* wrow_h = reinterpret_cast<const uint4*>(wt_h + (size_t)fr * 1024 + fg * 8);   // + tap * 8 + half * 4 (uint4 units)
-  const uint4* wrow_l = reinterpret_cast<const uint4*>(wt_l + (size_t)fr * 1024 + fg * 8);
+  // a wave's B fragment of a tap is 1 KiB of the table (row fr, 8 channels at fg * 8 of the tap's channel half): the workgroup fetches
+  // the 2 x 16 fragments of a half ONCE into LDS in fragment order (lane-contiguous: conflict free) instead of once per wave
+  const uint4* wsrc_h = reinterpret_cast<const uint4*>(wt_h + (size_t)fr * 1024 + fg * 8) + wave * 8;   // taps wave, wave + 4, ... (+ half * 4)
+  const uint4* wsrc_l = reinterpret_cast<const uint4*>(wt_l + (size_t)fr * 1024 + fg * 8) + wave * 8;
 
+  // the raw pooled tile of a channel half (121 windows x (8 gradient chunks + 2 code chunks) of 16 bytes): every load of a half is
+  // requested before the first is used, and the second half's before the matrix phase of the first -- a load per loop pass, waited for
+  // one after the other, left five exposed latencies per half
+  constexpr int SU = (NPOOL * 10 + 255) / 256;
+  uint4 sv[SU];
+  auto load_raw = [&](int half) {
+#pragma unroll
+    for (int u = 0; u < SU; ++u) {
+      const int i = u * 256 + tid;
+      const int pos = i / 10, v = i - pos * 10;
+      const int ry = pos / PT, rx = pos - ry * PT;
+      const int qy = qy0 + ry, qx = qx0 + rx;
+      const bool ok = i < NPOOL * 10 && (unsigned)qy < (unsigned)oh2 && (unsigned)qx < (unsigned)ow2;
+      const size_t base = ((size_t)img * oh2 + qy) * ow2 + qx;
+      sv[u] = v < 8 ? make_uint4(0, 0, 0, 0) : make_uint4(0x0F0F0F0Fu, 0x0F0F0F0Fu, 0x0F0F0F0Fu, 0x0F0F0F0Fu);
+      if (ok) sv[u] = v < 8 ? ((v >> 2) ? dpool_l : dpool_h)[base * 8 + half * 4 + (v & 3)] : arg[base * 4 + half * 2 + (v - 8)];
+    }
+  };
+  SP_ST(unsigned long long st[4] = {0, 0, 0, 0};)
+  SP_T(tb)
+  load_raw(0);
 #pragma unroll 1
   for (int half = 0; half < 2; ++half) {
-    // (no barrier here: the raw tile's readers passed the barrier below in the first half; the halo tile is rewritten only after the next one)
+    SP_T(t0)
     // ---- stage the pooled gradient pair and the argmax codes of this channel half (zeros / code 15 outside the grid)
-    for (int i = tid; i < NPOOL * 10; i += 256) {
+#pragma unroll
+    for (int u = 0; u < SU; ++u) {
+      const int i = u * 256 + tid;
+      if (i >= NPOOL * 10) continue;
       const int pos = i / 10, v = i - pos * 10;
-      const int qy = qy0 + pos / PT, qx = qx0 + pos % PT;
-      const bool ok = (unsigned)qy < (unsigned)oh2 && (unsigned)qx < (unsigned)ow2;
-      const size_t base = ((size_t)img * oh2 + qy) * ow2 + qx;
+      const int ry = pos / PT, lp = ry * PTS + (pos - ry * PT);
       if (v < 8) {
-        const int pl = v >> 2, c = v & 3;
-        uint4 val = make_uint4(0, 0, 0, 0);
-        if (ok) val = (pl ? dpool_l : dpool_h)[base * 8 + half * 4 + c];
-        sDp[(pl * 4 + c) * NPOOL + pos] = val;
+        sDp[((v >> 2) * NPOOL_PAD + lp) * 4 + (v & 3)] = sv[u];
       } else {
-        uint4 val = make_uint4(0x0F0F0F0Fu, 0x0F0F0F0Fu, 0x0F0F0F0Fu, 0x0F0F0F0Fu);
-        if (ok) val = arg[base * 4 + half * 2 + (v - 8)];
-        sArg[(2 * (v - 8)) * NPOOL + pos] = make_uint2(val.x, val.y);
-        sArg[(2 * (v - 8) + 1) * NPOOL + pos] = make_uint2(val.z, val.w);
+        sArg[lp * 4 + 2 * (v - 8)] = make_uint2(sv[u].x, sv[u].y);
+        sArg[lp * 4 + 2 * (v - 8) + 1] = make_uint2(sv[u].z, sv[u].w);
       }
     }
     __syncthreads();
+    SP_T(t1)
     // ---- max-pool backward into the halo tile, one pass per pixel-parity class
     pool_bwd_class_pair<0, 0>(sDz1, sDp, sArg, tid, a0, b0, qy0, qx0, oh, ow);
     pool_bwd_class_pair<0, 1>(sDz1, sDp, sArg, tid, a0, b0, qy0, qx0, oh, ow);
     pool_bwd_class_pair<1, 0>(sDz1, sDp, sArg, tid, a0, b0, qy0, qx0, oh, ow);
     pool_bwd_class_pair<1, 1>(sDz1, sDp, sArg, tid, a0, b0, qy0, qx0, oh, ow);
     __syncthreads();
+    SP_T(t2)
+    // ---- the weight fragments of this half into the region the raw tile just left: wave w brings taps w, w + 4, w + 8, w + 12
+    {
+      uint4 th[4], tl[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        th[k] = wsrc_h[k * 32 + half * 4];
+        tl[k] = wsrc_l[k * 32 + half * 4];
+      }
+      if (half == 0) load_raw(1);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        sW[(wave + 4 * k) * 64 + lane] = th[k];
+        sW[(16 + wave + 4 * k) * 64 + lane] = tl[k];
+      }
+    }
+    __syncthreads();
     // ---- implicit GEMM over the 16 taps of this channel half: wave w owns tile rows 4w..4w+3 (one 16-position M tile each)
 #pragma unroll
     for (int dpi = 0; dpi < 4; ++dpi) {
-      uint4 bh[4], bl[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        bh[t] = wrow_h[(dpi * 4 + t) * 8 + half * 4];
-        bl[t] = wrow_l[(dpi * 4 + t) * 8 + half * 4];
-      }
 #pragma unroll
       for (int dqi = 0; dqi < 4; ++dqi) {
-        const bf16x8 wh = __builtin_bit_cast(bf16x8, bh[dqi]), wl = __builtin_bit_cast(bf16x8, bl[dqi]);
+        const bf16x8 wh = __builtin_bit_cast(bf16x8, sW[(dpi * 4 + dqi) * 64 + lane]);
+        const bf16x8 wl = __builtin_bit_cast(bf16x8, sW[(16 + dpi * 4 + dqi) * 64 + lane]);
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
           const int pos = (wave * 4 + m + dpi) * HT + fr + dqi;
@@ -172,10 +237,14 @@ __global__ __launch_bounds__(256, 2) void k_stem_bwd_pair(const uint4* __restric
         }
       }
     }
+    __syncthreads();                     // the weights are dead: the next half's raw tile, or the output tile, takes their place
+    SP_T(t3)
+    SP_ST(st[0] += t1 - t0; st[1] += t2 - t1; st[2] += t3 - t2;)
   }
 
   // ---- epilogue: D[row = fg*4 + j (position column)][col = fr = (py*2+px)*3 + c] -> sOut[c][2a+py][2b+px]
-  //      (the raw pooled tile is dead: every wave passed the barrier after its last read of it)
+  //      (the weights are dead: every wave passed the barrier after its last read of them)
+  SP_T(t4)
   if (fr < 12) {
     const int pq = fr / 3, c = fr - pq * 3;
     const int py = pq >> 1, px = pq & 1;
@@ -183,7 +252,7 @@ __global__ __launch_bounds__(256, 2) void k_stem_bwd_pair(const uint4* __restric
     for (int m = 0; m < 4; ++m)
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        sOut[(c * OT + 2 * (wave * 4 + m) + py) * OLD + 2 * (fg * 4 + j) + px] = acc[m][j];
+        sOut[c * OPL + (2 * (wave * 4 + m) + py) * OLD + 2 * (fg * 4 + j) + px] = acc[m][j];
   }
   __syncthreads();
   const size_t plane = (size_t)h * w;
@@ -193,11 +262,18 @@ __global__ __launch_bounds__(256, 2) void k_stem_bwd_pair(const uint4* __restric
     const int gy = 2 * a0 + y, gx = 2 * b0 + x4 * 4;
     if (gy < h && gx < w) {
       const float s = istd.v[c];
-      const float* r = sOut + (c * OT + y) * OLD + x4 * 4;
+      const float* r = sOut + c * OPL + y * OLD + x4 * 4;
       *reinterpret_cast<float4*>(grad + ((size_t)img * 3 + c) * plane + (size_t)gy * w + gx) =
           make_float4(r[0] * s, r[1] * s, r[2] * s, r[3] * s);
     }
   }
+  SP_T(t6)
+  SP_ST(if (lane == 0) {
+    for (int k = 0; k < 3; ++k) atomicAdd(&g_sp_stamps[0][k], st[k]);
+    atomicAdd(&g_sp_stamps[0][3], t6 - t4);
+    atomicAdd(&g_sp_stamps[0][4], t6 - tb);
+    atomicAdd(&g_sp_stamps[0][5], 1ull);
+  })
 }
 }  // namespace
 
@@ -224,7 +300,8 @@ extern "C" int rart_engine_stem_bwd_fused_pair(const void* dpool_hi, const void*
 // padded hi / lo image and the 112 x 112 x 64 stem-output pair (2 x 411 MB per 256 images): 0.77 ms of a 10.1 ms forward.
 //
 // Same structure as k_stem_fwd_fused (csrc/stem_fused.hip): a workgroup loops over 8 x 8 tiles of POOLED positions; the 39 x 39 input
-// patch behind the 17 x 17 stem outputs the tile's windows touch is staged in LDS as two [39][40 px][4 ch] bf16 planes; the convolution
+// patch behind the 17 x 17 stem outputs the tile's windows touch is staged in LDS as two planes of 39 rows of [40 px][4 ch] bf16 (rows in
+// pairs of 784 bytes, see SP_PW); the convolution
 // is the row-tap implicit GEMM (a tap = one filter row of 8 px x 4 ch) read straight from the patch, operands swapped so a lane owns 4
 // consecutive channels of one position.  What the pair changes: both weight planes are LDS resident (2 x 29.7 KB), and the stem-output
 // tile is kept as fp32 -- the value hi + lo of the pair the unfused chain would have written, so the pool's comparisons, argmax codes and
@@ -236,13 +313,24 @@ constexpr int SP_PT = 8;                        // pooled tile side
 constexpr int SP_R = 2 * SP_PT + 1;             // stem-output region side (17)
 constexpr int SP_NPOS = SP_R * SP_R;            // 289
 constexpr int SP_PH = 2 * (SP_R - 1) + 7;       // patch rows (39)
-constexpr int SP_PW = 40;                       // patch row stride in pixels
-constexpr int SP_PLANE = SP_PH * SP_PW * 8;     // bytes per hi / lo plane (12 480)
+constexpr int SP_SW = 40;                       // pixels staged per patch row (39 + the zero column the 8th pixel of the last tap reads)
+constexpr int SP_PW = 49;                       // stride of a PAIR of patch rows in 16-byte slots: = 1 mod 16, so going from the 17th position
+                                                // of a row to the 1st of the next (two patch rows down) continues the bank sequence and an A
+                                                // fragment read is conflict free.  A single-row stride of 49 pixels would put the odd row
+                                                // taps 8 bytes off the 16-byte alignment of the fragment reads (ds_read_b128), so the odd row of a pair
+                                                // sits SP_ODD bytes into it instead
+constexpr int SP_ODD = 400;                     // byte offset of the odd patch row in its pair (>= SP_SW * 8, a multiple of 16)
+constexpr int SP_PLANE = (SP_PH + 1) / 2 * SP_PW * 16;     // bytes per hi / lo plane (15 680)
+// (SP_PW, SP_ODD, SP_R and the fragment addresses are mirrored in tests/test_stem_pair_bank_model.py)
+__device__ __forceinline__ constexpr int sp_row_off(int row) { return (row >> 1) * (SP_PW * 16) + (row & 1) * SP_ODD; }
+static_assert(SP_ODD % 16 == 0 && SP_ODD >= SP_SW * 8 && SP_PW * 16 - SP_ODD >= SP_SW * 8, "both rows of a pair fit its stride");
 constexpr int SP_WROW = 464;                    // weight row stride in LDS (224 k x 2 B + 16 pad: conflict-free b128 reads)
 constexpr int SP_YROW = 272;                    // stem-output tile row stride: 64 fp32 + 16 B pad
 constexpr int SP_W_BYTES = 64 * SP_WROW;        // 29 696 per plane
 constexpr int SP_T_BYTES = SP_NPOS * SP_YROW;   // 78 608 (>= 2 * SP_PLANE: the tile aliases the patch)
-constexpr int SP_NT = 3;                        // 32-position M tiles per wave row (4 wave rows x 3 >= 10 tiles)
+constexpr int SP_NT = 3;                        // 32-position M tiles of wave rows 0 and 1; wave rows 2 and 3 take 2: 10 tiles cover the 289
+                                                // positions, and every SIMD holds one wave of each kind (waves w and w + 4)
+constexpr int SP_U = (SP_PH * SP_SW + 511) / 512;   // patch pixels a thread stages per tile (4)
 static_assert(SP_T_BYTES >= 2 * SP_PLANE, "the stem-output tile must cover the patch it aliases");
 
 struct StemNormP { float mean[3], istd[3]; };
@@ -270,91 +358,114 @@ __global__ __launch_bounds__(512, 1) void k_stem_fwd_pair(const void* __restrict
     *reinterpret_cast<uint4*>(sW + pl * SP_W_BYTES + row * SP_WROW + ch * 16) =
         *reinterpret_cast<const uint4*>((pl ? w_l : w_h) + (size_t)row * 224 + ch * 8);
   }
+  const int mt0 = wm < 2 ? wm * SP_NT : 2 * SP_NT + (wm - 2) * (SP_NT - 1);     // first M tile of this wave row: 0, 3, 6, 8
+  const int n_mt = wm < 2 ? SP_NT : SP_NT - 1;
   uint32_t a_off[SP_NT];
 #pragma unroll
   for (int i = 0; i < SP_NT; ++i) {
-    int p = (wm * SP_NT + i) * 32 + (lane & 31);
+    int p = (mt0 + i) * 32 + (lane & 31);
     p = p < SP_NPOS ? p : SP_NPOS - 1;          // rows past the region recompute the last position; never stored
     const int py = p / SP_R, px = p - py * SP_R;
-    a_off[i] = (uint32_t)(((2 * py) * SP_PW + 2 * px) * 8 + kq * 16);
+    a_off[i] = (uint32_t)(py * (SP_PW * 16) + 2 * px * 8 + kq * 16);
   }
   const uint32_t w_off = (uint32_t)((wn * 32 + (lane & 31)) * SP_WROW + kq * 16);
   float bz[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) bz[r] = bias ? bias[wn * 32 + (r & 3) + 8 * (r >> 2) + 4 * kq] : 0.f;
 
+  // the source values of a tile's patch (4 pixels x 3 values per thread).  The fp32 instance requests them one tile ahead: the loads of
+  // tile t + gridDim.x are issued before the matrix phase of tile t and held in registers until the loop top normalises, splits and
+  // writes them.  The uint8 instance loads at the loop top: with its byte loads beside the MFMAs it measured slower ("Stem
+  // pair kernels", has the figures)
+  constexpr bool PREFETCH = !SRC_U8 || RART_STEM_U8_PREFETCH;
+  float v01[SP_U][3];
+  bool ok[SP_U];
+  auto load_patch = [&](int t) {
+    const int img = t / (tiles_y * tiles_x);
+    const int tr = t - img * (tiles_y * tiles_x);
+    const int in_y0 = 4 * ((tr / tiles_x) * SP_PT) - 5, in_x0 = 4 * ((tr % tiles_x) * SP_PT) - 5;      // input pixel of patch (0, 0)
+#pragma unroll
+    for (int u = 0; u < SP_U; ++u) {
+      const int i = u * 512 + tid;
+      const int pr = i / SP_SW, pc = i - pr * SP_SW;
+      const int y = in_y0 + pr, x = in_x0 + pc;
+      ok[u] = t < n_tiles && i < SP_PH * SP_SW && (unsigned)y < (unsigned)h && (unsigned)x < (unsigned)w && pc < SP_PH;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        v01[u][c] = 0.f;
+        if (ok[u]) {
+          if (SRC_U8) v01[u][c] = (float)((const uint8_t*)src)[(((size_t)img * h + y) * w + x) * 3 + c];
+          else v01[u][c] = ((const float*)src)[(((size_t)img * 3 + c) * h + y) * w + x];
+        }
+      }
+    }
+  };
+  if (PREFETCH) load_patch(blockIdx.x);
+
+  SP_ST(unsigned long long fs[6] = {0, 0, 0, 0, 0, 0};)
+  SP_T(tf0)
   for (int t = blockIdx.x; t < n_tiles; t += gridDim.x) {
     const int img = t / (tiles_y * tiles_x);
     const int tr = t - img * (tiles_y * tiles_x);
     const int q0y = (tr / tiles_x) * SP_PT, q0x = (tr % tiles_x) * SP_PT;
-    const int in_y0 = 4 * q0y - 5, in_x0 = 4 * q0x - 5;          // input pixel of patch (0, 0)
+    if (!PREFETCH) load_patch(t);
+    SP_T(t0)
     __syncthreads();                                               // previous tile's pool is done with the LDS tile
     // ---- stage the patch: (x - mean) / std as hi + lo bf16, zeros outside the image and in the 4th channel
-    {
-      constexpr int U = (SP_PH * SP_PW + 511) / 512;               // 4
-      float v01[U][3];
-      bool ok[U];
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int i = u * 512 + tid;
-        const int pr = i / SP_PW, pc = i - pr * SP_PW;
-        const int y = in_y0 + pr, x = in_x0 + pc;
-        ok[u] = i < SP_PH * SP_PW && (unsigned)y < (unsigned)h && (unsigned)x < (unsigned)w && pc < SP_PH;
+    for (int u = 0; u < SP_U; ++u) {
+      const int i = u * 512 + tid;
+      if (i >= SP_PH * SP_SW) continue;
+      const int pr = i / SP_SW, po = sp_row_off(pr) + (i - pr * SP_SW) * 8;
+      uint32_t hv[3] = {0, 0, 0}, lv[3] = {0, 0, 0};
+      if (ok[u]) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-          v01[u][c] = 0.f;
-          if (ok[u]) {
-            if (SRC_U8) v01[u][c] = (float)((const uint8_t*)src)[(((size_t)img * h + y) * w + x) * 3 + c];
-            else v01[u][c] = ((const float*)src)[(((size_t)img * 3 + c) * h + y) * w + x];
-          }
+          const float x01 = SRC_U8 ? v01[u][c] * (1.0f / 255.0f) : v01[u][c];
+          const float v = (x01 - nm.mean[c]) * nm.istd[c];
+          hv[c] = sp_pack2(v, 0.f) & 0xFFFFu;
+          lv[c] = sp_pack2(v - __uint_as_float(hv[c] << 16), 0.f) & 0xFFFFu;
         }
       }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int i = u * 512 + tid;
-        if (i >= SP_PH * SP_PW) continue;
-        uint32_t hv[3] = {0, 0, 0}, lv[3] = {0, 0, 0};
-        if (ok[u]) {
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            const float x01 = SRC_U8 ? v01[u][c] * (1.0f / 255.0f) : v01[u][c];
-            const float v = (x01 - nm.mean[c]) * nm.istd[c];
-            hv[c] = sp_pack2(v, 0.f) & 0xFFFFu;
-            lv[c] = sp_pack2(v - __uint_as_float(hv[c] << 16), 0.f) & 0xFFFFu;
-          }
-        }
-        *reinterpret_cast<uint2*>(sP + i * 8) = make_uint2(hv[0] | (hv[1] << 16), hv[2]);
-        *reinterpret_cast<uint2*>(sP + SP_PLANE + i * 8) = make_uint2(lv[0] | (lv[1] << 16), lv[2]);
-      }
+      *reinterpret_cast<uint2*>(sP + po) = make_uint2(hv[0] | (hv[1] << 16), hv[2]);
+      *reinterpret_cast<uint2*>(sP + SP_PLANE + po) = make_uint2(lv[0] | (lv[1] << 16), lv[2]);
     }
     __syncthreads();
+    SP_T(t1)
+    if (PREFETCH) load_patch(t + gridDim.x);                       // the next tile's source (nothing past the last tile)
     // ---- implicit GEMM: 7 row taps x 2 k-steps x 3 products, D^T accumulators (register -> channel, lane -> position)
     f32x16 acc[SP_NT];
 #pragma unroll
     for (int i = 0; i < SP_NT; ++i)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][r] = bz[r];
+    auto row_taps = [&](auto nt) {                                 // (the tile count is a compile-time constant of each instance)
 #pragma unroll
-    for (int r = 0; r < 7; ++r)
+      for (int r = 0; r < 7; ++r)
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 wh = *reinterpret_cast<const bf16x8*>(sW + w_off + r * 64 + ks * 32);
-        const bf16x8 wl = *reinterpret_cast<const bf16x8*>(sW + SP_W_BYTES + w_off + r * 64 + ks * 32);
+        for (int ks = 0; ks < 2; ++ks) {
+          const bf16x8 wh = *reinterpret_cast<const bf16x8*>(sW + w_off + r * 64 + ks * 32);
+          const bf16x8 wl = *reinterpret_cast<const bf16x8*>(sW + SP_W_BYTES + w_off + r * 64 + ks * 32);
 #pragma unroll
-        for (int i = 0; i < SP_NT; ++i) {
-          const bf16x8 ah = *reinterpret_cast<const bf16x8*>(sP + a_off[i] + r * (SP_PW * 8) + ks * 32);
-          const bf16x8 al = *reinterpret_cast<const bf16x8*>(sP + a_off[i] + SP_PLANE + r * (SP_PW * 8) + ks * 32);
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, al, acc[i], 0, 0, 0);
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, ah, acc[i], 0, 0, 0);
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, ah, acc[i], 0, 0, 0);
+          for (int i = 0; i < decltype(nt)::value; ++i) {
+            const bf16x8 ah = *reinterpret_cast<const bf16x8*>(sP + a_off[i] + sp_row_off(r) + ks * 32);
+            const bf16x8 al = *reinterpret_cast<const bf16x8*>(sP + a_off[i] + SP_PLANE + sp_row_off(r) + ks * 32);
+            acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, al, acc[i], 0, 0, 0);
+            acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, ah, acc[i], 0, 0, 0);
+            acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, ah, acc[i], 0, 0, 0);
+          }
         }
-      }
+    };
+    if (wm < 2) row_taps(std::integral_constant<int, SP_NT>());
+    else row_taps(std::integral_constant<int, SP_NT - 1>());
+    SP_T(t2)
     __syncthreads();                                               // every wave is done reading the patch
+    SP_T(t3)
     // ---- ReLU, the value of the hi + lo pair (what the unfused chain stores), into the LDS tile [position][64 ch] fp32
 #pragma unroll
     for (int i = 0; i < SP_NT; ++i) {
-      const int p = (wm * SP_NT + i) * 32 + (lane & 31);
-      if (p < SP_NPOS) {
+      const int p = (mt0 + i) * 32 + (lane & 31);
+      if (i < n_mt && p < SP_NPOS) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           float v[4];
@@ -370,6 +481,7 @@ __global__ __launch_bounds__(512, 1) void k_stem_fwd_pair(const void* __restrict
       }
     }
     __syncthreads();
+    SP_T(t4)
     // ---- 3x3/2 max pool (pad 1) of the pair values: first maximum in scan order, code 15 when the maximum is <= 0
     {
       const int c = tid & 7, q = tid >> 3;          // 64 pooled positions x 8 channel groups = 512 threads
@@ -413,7 +525,15 @@ __global__ __launch_bounds__(512, 1) void k_stem_fwd_pair(const void* __restrict
                                      code[4] | (code[5] << 8) | (code[6] << 16) | (code[7] << 24));
       }
     }
+    SP_T(t5)
+    SP_ST(fs[0] += t1 - t0; fs[1] += t2 - t1; fs[2] += t3 - t2; fs[3] += t4 - t3; fs[4] += t5 - t4; fs[5] += 1;)
   }
+  SP_T(tf1)
+  SP_ST(if (lane == 0) {
+    for (int k = 0; k < 6; ++k) atomicAdd(&g_sp_stamps[1][k], fs[k]);
+    atomicAdd(&g_sp_stamps[1][6], tf1 - tf0);
+    atomicAdd(&g_sp_stamps[1][7], 1ull);
+  })
 }
 #pragma clang fp contract(fast)
 }  // namespace
@@ -439,3 +559,14 @@ extern "C" int rart_engine_stem_fwd_fused_pair(const void* src, int src_is_u8, c
   RART_CHECK_LAUNCH("rart_engine_stem_fwd_fused_pair");
   return RART_OK;
 }
+
+#ifdef RART_STEM_STAMPS
+extern "C" int rart_debug_stem_stamps(unsigned long long* out16, int reset) {
+  if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_sp_stamps), sizeof(unsigned long long) * 16) != hipSuccess) return 1;
+  if (reset) {
+    unsigned long long z[16] = {0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_sp_stamps), z, sizeof(z)) != hipSuccess) return 1;
+  }
+  return 0;
+}
+#endif
