@@ -29,8 +29,7 @@ import ctypes
 from .. import _lib
 from .convstem_engine import ConvStem
 from .convstem_torch import convstem_of
-from .engine_base import (F_GELU, F_GELU_BWD, F_GELU_KEEP, F_OUT_F32, RowEngine, conv_desc, gemm_pair_desc, k32, lo_off, pad_k, pad_rows,
-                          pair, rows_mult)
+from .engine_base import F_GELU, F_GELU_BWD, F_GELU_KEEP, F_OUT_F32, RowEngine, act, k32, pad_k
 
 STEM_K = 64                      # 3 x 4 x 4 = 48 columns, padded to the K granularity of both GEMMs
 DS_TAPS = [(0, 0), (0, 1), (1, 0), (1, 1)]
@@ -49,36 +48,17 @@ class ConvNeXtEngine(RowEngine):
         b2' = gamma * b2 (one fp32 product per element).  The bf16 engine then rounds gamma * W2 to bf16 once, where the module
         multiplies the fp32 fc2 output by gamma; the reference-precision engine splits gamma * W2 into hi + lo, so it represents the
         fp32 product to 16 significand bits like every other weight -- no rounding beyond what the pair format already carries."""
-        torch = _lib.require_gpu()
-        dev = self.device
-        m = model
+        m, f32, tab = model, self._f32, self._table
         self.depths, self.dims = tuple(m.depths), tuple(m.dims)
         self.grn = bool(getattr(m, 'use_grn', False))          # ConvNeXt-V2: GRN after the GELU, no layer scale
         fold = self.fold_layer_scale and not self.grn
-
-        def f32(t):
-            return t.detach().to(dev, torch.float32).contiguous()
-
-        if self.x3:
-            def tab(w32):                  # pair planes [2][rows padded to 256][K]
-                return pair(pad_rows(f32(w32), 256))
-            fwd = bwd = tab
-        else:
-            def fwd(w32):                  # bf16 [rows padded to 128 / 64][K]
-                w = f32(w32).to(torch.bfloat16)
-                return pad_rows(w, rows_mult(w.shape[0]))
-            bwd = fwd
         c0 = self.dims[0]
         cvst = convstem_of(m)
         self.cvst = ConvStem(self, cvst) if cvst is not None else None                   # `convnext_base_cvst`: the stem is its chain
         if self.cvst is None:
             sw = pad_k(f32(m.stem[0].weight).reshape(c0, 48), STEM_K)                   # [c0][c*16 + r*4 + s], zero columns 48..63
-            if self.x3:
-                self.stem_w = fwd(sw)
-            else:
-                swb = sw.to(torch.bfloat16)
-                self.stem_w = pad_rows(torch.cat([swb, swb], 1), 128)                   # hi | lo taps of the image pair
-            self.stem_wd = bwd(sw.t())                                                   # [64][c0]
+            self.stem_w = self._input_table(sw, 128)                                    # bf16: [hi | hi] taps of the image pair
+            self.stem_wd = tab(sw, transpose=True)                                      # [64][c0]
             self.stem_b = f32(m.stem[0].bias)
             self.stem_g, self.stem_nb = f32(m.stem[1].weight), f32(m.stem[1].bias)
         self.stages = []
@@ -89,8 +69,8 @@ class ConvNeXtEngine(RowEngine):
                 w = f32(conv.weight)                                                     # [cout][cin][2][2]
                 cout, cin = w.shape[0], w.shape[1]
                 S.update(ds_g=f32(ln.weight), ds_nb=f32(ln.bias), ds_bias=f32(conv.bias),
-                         ds_w=fwd(w.permute(0, 2, 3, 1).reshape(cout, 4 * cin)),         # k = (ty * 2 + tx) * cin + c
-                         ds_wd=[bwd(w[:, :, py, px].t()) for py, px in DS_TAPS])         # per input parity: [cin][cout]
+                         ds_w=tab(w.permute(0, 2, 3, 1).reshape(cout, 4 * cin)),         # k = (ty * 2 + tx) * cin + c
+                         ds_wd=[tab(w[:, :, py, px], transpose=True) for py, px in DS_TAPS])   # per input parity: [cin][cout]
             for blk in st.blocks:
                 c = blk.conv_dw.weight.shape[0]
                 g = f32(blk.gamma) if fold else None
@@ -99,78 +79,38 @@ class ConvNeXtEngine(RowEngine):
                 S['blocks'].append(dict(
                     dw_w=f32(blk.conv_dw.weight).reshape(c, 49).t().contiguous(), dw_b=f32(blk.conv_dw.bias),
                     ng=f32(blk.norm.weight), nb=f32(blk.norm.bias),
-                    fc1_w=fwd(w1), fc1_b=f32(blk.mlp.fc1.bias), fc1_wd=bwd(w1.t()),
-                    fc2_w=fwd(w2), fc2_b=(g * f32(blk.mlp.fc2.bias)).contiguous() if fold else f32(blk.mlp.fc2.bias),
-                    fc2_wd=bwd(w2.t())))
+                    fc1_w=tab(w1), fc1_b=f32(blk.mlp.fc1.bias), fc1_wd=tab(w1, transpose=True),
+                    fc2_w=tab(w2), fc2_b=(g * f32(blk.mlp.fc2.bias)).contiguous() if fold else f32(blk.mlp.fc2.bias),
+                    fc2_wd=tab(w2, transpose=True)))
                 if self.grn:
                     S['blocks'][-1].update(grn_w=f32(blk.mlp.grn.weight), grn_b=f32(blk.mlp.grn.bias))
             self.stages.append(S)
         self.head_g, self.head_nb = f32(m.head.norm.weight), f32(m.head.norm.bias)
         self.n_classes = m.head.fc.out_features
         self.head_kpad = k32(self.n_classes)
-        hw = f32(m.head.fc.weight)
-        self.head_w = fwd(hw)
-        self.head_wd = bwd(pad_k(hw.t(), self.head_kpad))
+        self.head_w = tab(m.head.fc.weight)
+        self.head_wd = tab(m.head.fc.weight, self.head_kpad, transpose=True)
         self.head_b = f32(m.head.fc.bias)
 
     # ------------------------------------------------------------------ ConvNeXt's own precision-generic launches
-    def _conv(self, src, w, dst, B, grid, src_hw, k_per_tap, taps, n_cols, dst_hw, stride, dst_stride, dst_off, bias=None):
-        """implicit-GEMM convolution on NHWC src (k_per_tap channels per pixel) -> dst (n_cols channels per pixel)"""
-        if self.x3:
-            self._launch_pair(gemm_pair_desc(src, w, dst, n_cols, k_per_tap, k_per_tap * len(taps), n_cols, w.shape[1], bias=bias, batch=B,
-                                             grid=grid, src_hw=src_hw, stride=stride, k_per_tap=k_per_tap, taps=taps, dst_hw=dst_hw,
-                                             dst_stride=dst_stride, dst_org=dst_off))
-        else:
-            self._launch_conv(conv_desc(src, w, dst, B, grid, src_hw, k_per_tap, k_per_tap, taps, n_cols, dst_hw, n_cols, bias=bias,
-                                        stride=stride, dst_stride=dst_stride, dst_org=dst_off))
-
     def _dwconv_ln(self, x, L, out, y, B, H, W, C):
-        lib, sp = self.lib, _lib.stream_ptr()
-        if self.x3:
-            (xh, xl), (oh, ol) = self._hl(x), self._hl(out)
-            yh, yl = self._hl(y) if y is not None else (None, None)
-            _lib.check(lib.rart_cnx_dwconv_ln_pair(xh, xl, _lib.ptr(L['dw_w']), _lib.ptr(L['dw_b']), _lib.ptr(L['ng']), _lib.ptr(L['nb']),
-                                                   oh, ol, yh, yl, B, H, W, C, 1e-6, sp))
-        else:
-            _lib.check(lib.rart_cnx_dwconv_ln_bf16(_lib.ptr(x), _lib.ptr(L['dw_w']), _lib.ptr(L['dw_b']), _lib.ptr(L['ng']),
-                                                   _lib.ptr(L['nb']), _lib.ptr(out), _lib.ptr(y), B, H, W, C, 1e-6, sp))
+        self._rows('cnx_dwconv_ln', act(x), L['dw_w'], L['dw_b'], L['ng'], L['nb'], act(out), act(y), B, H, W, C, 1e-6)
 
     def _dwconv_bwd(self, dz, L, res, dx, B, H, W, C):
-        lib, sp = self.lib, _lib.stream_ptr()
-        if self.x3:
-            (zh, zl), (oh, ol) = self._hl(dz), self._hl(dx)
-            rh, rl = self._hl(res) if res is not None else (None, None)
-            _lib.check(lib.rart_cnx_dwconv_bwd_pair(zh, zl, _lib.ptr(L['dw_w']), rh, rl, oh, ol, B, H, W, C, sp))
-        else:
-            _lib.check(lib.rart_cnx_dwconv_bwd_bf16(_lib.ptr(dz), _lib.ptr(L['dw_w']), _lib.ptr(res), _lib.ptr(dx), B, H, W, C, sp))
+        self._rows('cnx_dwconv_bwd', act(dz), L['dw_w'], act(res), act(dx), B, H, W, C)
 
     def _grn(self, y, L, G, z, B, P, C):
         """ConvNeXt-V2: G = the per-image channel norms of the GELU output y [B][P][C], then z = GRN(y) (z may be y)"""
-        lib, sp = self.lib, _lib.stream_ptr()
-        if self.x3:
-            (yh, yl), (zh, zl) = self._hl(y), self._hl(z)
-            _lib.check(lib.rart_cnx_grn_stats_pair(yh, yl, _lib.ptr(G), B, P, C, sp))
-            _lib.check(lib.rart_cnx_grn_apply_pair(yh, yl, _lib.ptr(G), _lib.ptr(L['grn_w']), _lib.ptr(L['grn_b']), zh, zl, B, P, C, 1e-6, sp))
-        else:
-            _lib.check(lib.rart_cnx_grn_stats_bf16(_lib.ptr(y), _lib.ptr(G), B, P, C, sp))
-            _lib.check(lib.rart_cnx_grn_apply_bf16(_lib.ptr(y), _lib.ptr(G), _lib.ptr(L['grn_w']), _lib.ptr(L['grn_b']), _lib.ptr(z), B, P, C,
-                                                   1e-6, sp))
+        self._rows('cnx_grn_stats', act(y), G, B, P, C)
+        self._rows('cnx_grn_apply', act(y), G, L['grn_w'], L['grn_b'], act(z), B, P, C, 1e-6)
 
     def _grn_bwd(self, g, y, u, G, L, B, P, C):
         """ConvNeXt-V2: g = the gradient of the GRN output -> in place, the gradient of fc1's pre-activation u (GRN backward times
         GELU'(u)); y and G are the forward's GELU output and channel norms"""
         torch = _lib.require_gpu()
-        lib, sp = self.lib, _lib.stream_ptr()
         a = self._get('g_grn_a', (B, C), torch.float32)
-        if self.x3:
-            (gh, gl), (yh, yl), (uh, ul) = self._hl(g), self._hl(y), self._hl(u)
-            _lib.check(lib.rart_cnx_grn_bwd_reduce_pair(gh, gl, yh, yl, _lib.ptr(L['grn_w']), _lib.ptr(a), B, P, C, sp))
-            _lib.check(lib.rart_cnx_grn_bwd_apply_pair(gh, gl, yh, yl, uh, ul, _lib.ptr(G), _lib.ptr(a), _lib.ptr(L['grn_w']), gh, gl, B, P, C,
-                                                       1e-6, sp))
-        else:
-            _lib.check(lib.rart_cnx_grn_bwd_reduce_bf16(_lib.ptr(g), _lib.ptr(y), _lib.ptr(L['grn_w']), _lib.ptr(a), B, P, C, sp))
-            _lib.check(lib.rart_cnx_grn_bwd_apply_bf16(_lib.ptr(g), _lib.ptr(y), _lib.ptr(u), _lib.ptr(G), _lib.ptr(a), _lib.ptr(L['grn_w']),
-                                                       _lib.ptr(g), B, P, C, 1e-6, sp))
+        self._rows('cnx_grn_bwd_reduce', act(g), act(y), L['grn_w'], a, B, P, C)
+        self._rows('cnx_grn_bwd_apply', act(g), act(y), act(u), G, a, L['grn_w'], act(g), B, P, C, 1e-6)
 
     def _downsample(self, x, S, out, B, H, W):
         """LayerNorm of the H x W stage output x, then the 2x2 stride-2 conv into out (H/2 x W/2)"""
@@ -178,7 +118,7 @@ class ConvNeXtEngine(RowEngine):
         cin, cout = self.dims[si - 1], self.dims[si]
         ln = self._act('ds_ln%d' % si, (B * H * W, cin))
         self._ln(x, S['ds_g'], S['ds_nb'], ln, B * H * W, cin)
-        self._conv(ln, S['ds_w'], out, B, (H // 2, W // 2), (H, W), cin, DS_TAPS, cout, (H // 2, W // 2), (2, 2), (1, 1), (0, 0),
+        self._conv(ln, S['ds_w'], out, B, (H // 2, W // 2), (H, W), cin, DS_TAPS, cout, (H // 2, W // 2), cout, (2, 2), (1, 1), (0, 0),
                    bias=S['ds_bias'])
 
     def _downsample_scatter(self, g, S, out, B, H, W):
@@ -187,16 +127,14 @@ class ConvNeXtEngine(RowEngine):
         si = S['index']
         cin, cout = self.dims[si - 1], self.dims[si]
         for p, (py, px) in enumerate(DS_TAPS):
-            self._conv(g, S['ds_wd'][p], out, B, (H // 2, W // 2), (H // 2, W // 2), cout, [(0, 0)], cin, (H, W), (1, 1), (2, 2), (py, px))
+            self._conv(g, S['ds_wd'][p], out, B, (H // 2, W // 2), (H // 2, W // 2), cout, [(0, 0)], cin, (H, W), cin, (1, 1), (2, 2),
+                       (py, px))
 
     # ------------------------------------------------------------------ forward
     def _forward(self, src, src_is_u8, mean, std, keep=False):
         torch = _lib.require_gpu()
         lib, sp = self.lib, _lib.stream_ptr()
-        if src_is_u8:
-            B, Himg, Wimg = src.shape[0], src.shape[1], src.shape[2]
-        else:
-            B, Himg, Wimg = src.shape[0], src.shape[2], src.shape[3]
+        B, Himg, Wimg = self._image_dims(src, src_is_u8)
         if Himg % 32 or Wimg % 32:
             raise ValueError('ConvNeXt needs image sides that are multiples of 32 (got %dx%d)' % (Himg, Wimg))
         H, W = Himg // 4, Wimg // 4
@@ -211,11 +149,7 @@ class ConvNeXtEngine(RowEngine):
             _lib.check(lib.rart_cnx_patchify(_lib.ptr(src), 1 if src_is_u8 else 0, _lib.ptr(patches[0]), _lib.ptr(patches[1]), B, Himg, Wimg,
                                              4, STEM_K, meanf, stdf, sp))
             xs = self._act('stem', (B * H * W, c0))
-            if self.x3:
-                self._gemm_pair(patches, self.stem_w, xs, B * H * W, c0, STEM_K, STEM_K, c0, bias=self.stem_b)
-            else:
-                self._gemm(patches[0], self.stem_w, xs, B * H * W, STEM_K, c0, STEM_K, c0, bias=self.stem_b, n_taps=2,
-                           tap_src_off=[0, lo_off(patches)])
+            self._input_gemm(patches, self.stem_w, xs, B * H * W, c0, STEM_K, bias=self.stem_b)
             self._ln(xs, self.stem_g, self.stem_nb, x, B * H * W, c0)
         saved, stage_out = [], []
         for si, S in enumerate(self.stages):
@@ -257,43 +191,27 @@ class ConvNeXtEngine(RowEngine):
                 self._mm(hid, L['fc2_w'], x, rows, C, 4 * C, bias=L['fc2_b'], res=x)       # in place: x + gamma * fc2(...)
         cl = self.dims[-1]
         pooled = self._act('pooled', (B, cl))
-        if self.x3:
-            _lib.check(lib.rart_engine_avgpool_pair(_lib.ptr(x[0]), x[0].numel(), _lib.ptr(pooled[0]), pooled[0].numel(), B, H * W, cl, sp))
-        else:
-            _lib.check(lib.rart_engine_avgpool(_lib.ptr(x), _lib.ptr(pooled), B, H * W, cl, sp))
+        self._avgpool(x, pooled, B, H * W, cl)
         pl = self._act('pooled_ln', (B, cl))
         self._ln(pooled, self.head_g, self.head_nb, pl, B, cl)
-        logits = torch.empty(B, self.n_classes, dtype=torch.float32, device=self.device)
-        self._mm(pl, self.head_w, logits, B, self.n_classes, cl, bias=self.head_b, flags=F_OUT_F32)
         if keep:
             self._saved = (saved, stage_out, xs, pooled, (B, Himg, Wimg))
-        return logits
+        return self._head_logits(pl, B, cl)
 
     # ------------------------------------------------------------------ backward to the input
     def forward_backward(self, x01, mean, std, y, kind, y_target=None, scale=1.0):
         """-> (logits fp32, loss_indiv, d(sum_i scale*loss_i)/dx01 fp32 NCHW, pred int32); same contract as
         ResNet50Engine.forward_backward."""
-        from ..noise.adv import logit_loss
         torch = _lib.require_gpu()
-        lib, sp = self.lib, _lib.stream_ptr()
-        x01 = x01.detach().float().contiguous()
-        logits = self._forward(x01, False, mean, std, keep=True)
+        cl = self.dims[-1]
+        logits, loss, pred, dpl = self._forward_loss(x01, mean, std, y, kind, y_target, scale, 'g_pooled_ln', cl)
         saved, stage_out, xs, pooled, (B, Himg, Wimg) = self._saved
-        loss, dl, pred = logit_loss(logits, y, kind, y_target, scale)
-        self.last_dlogits = dl
-        cl, kp = self.dims[-1], self.head_kpad
-        dlb = self._dlogits_rows(dl, 'g_dl', B, kp)
-        dpl = self._act('g_pooled_ln', (B, cl))
-        self._mm(dlb, self.head_wd, dpl, B, cl, kp)
         dpooled = self._act('g_pooled', (B, cl))
         self._ln_bwd(dpl, pooled, self.head_g, None, dpooled, B, cl)
         H, W = Himg // 32, Wimg // 32
         n_st = len(self.stages)
         gx = self._act('g_x%d' % (n_st - 1), (B * H * W, cl))
-        if self.x3:
-            _lib.check(lib.rart_cnx_pool_bwd_pair(_lib.ptr(dpooled[0]), _lib.ptr(dpooled[1]), _lib.ptr(gx[0]), _lib.ptr(gx[1]), B, H * W, cl, sp))
-        else:
-            _lib.check(lib.rart_cnx_pool_bwd_bf16(_lib.ptr(dpooled), _lib.ptr(gx), B, H * W, cl, sp))
+        self._pool_bwd(dpooled, gx, B, H * W, cl)
         k = len(saved)
         for si in range(n_st - 1, -1, -1):
             S, C = self.stages[si], self.dims[si]
@@ -329,7 +247,4 @@ class ConvNeXtEngine(RowEngine):
         self._ln_bwd(gx, xs, self.stem_g, None, gs, rows, c0)
         dpatch = self._get('g_patch', (rows, STEM_K), torch.float32)
         self._mm(gs, self.stem_wd, dpatch, rows, STEM_K, c0, flags=F_OUT_F32)
-        grad = torch.empty(B, 3, Himg, Wimg, dtype=torch.float32, device=self.device)
-        _lib.check(lib.rart_vit_unpatchify_from_f32(_lib.ptr(dpatch), _lib.ptr(grad), B, Himg, Wimg, 4, STEM_K,
-                                                    (ctypes.c_float * 3)(*std), sp))
-        return logits, loss, grad, pred
+        return logits, loss, self._unpatchify(dpatch, B, Himg, Wimg, 4, std, ld=STEM_K), pred

@@ -28,10 +28,10 @@ import ctypes
 
 from .. import _lib
 from .convnext_engine import DS_TAPS, STEM_K, ConvNeXtEngine
-from .engine_base import F_GELU_BWD, F_OUT_F32
+from .engine_base import F_GELU_BWD, RowTrainMixin
 
 
-class ConvNeXtTrainEngine(ConvNeXtEngine):
+class ConvNeXtTrainEngine(RowTrainMixin, ConvNeXtEngine):
     fold_layer_scale = False
 
     def __init__(self, model, device='cuda', on_grad_ready=None):
@@ -39,9 +39,7 @@ class ConvNeXtTrainEngine(ConvNeXtEngine):
         if dp:
             raise NotImplementedError('ConvNeXtTrainEngine: drop_path_rate > 0 (stochastic depth) is not implemented; the reference '
                                       'adversarial-training configs use 0.0 (max rate here %g)' % max(dp))
-        super().__init__(model, device, 'bf16')
-        self.model = model
-        self.on_grad_ready = on_grad_ready or (lambda p: None)
+        super().__init__(model, device, on_grad_ready)
         lib = self.lib
         for si, c in enumerate(self.dims):
             ok = lib.rart_wgrad_direct_supported(c, 4 * c, 1) and lib.rart_wgrad_direct_supported(4 * c, c, 1)
@@ -51,24 +49,10 @@ class ConvNeXtTrainEngine(ConvNeXtEngine):
                 raise ValueError('ConvNeXtTrainEngine: stage width %d is outside the weight-gradient kernels (64 or a multiple of 128, '
                                  'at most 1024)' % c)
 
-    def repack(self):
-        """fp32 master weights -> bf16 tables; call after every optimizer step."""
-        self.refold(self.model)
-
     # ------------------------------------------------------------------ helpers
     def _ready(self, *params):
         for p in params:
             self.on_grad_ready(p)
-
-    def _ln_full(self, dy, x, gamma, dx, rows, c, norm):
-        """dx (nullable) = LayerNorm backward of dy against x; norm.weight.grad / norm.bias.grad = dgamma / dbeta"""
-        lib = self.lib
-        need = lib.rart_layernorm_bwd_workspace_bytes(c)
-        ws = self._scratch('ln_ws', need)
-        _lib.check(lib.rart_layernorm_bwd_full_bf16(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(gamma), None, _lib.ptr(dx), rows, c, c, c, 0, c,
-                                                    1e-6, _lib.ptr(norm.weight.grad), _lib.ptr(norm.bias.grad), 0, _lib.ptr(ws), need,
-                                                    _lib.stream_ptr()))
-        self._ready(norm.weight, norm.bias)
 
     def _linear_wgrad(self, lin, x, dz, rows):
         """Linear weight [n_out][c_in] over NHWC rows: x [rows][c_in], dz [rows][n_out]"""
@@ -110,11 +94,9 @@ class ConvNeXtTrainEngine(ConvNeXtEngine):
         """train-mode forward -> fp32 logits [B][classes]; keeps what backward() needs"""
         torch = _lib.require_gpu()
         lib, sp = self.lib, _lib.stream_ptr()
-        if src_is_u8:
-            B, Himg, Wimg = src.shape[0], src.shape[1], src.shape[2]
-        else:
+        if not src_is_u8:
             src = src.detach().float().contiguous()
-            B, Himg, Wimg = src.shape[0], src.shape[2], src.shape[3]
+        B, Himg, Wimg = self._image_dims(src, src_is_u8)
         if Himg % 32 or Wimg % 32:
             raise ValueError('ConvNeXt needs image sides that are multiples of 32 (got %dx%d)' % (Himg, Wimg))
         H, W = Himg // 4, Wimg // 4
@@ -124,8 +106,7 @@ class ConvNeXtTrainEngine(ConvNeXtEngine):
         _lib.check(lib.rart_cnx_patchify(_lib.ptr(src), 1 if src_is_u8 else 0, _lib.ptr(patches[0]), _lib.ptr(patches[1]), B, Himg, Wimg,
                                          4, STEM_K, meanf, stdf, sp))
         xs = self._get('t_stem', (B * H * W, c0))
-        lo_off = (patches[1].data_ptr() - patches[0].data_ptr()) // 2
-        self._gemm(patches[0], self.stem_w, xs, B * H * W, STEM_K, c0, STEM_K, c0, bias=self.stem_b, n_taps=2, tap_src_off=[0, lo_off])
+        self._input_gemm(patches, self.stem_w, xs, B * H * W, c0, STEM_K, bias=self.stem_b)
         x = self._get('t_x0_0', (B * H * W, c0))
         self._ln(xs, self.stem_g, self.stem_nb, x, B * H * W, c0)
         blocks, stage_out = [], []
@@ -163,13 +144,11 @@ class ConvNeXtTrainEngine(ConvNeXtEngine):
                 x = xo
         cl = self.dims[-1]
         pooled = self._get('t_pooled', (B, cl))
-        _lib.check(lib.rart_engine_avgpool(_lib.ptr(x), _lib.ptr(pooled), B, H * W, cl, sp))
+        self._avgpool(x, pooled, B, H * W, cl)
         pl = self._get('t_pooled_ln', (B, cl))
         self._ln(pooled, self.head_g, self.head_nb, pl, B, cl)
-        logits = torch.empty(B, self.n_classes, dtype=torch.float32, device=self.device)
-        self._mm(pl, self.head_w, logits, B, self.n_classes, cl, bias=self.head_b, flags=F_OUT_F32)
         self._saved = (blocks, stage_out, xs, pooled, pl, patches, (B, Himg, Wimg))
-        return logits
+        return self._head_logits(pl, B, cl)
 
     # ------------------------------------------------------------------ backward to every parameter
     def backward(self, dlogits):
@@ -187,11 +166,11 @@ class ConvNeXtTrainEngine(ConvNeXtEngine):
         dpl = self._get('g_pooled_ln', (B, cl))
         self._mm(dlb, self.head_wd, dpl, B, cl, kp)
         dpooled = self._get('g_pooled', (B, cl))
-        self._ln_full(dpl, pooled, self.head_g, dpooled, B, cl, m.head.norm)
+        self._ln_bwd_full(dpl, pooled, self.head_g, None, dpooled, B, cl, m.head.norm)
         H, W = Himg // 32, Wimg // 32
         n_st = len(self.stages)
         gx = self._get('g_x%d' % (n_st - 1), (B * H * W, cl))
-        _lib.check(lib.rart_cnx_pool_bwd_bf16(_lib.ptr(dpooled), _lib.ptr(gx), B, H * W, cl, sp))
+        self._pool_bwd(dpooled, gx, B, H * W, cl)
         k = len(blocks)
         for si in range(n_st - 1, -1, -1):
             S, C, stage = self.stages[si], self.dims[si], m.stages[si]
@@ -231,7 +210,7 @@ class ConvNeXtTrainEngine(ConvNeXtEngine):
                 # 5. fc1 dgrad
                 self._mm(dh, L['fc1_wd'], dln, rows, C, 4 * C)
                 # 6. LayerNorm against the kept conv output
-                self._ln_full(dln, y, L['ng'], dz, rows, C, blk.norm)
+                self._ln_bwd_full(dln, y, L['ng'], None, dz, rows, C, blk.norm)
                 # 7. depthwise conv weight and bias
                 ws = self._scratch('dw_ws', dw_need)
                 _lib.check(lib.rart_cnx_dwconv_wgrad_bf16(_lib.ptr(x_in), _lib.ptr(dz), _lib.ptr(blk.conv_dw.weight.grad),
@@ -249,12 +228,12 @@ class ConvNeXtTrainEngine(ConvNeXtEngine):
                 self._downsample_scatter(gx, S, gds, B, 2 * H, 2 * W)
                 H, W = 2 * H, 2 * W
                 gprev = self._get('g_x%d' % (si - 1), (B * H * W, cin))
-                self._ln_full(gds, stage_out[si - 1], S['ds_g'], gprev, B * H * W, cin, stage.downsample[0])
+                self._ln_bwd_full(gds, stage_out[si - 1], S['ds_g'], None, gprev, B * H * W, cin, stage.downsample[0])
                 gx = gprev
         # ---- stem: x0 = LN(patches . W^T + b)
         c0, rows = self.dims[0], B * H * W
         gs = self._get('g_stem', (rows, c0))
-        self._ln_full(gx, xs, self.stem_g, gs, rows, c0, m.stem[1])
+        self._ln_bwd_full(gx, xs, self.stem_g, None, gs, rows, c0, m.stem[1])
         self._colsum(gs, c0, rows, c0, m.stem[0].bias.grad)
         self._ready(m.stem[0].bias)
         wst = self._get('g_stem_w', (c0, STEM_K), self.stem_b.dtype)

@@ -18,7 +18,7 @@ Kept by the forward: the convolution outputs u_i (the LayerNorm-GELU backward re
 import ctypes
 
 from .. import _lib
-from .engine_base import F_OUT_F32, conv_desc, gemm_pair_desc, k32, lo_off, pad_k, pad_rows, pair, rows_mult
+from .engine_base import F_OUT_F32, act, k32, pad_k, rows_mult
 
 IM2COL_LD = 32                   # 3 x 3 x 3 = 27 columns, padded to the K step of both GEMMs
 TAPS9 = [(ky - 1, kx - 1) for ky in range(3) for kx in range(3)]
@@ -46,16 +46,7 @@ class ConvStem:
         """(Re)build the weight tables from the module `stem` (convstem_torch.ConvStem) in the owning engine's precision"""
         torch = _lib.require_gpu()
         eng = self.eng
-        dev = eng.device
-
-        def f32(t):
-            return t.detach().to(dev, torch.float32).contiguous()
-
-        def tab(w2d):                # fp32 [rows][K] -> the GEMM's table: pair planes (rows to 256) or bf16 (rows to 128 / 64)
-            if eng.x3:
-                return pair(pad_rows(w2d.contiguous(), 256))
-            w = w2d.to(torch.bfloat16)
-            return pad_rows(w, rows_mult(w.shape[0]))
+        dev, f32, tab = eng.device, eng._f32, eng._table
 
         self.units = []
         ld_in = None
@@ -72,12 +63,8 @@ class ConvStem:
                 if cin != 3:
                     raise NotImplementedError('the ConvStem reads a 3-channel image')
                 w0 = pad_k(w.reshape(cout, 27), IM2COL_LD)                             # [cout][c * 9 + ky * 3 + kx], zero columns 27 .. 31
-                if eng.x3:
-                    U['w'] = tab(w0)
-                else:
-                    w0b = w0.to(torch.bfloat16)
-                    U['w'] = pad_rows(torch.cat([w0b, w0b], 1), rows_mult(cout))       # hi | lo taps of the image pair
-                U['wd'] = tab(pad_k(w0.t(), k32(cout)))                                # [32][k32(cout)]
+                U['w'] = eng._input_table(w0, rows_mult(cout))                         # bf16: [hi | hi] taps of the image pair
+                U['wd'] = tab(w0, k32(cout), transpose=True)                           # [32][k32(cout)]
             else:
                 wp = torch.zeros(cout, 3, 3, ld_in, dtype=torch.float32, device=dev)
                 wp[..., :cin] = w.permute(0, 2, 3, 1)
@@ -96,37 +83,14 @@ class ConvStem:
                 raise NotImplementedError('the closing convolution of a ConvStem is 1x1')
             pw = pw.reshape(pw.shape[0], pw.shape[1])                                  # [D][cin]
             kp = k32(pw.shape[1])
-            self.proj = dict(n=pw.shape[0], k=kp, w=tab(pad_k(pw, kp)), wd=tab(pw.t()), bias=f32(stem.proj.bias))
+            self.proj = dict(n=pw.shape[0], k=kp, w=tab(pw, kp), wd=tab(pw, transpose=True), bias=f32(stem.proj.bias))
 
     # ------------------------------------------------------------------ launches
-    def _conv(self, src, w, dst, B, grid, src_hw, src_ld, taps, n_cols, dst_hw, dst_ld, stride, dst_stride, dst_org, bias=None):
-        """implicit-GEMM convolution on NHWC src (rows src_ld apart, all of them contracted) -> n_cols channels of dst (rows dst_ld apart)"""
-        eng = self.eng
-        if eng.x3:
-            eng._launch_pair(gemm_pair_desc(src, w, dst, n_cols, src_ld, src_ld * len(taps), dst_ld, w.shape[1], bias=bias, batch=B, grid=grid,
-                                            src_hw=src_hw, stride=stride, k_per_tap=src_ld, taps=taps, dst_hw=dst_hw, dst_stride=dst_stride,
-                                            dst_org=dst_org))
-        else:
-            eng._launch_conv(conv_desc(src, w, dst, B, grid, src_hw, src_ld, src_ld, taps, n_cols, dst_hw, dst_ld, bias=bias, stride=stride,
-                                       dst_stride=dst_stride, dst_org=dst_org))
-
     def _ln_gelu(self, u, U, out, rows, ld_out):
-        eng, lib, sp = self.eng, self.eng.lib, _lib.stream_ptr()
-        (uh, ul), (oh, ol) = eng._hl(u), eng._hl(out)
-        if eng.x3:
-            _lib.check(lib.rart_ln_gelu_pair(uh, ul, _lib.ptr(U['g']), _lib.ptr(U['b']), oh, ol, rows, U['c'], U['ld'], ld_out, U['eps'], sp))
-        else:
-            _lib.check(lib.rart_ln_gelu_bf16(uh, _lib.ptr(U['g']), _lib.ptr(U['b']), oh, rows, U['c'], U['ld'], ld_out, U['eps'], sp))
+        self.eng._rows('ln_gelu', act(u), U['g'], U['b'], act(out), rows, U['c'], U['ld'], ld_out, U['eps'])
 
     def _ln_gelu_bwd(self, dy, ld_dy, u, U, dx, rows):
-        eng, lib, sp = self.eng, self.eng.lib, _lib.stream_ptr()
-        (dh, dl), (uh, ul), (oh, ol) = eng._hl(dy), eng._hl(u), eng._hl(dx)
-        if eng.x3:
-            _lib.check(lib.rart_ln_gelu_bwd_pair(dh, dl, uh, ul, _lib.ptr(U['g']), _lib.ptr(U['b']), oh, ol, rows, U['c'], ld_dy, U['ld'],
-                                                 U['ld'], U['eps'], sp))
-        else:
-            _lib.check(lib.rart_ln_gelu_bwd_bf16(dh, uh, _lib.ptr(U['g']), _lib.ptr(U['b']), oh, rows, U['c'], ld_dy, U['ld'], U['ld'],
-                                                 U['eps'], sp))
+        self.eng._rows('ln_gelu_bwd', act(dy), act(u), U['g'], U['b'], act(dx), rows, U['c'], ld_dy, U['ld'], U['ld'], U['eps'])
 
     # ------------------------------------------------------------------ forward / backward
     def forward(self, src, src_is_u8, mean, std, B, Himg, Wimg, out, **slot):
@@ -147,16 +111,12 @@ class ConvStem:
             c, ld = U['c'], U['ld']
             if i == 0:
                 u = eng._act('cvst_u0', (rows, ld))
-                if eng.x3:
-                    eng._gemm_pair(patches, U['w'], u, rows, c, IM2COL_LD, IM2COL_LD, ld, bias=U['bias'])
-                else:
-                    eng._gemm(patches[0], U['w'], u, rows, IM2COL_LD, c, IM2COL_LD, ld, bias=U['bias'], n_taps=2,
-                              tap_src_off=[0, lo_off(patches)])
+                eng._input_gemm(patches, U['w'], u, rows, c, IM2COL_LD, ldc=ld, bias=U['bias'])
             else:
                 H, W = H // 2, W // 2
                 rows = B * H * W
                 u = eng._act('cvst_u%d' % i, (rows, ld))
-                self._conv(a, U['w'], u, B, (H, W), (2 * H, 2 * W), self.units[i - 1]['ld'], TAPS9, c, (H, W), ld, (2, 2), (1, 1), (0, 0),
+                eng._conv(a, U['w'], u, B, (H, W), (2 * H, 2 * W), self.units[i - 1]['ld'], TAPS9, c, (H, W), ld, (2, 2), (1, 1), (0, 0),
                            bias=U['bias'])
             kept.append(u)
             if i == n - 1 and self.proj is None:
@@ -196,7 +156,7 @@ class ConvStem:
                 P = self.units[i - 1]
                 da, ld_da = eng._act('cvst_da%d' % (i - 1), (4 * rows, P['ld'])), P['ld']
                 for (py, px), taps, w in U['wd']:
-                    self._conv(du, w, da, B, (H, W), (H, W), U['ld'], taps, P['c'], (2 * H, 2 * W), P['ld'], (1, 1), (2, 2), (py, px))
+                    eng._conv(du, w, da, B, (H, W), (H, W), U['ld'], taps, P['c'], (2 * H, 2 * W), P['ld'], (1, 1), (2, 2), (py, px))
                 H, W = 2 * H, 2 * W
                 rows = B * H * W
         dpatch = eng._get('cvst_dpatch', (rows, IM2COL_LD), torch.float32)

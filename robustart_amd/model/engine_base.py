@@ -2,9 +2,16 @@
 helpers, the tap geometry of a convolution, the split-K heuristics of the weight gradient, and `EngineBase` (device, buffers,
 profiling, both weight-gradient paths) that every engine inherits.
 
-The builders take tensors or None and only read `data_ptr()`, so they run on CPU tensors as well.  Every engine keeps the adapter that
-encodes its own convention: ResNet-50's conv form and [hi | lo | hi] weight tables (engine.py), the row form of ViT-B/16, MLP-Mixer and
-ConvNeXt with its precision-generic launches (`RowEngine` below)."""
+The builders take tensors or None and only read `data_ptr()`, so they run on CPU tensors as well.  ResNet-50 keeps the adapter that
+encodes its own convention, the conv form and [hi | lo | hi] weight tables (engine.py).  The row form of ViT-B/16, MLP-Mixer, ConvNeXt
+and the ConvStem chain lives in `RowEngine`, once for both precisions:
+  tables    `_f32` (fp32 copy on the device), `_table` (row table of a GEMM weight or of its transpose) and `_input_table` (the table
+            of the GEMM that reads the image pair): the caller names the form, the builder picks the precision
+  launches  `_mm` / `_input_gemm` / `_conv` (GEMM, image-pair GEMM, implicit-GEMM convolution), `_rows` (any row kernel whose
+            rart_*_pair and rart_*_bf16 entries differ by hi / lo pointer pairs alone, activations marked with `act`), and the named
+            irregular ones: `_avgpool`, `_pool_bwd`, `_patchify`, `_unpatchify`
+  chain     `_image_dims`, `_head_logits`, `_forward_loss` (the prologue of every `forward_backward`)
+`RowTrainMixin` is what the three train engines of these models share: model, `on_grad_ready`, `repack`, the kept forward."""
 import ctypes
 
 from .. import _lib
@@ -81,6 +88,11 @@ def pair(t):
     """fp32 tensor -> [2][...] bf16 planes (hi, lo)"""
     import torch
     return torch.stack(split_hi_lo(t)).contiguous()
+
+
+def act(t):
+    """marks an argument of `RowEngine._rows` as an activation: a bf16 tensor, in reference precision a pair [2][...] (None: null)"""
+    return (t,)
 
 
 def interleave_k32(hi, lo):
@@ -433,8 +445,39 @@ class EngineBase:
 
 class RowEngine(EngineBase):
     """The row form of ViT-B/16, MLP-Mixer and ConvNeXt: activations are dense [rows][features] matrices (tokens, NHWC pixels).
-    `_gemm` / `_gemm_pair` are the two GEMM launchers; the helpers after them take either precision: a bf16 tensor or a pair
-    [2][...], the bf16 or the pair library entry."""
+    `_gemm` / `_gemm_pair` are the two GEMM launchers; the table builders before them and the helpers after them take either
+    precision: a bf16 tensor or a pair [2][...], the bf16 or the pair library entry."""
+
+    # ------------------------------------------------------------------ weight tables, in the engine's precision
+    def _f32(self, t):
+        """fp32 copy of a parameter on the engine's device"""
+        import torch
+        return t.detach().to(self.device, torch.float32).contiguous()
+
+    def _table(self, w2d, k_pad=None, transpose=False, interleave=False):
+        """row table of the GEMM weight w2d [rows][K], or with `transpose` of W^T (the backward-to-input table), K zero-padded to
+        k_pad: pair planes [2][rows padded to the 256-row tile of rart_gemm_pair_bf16][K] in reference precision, else bf16 with rows
+        padded to rows_mult(rows).  Padding rows are zero and never stored.  interleave (pair planes with K a multiple of 32): keep
+        their interleaved copy beside them in `_w_il`, keyed by their address (GP_W_INTERLEAVED: one 128-byte line per row and K step)"""
+        import torch
+        w = w2d.detach().to(self.device, torch.float32)
+        if self.x3:
+            t = pair(pad_rows(pad_k(w.t() if transpose else w, k_pad), 256))
+            if interleave and t.shape[2] % 32 == 0:
+                self._w_il[t.data_ptr()] = interleave_k32(t[0], t[1])
+            return t
+        w = w.to(torch.bfloat16)
+        t = pad_k(w.t() if transpose else w, k_pad)
+        return pad_rows(t, rows_mult(t.shape[0]))
+
+    def _input_table(self, w2d, rows_mult, interleave=False):
+        """table of the GEMM that reads the image pair (`_input_gemm`): the pair table in reference precision, else bf16 [hi | hi]
+        columns, which the hi and the lo plane of the image meet as two taps, rows padded to a multiple of `rows_mult`"""
+        if self.x3:
+            return self._table(w2d, interleave=interleave)
+        import torch
+        w = w2d.detach().to(self.device, torch.float32).to(torch.bfloat16)
+        return pad_rows(torch.cat([w, w], 1), rows_mult)
 
     def _gemm(self, src, wgt, dst, rows, k, n_cols, src_ld, dst_ld, bias=None, res=None, flags=0, n_taps=1,
               tap_src_off=None, rows_per_image=None, dst_rows_per_image=None, dst_row_off=0, batched=None,
@@ -469,25 +512,57 @@ class RowEngine(EngineBase):
         else:       # rart_conv_desc has no source row offset: start at that row
             self._gemm(a.view(-1, lda)[src_row_off:] if src_row_off else a, w, dst, M, K, N, lda, ldc, mask=aux, **kw)
 
+    def _input_gemm(self, patches, w, dst, rows, N, K, ldc=None, **kw):
+        """dst[rows][N] = patches . w^T for the image pair `patches` [2][rows][K] and its `_input_table`: the pair GEMM, or in bf16
+        the hi and the lo plane as two taps of the [hi | hi] columns; kw: as `_mm`'s"""
+        if self.x3:
+            self._gemm_pair(patches, w, dst, rows, N, K, K, ldc or N, **kw)
+        else:
+            self._gemm(patches[0], w, dst, rows, K, N, K, ldc or N, n_taps=2, tap_src_off=[0, lo_off(patches)], **kw)
+
+    def _conv(self, src, w, dst, B, grid, src_hw, src_ld, taps, n_cols, dst_hw, dst_ld, stride, dst_stride, dst_org, bias=None):
+        """implicit-GEMM convolution on NHWC src (rows src_ld apart, all of them contracted) -> n_cols channels of dst (rows dst_ld apart)"""
+        if self.x3:
+            self._launch_pair(gemm_pair_desc(src, w, dst, n_cols, src_ld, src_ld * len(taps), dst_ld, w.shape[1], bias=bias, batch=B,
+                                             grid=grid, src_hw=src_hw, stride=stride, k_per_tap=src_ld, taps=taps, dst_hw=dst_hw,
+                                             dst_stride=dst_stride, dst_org=dst_org))
+        else:
+            self._launch_conv(conv_desc(src, w, dst, B, grid, src_hw, src_ld, src_ld, taps, n_cols, dst_hw, dst_ld, bias=bias,
+                                        stride=stride, dst_stride=dst_stride, dst_org=dst_org))
+
+    def _rows(self, stem, *args):
+        """one launch of the row kernel rart_<stem>_pair / rart_<stem>_bf16, entries that differ by hi / lo pointer pairs alone.
+        args in the entry's order: `act(t)` for an activation (hi and lo pointer in reference precision, one pointer in bf16), any
+        other tensor (fp32 parameters, statistics) as it is, scalars as they are; the stream is appended"""
+        x3, a = self.x3, []
+        for v in args:
+            if isinstance(v, tuple):             # act(t)
+                t, = v
+                a += [_lib.ptr(p) for p in ((t,) if not x3 else (None, None) if t is None else (t[0], t[1]))]
+            else:
+                a.append(_lib.ptr(v) if hasattr(v, 'data_ptr') else v)
+        _lib.check(getattr(self.lib, 'rart_%s_%s' % (stem, 'pair' if x3 else 'bf16'))(*a, _lib.stream_ptr()))
+
     def _ln(self, x, g, b, out, rows, c, ld_in=None, ld_out=None):
         """out = LayerNorm(x) over the c features of `rows` rows ld_in / ld_out elements apart (default: dense)"""
-        lib, sp = self.lib, _lib.stream_ptr()
-        (xh, xl), (oh, ol) = self._hl(x), self._hl(out)
-        if self.x3:
-            _lib.check(lib.rart_layernorm_pair(xh, xl, _lib.ptr(g), _lib.ptr(b), oh, ol, rows, c, ld_in or c, ld_out or c, 1e-6, sp))
-        else:
-            _lib.check(lib.rart_layernorm_bf16(xh, _lib.ptr(g), _lib.ptr(b), oh, rows, c, ld_in or c, ld_out or c, 1e-6, sp))
+        self._rows('layernorm', act(x), g, b, act(out), rows, c, ld_in or c, ld_out or c, 1e-6)
 
     def _ln_bwd(self, dy, x, g, res, dx, rows, c, strides=None):
         """dx = LayerNorm'(x)^T dy (+ res); strides: the row strides of (dy, x, res, dx), default dense"""
-        lib, sp = self.lib, _lib.stream_ptr()
         ld = strides or (c, c, c if res is not None else 0, c)
-        (dh, dl), (xh, xl), (oh, ol) = self._hl(dy), self._hl(x), self._hl(dx)
-        rh, rl = self._hl(res) if res is not None else (None, None)
-        if self.x3:
-            _lib.check(lib.rart_layernorm_bwd_pair(dh, dl, xh, xl, _lib.ptr(g), rh, rl, oh, ol, rows, c, *ld, 1e-6, sp))
+        self._rows('layernorm_bwd', act(dy), act(x), g, act(res), act(dx), rows, c, *ld, 1e-6)
+
+    def _avgpool(self, x, out, B, P, C):
+        """out[B][C] = the mean over the P rows of every image of x [B][P][C]"""
+        lib, sp = self.lib, _lib.stream_ptr()
+        if self.x3:          # the pair entry takes the hi pointers and the plane sizes
+            _lib.check(lib.rart_engine_avgpool_pair(_lib.ptr(x[0]), x[0].numel(), _lib.ptr(out[0]), out[0].numel(), B, P, C, sp))
         else:
-            _lib.check(lib.rart_layernorm_bwd_bf16(dh, xh, _lib.ptr(g), rh, oh, rows, c, *ld, 1e-6, sp))
+            _lib.check(lib.rart_engine_avgpool(_lib.ptr(x), _lib.ptr(out), B, P, C, sp))
+
+    def _pool_bwd(self, dpooled, dx, B, P, C):
+        """the backward of `_avgpool`: dx[B][P][C] = dpooled[B][C] / P at every row"""
+        self._rows('cnx_pool_bwd', act(dpooled), act(dx), B, P, C)
 
     def _fc1_gelu(self, ln, w, b, hid, u, rows, K, N, keep):
         """hid = gelu(ln . w^T + b), the fc1 of a transformer MLP; keep: u receives the pre-activation (GELU' in the backward)"""
@@ -507,25 +582,50 @@ class RowEngine(EngineBase):
                                               B, H, W, ps, meanf, stdf, _lib.stream_ptr()))
         return patches
 
-    def _unpatchify(self, dpatch, B, H, W, ps, std):
-        """-> d(loss)/d(x01) fp32 NCHW from the patch gradient [B * patches][3 * ps * ps]: bf16, or fp32 in reference precision"""
+    def _unpatchify(self, dpatch, B, H, W, ps, std, ld=None):
+        """-> d(loss)/d(x01) fp32 NCHW from the patch gradient [B * patches][ld] (default 3 * ps * ps columns), bf16 or fp32"""
         torch = _lib.require_gpu()
         grad = torch.empty(B, 3, H, W, dtype=torch.float32, device=self.device)
-        fn = self.lib.rart_vit_unpatchify_from_f32 if self.x3 else self.lib.rart_vit_unpatchify_f32
-        _lib.check(fn(_lib.ptr(dpatch), _lib.ptr(grad), B, H, W, ps, 3 * ps * ps, (ctypes.c_float * 3)(*std), _lib.stream_ptr()))
+        fn = self.lib.rart_vit_unpatchify_from_f32 if dpatch.dtype == torch.float32 else self.lib.rart_vit_unpatchify_f32
+        _lib.check(fn(_lib.ptr(dpatch), _lib.ptr(grad), B, H, W, ps, ld or 3 * ps * ps, (ctypes.c_float * 3)(*std), _lib.stream_ptr()))
         return grad
 
-    # train engines (ViTTrainEngine, MixerTrainEngine): they set `on_grad_ready`, called once per parameter after the last kernel
-    # that writes or reads its gradient has been enqueued
-    def _ln_bwd_full(self, dy, x, gamma, res, dx, rows, strides, norm):
+    # ------------------------------------------------------------------ the ends of every chain
+    @staticmethod
+    def _image_dims(src, src_is_u8):
+        """-> (B, H, W) of an image batch, u8 NHWC or fp32 NCHW"""
+        return (src.shape[0], src.shape[1], src.shape[2]) if src_is_u8 else (src.shape[0], src.shape[2], src.shape[3])
+
+    def _head_logits(self, feat, B, K):
+        """-> the fp32 logits [B][n_classes] = feat[B][K] . head_w^T + head_b"""
+        torch = _lib.require_gpu()
+        logits = torch.empty(B, self.n_classes, dtype=torch.float32, device=self.device)
+        self._mm(feat, self.head_w, logits, B, self.n_classes, K, bias=self.head_b, flags=F_OUT_F32)
+        return logits
+
+    def _forward_loss(self, x01, mean, std, y, kind, y_target, scale, name, K):
+        """the prologue of every `forward_backward`: the forward that keeps its activations in `_saved`, the loss, and the head's dgrad
+        GEMM -> (logits, loss, pred, the gradient [B][K] of the head's input in buffer `name`)"""
+        from ..noise.adv import logit_loss
+        logits = self._forward(x01.detach().float().contiguous(), False, mean, std, keep=True)
+        loss, dl, pred = logit_loss(logits, y, kind, y_target, scale)
+        self.last_dlogits = dl           # exposed for the parity tests (same upstream gradient for the reference)
+        B, kp = logits.shape[0], self.head_kpad
+        dfeat = self._act(name, (B, K))
+        self._mm(self._dlogits_rows(dl, 'g_dl', B, kp), self.head_wd, dfeat, B, K, kp)
+        return logits, loss, pred, dfeat
+
+    # train engines (`RowTrainMixin`): they set `on_grad_ready`, called once per parameter after the last kernel that writes or reads
+    # its gradient has been enqueued
+    def _ln_bwd_full(self, dy, x, gamma, res, dx, rows, c, norm, strides=None):
         """the backward of `_ln_bwd` plus the gradients of `norm`'s weight and bias (bf16)"""
-        lib, D = self.lib, self.D
-        need = lib.rart_layernorm_bwd_workspace_bytes(D)
+        lib = self.lib
+        ld = strides or (c, c, c if res is not None else 0, c)
+        need = lib.rart_layernorm_bwd_workspace_bytes(c)
         ws = self._scratch('ln_ws', need)
         _lib.check(lib.rart_layernorm_bwd_full_bf16(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(gamma), _lib.ptr(res), _lib.ptr(dx), rows,
-                                                    D, strides[0], strides[1], strides[2], strides[3], 1e-6,
-                                                    _lib.ptr(norm.weight.grad), _lib.ptr(norm.bias.grad), 0, _lib.ptr(ws), need,
-                                                    _lib.stream_ptr()))
+                                                    c, *ld, 1e-6, _lib.ptr(norm.weight.grad), _lib.ptr(norm.bias.grad), 0,
+                                                    _lib.ptr(ws), need, _lib.stream_ptr()))
         self.on_grad_ready(norm.weight)
         self.on_grad_ready(norm.bias)
 
@@ -542,3 +642,22 @@ class RowEngine(EngineBase):
         b, sh, gh = dz_images if dz_images is not None else (1, rows, rows)
         self._wgrad_transposed(dz, (b, sh, 1, n_pad, gh, 1), x, (1, rows, 1, c_in, rows, 1, 1, ROW_TAPS[1]), n_out, grad,
                                (1, c_in, c_in), row_grid=True)
+
+
+class RowTrainMixin:
+    """What the train engines of the row models share, mixed in before the evaluation engine they extend (bf16): the module whose
+    `.grad` tensors `backward` fills, `on_grad_ready(param)`, `repack` and the forward that keeps its activations."""
+
+    def __init__(self, model, device='cuda', on_grad_ready=None):
+        super().__init__(model, device)
+        self.model = model
+        self.on_grad_ready = on_grad_ready or (lambda p: None)
+
+    def repack(self):
+        """fp32 master weights -> bf16 tables; call after every optimizer step."""
+        self.refold(self.model)
+
+    def forward(self, src, src_is_u8, mean, std):
+        if not src_is_u8:
+            src = src.detach().float().contiguous()
+        return self._forward(src, src_is_u8, mean, std, keep=True)

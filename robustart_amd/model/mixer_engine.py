@@ -13,7 +13,7 @@ precision 'bf16': bf16 storage, fp32 accumulation; 'bf16x3' (alias 'fp32x'): eve
 bf16 planes, three MFMA products per contraction (rart_gemm_pair_bf16, rart_tokmix_pair), as ViTEngine's reference-precision mode.
 Every dimension is read from the module."""
 from .. import _lib
-from .engine_base import (F_GELU, F_GELU_BWD, F_GELU_KEEP, F_OUT_F32, RowEngine, k32, lo_off, pad_k, pad_rows, pair, rows_mult, tokmix_desc)
+from .engine_base import F_GELU, F_GELU_BWD, F_GELU_KEEP, F_OUT_F32, RowEngine, k32, pad_k, pair, tokmix_desc
 
 
 class MixerEngine(RowEngine):
@@ -26,57 +26,31 @@ class MixerEngine(RowEngine):
         """(Re)build every weight table from `model`'s current parameters, among them the token tables W1 [Ht][T], W2 [T][Ht] and
         their transposes, K padded to a multiple of 32 with zero columns, in the engine's precision."""
         torch = _lib.require_gpu()
-        m, dev = model, self.device
-        x3 = self.x3
+        m, f32 = model, self._f32
 
-        def f32(t):
-            return t.detach().to(dev, torch.float32).contiguous()
-
-        def bf(w2d):
-            return w2d.detach().to(dev, torch.float32).to(torch.bfloat16)
-
-        def wt(w, n_cols):                      # row GEMM forward table
-            return pad_rows(bf(w), rows_mult(n_cols))
-
-        def wd(w, k_pad=None):                  # row GEMM backward-to-input table (W^T)
-            t = pad_k(bf(w).t(), k_pad)
-            return pad_rows(t, rows_mult(t.shape[0]))
-
-        def tab(w, k_pad=None):                 # pair table of rart_gemm_pair_bf16: rows padded to its 256-row tile
-            return pair(pad_rows(pad_k(f32(w), k_pad), 256))
-
-        def tok(w):                             # token table [M][K rounded up to 32]
+        def tok(w):                             # token table [M][K rounded up to 32], no row padding
             w = pad_k(f32(w), k32(w.shape[1])).contiguous()
-            return pair(w) if x3 else w.to(torch.bfloat16).contiguous()
+            return pair(w) if self.x3 else w.to(torch.bfloat16).contiguous()
         pe = m.stem.proj.weight.detach().reshape(self.D, -1)
+        self.pe_w = self._input_table(pe, 128)                                         # [hi | hi] taps of the input pair in bf16
+        self.pe_wd = self._table(pe, transpose=True)
         self.pe_b = f32(m.stem.proj.bias)
         self.ng, self.nb = f32(m.norm.weight), f32(m.norm.bias)
         self.n_classes = m.head.out_features
         self.head_b = f32(m.head.bias)
         self.head_kpad = k32(self.n_classes)
+        self.head_w = self._table(m.head.weight)
+        self.head_wd = self._table(m.head.weight, self.head_kpad, transpose=True)
         self.layers = []
         for blk in m.blocks:
             mt, mc = blk.mlp_tokens, blk.mlp_channels
-            L = dict(n1g=f32(blk.norm1.weight), n1b=f32(blk.norm1.bias), n2g=f32(blk.norm2.weight), n2b=f32(blk.norm2.bias),
-                     tok_hidden=mt.fc1.out_features, hidden=mc.fc1.out_features,
-                     t1=tok(mt.fc1.weight), t1_b=f32(mt.fc1.bias), t2=tok(mt.fc2.weight), t2_b=f32(mt.fc2.bias),
-                     t1d=tok(mt.fc1.weight.t()), t2d=tok(mt.fc2.weight.t()),
-                     fc1_b=f32(mc.fc1.bias), fc2_b=f32(mc.fc2.bias))
-            if x3:
-                L.update(fc1_w=tab(mc.fc1.weight), fc2_w=tab(mc.fc2.weight), fc1_wd=tab(mc.fc1.weight.t()), fc2_wd=tab(mc.fc2.weight.t()))
-            else:
-                L.update(fc1_w=wt(mc.fc1.weight, mc.fc1.out_features), fc2_w=wt(mc.fc2.weight, self.D), fc1_wd=wd(mc.fc1.weight),
-                         fc2_wd=wd(mc.fc2.weight))
-            self.layers.append(L)
-        if x3:
-            self.pe_w, self.pe_wd = tab(pe), tab(pe.t())
-            self.head_w, self.head_wd = tab(m.head.weight), tab(m.head.weight.t(), self.head_kpad)
-        else:
-            peb = bf(pe)
-            self.pe_w = pad_rows(torch.cat([peb, peb], 1), 128)                        # hi | lo taps of the input pair
-            self.pe_wd = wd(pe)
-            self.head_w = wt(m.head.weight, self.n_classes)
-            self.head_wd = wd(m.head.weight, self.head_kpad)
+            self.layers.append(dict(
+                n1g=f32(blk.norm1.weight), n1b=f32(blk.norm1.bias), n2g=f32(blk.norm2.weight), n2b=f32(blk.norm2.bias),
+                tok_hidden=mt.fc1.out_features, hidden=mc.fc1.out_features,
+                t1=tok(mt.fc1.weight), t1_b=f32(mt.fc1.bias), t2=tok(mt.fc2.weight), t2_b=f32(mt.fc2.bias),
+                t1d=tok(mt.fc1.weight.t()), t2d=tok(mt.fc2.weight.t()),
+                fc1_w=self._table(mc.fc1.weight), fc1_b=f32(mc.fc1.bias), fc1_wd=self._table(mc.fc1.weight, transpose=True),
+                fc2_w=self._table(mc.fc2.weight), fc2_b=f32(mc.fc2.bias), fc2_wd=self._table(mc.fc2.weight, transpose=True)))
 
     # ------------------------------------------------------------------ launches
     def _tokmix(self, a, x, dst, M, K, B, bias=None, res=None, aux=None, flags=0):
@@ -87,12 +61,7 @@ class MixerEngine(RowEngine):
 
     # ------------------------------------------------------------------ forward
     def _forward(self, src, src_is_u8, mean, std, keep=False):
-        torch = _lib.require_gpu()
-        lib, sp = self.lib, _lib.stream_ptr()
-        if src_is_u8:
-            B, Himg, Wimg = src.shape[0], src.shape[1], src.shape[2]
-        else:
-            B, Himg, Wimg = src.shape[0], src.shape[2], src.shape[3]
+        B, Himg, Wimg = self._image_dims(src, src_is_u8)
         D, ps, T = self.D, self.ps, self.T
         assert (Himg // ps) * (Wimg // ps) == T, 'image size does not match the token-mixing MLP (%d tokens)' % T
         kk = 3 * ps * ps
@@ -100,10 +69,9 @@ class MixerEngine(RowEngine):
         patches = self._patchify(src, src_is_u8, mean, std, B, Himg, Wimg, ps)
         x = self._act('x0' if keep else 'x', (B, T, D))
         if self.x3:
-            self._gemm_pair(patches, self.pe_w, x, rows, D, kk, kk, D, bias=self.pe_b)
-        else:
-            self._gemm(patches[0], self.pe_w, x, rows, kk, D, kk, D, bias=self.pe_b, n_taps=2, tap_src_off=[0, lo_off(patches)],
-                       rows_per_image=T)
+            self._input_gemm(patches, self.pe_w, x, rows, D, kk, bias=self.pe_b)
+        else:                # the bf16 descriptor takes the rows image by image
+            self._input_gemm(patches, self.pe_w, x, rows, D, kk, bias=self.pe_b, rows_per_image=T)
         ln = self._act('ln', (B, T, D))
         saved = []
         for li, L in enumerate(self.layers):
@@ -127,38 +95,22 @@ class MixerEngine(RowEngine):
             x = xo
         self._ln(x, self.ng, self.nb, ln, rows, D)
         pooled = self._act('pooled', (B, D))
-        if self.x3:
-            _lib.check(lib.rart_engine_avgpool_pair(_lib.ptr(ln[0]), ln[0].numel(), _lib.ptr(pooled[0]), pooled[0].numel(), B, T, D, sp))
-        else:
-            _lib.check(lib.rart_engine_avgpool(_lib.ptr(ln), _lib.ptr(pooled), B, T, D, sp))
-        logits = torch.empty(B, self.n_classes, dtype=torch.float32, device=self.device)
-        self._mm(pooled, self.head_w, logits, B, self.n_classes, D, bias=self.head_b, flags=F_OUT_F32)
+        self._avgpool(ln, pooled, B, T, D)
         if keep:
             self._saved = (saved, x, (B, Himg, Wimg))
-        return logits
+        return self._head_logits(pooled, B, D)
 
     # ------------------------------------------------------------------ backward to the input
     def forward_backward(self, x01, mean, std, y, kind, y_target=None, scale=1.0):
         """-> (logits fp32, loss_indiv, d(sum_i scale*loss_i)/dx01 fp32 NCHW, pred int32); same contract as
         ResNet50Engine.forward_backward."""
-        from ..noise.adv import logit_loss
         torch = _lib.require_gpu()
-        lib, sp = self.lib, _lib.stream_ptr()
-        x01 = x01.detach().float().contiguous()
-        logits = self._forward(x01, False, mean, std, keep=True)
+        D, T = self.D, self.T
+        logits, loss, pred, dpool = self._forward_loss(x01, mean, std, y, kind, y_target, scale, 'g_pool', D)
         saved, x_last, (B, Himg, Wimg) = self._saved
-        loss, dl, pred = logit_loss(logits, y, kind, y_target, scale)
-        self.last_dlogits = dl
-        D, T, kp = self.D, self.T, self.head_kpad
         rows = B * T
-        dlb = self._dlogits_rows(dl, 'g_dl', B, kp)
-        dpool = self._act('g_pool', (B, D))
-        self._mm(dlb, self.head_wd, dpool, B, D, kp)
         dln = self._act('g_ln', (B, T, D))
-        if self.x3:
-            _lib.check(lib.rart_cnx_pool_bwd_pair(_lib.ptr(dpool[0]), _lib.ptr(dpool[1]), _lib.ptr(dln[0]), _lib.ptr(dln[1]), B, T, D, sp))
-        else:
-            _lib.check(lib.rart_cnx_pool_bwd_bf16(_lib.ptr(dpool), _lib.ptr(dln), B, T, D, sp))
+        self._pool_bwd(dpool, dln, B, T, D)
         dx = self._act('g_x', (B, T, D))
         self._ln_bwd(dln, x_last, self.ng, None, dx, rows, D)
         dxm = self._act('g_xm', (B, T, D))

@@ -18,25 +18,11 @@ gradient arena, train/arena.py); `on_grad_ready(param)` lets the arena launch a 
 import ctypes
 
 from .. import _lib
-from .engine_base import F_GELU_BWD, tokmix_wgrad_desc, wgrad_split_tokens
+from .engine_base import F_GELU_BWD, RowTrainMixin, tokmix_wgrad_desc, wgrad_split_tokens
 from .mixer_engine import MixerEngine
 
 
-class MixerTrainEngine(MixerEngine):
-    def __init__(self, model, device='cuda', on_grad_ready=None):
-        super().__init__(model, device)
-        self.model = model
-        self.on_grad_ready = on_grad_ready or (lambda p: None)
-
-    def repack(self):
-        """fp32 master weights -> bf16 tables; call after every optimizer step."""
-        self.refold(self.model)
-
-    def forward(self, src, src_is_u8, mean, std):
-        if not src_is_u8:
-            src = src.detach().float().contiguous()
-        return self._forward(src, src_is_u8, mean, std, keep=True)
-
+class MixerTrainEngine(RowTrainMixin, MixerEngine):
     # ------------------------------------------------------------------ token-mixing parameter gradients
     def _tok_wgrad(self, p, q, M, N, B, grad, accumulate=0):
         """grad[M][N] (+)= sum_b sum_d p_b[m][d] q_b[n][d] for dense bf16 slabs p [B][M][D], q [B][N][D]: rart_tokmix_wgrad_bf16 over
@@ -79,9 +65,9 @@ class MixerTrainEngine(MixerEngine):
         dpool = self._get('g_pool', (B, D))
         self._mm(dlb, self.head_wd, dpool, B, D, kp)
         dln = self._get('g_ln', (B, T, D))
-        _lib.check(lib.rart_cnx_pool_bwd_bf16(_lib.ptr(dpool), _lib.ptr(dln), B, T, D, sp))
+        self._pool_bwd(dpool, dln, B, T, D)
         dx = self._get('g_x', (B, T, D))
-        self._ln_bwd_full(dln, x_last, self.ng, None, dx, rows, (D, D, 0, D), m.norm)
+        self._ln_bwd_full(dln, x_last, self.ng, None, dx, rows, D, m.norm)
         dxm = self._get('g_xm', (B, T, D))
         ln = self._get('ln', (B, T, D))
         for li in range(len(self.layers) - 1, -1, -1):
@@ -102,7 +88,7 @@ class MixerTrainEngine(MixerEngine):
             self._colsum(dh, Hc, rows, Hc, mc.fc1.bias.grad)
             self.on_grad_ready(mc.fc1.bias)
             self._mm(dh, L['fc1_wd'], dln, rows, D, Hc)
-            self._ln_bwd_full(dln, xm, L['n2g'], dx, dxm, rows, (D, D, D, D), blk.norm2)
+            self._ln_bwd_full(dln, xm, L['n2g'], dx, dxm, rows, D, blk.norm2)
             # ---- token mixing: xm = x_in + W2 gelu(W1 LN1(x_in) + b1) + b2, per image and channel
             htok = self._get('htok', (B, Ht, D))
             _lib.check(lib.rart_gelu_bf16(_lib.ptr(u_tok), _lib.ptr(htok), u_tok.numel(), sp))
@@ -118,7 +104,7 @@ class MixerTrainEngine(MixerEngine):
             self._tok_rowsum(dht, Ht, B, mt.fc1.bias.grad)
             self.on_grad_ready(mt.fc1.bias)
             self._tokmix(L['t1d'], dht, dln, T, Ht, B)
-            self._ln_bwd_full(dln, x_in, L['n1g'], dxm, dx, rows, (D, D, D, D), blk.norm1)
+            self._ln_bwd_full(dln, x_in, L['n1g'], dxm, dx, rows, D, blk.norm1)
         # ---- stem: x0 = patch_embed(patches) + bias
         self._colsum(dx, D, rows, D, m.stem.proj.bias.grad)
         self.on_grad_ready(m.stem.proj.bias)

@@ -17,8 +17,7 @@ import os
 from .. import _lib
 from .convstem_engine import ConvStem
 from .convstem_torch import convstem_of
-from .engine_base import (F_GELU_BWD, F_OUT_F32, GP_OUT_F32, RowEngine, cints, interleave_k32, k32, lo_off, pad_k, pad_rows, pair,
-                          rows_mult)
+from .engine_base import F_GELU_BWD, F_OUT_F32, GP_OUT_F32, RowEngine, cints, k32
 
 
 class ViTEngine(RowEngine):
@@ -40,43 +39,15 @@ class ViTEngine(RowEngine):
         """(Re)build every weight table from `model`'s current parameters, in the engine's precision.  Parameters already on the
         GPU are packed there (a dozen small torch ops per layer), so the adversarial-training loop can refresh the attack engine
         every iteration, like ResNet50Engine.refold."""
-        torch = _lib.require_gpu()
-        m, dev = model, self.device
+        m, f32 = model, self._f32
         self._w_il = {}
-
-        def f32(t):
-            return t.detach().to(dev, torch.float32).contiguous()
-
-        def bf(w2d):                                         # fp32 [rows][k] (any device) -> bf16 on the engine's device
-            return w2d.detach().to(dev, torch.float32).to(torch.bfloat16)
-
-        def tab(w2d, k_pad=None):
-            """pair table [2][rows][K]; rows padded to the 256-row tile of rart_gemm_pair_bf16 (zero, never stored)"""
-            t = pair(pad_rows(pad_k(w2d.detach().to(dev, torch.float32), k_pad), 256))
-            if self.pair_w_interleaved and t.shape[2] % 32 == 0:
-                # per row and 32-deep K step the hi slice then the lo slice (GP_W_INTERLEAVED: one 128-byte line per row and step);
-                # kept beside the planes, keyed by their address
-                self._w_il[t.data_ptr()] = interleave_k32(t[0], t[1])
-            return t
-
-        def fwd(w):                                          # forward table W [out][in]
-            return tab(w) if self.x3 else pad_rows(bf(w), rows_mult(w.shape[0]))
-
-        def bwd(w, k_pad=None):                              # backward-to-input table W^T [in][out]: dx[rows][in] = dy[rows][out] . W
-            if self.x3:
-                return tab(w.t(), k_pad)
-            t = pad_k(bf(w).t(), k_pad)
-            return pad_rows(t, rows_mult(t.shape[0]))
+        il = dict(interleave=self.pair_w_interleaved)       # `_table`: the copies of the pair tables in `_w_il`
         cvst = convstem_of(m)
         self.cvst = ConvStem(self, cvst) if cvst is not None else None                 # `vit_base_cvst`: the patch embedding is its chain
         if self.cvst is None:
             pe = m.patch_embed.weight.detach().reshape(self.D, -1)                     # [D][c*ps*ps + r*ps + s]
-            if self.x3:
-                self.pe_w = fwd(pe)
-            else:
-                peb = bf(pe)
-                self.pe_w = pad_rows(torch.cat([peb, peb], 1), 128)                    # [hi | hi] columns: the taps of the image pair
-            self.pe_wd = bwd(pe)
+            self.pe_w = self._input_table(pe, 128, **il)
+            self.pe_wd = self._table(pe, transpose=True, **il)
             self.pe_b = f32(m.patch_embed.bias)
         pos = f32(m.pos_embed)[0]
         self.pos = pos.contiguous()
@@ -84,29 +55,23 @@ class ViTEngine(RowEngine):
         self.tokens = pos.shape[0]
         self.layers = []
         for blk in m.blocks:
-            self.layers.append(dict(
-                n1g=f32(blk.norm1.weight), n1b=f32(blk.norm1.bias), n2g=f32(blk.norm2.weight), n2b=f32(blk.norm2.bias),
-                qkv_w=fwd(blk.attn.qkv.weight), qkv_b=f32(blk.attn.qkv.bias),
-                proj_w=fwd(blk.attn.proj.weight), proj_b=f32(blk.attn.proj.bias),
-                fc1_w=fwd(blk.fc1.weight), fc1_b=f32(blk.fc1.bias),
-                fc2_w=fwd(blk.fc2.weight), fc2_b=f32(blk.fc2.bias), hidden=blk.fc1.out_features,
-                qkv_wd=bwd(blk.attn.qkv.weight), proj_wd=bwd(blk.attn.proj.weight),
-                fc1_wd=bwd(blk.fc1.weight), fc2_wd=bwd(blk.fc2.weight)))
+            L = dict(n1g=f32(blk.norm1.weight), n1b=f32(blk.norm1.bias), n2g=f32(blk.norm2.weight), n2b=f32(blk.norm2.bias),
+                     hidden=blk.fc1.out_features)
+            for name, lin in (('qkv', blk.attn.qkv), ('proj', blk.attn.proj), ('fc1', blk.fc1), ('fc2', blk.fc2)):
+                L[name + '_w'], L[name + '_b'] = self._table(lin.weight, **il), f32(lin.bias)
+                L[name + '_wd'] = self._table(lin.weight, transpose=True, **il)     # dx[rows][in] = dy[rows][out] . W
+            self.layers.append(L)
         self.ng, self.nb = f32(m.norm.weight), f32(m.norm.bias)
         self.n_classes = m.head.out_features
-        self.head_w = fwd(m.head.weight)
+        self.head_w = self._table(m.head.weight, **il)
         self.head_b = f32(m.head.bias)
         self.head_kpad = k32(self.n_classes)
-        self.head_wd = bwd(m.head.weight, self.head_kpad)
+        self.head_wd = self._table(m.head.weight, self.head_kpad, transpose=True, **il)
 
     # ------------------------------------------------------------------ forward
     def _forward(self, src, src_is_u8, mean, std, keep=False):
-        torch = _lib.require_gpu()
         lib, sp = self.lib, _lib.stream_ptr()
-        if src_is_u8:
-            B, Himg, Wimg = src.shape[0], src.shape[1], src.shape[2]
-        else:
-            B, Himg, Wimg = src.shape[0], src.shape[2], src.shape[3]
+        B, Himg, Wimg = self._image_dims(src, src_is_u8)
         D, ps = self.D, self.ps
         P = (Himg // ps) * (Wimg // ps)
         T = P + 1
@@ -120,10 +85,7 @@ class ViTEngine(RowEngine):
             self.cvst.forward(src, src_is_u8, mean, std, B, Himg, Wimg, x, **slot)
         else:
             patches = self._patchify(src, src_is_u8, mean, std, B, Himg, Wimg, ps)
-            if self.x3:
-                self._mm(patches, self.pe_w, x, B * P, D, kk, bias=self.pe_b, **slot)
-            else:       # the image pair as two taps of the [hi | hi]-column table
-                self._gemm(patches[0], self.pe_w, x, B * P, kk, D, kk, D, bias=self.pe_b, n_taps=2, tap_src_off=[0, lo_off(patches)], **slot)
+            self._input_gemm(patches, self.pe_w, x, B * P, D, kk, bias=self.pe_b, **slot)
         if self.x3:
             _lib.check(lib.rart_vit_add_pos_cls_pair(xh, xl, _lib.ptr(self.cls_pos0), _lib.ptr(self.pos), B, T, D, sp))
         else:
@@ -157,9 +119,7 @@ class ViTEngine(RowEngine):
             self._saved = (saved, x, (B, Himg, Wimg, P, T))
         cls = self._act('cls', (B, D))
         self._ln(x, self.ng, self.nb, cls, B, D, ld_in=T * D)                # the class-token row of every image
-        logits = torch.empty(B, self.n_classes, dtype=torch.float32, device=self.device)
-        self._mm(cls, self.head_w, logits, B, self.n_classes, D, bias=self.head_b, flags=F_OUT_F32)
-        return logits
+        return self._head_logits(cls, B, D)
 
     # ------------------------------------------------------------------ attention, per (image, head)
     def _pair_fused(self, T):
@@ -322,17 +282,11 @@ class ViTEngine(RowEngine):
     def forward_backward(self, x01, mean, std, y, kind, y_target=None, scale=1.0):
         """-> (logits fp32, loss_indiv, d(sum_i scale*loss_i)/dx01 fp32 NCHW, pred int32); same contract as
         ResNet50Engine.forward_backward."""
-        from ..noise.adv import logit_loss
         torch = _lib.require_gpu()
-        x01 = x01.detach().float().contiguous()
-        logits = self._forward(x01, False, mean, std, keep=True)
+        D = self.D
+        logits, loss, pred, dcls = self._forward_loss(x01, mean, std, y, kind, y_target, scale, 'dcls', D)
         saved, x_last, (B, Himg, Wimg, P, T) = self._saved
-        loss, dl, pred = logit_loss(logits, y, kind, y_target, scale)
-        self.last_dlogits = dl           # exposed for the parity tests (same upstream gradient for the reference)
-        D, rows, kp = self.D, B * T, self.head_kpad
-        dlb = self._dlogits_rows(dl, 'g_dl', B, kp)
-        dcls = self._act('dcls', (B, D))
-        self._mm(dlb, self.head_wd, dcls, B, D, kp)
+        rows = B * T
         dx = self._act('g_x_a', (B, T, D))
         dx.zero_()                                      # only the class token receives gradient from the head
         self._ln_bwd(dcls, x_last, self.ng, None, dx, B, D, strides=(D, T * D, 0, T * D))

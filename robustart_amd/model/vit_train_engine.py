@@ -14,25 +14,11 @@ Gradients are written into the parameters' `.grad` tensors (views of the flat gr
 `on_grad_ready(param)` lets the arena launch a bucket's all-reduce as soon as its last gradient exists.
 """
 from .. import _lib
-from .engine_base import F_GELU_BWD
+from .engine_base import F_GELU_BWD, RowTrainMixin
 from .vit_engine import ViTEngine
 
 
-class ViTTrainEngine(ViTEngine):
-    def __init__(self, model, device='cuda', on_grad_ready=None):
-        super().__init__(model, device)
-        self.model = model
-        self.on_grad_ready = on_grad_ready or (lambda p: None)
-
-    def repack(self):
-        """fp32 master weights -> bf16 tables; call after every optimizer step."""
-        self.refold(self.model)
-
-    def forward(self, src, src_is_u8, mean, std):
-        if not src_is_u8:
-            src = src.detach().float().contiguous()
-        return self._forward(src, src_is_u8, mean, std, keep=True)
-
+class ViTTrainEngine(RowTrainMixin, ViTEngine):
     # ------------------------------------------------------------------ backward to every parameter
     def backward(self, dlogits):
         """dlogits: fp32 [B][classes] = d(loss)/dlogits of the last forward().  Fills .grad of every parameter."""
@@ -46,10 +32,10 @@ class ViTTrainEngine(ViTEngine):
         dlb = self._dlogits_rows(dl, 'g_dl', B, self.head_kpad)
         self._linear_grads(m.head, dlb, self.head_kpad, self._buf['cls'], B)
         dcls = self._get('dcls', (B, D))
-        self._gemm(dlb, self.head_wd, dcls, B, self.head_kpad, D, self.head_kpad, D)
+        self._mm(dlb, self.head_wd, dcls, B, D, self.head_kpad)
         dx = self._get('g_x_a', (B, T, D))
         dx.zero_()
-        self._ln_bwd_full(dcls, x_last, self.ng, None, dx, B, (D, T * D, 0, T * D), m.norm)
+        self._ln_bwd_full(dcls, x_last, self.ng, None, dx, B, D, m.norm, strides=(D, T * D, 0, T * D))
         dqkv = self._get('g_qkv', (rows, 3 * D))
         ln = self._get('ln', (B, T, D))
         for li in range(len(self.layers) - 1, -1, -1):
@@ -63,29 +49,29 @@ class ViTTrainEngine(ViTEngine):
             self._colsum(dx, D, rows, D, blk.fc2.bias.grad)
             self.on_grad_ready(blk.fc2.bias)
             dh = self._get('g_hid', (rows, hidden))
-            self._gemm(dx, L['fc2_wd'], dh, rows, D, hidden, D, hidden, mask=u, flags=F_GELU_BWD)     # du = (dx W2) * gelu'(u)
+            self._mm(dx, L['fc2_wd'], dh, rows, hidden, D, flags=F_GELU_BWD, aux=u)                   # du = (dx W2) * gelu'(u)
             self._ln(xm, L['n2g'], L['n2b'], ln, rows, D)
             self._linear_grads(blk.fc1, dh, hidden, ln, rows)
             self._colsum(dh, hidden, rows, hidden, blk.fc1.bias.grad)
             self.on_grad_ready(blk.fc1.bias)
             dln = self._get('g_ln', (rows, D))
-            self._gemm(dh, L['fc1_wd'], dln, rows, hidden, D, hidden, D)
+            self._mm(dh, L['fc1_wd'], dln, rows, D, hidden)
             dxm = self._get('g_xm', (B, T, D))
-            self._ln_bwd_full(dln, xm, L['n2g'], dx, dxm, rows, (D, D, D, D), blk.norm2)
+            self._ln_bwd_full(dln, xm, L['n2g'], dx, dxm, rows, D, blk.norm2)
             # ---- attention: xm = x_in + proj(attn(LN1(x_in)))
             self._linear_grads(blk.attn.proj, dxm, D, att, rows)
             self._colsum(dxm, D, rows, D, blk.attn.proj.bias.grad)
             self.on_grad_ready(blk.attn.proj.bias)
             datt = self._get('g_att', (rows, D))
-            self._gemm(dxm, L['proj_wd'], datt, rows, D, D, D, D)
+            self._mm(dxm, L['proj_wd'], datt, rows, D, D)
             _lib.check(lib.rart_vit_attention_bwd(_lib.ptr(qkv), _lib.ptr(att), _lib.ptr(datt), _lib.ptr(dqkv), B, T, self.H,
                                                   self.hd, sp))
             self._ln(x_in, L['n1g'], L['n1b'], ln, rows, D)
             self._linear_grads(blk.attn.qkv, dqkv, 3 * D, ln, rows)
             self._colsum(dqkv, 3 * D, rows, 3 * D, blk.attn.qkv.bias.grad)
             self.on_grad_ready(blk.attn.qkv.bias)
-            self._gemm(dqkv, L['qkv_wd'], dln, rows, 3 * D, D, 3 * D, D)
-            self._ln_bwd_full(dln, x_in, L['n1g'], dxm, dx, rows, (D, D, D, D), blk.norm1)
+            self._mm(dqkv, L['qkv_wd'], dln, rows, D, 3 * D)
+            self._ln_bwd_full(dln, x_in, L['n1g'], dxm, dx, rows, D, blk.norm1)
         # ---- embeddings: x0[b][0] = cls + pos[0]; x0[b][1+p] = patch_embed(patch p) + pos[1+p]
         # derive every gradient that READS pos_embed.grad before the first on_grad_ready: with a small dist.bucket_mb the
         # {cls_token, pos_embed} bucket would otherwise start its asynchronous all-reduce (in place, on the RCCL stream)

@@ -1,33 +1,14 @@
 """The shared launch layer (robustart_amd/model/engine_base.py) without a GPU: descriptors built from CPU tensors, field by field,
 through the builders and through the engines' adapters with the library call replaced by a recorder."""
+import importlib.util
+import json
+import os
+
 import torch
+from _recorder import Recorder as _Recorder
 
 from robustart_amd import _lib
 from robustart_amd.model import engine_base as eb
-
-
-class _Recorder:
-    """stands in for the library: answers every rart_* entry and records (name, arguments); `descs`: the descriptors of the GEMM launches"""
-
-    def __init__(self):
-        self.calls, self.gemm256, self.supported = [], 0, None      # supported(name, args): the answer of every rart_*_supported
-
-    @property
-    def descs(self):
-        return [a[0]._obj for n, a in self.calls if n in ('rart_conv_igemm_bf16', 'rart_gemm_pair_bf16')]
-
-    def __getattr__(self, name):
-        if not name.startswith('rart_'):
-            raise AttributeError(name)
-        if name == 'rart_gemm256_supported':
-            return lambda *a: self.gemm256
-        if name.endswith('_supported') and self.supported is not None:
-            return lambda *a: self.supported(name, a)
-
-        def call(*args):
-            self.calls.append((name, args))
-            return 0
-        return call
 
 
 def _engine(cls, monkeypatch, **attrs):
@@ -798,3 +779,26 @@ def test_both_resnet_engines_build_from_the_one_geometry():
     w = torch.randn(64, 3, 7, 7)
     rows = eb.stem_rows(w).view(64, 7, 8, 4)
     assert torch.equal(rows[:, :, :7, :3], w.permute(0, 2, 3, 1)) and not rows[:, :, 7].any() and not rows[..., 3].any()
+
+
+# ---------------------------------------------------------------------- the row engines against the recorded trace
+def test_row_engines_launch_what_the_recorded_trace_says():
+    """every launch (entry, scalars, descriptor fields, pointers by buffer / table name) and every weight table (shape, dtype, bytes)
+    of the row engines and their train engines on tiny modules, in both precisions, equals tests/golden/row_engine_trace.json, which
+    tests/golden/make_row_engine_trace.py recorded before these engines moved onto RowEngine's table builder and call path"""
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+    spec = importlib.util.spec_from_file_location('make_row_engine_trace', os.path.join(golden, 'make_row_engine_trace.py'))
+    make = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(make)
+    with open(os.path.join(golden, 'row_engine_trace.json')) as f:
+        want = json.load(f)
+    got = make.record()
+    assert sorted(got) == sorted(want)
+    for case in sorted(want):
+        w, g = want[case], got[case]
+        for i, (a, b) in enumerate(zip(w['launches'], g['launches'])):
+            assert a == b, '%s: launch %d is %s, recorded %s' % (case, i, b, a)
+        assert len(w['launches']) == len(g['launches']), case
+        assert sorted(w['tables']) == sorted(g['tables']), case
+        for name in sorted(w['tables']):
+            assert w['tables'][name] == g['tables'][name], '%s: table %s' % (case, name)

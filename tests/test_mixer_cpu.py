@@ -6,6 +6,7 @@ import re
 
 import pytest
 import torch
+from _recorder import Recorder as _Recorder
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ['rart_tokmix_bf16', 'rart_tokmix_pair']
@@ -202,22 +203,6 @@ def test_argument_checks_of_the_tokmix_entries_without_gpu():
 
 
 # ---------------------------------------------------------------------- the engine's descriptors, recorded
-class _Recorder:
-    def __init__(self):
-        self.calls = []
-
-    def _rec(self, kind):
-        def f(d, stream):
-            self.calls.append((kind, d._obj))
-            return 0
-        return f
-
-    def __getattr__(self, name):
-        if name.startswith('rart_tokmix_') or name in ('rart_conv_igemm_bf16', 'rart_gemm_pair_bf16'):
-            return self._rec(name)
-        raise AttributeError(name)
-
-
 def _cpu_engine(monkeypatch, model, precision):
     from robustart_amd import _lib
     from robustart_amd.model.engine_base import check_precision
@@ -272,7 +257,7 @@ def test_token_gemm_descriptors(monkeypatch, precision):
     eng._tokmix(L['t1d'], h, ln, T, Ht, B)
     kinds = [k for k, _ in eng.lib.calls]
     assert kinds == ['rart_tokmix_pair' if x3 else 'rart_tokmix_bf16'] * 4
-    d = [c for _, c in eng.lib.calls]
+    d = [a[0]._obj for _, a in eng.lib.calls]
 
     def planes(t):
         return (t[0].data_ptr(), t[1].data_ptr()) if x3 else (t.data_ptr(), None)

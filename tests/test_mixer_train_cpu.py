@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 import torch
+from _recorder import Recorder as _Recorder
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ['rart_tokmix_wgrad_bf16', 'rart_tok_rowsum_workspace_bytes', 'rart_tok_rowsum_bf16']
@@ -155,22 +156,6 @@ def test_the_split_rule_at_the_training_batch():
 
 
 # ---------------------------------------------------------------------- the engine's launches, recorded
-class _Recorder:
-    """stands in for the library: every rart_* call is recorded and succeeds"""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        if not name.startswith('rart_'):
-            raise AttributeError(name)
-
-        def f(*args):
-            self.calls.append((name, args))
-            return 4096 if name.endswith('_workspace_bytes') else 0
-        return f
-
-
 def _val(a):
     return a.value if isinstance(a, ctypes.c_void_p) else a
 
