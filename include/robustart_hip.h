@@ -814,6 +814,25 @@ int rart_label_smooth_ce_mix_f32(const float* logits, const int64_t* labels_a, c
 int rart_mix_batch_f32(const void* src, int src_is_u8, const int32_t* perm, float* dst, int n, int h, int w, int mode, double lam,
                        int y0, int y1, int x0, int x1, rart_stream_t stream);
 
+/* ---- ColorJitter of a batch (csrc/color_jitter.hip; robustart_amd/train/jitter.py) -----------------------------------------------------
+ * torchvision's ColorJitter on PIL images is a chain of Pillow calls; this entry computes the same bytes on uint8 NHWC [n][h][w][3].
+ * One record per sample: up to four operations in application order,
+ *   0 brightness  Image.blend(black, img, factor[0])           1 contrast    Image.blend(grey(m), img, factor[1]), m = int(mean(L) + 0.5)
+ *   2 saturation  Image.blend(L as RGB, img, factor[2])        3 hue         RGB -> HSV, H += hue_shift (mod 256), HSV -> RGB
+ * with Pillow's convert('L'), blend (fp32, product and sum rounded separately, clamped, truncated) and HSV conversions; the contrast
+ * mean is taken of the image as the operations before it left it.  An id outside 0..3, or one that an earlier slot of the record already
+ * carries, skips the slot; a record of four skips copies the sample.  The records live on the device and are not inspected by the
+ * host: the caller validates them before the upload (robustart_amd/train/jitter.py, pack_jitter). */
+typedef struct rart_jitter_rec {
+  uint8_t op[4];      /* operation ids in application order */
+  float factor[3];    /* blend factors of brightness, contrast, saturation (indexed by id), >= 0 */
+  uint32_t hue_shift; /* 0..255 */
+} rart_jitter_rec;    /* 20 bytes, no padding */
+/* dst == src (in place) or disjoint buffers; any other overlap is refused.  params: n records on the device.  lsum: n words of device
+ * workspace (the per-sample luminance sums of the contrast mean); the entry clears it on `stream` itself.  h * w <= 2^24 (the 32-bit
+ * luminance sum), n * h * w * 3 < 2^32.  Two launches: the luminance sums of the samples with a contrast slot, then every slot per pixel. */
+int rart_color_jitter_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, const void* params, uint32_t* lsum, rart_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * Train-mode conv + BatchNorm support (cls_solver training step): the contractions run on
  * rart_conv_igemm_bf16; these are the HBM-bound kernels around it.  Activations are bf16 [rows][channels]

@@ -212,6 +212,7 @@ SIGNATURES = {
                                              c_void_p, c_void_p]),
     'rart_mix_batch_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_int,
                                    c_int, c_void_p]),
+    'rart_color_jitter_u8': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'rart_bn_workspace_bytes': (c_size_t, [c_size_t, c_int]),
     'rart_bn_train_forward_bf16': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
@@ -245,6 +246,11 @@ class ConvDesc(ctypes.Structure):
                 ('src_z_outer', ctypes.c_int64), ('src_z_inner', ctypes.c_int64), ('wgt_z_outer', ctypes.c_int64),
                 ('wgt_z_inner', ctypes.c_int64), ('dst_z_outer', ctypes.c_int64), ('dst_z_inner', ctypes.c_int64),
                 ('sign_out', c_void_p), ('dst_pair_off', ctypes.c_int64), ('res_pair_off', ctypes.c_int64), ('bn_stats_out', c_void_p)]
+
+
+class JitterRec(ctypes.Structure):
+    """rart_jitter_rec (include/robustart_hip.h): one sample's ColorJitter plan, 20 bytes."""
+    _fields_ = [('op', ctypes.c_uint8 * 4), ('factor', ctypes.c_float * 3), ('hue_shift', ctypes.c_uint32)]
 
 
 class FixedPointInfo(ctypes.Structure):

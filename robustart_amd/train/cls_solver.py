@@ -119,18 +119,22 @@ def read_meta_file(path):
 
 
 class FileImageNet(torch.utils.data.Dataset):
-    """`data.read_from: fs` with `data.<split>.{root_dir, meta_file, image_reader.type: pil, transforms.type}`
-    (exp/imagenet_c_loop_mini/config_vit_base.yaml:80-104): files are decoded on the host by PIL (the reference's 'pil'
+    """`data.read_from: fs` with `data.<split>.{root_dir, meta_file, image_reader.type: pil, transforms}`
+    (exp/imagenet_c_loop_mini/config_vit_base.yaml:80-104; `transforms` as the mapping {type: ...} or as a list of torchvision entries,
+    read_transforms): files are decoded on the host by PIL (the reference's 'pil'
     reader) and the transform's arithmetic runs on the GPU:
       ONECROP  = Resize([test_resize, test_resize]) (PIL bilinear, what torchvision applies to a PIL image) + CenterCrop(
                  input_size) -> rart_pil_resize_u8 with the fused centre crop, bit-exact with Pillow;
       STANDARD = RandomResizedCrop(input_size) + RandomHorizontalFlip: the crop box / flip are drawn on the host from
                  (seed, global index) (a pure function of the sample, like every draw of this path), the resize runs in
-                 the same kernel.  ColorJitter of the reference's commented variant is not applied.
+                 the same kernel.  `flip=False` (a transform list without RandomHorizontalFlip) never flips.  `jitter` (the ranges of
+                 a list's ColorJitter entry, train/jitter.py) is applied to the finished uint8 batch after the resize and the flip,
+                 one rart_color_jitter_u8 call for the whole batch, bit-exact with Pillow; the mapping form carries no jitter.
     Output is the uint8 NHWC batch the corruption kernels and the engines' u8 entry consume; normalisation happens in
     the engine's input kernel."""
 
-    def __init__(self, root_dir, meta_file, size=224, test_resize=256, transform='ONECROP', reader='pil', limit=None, seed=0):
+    def __init__(self, root_dir, meta_file, size=224, test_resize=256, transform='ONECROP', reader='pil', limit=None, seed=0,
+                 jitter=None, flip=True):
         if reader != 'pil':
             raise NotImplementedError("image_reader.type %r: only 'pil' is available in this build" % (reader,))
         if transform not in ('ONECROP', 'STANDARD'):
@@ -140,6 +144,7 @@ class FileImageNet(torch.utils.data.Dataset):
             self.items = self.items[:int(limit)]
         self.size, self.test_resize, self.transform, self.seed = int(size), int(test_resize), transform, int(seed)
         self.n = len(self.items)
+        self.jitter, self.flip = jitter, bool(flip)
 
     def __len__(self):
         return self.n
@@ -183,8 +188,110 @@ class FileImageNet(torch.utils.data.Dataset):
                 y, x, h, w, flip = self.box(i, arr.shape[:2], epoch)
                 src = torch.from_numpy(arr[y:y + h, x:x + w].copy()).to(dev, non_blocking=True)[None]
                 img = pil_resize(src, (self.size, self.size), 1)[0]
-                out[k] = img.flip(1) if flip else img
+                out[k] = img.flip(1) if flip and self.flip else img
+        if self.transform == 'STANDARD' and self.jitter is not None:
+            from .jitter import apply_jitter, draw_jitter
+            apply_jitter(out, [draw_jitter(self.jitter, self.seed, epoch, i) for i in indices])
         return out, torch.tensor(labs, dtype=torch.int64, device=dev)
+
+
+def _entry(e, where):
+    """one entry of a transform list -> (type, kwargs)"""
+    if isinstance(e, str):
+        return e, {}
+    if not isinstance(e, dict) or not isinstance(e.get('type'), str) or not isinstance(e.get('kwargs') or {}, dict):
+        raise ValueError('%s: an entry must be a mapping {type: NAME, kwargs: {...}}, got %r' % (where, e))
+    return e['type'], dict(e.get('kwargs') or {})
+
+
+def _square(v, where):
+    """`size: s` or `size: [s, s]` -> s; None when the two sides differ"""
+    if isinstance(v, (list, tuple)):
+        if len(v) == 1:
+            v = [v[0], v[0]]
+        if len(v) != 2 or any(isinstance(s, bool) or not isinstance(s, int) for s in v):
+            raise ValueError('%s: size must be an int or a pair of ints, got %r' % (where, v))
+        return int(v[0]) if v[0] == v[1] else None
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise ValueError('%s: size must be an int or a pair of ints, got %r' % (where, v))
+    return int(v)
+
+
+_LIST_TYPES = ('RandomResizedCrop', 'RandomHorizontalFlip', 'ColorJitter', 'ToTensor', 'Normalize', 'Resize', 'CenterCrop')
+
+
+def read_transforms(dcfg, split):
+    """`data.<split>.transforms` in either form -> {'type': 'ONECROP' / 'STANDARD', 'test_resize': int, 'jitter': ranges or None,
+    'flip': bool}, the arguments FileImageNet takes.
+      mapping {type: T} (or absent):  T (default ONECROP for test, STANDARD otherwise), data.test_resize, no jitter, flip on.
+      list, a split other than test (exp/imagenet_s_loop/config_convnext_base.yaml:61-77): RandomResizedCrop(size = data.input_size),
+          [RandomHorizontalFlip], [ColorJitter(...)], ToTensor, Normalize -> STANDARD, the jitter ranges of train/jitter.py, flip only
+          when the entry is there.
+      list, the test split (same file :88-101): Resize([r, r]) or Resize(r), CenterCrop(data.input_size), ToTensor, Normalize
+          -> ONECROP with test_resize = r.
+    ToTensor + Normalize are the engines' input kernel, which applies the ImageNet constants: another mean / std, a non-square Resize
+    and any entry type outside these raise NotImplementedError; an entry out of place or a size other than data.input_size, ValueError."""
+    sec = dcfg.get(split) or {}
+    tr = sec.get('transforms')
+    size = int(dcfg.get('input_size', 224))
+    train = split != 'test'                # as the mapping form's default reads the split
+    where = 'data.%s.transforms' % split
+    if not tr or isinstance(tr, dict):                 # absent, null or empty reads as the mapping form's defaults, as before
+        return {'type': (tr or {}).get('type', 'STANDARD' if train else 'ONECROP'), 'test_resize': int(dcfg.get('test_resize', 256)),
+                'jitter': None, 'flip': True}
+    if not isinstance(tr, (list, tuple)):
+        raise ValueError('%s: a mapping {type: ...} or a list of torchvision entries, got %r' % (where, tr))
+    entries = [_entry(e, where) for e in tr]
+    for t, _ in entries:
+        if t not in _LIST_TYPES:
+            raise NotImplementedError('%s: entry type %r is not available in this build (%s)' % (where, t, ', '.join(_LIST_TYPES)))
+    names = [t for t, _ in entries]
+    if names[-2:] != ['ToTensor', 'Normalize']:
+        raise ValueError('%s: the list must end with ToTensor, Normalize, got %s' % (where, names))
+    nk = entries[-1][1]
+    mean, std = nk.get('mean', IMAGENET_MEAN), nk.get('std', IMAGENET_STD)
+    if [float(v) for v in mean] != list(IMAGENET_MEAN) or [float(v) for v in std] != list(IMAGENET_STD):
+        raise NotImplementedError('%s: Normalize mean %r std %r: the solver applies the ImageNet constants %r / %r only'
+                                  % (where, mean, std, IMAGENET_MEAN, IMAGENET_STD))
+    head = entries[:-2]
+    out = {'type': 'STANDARD' if train else 'ONECROP', 'test_resize': int(dcfg.get('test_resize', 256)), 'jitter': None, 'flip': False}
+    if train:
+        if not head or head[0][0] != 'RandomResizedCrop':
+            raise ValueError('%s: a train list must start with RandomResizedCrop, got %s' % (where, names))
+        kw = head[0][1]
+        if set(kw) - {'size'}:
+            raise NotImplementedError('%s: RandomResizedCrop kwargs %s (only size; scale and ratio keep torchvision\'s defaults)'
+                                      % (where, sorted(set(kw) - {'size'})))
+        if _square(kw.get('size'), where + ' RandomResizedCrop') != size:
+            raise ValueError('%s: RandomResizedCrop size %r must equal data.input_size %d' % (where, kw.get('size'), size))
+        rest = head[1:]
+        if rest and rest[0][0] == 'RandomHorizontalFlip':
+            if float(rest[0][1].get('p', 0.5)) != 0.5 or set(rest[0][1]) - {'p'}:
+                raise NotImplementedError('%s: RandomHorizontalFlip kwargs %r (only p = 0.5)' % (where, rest[0][1]))
+            out['flip'] = True
+            rest = rest[1:]
+        if rest and rest[0][0] == 'ColorJitter':
+            from .jitter import jitter_ranges
+            out['jitter'] = jitter_ranges(rest[0][1])
+            rest = rest[1:]
+        if rest:
+            raise ValueError('%s: %s is out of place: a train list is RandomResizedCrop, [RandomHorizontalFlip], [ColorJitter], ToTensor, '
+                             'Normalize' % (where, rest[0][0]))
+        return out
+    if [t for t, _ in head] != ['Resize', 'CenterCrop']:
+        raise ValueError('%s: a test list must be Resize, CenterCrop, ToTensor, Normalize, got %s' % (where, names))
+    (_, rk), (_, ck) = head
+    if set(rk) - {'size'} or set(ck) - {'size'}:
+        raise NotImplementedError('%s: Resize / CenterCrop kwargs other than size (%s)' % (where, sorted((set(rk) | set(ck)) - {'size'})))
+    r = _square(rk.get('size'), where + ' Resize')
+    if r is None:
+        raise NotImplementedError('%s: a non-square Resize %r (ONECROP resizes to [r, r])' % (where, rk.get('size')))
+    if _square(ck.get('size'), where + ' CenterCrop') != size:
+        raise ValueError('%s: CenterCrop size %r must equal data.input_size %d' % (where, ck.get('size'), size))
+    if r < size:
+        raise ValueError('%s: Resize %d is smaller than the CenterCrop %d' % (where, r, size))
+    out.update(test_resize=r, flip=True)
+    return out
 
 
 def make_dataset(dcfg, n, size, split='test'):
@@ -198,10 +305,10 @@ def make_dataset(dcfg, n, size, split='test'):
         sec = dcfg.get(split) or {}
         if not sec.get('root_dir') or not sec.get('meta_file'):
             raise ValueError('data.read_from: %s needs data.%s.root_dir and data.%s.meta_file' % (rf, split, split))
-        return FileImageNet(sec['root_dir'], sec['meta_file'], size, int(dcfg.get('test_resize', 256)),
-                            (sec.get('transforms') or {}).get('type', 'ONECROP' if split == 'test' else 'STANDARD'),
+        t = read_transforms(dcfg, split)
+        return FileImageNet(sec['root_dir'], sec['meta_file'], size, t['test_resize'], t['type'],
                             (sec.get('image_reader') or {}).get('type', 'pil'), dcfg.get('limit_samples'),
-                            int(dcfg.get('seed', 0)))
+                            int(dcfg.get('seed', 0)), jitter=t['jitter'], flip=t['flip'])
     if rf != 'fake':
         raise NotImplementedError("data.read_from %r ('fake', 'structured', 'fs')" % (rf,))
     return FakeImageNet(n, size)
