@@ -280,8 +280,9 @@ def l1_projection(x2, y2, eps1):
     onto the intersection of the L1 ball around x2 and the box).  Per coordinate the perturbation magnitude |y| shrinks by
     clip(alpha, -u, |y|), u = min(min(1 - x - y, x + y), 0) being what the box alone demands; alpha is the root of the
     piecewise-linear budget equation, found on the sorted breakpoints."""
-    x = x2.clone().float().reshape(x2.shape[0], -1)
-    y = y2.clone().float().reshape(y2.shape[0], -1)
+    dt = torch.float64 if x2.dtype == torch.float64 and y2.dtype == torch.float64 else torch.float32      # fp64 in, fp64 throughout
+    x = x2.clone().to(dt).reshape(x2.shape[0], -1)
+    y = y2.clone().to(dt).reshape(y2.shape[0], -1)
     sigma = y.clone().sign()
     u = torch.min(1 - x - y, x + y)
     u = torch.min(torch.zeros_like(y), u)
