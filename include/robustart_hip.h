@@ -833,6 +833,25 @@ typedef struct rart_jitter_rec {
  * luminance sum), n * h * w * 3 < 2^32.  Two launches: the luminance sums of the samples with a contrast slot, then every slot per pixel. */
 int rart_color_jitter_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, const void* params, uint32_t* lsum, rart_stream_t stream);
 
+/* ---- Prediction / confidence / correctness over a class subset (csrc/logit_confidence.hip; robustart_amd/metrics/confidence.py) -----
+ * What the ImageNet-A / ImageNet-O evaluation keeps of a sample.  logits: fp32 [rows][ld], ld >= classes, no row alignment assumed.
+ * subset: n_subset class indices on the device, each in [0, classes) (NOT range-checked on the device: the caller's contract, as for
+ * the labels of rart_label_smooth_ce_f32); NULL or n_subset == 0 selects all classes.  K = the number of selected classes, z = the K
+ * selected logits of a row in subset order:
+ *   pred[r]    = the LOWEST position in [0, K) that attains max z: a subset coordinate, the label an image-folder dataset over the
+ *                subset's class folders gives its samples
+ *   conf[r]    = 1 / sum_j expf(z_j - max z), the largest soft-max probability over the subset: fp32, accurate expf, IEEE division
+ *   correct[r] = pred[r] == labels[r] (int64, subset coordinates; a label outside [0, K) gives 0); labels == NULL writes 0 everywhere
+ *                (the out-of-distribution set)
+ * Special values: a -inf entry contributes 0; if any selected logit is NaN, conf is NaN and pred the position of the first NaN
+ * (numpy.argmax); a +inf logit or a row of -inf only gives conf = NaN and pred = the first position of the maximum.
+ * One launch, no workspace, no atomics; rows are walked with a grid stride (rows is 64-bit) and K has no ceiling (K <= 1024 is held in
+ * registers, larger K loops over the row twice).  A row's three outputs depend on its K values alone: they are bit-identical whatever
+ * else the launch holds.  rows == 0 returns RART_OK and launches nothing; rows < 0, classes < 1, ld < classes, n_subset outside
+ * [0, classes] or a NULL logits / pred / conf / correct with rows > 0 is RART_ERR_INVALID, decided before any HIP call. */
+int rart_logit_confidence_f32(const float* logits, int64_t rows, int classes, int64_t ld, const int32_t* subset, int n_subset,
+                              const int64_t* labels, int32_t* pred, float* conf, uint8_t* correct, rart_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * Train-mode conv + BatchNorm support (cls_solver training step): the contractions run on
  * rart_conv_igemm_bf16; these are the HBM-bound kernels around it.  Activations are bf16 [rows][channels]

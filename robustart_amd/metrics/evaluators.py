@@ -1,7 +1,15 @@
-"""Evaluators over `results.txt.all` files (see package docstring for the reference anchors)."""
+"""Evaluators over `results.txt.all` files (see package docstring for the reference anchors).
+
+The natural-distribution evaluators at the end (ImageNet-A / -O / -P) read the lines ConfidenceWriter writes.  The reference's
+`ImageNetAEvaluator` (RobustART/metrics/imageneta_evaluator.py) is a line-for-line copy of its ImageNet-P evaluator that keys its
+result dict with a list: it raises TypeError and computes nothing about ImageNet-A.  The one here reports what the reference's
+`calibration_tools.show_calibration_results` logs for that set -- accuracy, RMS calibration error, AURRA.
+"""
 import json
 
 import numpy as np
+
+from . import calibration
 
 
 def parse_line(line):
@@ -161,3 +169,104 @@ def transfer_rate(src_clean_path, tgt_clean_path, transfer_path):
             if e != f:
                 after += 1
     return after / before
+
+
+def _load_confidence(res_file):
+    """(confidence fp64 [n], correct fp64 [n], num_correct) of a ConfidenceWriter file, read as imageneto_evaluator.py:36-42 reads
+    it: the `confidence` and `correct` lists of the lines concatenated, `num_correct` summed."""
+    confidence, correct, num_correct = [], [], 0
+    for line in _lines(res_file):
+        obj = json.loads(line)
+        confidence += obj['confidence']
+        correct += obj['correct']
+        num_correct += obj['num_correct']
+    return np.array(confidence, dtype=np.float64), np.array(correct, dtype=np.float64), num_correct
+
+
+class _MeanOfValues(object):
+    """get_mean as ImageNetSEvaluator carries it: the reference iterates `for key, item in dict`, which unpacks the KEYS; here the
+    mean runs over the values."""
+
+    def get_mean(self):
+        mean = float(np.mean([v for v in self.metric.metric.values() if v is not None]))
+        return {'Mean': mean}
+
+    def clear(self):
+        self.metric.metric = {}
+
+
+class ImageNetAEvaluator(_MeanOfValues):
+    """ImageNet-A: {'top1', 'RMS_calib_error', 'AURRA'}, all in percent (calibration_tools.py:123-130 logs the last two as
+    100 * calib_err(p='2') and 100 * aurra).  beta is calib_err's bin size.  A file of fewer than beta samples has no bin, hence no
+    calibration error (calib_err raises ValueError, the reference IndexError): 'RMS_calib_error' is then None, and the other two
+    numbers are still reported -- ImageNet-A itself has 7500 samples."""
+
+    def __init__(self, beta=100):
+        self.metric = Metric()
+        self.beta = int(beta)
+
+    def eval(self, res_file):
+        confidence, correct, _ = _load_confidence(res_file)
+        if len(confidence) == 0:
+            raise ValueError('ImageNetAEvaluator: %s holds no samples' % res_file)
+        result_dict = {'top1': 100 * float(np.mean(correct)),
+                       'RMS_calib_error': (100 * calibration.calib_err(confidence, correct, p='2', beta=self.beta)
+                                           if len(confidence) >= self.beta else None),
+                       'AURRA': 100 * calibration.aurra(confidence, correct)}
+        self.metric.update(result_dict)
+        return result_dict
+
+
+class ImageNetOEvaluator(_MeanOfValues):
+    """imageneto_evaluator.py:27-63: the anomaly score of a sample is minus its confidence, the out-of-distribution samples are
+    the positive class, and the reported number is 100 * AUPR.  AUROC and FPR95 of the same call stay on `last_measures`."""
+
+    def __init__(self):
+        self.metric = Metric()
+        self.last_measures = None
+
+    def eval(self, res_file_in=None, res_file_out=None):
+        assert res_file_in is not None and res_file_out is not None
+        confidence_in, _, _ = _load_confidence(res_file_in)
+        confidence_out, _, _ = _load_confidence(res_file_out)
+        in_score = -confidence_in
+        out_score = -confidence_out
+        auroc, aupr, fpr = calibration.get_measures(out_score, in_score)
+        self.last_measures = {'AUROC': 100 * auroc, 'AUPR': 100 * aupr, 'FPR95': 100 * fpr}
+        result_dict = {'AUPR': 100 * aupr}
+        self.metric.update(result_dict)
+        return result_dict
+
+    def get_mean(self):
+        out = super().get_mean()
+        self.metric.update(out)               # imageneto_evaluator.py:73-74
+        self.metric.set_cmp_key('Mean')
+        return out
+
+
+class ImageNetPEvaluator(_MeanOfValues):
+    """imagenetp_evaluator.py:27-44: the flip rate of a perturbation -- per sequence the share of frames whose prediction differs
+    from the previous frame's (from the FIRST frame's when 'noise' is in the perturbation's name), averaged over the sequences.
+    Reads lines {"predictions": [...]}, one per sequence.  Only the evaluator is mirrored: decoding the sequences is out of scope."""
+
+    def __init__(self):
+        self.metric = Metric()
+
+    def load_res(self, res_file):
+        return [np.array(json.loads(line)['predictions']) for line in _lines(res_file)]
+
+    def eval(self, res_file, perturbation=None):
+        predictions = self.load_res(res_file)
+        noise_perturbation = 'noise' in perturbation
+        result = 0
+        for vid_preds in predictions:
+            result_for_vid = []
+            prev_pred = vid_preds[0]
+            for pred in vid_preds[1:]:
+                result_for_vid.append(int(prev_pred != pred))
+                if not noise_perturbation:
+                    prev_pred = pred
+            result += np.mean(result_for_vid) / len(predictions)
+        result_dict = {perturbation: float(result)}
+        self.metric.update(result_dict)
+        return result_dict

@@ -4,6 +4,11 @@ Layout (exprs/nips_benchmark/batch_eval_transfer/parse_transfer.py:27-31, batch_
 `<root>/<model>/<noise>_<eps>/results.txt.all` (clean: `none_0`; transfer: `<src>_To_<tgt>/<attack>_<eps>/...`).
 Every rank appends its shard to `results.txt.rank<r>` as {"prediction": p, "label": y, "score": [...], "index": i};
 rank 0 merges the shards ordered by the global sample index, so the file is identical for every world size.
+
+ConfidenceWriter (the ImageNet-A / ImageNet-O evaluation) keeps the sharding and the merge and writes, per SAMPLE,
+{"confidence": [c], "correct": [b], "num_correct": b, "prediction": p, "label": y, "index": i}: the key set the reference's
+ImageNetOEvaluator reads (imageneto_evaluator.py:36-50 concatenates the `confidence` / `correct` lists of the lines and sums
+`num_correct`, so it reads this file unchanged), one sample per line so that the file is the same for every batch size too.
 """
 import json
 import os
@@ -49,3 +54,22 @@ class ResultWriter(object):
                 for rec in recs:
                     f.write(json.dumps(rec) + '\n')
         return out
+
+
+class ConfidenceWriter(ResultWriter):
+    """Result files of the subset evaluation (metrics/confidence.py): same shards, same merge by global index as ResultWriter."""
+
+    def __init__(self, save_dir, rank=0, world=1):
+        super().__init__(save_dir, rank, world, with_score=False)
+
+    def write_batch(self, pred, conf, correct, labels, indices):
+        """pred int32 / conf fp32 / correct uint8: the three outputs of subset_confidence, [b] on any device -- 9 bytes per sample
+        cross to the host, not the score vectors.  labels: (b,) tensor or sequence in subset coordinates, None for a set without
+        labels (written as -1).  indices: global sample indices.  The confidence is written as the double that equals the fp32
+        value, so reading the file back loses nothing."""
+        pred, conf, correct = pred.tolist(), conf.tolist(), correct.tolist()
+        lab = [-1] * len(pred) if labels is None else (labels.tolist() if hasattr(labels, 'tolist') else list(labels))
+        for j in range(len(pred)):
+            b = int(correct[j])
+            self.f.write(json.dumps({'confidence': [conf[j]], 'correct': [b], 'num_correct': b, 'prediction': int(pred[j]),
+                                     'label': int(lab[j]), 'index': int(indices[j])}) + '\n')

@@ -139,12 +139,32 @@ class FileImageNet(torch.utils.data.Dataset):
             raise NotImplementedError("image_reader.type %r: only 'pil' is available in this build" % (reader,))
         if transform not in ('ONECROP', 'STANDARD'):
             raise NotImplementedError('transforms.type %r (ONECROP / STANDARD)' % (transform,))
-        self.root, self.items = root_dir, read_meta_file(meta_file)
+        self.root, self.items = root_dir, (read_meta_file(meta_file) if meta_file is not None else [])
+        self.classes = None                 # from_folder: the sorted class-folder names, label = position
         if limit:
             self.items = self.items[:int(limit)]
         self.size, self.test_resize, self.transform, self.seed = int(size), int(test_resize), transform, int(seed)
         self.n = len(self.items)
         self.jitter, self.flip = jitter, bool(flip)
+
+    @classmethod
+    def from_folder(cls, root_dir, size=224, test_resize=256, transform='ONECROP', reader='pil', limit=None, seed=0):
+        """An image-folder set `<root>/<class folder>/<file>` (imagenet-a, imagenet-o and the in-distribution folder of
+        exp/imagenet-a_o-loop): class folders sorted by name, files sorted by name inside each, label = the position of the folder --
+        torchvision's ImageFolder order.  `classes` keeps the folder names.  Entries of the root that are not directories (ImageNet-A
+        ships a README.txt) are skipped; decode, ONECROP and the resize are FileImageNet's."""
+        if not os.path.isdir(root_dir):
+            raise ValueError('image folder %r is not a directory' % (root_dir,))
+        self = cls(root_dir, None, size, test_resize, transform, reader, None, seed)
+        self.classes = sorted(d for d in os.listdir(root_dir) if os.path.isdir(os.path.join(root_dir, d)))
+        for lab, d in enumerate(self.classes):
+            for f in sorted(os.listdir(os.path.join(root_dir, d))):
+                if os.path.isfile(os.path.join(root_dir, d, f)):
+                    self.items.append((os.path.join(d, f), lab))
+        if limit:
+            self.items = self.items[:int(limit)]
+        self.n = len(self.items)
+        return self
 
     def __len__(self):
         return self.n
@@ -548,9 +568,139 @@ def build_model(cfg, args=None):
     return model
 
 
+def natural_mode(dcfg):
+    """`data.test.imagenet_a&o: True` (exp/imagenet-a_o-loop/config_vit_base.yaml:79-84): the ImageNet-A / ImageNet-O evaluation."""
+    return bool(((dcfg or {}).get('test') or {}).get('imagenet_a&o', False))
+
+
+def read_class_map(tcfg, num_classes):
+    """The model's class index -> wnid: the lines of `data.test.class_index_file` (one wnid per line, the line number is the class
+    index) or, without that key, the sorted sub-directory names of `imagenet_val_root_dir` (the order an image-folder training set
+    gives its classes).  The count must equal the model's num_classes."""
+    path = tcfg.get('class_index_file')
+    if path:
+        with open(path) as f:
+            names = [ln.strip() for ln in f if ln.strip()]
+        src = 'data.test.class_index_file %s' % path
+    else:
+        root = tcfg.get('imagenet_val_root_dir')
+        if not root or not os.path.isdir(root):
+            raise ValueError('data.test: imagenet_a&o needs class_index_file or a directory imagenet_val_root_dir with one folder per '
+                             'class, got %r' % (root,))
+        names = sorted(d for d in os.listdir(root) if os.path.isdir(os.path.join(root, d)))
+        src = 'data.test.imagenet_val_root_dir %s' % root
+    if len(names) != int(num_classes):
+        raise ValueError('%s names %d classes, the model has num_classes = %d' % (src, len(names), int(num_classes)))
+    if len(set(names)) != len(names):
+        raise ValueError('%s names a class twice' % src)
+    return names
+
+
+def subset_of(folder_names, class_map, what):
+    """class indices of a folder set's class names, in folder order -> list of ints; a name the map lacks is a ValueError"""
+    pos = {w: i for i, w in enumerate(class_map)}
+    for w in folder_names:
+        if w not in pos:
+            raise ValueError('%s: class folder %r is not in the class map' % (what, w))
+    return [pos[w] for w in folder_names]
+
+
+def natural_datasets(cfg):
+    """The config side of the ImageNet-A / -O evaluation, all of it on the host: the class map, the three folder sets and the two
+    class subsets -> {'a': (dataset, indices), 'o_in': (dataset, indices), 'o_out': (dataset, indices)}."""
+    dcfg = cfg.get('data', {})
+    tcfg = dcfg.get('test') or {}
+    num_classes = int(((cfg.get('model') or {}).get('kwargs') or {}).get('num_classes', 1000))
+    class_map = read_class_map(tcfg, num_classes)
+    t = read_transforms(dcfg, 'test')
+    size = int(dcfg.get('input_size', 224))
+    sets = {}
+    for key, name in (('a', 'imagenet_a_root_dir'), ('o_out', 'imagenet_o_root_dir'), ('o_in', 'imagenet_o_folder')):
+        if not tcfg.get(name):
+            raise ValueError('data.test: imagenet_a&o needs data.test.%s' % name)
+        sets[key] = FileImageNet.from_folder(tcfg[name], size, t['test_resize'], t['type'], (tcfg.get('image_reader') or {}).get('type', 'pil'),
+                                             dcfg.get('limit_samples'), int(dcfg.get('seed', 0)))
+    if sets['o_in'].classes != sets['o_out'].classes:
+        raise ValueError('data.test.imagenet_o_folder must hold exactly the class folders of imagenet_o_root_dir: %d vs %d folders, '
+                         'differing in %s' % (len(sets['o_in'].classes), len(sets['o_out'].classes),
+                                              sorted(set(sets['o_in'].classes) ^ set(sets['o_out'].classes))[:5]))
+    sub_a = subset_of(sets['a'].classes, class_map, 'data.test.imagenet_a_root_dir')
+    sub_o = subset_of(sets['o_out'].classes, class_map, 'data.test.imagenet_o_root_dir')
+    for sub, name in ((sub_a, 'imagenet_a_root_dir'), (sub_o, 'imagenet_o_root_dir')):
+        if sub != sorted(sub):
+            # the label of a folder sample is the folder's position, the prediction the class's rank in the subset: they are the same
+            # coordinate only when the class map orders the folders as their names do
+            raise ValueError('data.test.%s: the class map does not keep the order of the class folders\' names' % name)
+    return {'a': (sets['a'], sub_a), 'o_in': (sets['o_in'], sub_o), 'o_out': (sets['o_out'], sub_o)}
+
+
+def evaluate_natural(cfg, args, rank, world, device, model=None):
+    """`data.test.imagenet_a&o`: three passes over sharded indices -- ImageNet-A, the in-distribution set of ImageNet-O's classes, and
+    ImageNet-O (out of distribution, no labels).  Per batch: engine logits -> rart_logit_confidence_f32 over the set's class subset ->
+    ConfidenceWriter.  After the barrier rank 0 computes the metrics from the merged files, as the reference does."""
+    if not getattr(args, 'save_dir', None):
+        raise ValueError('data.test.imagenet_a&o needs --save-dir: the metrics are computed from the merged result files')
+    if (getattr(args, 'attack', None) and args.attack != 'none') or getattr(args, 'corruption', None):
+        raise ValueError('data.test.imagenet_a&o cannot be combined with --attack / --corruption: no config of imagenet-a_o-loop has noise')
+    dcfg = cfg.get('data', {})
+    bs = int(dcfg.get('batch_size', 64))
+    plan = natural_datasets(cfg)
+    if device.type != 'cuda':
+        raise RuntimeError('data.test.imagenet_a&o runs on the GPU (the resize and the subset confidence are HIP kernels; no CPU fallback)')
+    from ..metrics import (ConfidenceWriter, ImageNetAEvaluator, ImageNetOEvaluator, class_subset, result_dir, subset_confidence)
+    model = model or build_model(cfg, args)
+    model = model.to(device).eval()
+    use_hip = args.engine == 'hip'
+    if use_hip:
+        from ..model.engine import EngineModel
+        prec = getattr(args, 'precision', None) or cfg.get('engine_precision', 'bf16')
+        f_model = EngineModel(model, takes_normalized=False, precision=prec)
+    mean = torch.tensor(IMAGENET_MEAN, device=device).view(1, 3, 1, 1)
+    std = torch.tensor(IMAGENET_STD, device=device).view(1, 3, 1, 1)
+    num_classes = int(((cfg.get('model') or {}).get('kwargs') or {}).get('num_classes', 1000))
+    name = getattr(args, 'src_name', None) or cfg['model']['type']
+    barrier = dist.barrier if dist.is_available() and dist.is_initialized() else None
+    t0 = time.time()
+    paths, counts, subsets = {}, {}, {}
+    for key, noise_name, labelled in (('a', 'imagenet_a', True), ('o_in', 'imagenet_o_in', True), ('o_out', 'imagenet_o_out', False)):
+        ds, sub = plan[key]
+        if tuple(sub) not in subsets:
+            subsets[tuple(sub)] = class_subset(sub, num_classes, device)         # validated on the host, uploaded once
+        sub_dev = subsets[tuple(sub)]
+        writer = ConfidenceWriter(result_dir(args.save_dir, name, noise_name, '0'), rank, world)
+        idx = shard_indices(len(ds), rank, world)
+        for s in range(0, len(idx), bs):
+            items = idx[s:s + bs]
+            imgs, labels = ds.batch(items, device)
+            if use_hip:
+                logits = f_model.rart_engine.logits_from_u8(imgs, IMAGENET_MEAN, IMAGENET_STD)
+            else:
+                with torch.no_grad():
+                    logits = model((imgs.permute(0, 3, 1, 2).float() / 255.0 - mean) / std)
+            if logits.shape[1] != num_classes:
+                raise ValueError('the model returns %d logits, model.kwargs.num_classes says %d' % (logits.shape[1], num_classes))
+            pred, conf, correct = subset_confidence(logits.float(), sub_dev, labels if labelled else None)
+            writer.write_batch(pred, conf, correct, [ds.items[i][1] for i in items] if labelled else None, items)
+        paths[key] = writer.close(barrier=barrier)
+        counts[key] = len(ds)
+    res = None
+    if rank == 0:
+        ev_a, ev_o = ImageNetAEvaluator(), ImageNetOEvaluator()
+        a = ev_a.eval(paths['a'])
+        o = ev_o.eval(paths['o_in'], paths['o_out'])
+        res = {'imagenet_a': dict(a, count=counts['a']),
+               'imagenet_o': {'AUPR': o['AUPR'], 'AUROC': ev_o.last_measures['AUROC'], 'FPR95': ev_o.last_measures['FPR95'],
+                              'count_in': counts['o_in'], 'count_out': counts['o_out']},
+               'world_size': world, 'seconds': time.time() - t0}
+        print(json.dumps(res))
+    return res
+
+
 def evaluate(cfg, args, rank, world, device, model=None):
     """Clean / corrupted / attacked evaluation over the sharded dataset; returns the reduced metrics dict."""
     dcfg = cfg.get('data', {})
+    if natural_mode(dcfg):
+        return evaluate_natural(cfg, args, rank, world, device, model)
     n = int(dcfg.get('fake_size', dcfg.get('limit_samples', 256)))
     bs = int(dcfg.get('batch_size', 64))
     size = int(dcfg.get('input_size', 224))
