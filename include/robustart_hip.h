@@ -1077,6 +1077,62 @@ size_t rart_tok_rowsum_workspace_bytes(int rows, int batch);
 int rart_tok_rowsum_bf16(const void* x, int rows, int dim, int batch, int64_t stride, float* out, int accumulate, void* workspace,
                          size_t workspace_bytes, rart_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * JPEG reader (csrc/jpeg_entropy.h + csrc/jpeg_decode.hip): Image.open(f).convert('RGB') of the reference's 'pil' reader
+ * (imagenet_s_gen.py:177-196) split the way its DALI reader splits it (pgd_adv_train/resnet50/config.yaml:38) -- entropy decoding
+ * on the host, the arithmetic on the device -- and bit-exact with Pillow / libjpeg-turbo.
+ *
+ * Supported set: baseline SOF0, 8-bit samples and quantisation tables, one scan; grayscale, or three components with chroma (1,1)
+ * and luma (1,1) / (2,1) / (2,2) read as YCbCr (a JFIF APP0, or an Adobe APP14 with transform 1, or no Adobe marker and ids 1,2,3);
+ * restart intervals, optimised Huffman tables, fill bytes and FF00 stuffing included.  Any other file (progressive, SOF1,
+ * arithmetic, lossless, 12-bit, DNL, 16-bit tables, 4:4:0, CMYK, several scans, more than 2^26 pixels, not a JPEG) gives
+ * RART_ERR_UNSUPPORTED; a supported file with a truncated or corrupt stream gives RART_ERR_INVALID.
+ *
+ * rart_jpeg_probe / rart_jpeg_entropy_decode are HOST-ONLY (every pointer is a host pointer, no HIP call, safe from any number of
+ * threads at once).  probe fills `info` (info->status repeats the return value).  entropy_decode writes the coefficients of the
+ * scan to coef_host: per component, block-row-major over the MCU-padded block grid blocks_h x blocks_w, 64 int16 per block in
+ * natural (de-zigzagged) order, not dequantised; `capacity` counts int16 elements.  Unless it returns RART_OK or RART_ERR_INVALID
+ * coef_host is not written. */
+typedef struct rart_jpeg_info {
+  int32_t status;                 /* RART_OK: in the supported set */
+  int32_t height, width, ncomp;   /* ncomp 1 or 3 */
+  int32_t h_samp[3], v_samp[3];
+  int32_t blocks_w[3], blocks_h[3];   /* the MCU-padded block grid of each component */
+  int64_t coef_count;             /* 64 * the sum of the blocks */
+  uint16_t qt[3][64];             /* each component's quantisation table, natural order */
+} rart_jpeg_info;
+int rart_jpeg_probe(const uint8_t* data_host, size_t len, rart_jpeg_info* info_host);
+int rart_jpeg_entropy_decode(const uint8_t* data_host, size_t len, const rart_jpeg_info* info_host, int16_t* coef_host,
+                             size_t capacity);
+
+/* The device stage: dequantise + ISLOW IDCT (jidctint.c: idct8<11> over columns, idct8<18> over rows, + 128, clamp) into uint8
+ * component planes in the workspace (row stride 8 blocks_w), then libjpeg's upsampling (fancy h2v1 / h2v2 triangle filters; plain
+ * replication when the chroma plane is at most 2 samples wide; indices clamped to the component's real extent
+ * ceil(w h_samp / h_max) x ceil(h v_samp / v_max)) + YCbCr -> RGB into `out`, uint8 [height][width][3] per image, packed back to
+ * back.  Two launches for the whole batch, whatever n and however the images differ.
+ * One descriptor per image, in batch order; the batch's blocks are numbered image by image, component by component, block-row-major:
+ *   block_start[c] : number of component c's first block (absent components: the next image's first); its coefficients start
+ *                    at element 64 block_start[c] of `coef`.  Image 0 starts at 0, nothing is skipped.
+ *   qt_off         : element of `qt` (uint16) where the image's [3][64] tables start (natural order), a multiple of 8
+ *   plane_off[c]   : byte of the workspace where component c's plane starts, a multiple of 16
+ *   out_off        : byte of `out` where the image starts = 3 * the pixels of the images before it
+ *   h_samp, v_samp : luma's sampling factors (chroma is (1,1)); 1 / 1 for grayscale
+ * desc and desc_host hold the same n descriptors on the device and on the host: the host copy is validated against
+ * total_blocks / qt_count / workspace_bytes / out_bytes BEFORE any launch (RART_ERR_INVALID, RART_ERR_WORKSPACE), so a descriptor
+ * cannot make a kernel write outside the caller's buffers.  coef: total_blocks * 64 int16, 16-byte aligned. */
+typedef struct rart_jpeg_desc {
+  int64_t block_start[3];
+  int64_t plane_off[3];
+  int64_t qt_off, out_off;
+  int32_t height, width, ncomp, h_samp, v_samp;
+  int32_t blocks_w[3], blocks_h[3];
+  int32_t reserved_;
+} rart_jpeg_desc;
+size_t rart_jpeg_decode_workspace_bytes(const rart_jpeg_desc* desc_host, int n);
+int rart_jpeg_decode_u8(const rart_jpeg_desc* desc, const rart_jpeg_desc* desc_host, int n, const int16_t* coef, int64_t total_blocks,
+                        const uint16_t* qt, size_t qt_count, void* workspace, size_t workspace_bytes, uint8_t* out, size_t out_bytes,
+                        rart_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -228,6 +228,11 @@ SIGNATURES = {
     'rart_wgrad_reduce_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     'rart_pack_conv_weight_bf16': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                            ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_int, c_void_p]),
+    'rart_jpeg_probe': (c_int, [ctypes.c_char_p, c_size_t, c_void_p]),
+    'rart_jpeg_entropy_decode': (c_int, [ctypes.c_char_p, c_size_t, c_void_p, c_void_p, c_size_t]),
+    'rart_jpeg_decode_workspace_bytes': (c_size_t, [c_void_p, c_int]),
+    'rart_jpeg_decode_u8': (c_int, [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_int64, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
+                                    c_size_t, c_void_p]),
 }
 
 
@@ -253,6 +258,21 @@ class ConvDesc(ctypes.Structure):
 class JitterRec(ctypes.Structure):
     """rart_jitter_rec (include/robustart_hip.h): one sample's ColorJitter plan, 20 bytes."""
     _fields_ = [('op', ctypes.c_uint8 * 4), ('factor', ctypes.c_float * 3), ('hue_shift', ctypes.c_uint32)]
+
+
+class JpegInfo(ctypes.Structure):
+    """rart_jpeg_info (include/robustart_hip.h): what rart_jpeg_probe reads from a file's markers."""
+    _fields_ = [(n, ctypes.c_int32) for n in ('status', 'height', 'width', 'ncomp')] + \
+               [(n, ctypes.c_int32 * 3) for n in ('h_samp', 'v_samp', 'blocks_w', 'blocks_h')] + \
+               [('coef_count', ctypes.c_int64), ('qt', (ctypes.c_uint16 * 64) * 3)]
+
+
+class JpegDesc(ctypes.Structure):
+    """rart_jpeg_desc (include/robustart_hip.h): one image of a rart_jpeg_decode_u8 batch, 112 bytes."""
+    _fields_ = [('block_start', ctypes.c_int64 * 3), ('plane_off', ctypes.c_int64 * 3), ('qt_off', ctypes.c_int64),
+                ('out_off', ctypes.c_int64)] + \
+               [(n, ctypes.c_int32) for n in ('height', 'width', 'ncomp', 'h_samp', 'v_samp')] + \
+               [('blocks_w', ctypes.c_int32 * 3), ('blocks_h', ctypes.c_int32 * 3), ('reserved_', ctypes.c_int32)]
 
 
 class FixedPointInfo(ctypes.Structure):

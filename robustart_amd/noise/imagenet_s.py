@@ -6,7 +6,9 @@ between the ImageNet-S variants and the part that is arithmetic -- runs on the G
 rart_pil_resize_u8; the five 'opencv-*' operators run through rart_cv_resize_u8, a restatement of OpenCV's resize.cpp
 (OpenCV is not installed here, so those five are parity-unpinned -- see oracle/resize_cv_np.py).  Not available in this
 build (raise NotImplementedError, loudly): the 'opencv' and 'ffmpeg' decoders and the reference's memcached reader.  Unlike the reference (which passes float sizes to Image.resize and only works on
-Python <= 3.9, imagenet_s_gen.py:129,167) sizes are converted with int()."""
+Python <= 3.9, imagenet_s_gen.py:129,167) sizes are converted with int().
+decode_batch_gpu is the batched form of the 'pil' decoder for baseline JPEG files: Huffman decoding on host threads, the arithmetic in
+rart_jpeg_decode_u8, the same bytes as Pillow; FileImageNet(reader='hip') reads through it."""
 import random
 
 import numpy as np
@@ -59,6 +61,134 @@ def decode(path_or_bytes, decoder_type='pil'):
     src = io.BytesIO(path_or_bytes) if isinstance(path_or_bytes, (bytes, bytearray)) else path_or_bytes
     with Image.open(src) as img:
         return np.array(img.convert('RGB'))
+
+
+def jpeg_probe(data):
+    """rart_jpeg_probe on encoded bytes (host only) -> _lib.JpegInfo; info.status is 0 when the file is in the supported set
+    (baseline, one scan, grayscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0), 2 when Pillow has to decode it."""
+    import ctypes
+    info = _lib.JpegInfo()
+    _lib.load().rart_jpeg_probe(data, len(data), ctypes.byref(info))
+    return info
+
+
+def jpeg_entropy_decode(data, info, coef):
+    """rart_jpeg_entropy_decode (host only): the scan's coefficients into `coef`, a C-contiguous int16 numpy array of at least
+    info.coef_count elements -- per component, block-row-major, 64 per block in natural order, not dequantised.  -> status"""
+    import ctypes
+    assert coef.dtype == np.int16 and coef.flags['C_CONTIGUOUS']
+    return _lib.load().rart_jpeg_entropy_decode(data, len(data), ctypes.byref(info), coef.ctypes.data, coef.size)
+
+
+def _read_bytes(item):
+    if isinstance(item, (bytes, bytearray, memoryview)):
+        return bytes(item)
+    with open(item, 'rb') as f:
+        return f.read()
+
+
+_pinned = {}               # device -> (pinned staging buffer, the event of the last copy that read it)
+MAX_DECODE_WORKERS = 16
+decode_launches = 0        # rart_jpeg_decode_u8 calls made by decode_batch_gpu (one per batch that has a GPU-decodable file)
+
+
+def decode_batch_gpu(items, num_workers=8, timings=None):
+    """items: file paths or encoded bytes -> (images, used_gpu): a list of CUDA uint8 HxWx3 tensors equal to decode(item, 'pil')
+    bit for bit, and a bool per item.  Baseline JPEGs (jpeg_probe) are entropy-decoded on the host by a pool of
+    min(num_workers, 16) threads (ctypes releases the GIL) into one pinned buffer, cross the bus in one copy together with their
+    tables and descriptors, and are finished by rart_jpeg_decode_u8 in two launches for the whole batch; their images are views
+    of one packed buffer.  Every other file (used_gpu False) is decoded by decode(item, 'pil') and uploaded, as the 'pil' reader
+    does; what Pillow raises propagates.  timings: a dict that receives 'host_s', 'copy_s', 'device_s' (each phase is then
+    followed by a synchronize: a measurement aid)."""
+    global decode_launches
+    import ctypes
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    torch = _lib.require_gpu()
+    lib = _lib.load()
+    items = list(items)
+    n = len(items)
+    workers = max(1, min(int(num_workers), MAX_DECODE_WORKERS))
+    t0 = time.perf_counter()
+
+    def probe(item):
+        data = _read_bytes(item)
+        return data, jpeg_probe(data)
+
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        probed = list(pool.map(probe, items))
+        gpu_ids = [k for k in range(n) if probed[k][1].status == 0]
+        images, used = [None] * n, [False] * n
+        if gpu_ids:
+            m = len(gpu_ids)
+            descs = (_lib.JpegDesc * m)()
+            blk = pix = plane = 0
+            for j, k in enumerate(gpu_ids):
+                info, d = probed[k][1], descs[j]
+                d.height, d.width, d.ncomp = info.height, info.width, info.ncomp
+                d.h_samp, d.v_samp = info.h_samp[0], info.v_samp[0]
+                d.qt_off, d.out_off = j * 192, 3 * pix
+                for c in range(3):
+                    bw, bh = (info.blocks_w[c], info.blocks_h[c]) if c < info.ncomp else (0, 0)
+                    d.blocks_w[c], d.blocks_h[c], d.block_start[c] = bw, bh, blk
+                    d.plane_off[c] = plane
+                    blk += bw * bh
+                    plane += (bw * bh * 64 + 15) // 16 * 16
+                pix += info.height * info.width
+            # one staging buffer: descriptors | quantisation tables | coefficients, each region 16-byte aligned
+            desc_bytes = (ctypes.sizeof(descs) + 15) // 16 * 16
+            qt_bytes = m * 192 * 2
+            total = desc_bytes + qt_bytes + blk * 128
+            dev = torch.device('cuda', torch.cuda.current_device())
+            host, ev = _pinned.pop(dev, (None, None))      # taken out while in use: a concurrent caller stages in a buffer of its own
+            if ev is not None:
+                ev.synchronize()           # the previous batch's copy has left the buffer
+            if host is None or host.numel() < total:
+                host = torch.empty(int(total * 1.25), dtype=torch.uint8, pin_memory=True)
+            hnp = host.numpy()
+            ctypes.memmove(hnp.ctypes.data, ctypes.addressof(descs), ctypes.sizeof(descs))
+            qt = hnp[desc_bytes:desc_bytes + qt_bytes].view(np.uint16).reshape(m, 3, 64)
+            coef = hnp[desc_bytes + qt_bytes:total].view(np.int16)
+
+            def entropy(j):
+                data, info = probed[gpu_ids[j]]
+                qt[j] = np.ctypeslib.as_array(info.qt)
+                lo = descs[j].block_start[0] * 64
+                return jpeg_entropy_decode(data, info, coef[lo:lo + info.coef_count])
+
+            status = list(pool.map(entropy, range(m)))
+            if timings is not None:
+                timings['host_s'] = time.perf_counter() - t0
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+            dbuf = torch.empty(total, dtype=torch.uint8, device=dev)
+            dbuf.copy_(host[:total], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            _pinned[dev] = (host, ev)
+            if timings is not None:
+                torch.cuda.synchronize()
+                timings['copy_s'] = time.perf_counter() - t0
+                t0 = time.perf_counter()
+            out = torch.empty(3 * pix, dtype=torch.uint8, device=dev)
+            nb = lib.rart_jpeg_decode_workspace_bytes(ctypes.addressof(descs), m)
+            ws = _lib.workspace(nb, dev)
+            base = dbuf.data_ptr()
+            decode_launches += 1
+            _lib.check(lib.rart_jpeg_decode_u8(base, ctypes.addressof(descs), m, base + desc_bytes + qt_bytes, blk, base + desc_bytes,
+                                               m * 192, _lib.ptr(ws), nb, _lib.ptr(out), out.numel(), _lib.stream_ptr()))
+            if timings is not None:
+                torch.cuda.synchronize()
+                timings['device_s'] = time.perf_counter() - t0
+            for j, k in enumerate(gpu_ids):
+                if status[j] == 0:         # a stream the entropy decoder gave up on (truncated, corrupt) goes to Pillow below
+                    d = descs[j]
+                    images[k] = out[d.out_off:d.out_off + 3 * d.height * d.width].view(d.height, d.width, 3)
+                    used[k] = True
+    for k in range(n):
+        if images[k] is None:
+            images[k] = torch.from_numpy(decode(probed[k][0], 'pil')).cuda(non_blocking=True)
+    return images, used
 
 
 def _train_params(img_hw, rng):

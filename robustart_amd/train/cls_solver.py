@@ -119,7 +119,7 @@ def read_meta_file(path):
 
 
 class FileImageNet(torch.utils.data.Dataset):
-    """`data.read_from: fs` with `data.<split>.{root_dir, meta_file, image_reader.type: pil, transforms}`
+    """`data.read_from: fs` with `data.<split>.{root_dir, meta_file, image_reader.type: pil | hip, transforms}`
     (exp/imagenet_c_loop_mini/config_vit_base.yaml:80-104; `transforms` as the mapping {type: ...} or as a list of torchvision entries,
     read_transforms): files are decoded on the host by PIL (the reference's 'pil'
     reader) and the transform's arithmetic runs on the GPU:
@@ -131,12 +131,17 @@ class FileImageNet(torch.utils.data.Dataset):
                  a list's ColorJitter entry, train/jitter.py) is applied to the finished uint8 batch after the resize and the flip,
                  one rart_color_jitter_u8 call for the whole batch, bit-exact with Pillow; the mapping form carries no jitter.
     Output is the uint8 NHWC batch the corruption kernels and the engines' u8 entry consume; normalisation happens in
-    the engine's input kernel."""
+    the engine's input kernel.
+    reader='hip' (`image_reader.type: hip`, opt-in) decodes a batch's baseline JPEGs through noise.imagenet_s.decode_batch_gpu --
+    Huffman decoding on `num_workers` host threads, IDCT / upsampling / colour conversion on the GPU, bit-identical to the 'pil'
+    reader -- and hands every other file to PIL as 'pil' does; `decode_stats` counts the files that took each path."""
 
     def __init__(self, root_dir, meta_file, size=224, test_resize=256, transform='ONECROP', reader='pil', limit=None, seed=0,
-                 jitter=None, flip=True):
-        if reader != 'pil':
-            raise NotImplementedError("image_reader.type %r: only 'pil' is available in this build" % (reader,))
+                 jitter=None, flip=True, num_workers=8):
+        if reader not in ('pil', 'hip'):
+            raise NotImplementedError("image_reader.type %r: 'pil' and 'hip' are available in this build" % (reader,))
+        self.reader, self.num_workers = reader, int(num_workers)
+        self.decode_stats = {'gpu': 0, 'fallback': 0}          # reader='hip': files decoded on the GPU / by PIL
         if transform not in ('ONECROP', 'STANDARD'):
             raise NotImplementedError('transforms.type %r (ONECROP / STANDARD)' % (transform,))
         self.root, self.items = root_dir, (read_meta_file(meta_file) if meta_file is not None else [])
@@ -148,14 +153,14 @@ class FileImageNet(torch.utils.data.Dataset):
         self.jitter, self.flip = jitter, bool(flip)
 
     @classmethod
-    def from_folder(cls, root_dir, size=224, test_resize=256, transform='ONECROP', reader='pil', limit=None, seed=0):
+    def from_folder(cls, root_dir, size=224, test_resize=256, transform='ONECROP', reader='pil', limit=None, seed=0, num_workers=8):
         """An image-folder set `<root>/<class folder>/<file>` (imagenet-a, imagenet-o and the in-distribution folder of
         exp/imagenet-a_o-loop): class folders sorted by name, files sorted by name inside each, label = the position of the folder --
         torchvision's ImageFolder order.  `classes` keeps the folder names.  Entries of the root that are not directories (ImageNet-A
         ships a README.txt) are skipped; decode, ONECROP and the resize are FileImageNet's."""
         if not os.path.isdir(root_dir):
             raise ValueError('image folder %r is not a directory' % (root_dir,))
-        self = cls(root_dir, None, size, test_resize, transform, reader, None, seed)
+        self = cls(root_dir, None, size, test_resize, transform, reader, None, seed, num_workers=num_workers)
         self.classes = sorted(d for d in os.listdir(root_dir) if os.path.isdir(os.path.join(root_dir, d)))
         for lab, d in enumerate(self.classes):
             for f in sorted(os.listdir(os.path.join(root_dir, d))):
@@ -174,6 +179,15 @@ class FileImageNet(torch.utils.data.Dataset):
         from ..noise.imagenet_s import decode
         name, lab = self.items[i]
         return decode(os.path.join(self.root, name), 'pil'), lab
+
+    def decode_batch(self, indices, dev):
+        """reader='hip': the decoded images of `indices` as CUDA uint8 HxWx3 tensors (one decode_batch_gpu call)"""
+        from ..noise.imagenet_s import decode_batch_gpu
+        with torch.cuda.device(dev):
+            images, used = decode_batch_gpu([os.path.join(self.root, self.items[i][0]) for i in indices], self.num_workers)
+        self.decode_stats['gpu'] += sum(used)
+        self.decode_stats['fallback'] += len(used) - sum(used)
+        return images
 
     def __getitem__(self, i):
         img, lab = self.batch([i], 'cuda')
@@ -196,17 +210,24 @@ class FileImageNet(torch.utils.data.Dataset):
             raise RuntimeError('FileImageNet: the resize / crop of the transform runs on the GPU (no CPU fallback)')
         out = torch.empty(len(indices), self.size, self.size, 3, dtype=torch.uint8, device=dev)
         labs = []
+        decoded = self.decode_batch(indices, dev) if self.reader == 'hip' else None
         for k, i in enumerate(indices):
-            arr, lab = self.decode(i)
+            if decoded is not None:
+                arr, lab = decoded[k], self.items[i][1]               # already on the device
+            else:
+                arr, lab = self.decode(i)
             labs.append(lab)
             if self.transform == 'ONECROP':
                 r, t = self.test_resize, self.size
                 o = int(round((r - t) / 2.0))                         # torchvision CenterCrop
-                src = torch.from_numpy(arr).to(dev, non_blocking=True)[None]
+                src = (arr if decoded is not None else torch.from_numpy(arr).to(dev, non_blocking=True))[None]
                 out[k] = pil_resize(src, (r, r), 1, crop=(o, o, t, t))[0]
             else:
                 y, x, h, w, flip = self.box(i, arr.shape[:2], epoch)
-                src = torch.from_numpy(arr[y:y + h, x:x + w].copy()).to(dev, non_blocking=True)[None]
+                if decoded is not None:
+                    src = arr[y:y + h, x:x + w].contiguous()[None]
+                else:
+                    src = torch.from_numpy(arr[y:y + h, x:x + w].copy()).to(dev, non_blocking=True)[None]
                 img = pil_resize(src, (self.size, self.size), 1)[0]
                 out[k] = img.flip(1) if flip and self.flip else img
         if self.transform == 'STANDARD' and self.jitter is not None:
@@ -328,7 +349,7 @@ def make_dataset(dcfg, n, size, split='test'):
         t = read_transforms(dcfg, split)
         return FileImageNet(sec['root_dir'], sec['meta_file'], size, t['test_resize'], t['type'],
                             (sec.get('image_reader') or {}).get('type', 'pil'), dcfg.get('limit_samples'),
-                            int(dcfg.get('seed', 0)), jitter=t['jitter'], flip=t['flip'])
+                            int(dcfg.get('seed', 0)), jitter=t['jitter'], flip=t['flip'], num_workers=int(dcfg.get('num_workers') or 8))
     if rf != 'fake':
         raise NotImplementedError("data.read_from %r ('fake', 'structured', 'fs')" % (rf,))
     return FakeImageNet(n, size)
@@ -619,7 +640,7 @@ def natural_datasets(cfg):
         if not tcfg.get(name):
             raise ValueError('data.test: imagenet_a&o needs data.test.%s' % name)
         sets[key] = FileImageNet.from_folder(tcfg[name], size, t['test_resize'], t['type'], (tcfg.get('image_reader') or {}).get('type', 'pil'),
-                                             dcfg.get('limit_samples'), int(dcfg.get('seed', 0)))
+                                             dcfg.get('limit_samples'), int(dcfg.get('seed', 0)), num_workers=int(dcfg.get('num_workers') or 8))
     if sets['o_in'].classes != sets['o_out'].classes:
         raise ValueError('data.test.imagenet_o_folder must hold exactly the class folders of imagenet_o_root_dir: %d vs %d folders, '
                          'differing in %s' % (len(sets['o_in'].classes), len(sets['o_out'].classes),
