@@ -462,6 +462,22 @@ typedef struct rart_gemm_pair_desc {
   int tile_m;               /* 0 = automatic (256; 128 for short-K or small convolutions; 224 where it saves a pass); 128 / 224 / 256 force it */
 } rart_gemm_pair_desc;
 int rart_gemm_pair_bf16(const rart_gemm_pair_desc* desc_host, rart_stream_t stream);
+/* The same launch with a SECOND A source whose product lands in the same accumulation (a projection shortcut folded into the 1x1 it is
+ * added to): yc = relu(W3 . yb + Wds . x_strided + (b3 + bds)) without the shortcut's tensor ever reaching memory.  `one` describes the
+ * launch as rart_gemm_pair_bf16 takes it, conv = 1 (unbatched, no row re-basing).  The second source has one tap at offset 0: row
+ * m = (image, oy, ox) reads pixel (oy sy2, ox sx2) of a src2_h x src2_w image with lda2 elements per pixel, k2 channels (a multiple of 32;
+ * every row's pixel inside the image).  K of the launch = k_per_tap * n_taps + k2: the K steps of the first source run first, then those
+ * of the second, and the weight table's rows are [W1 | W2] along K (one.ldw covers both).  a2_hi null: exactly rart_gemm_pair_bf16(&one).
+ * Served under schedules 0 and 1 (224-row tiles included); under the opt-in schedules 2 and 3 such a launch takes the ping-pong kernel.
+ * A descriptor of its own, so that every caller of rart_gemm_pair_bf16 keeps its layout.  rart_gemm_pair_max_sources: how many A sources
+ * the loaded library takes per launch (2); the engines fold a shortcut only where it says so. */
+typedef struct rart_gemm_pair2_desc {
+  rart_gemm_pair_desc one;
+  const void *a2_hi, *a2_lo;
+  int lda2, k2, src2_h, src2_w, sy2, sx2;
+} rart_gemm_pair2_desc;
+int rart_gemm_pair2_bf16(const rart_gemm_pair2_desc* desc_host, rart_stream_t stream);
+int rart_gemm_pair_max_sources(void);
 /* Schedule of the 256-row tiles with 128 / 256 columns (round 6, csrc/gemm_pair_pp.hip): 1 (default; RART_PAIR_SCHEDULE in the environment
  * sets the initial value) = ping-pong -- the two halves of the workgroup alternate memory and matrix phases, counted vmcnt, no drain in the
  * steady state; 2 (opt-in: measured slower than 1, see the kernel's header) = ping-pong, and one-tap problems (1x1 convolutions, plain
@@ -507,6 +523,11 @@ typedef struct rart_conv_tail_desc {
   void* sign_next;
   void* dstn_hi;  void* dstn_lo;
   int relu_next;
+  /* optional (x_hi != null; c_mid = 64, res null): the block's stride-1 1x1 PROJECTION SHORTCUT as extra K steps of the 1x1 -- x_*: its
+   * input pair [batch][h][w][64]; tx_*: its [4 c_mid][64] matrix in the fragment order of t_*; bias_out then holds the sum of both biases:
+   * dst = relu(T . mid + TX . x + bias_out). */
+  const void* x_hi;  const void* x_lo;
+  const void* tx_hi;  const void* tx_lo;
 } rart_conv_tail_desc;
 int rart_conv3x3_tail_pair_supported(int c_mid);
 int rart_conv3x3_tail_pair(const rart_conv_tail_desc* desc_host, rart_stream_t stream);

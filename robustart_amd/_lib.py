@@ -13,7 +13,7 @@ c_void_p, c_int, c_size_t, c_u64, c_float = (ctypes.c_void_p, ctypes.c_int, ctyp
                                               ctypes.c_uint64, ctypes.c_float)
 c_double = ctypes.c_double
 
-ABI_VERSION = 110        # == RART_ABI_VERSION of include/robustart_hip.h; load() refuses a library built from another header
+ABI_VERSION = 110       # == RART_ABI_VERSION of include/robustart_hip.h; load() refuses a library built from another header
 
 # name -> (restype, argtypes); every symbol include/robustart_hip.h declares
 SIGNATURES = {
@@ -81,6 +81,8 @@ SIGNATURES = {
     'rart_logit_loss': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p,
                                 c_void_p, c_void_p, c_void_p]),
     'rart_conv_igemm_bf16': (c_int, [c_void_p, c_void_p]),
+    'rart_gemm_pair2_bf16': (c_int, [c_void_p, c_void_p]),
+    'rart_gemm_pair_max_sources': (c_int, []),
     'rart_conv3x3_halo_supported': (c_int, [c_int, c_int, c_int]),
     'rart_conv3x3_pack_frag_bf16': (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     'rart_pack_frag_bf16': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
@@ -301,6 +303,12 @@ class GemmPairDesc(ctypes.Structure):
                [('mask_bits', c_void_p), ('sign_out', c_void_p), ('tile_n', ctypes.c_int32), ('tile_m', ctypes.c_int32)]
 
 
+class GemmPair2Desc(ctypes.Structure):
+    """rart_gemm_pair2_desc (include/robustart_hip.h): a conv-mode pair launch `one` with a second A source."""
+    _fields_ = [('one', GemmPairDesc), ('a2_hi', c_void_p), ('a2_lo', c_void_p)] + \
+               [(n, ctypes.c_int32) for n in ('lda2', 'k2', 'src2_h', 'src2_w', 'sy2', 'sx2')]
+
+
 class TokmixDesc(ctypes.Structure):
     """rart_tokmix_desc (include/robustart_hip.h): MLP-Mixer's token-mixing GEMM, bf16 or pair."""
     _fields_ = [(n, c_void_p) for n in ('a_hi', 'a_lo', 'x_hi', 'x_lo', 'dst_hi', 'dst_lo', 'res_hi', 'res_lo', 'aux_hi', 'aux_lo', 'bias')] + \
@@ -321,7 +329,8 @@ class ConvTailDesc(ctypes.Structure):
                                         'sign_mid', 'sign_out', 'res_hi', 'res_lo', 'dst_hi', 'dst_lo')] + \
                [(n, ctypes.c_int32) for n in ('batch', 'h', 'w', 'c_mid', 'ldw', 'relu_mid', 'relu_out')] + \
                [('tap_dy', ctypes.c_int32 * 9), ('tap_dx', ctypes.c_int32 * 9)] + \
-               [(n, c_void_p) for n in ('n_hi', 'n_lo', 'bias_next', 'mask_next', 'sign_next', 'dstn_hi', 'dstn_lo')] + [('relu_next', ctypes.c_int32)]
+               [(n, c_void_p) for n in ('n_hi', 'n_lo', 'bias_next', 'mask_next', 'sign_next', 'dstn_hi', 'dstn_lo')] + [('relu_next', ctypes.c_int32)] + \
+               [(n, c_void_p) for n in ('x_hi', 'x_lo', 'tx_hi', 'tx_lo')]
 
 
 _lib = None

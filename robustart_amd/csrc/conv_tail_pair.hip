@@ -61,6 +61,9 @@ struct ConvTailDev {
   uint8_t* sign_next;
   uint16_t *dstn_hi, *dstn_lo;
   int relu_next;
+  // XS instances (C = 64, forward of a block with a stride-1 projection shortcut): the shortcut's input pair [M][64] and its table in
+  // fragment order ((blk * 4 + s) * 64 + lane, blk = 32 output channels); its product joins the 1x1's accumulation, res is null
+  const uint16_t *x_hi, *x_lo, *tx_hi, *tx_lo;
 };
 // round 6: the skip loads and the output stores are non-temporal accesses (see rart_gemm_pair_dev.h)
 typedef __attribute__((ext_vector_type(4))) uint32_t ct_u4;
@@ -145,8 +148,15 @@ __device__ __forceinline__ void ct_pointwise_frags(const f32x16* acc, const uint
     }
 }
 
-template <int C, bool NEXT>
-__global__ __launch_bounds__(256, (C == 64 && !NEXT) ? 3 : 2) void k_conv3x3_tail_pair(const ConvTailDev d) {
+// XS: the block's 1x1 PROJECTION SHORTCUT as extra K steps of the 1x1 phase.  A 1x1 convolution is position-local and lane (fr, h) owns position
+// fr, channels 16 s + 8 h .. + 7 of K step s of the B operand, so the shortcut's input fragments come straight from global memory (16 bytes per
+// plane and K step, no LDS); its table is a second fragment-ordered table.  The skip pair the shortcut's own launch wrote and this kernel
+// re-read (822 MB each way in layer1's first block at B = 256) never exists.
+// (XS without NEXT sits 2 registers above the 168 of three workgroups per CU: it is built for two, like the NEXT instances.)
+template <int C, bool NEXT, bool XS = false>
+__global__ __launch_bounds__(256, (C == 64 && !NEXT && !XS) ? 3 : 2) void k_conv3x3_tail_pair(const ConvTailDev d) {
+  static_assert(!XS || C == 64, "the shortcut source is built for layer1's first block: 64 input channels");
+  constexpr int KX = 4;                          // XS: 16-deep K steps of the shortcut (64 input channels)
   constexpr int NJ = C / 32;                     // 32-channel blocks of the 3x3's output
   constexpr int KS = C / 16;                     // 16-deep K steps of the 1x1
   constexpr int NOUT = 4 * C, NC = NOUT / 64;    // the 1x1's output channels, in chunks of 64
@@ -281,6 +291,19 @@ __global__ __launch_bounds__(256, (C == 64 && !NEXT) ? 3 : 2) void k_conv3x3_tai
     }
   }
 
+  bf16x8 xfh[XS ? KX : 1], xfl[XS ? KX : 1];                  // XS: the shortcut input's B-operand fragments of this lane's position
+  if (XS) {
+#pragma unroll
+    for (int s = 0; s < KX; ++s) {
+      uint4 vh = make_uint4(0, 0, 0, 0), vl = vh;
+      if (p_ok) {
+        vh = *reinterpret_cast<const uint4*>(d.x_hi + (size_t)p * 64 + 16 * s + 8 * h);
+        vl = *reinterpret_cast<const uint4*>(d.x_lo + (size_t)p * 64 + 16 * s + 8 * h);
+      }
+      xfh[s] = __builtin_bit_cast(bf16x8, vh);
+      xfl[s] = __builtin_bit_cast(bf16x8, vl);
+    }
+  }
   // ---- the 1x1, 64 output channels at a time: table fragments straight from L2, result transposed through the wave's LDS region
   uint8_t* const wreg = lds + wave * CT_WREG;                 // the wave's private region: fp32 staging, then (NEXT) the chunk as two bf16 planes
   float* sE = reinterpret_cast<float*>(wreg);
@@ -298,6 +321,8 @@ __global__ __launch_bounds__(256, (C == 64 && !NEXT) ? 3 : 2) void k_conv3x3_tai
   }
   const uint4* th_base = reinterpret_cast<const uint4*>(d.t_hi) + lane;
   const uint4* tl_base = reinterpret_cast<const uint4*>(d.t_lo) + lane;
+  const uint4* txh_base = reinterpret_cast<const uint4*>(XS ? d.tx_hi : d.t_hi) + lane;
+  const uint4* txl_base = reinterpret_cast<const uint4*>(XS ? d.tx_lo : d.t_lo) + lane;
   const bool relu_out = d.relu_out != 0;
 #pragma unroll 1
   for (int c = 0; c < NC; ++c) {
@@ -343,6 +368,21 @@ __global__ __launch_bounds__(256, (C == 64 && !NEXT) ? 3 : 2) void k_conv3x3_tai
           acc2[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, a2l[sg + s], acc2[b], 0, 0, 0);
           acc2[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, a2h[sg + s], acc2[b], 0, 0, 0);
           acc2[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, a2h[sg + s], acc2[b], 0, 0, 0);
+        }
+      }
+      if (XS) {                                     // the shortcut's K steps, after the intermediate's
+        uint4 th[KX], tl[KX];
+#pragma unroll
+        for (int s = 0; s < KX; ++s) {
+          th[s] = txh_base[((c * 2 + b) * KX + s) * 64];
+          tl[s] = txl_base[((c * 2 + b) * KX + s) * 64];
+        }
+#pragma unroll
+        for (int s = 0; s < KX; ++s) {
+          const bf16x8 wh = __builtin_bit_cast(bf16x8, th[s]), wl = __builtin_bit_cast(bf16x8, tl[s]);
+          acc2[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xfl[s], acc2[b], 0, 0, 0);
+          acc2[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, xfh[s], acc2[b], 0, 0, 0);
+          acc2[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xfh[s], acc2[b], 0, 0, 0);
         }
       }
     }
@@ -471,7 +511,11 @@ extern "C" int rart_conv3x3_tail_pair(const rart_conv_tail_desc* t, rart_stream_
   RART_CHECK_ARG(t->ldw % 8 == 0 && t->ldw >= 9 * t->c_mid, "rart_conv3x3_tail_pair: ldw must cover 9 taps x c_mid and keep 16-byte alignment");
   const long long M = (long long)t->batch * t->h * t->w;
   RART_CHECK_ARG(M * 4 * t->c_mid < (1ll << 31), "rart_conv3x3_tail_pair: tensors must stay below 2^31 elements (split the batch)");
-  ConvTailDev d;
+  const bool xs = t->x_hi != nullptr;
+  RART_CHECK_ARG(!xs || (t->x_lo && t->tx_hi && t->tx_lo), "rart_conv3x3_tail_pair: the shortcut source needs both input planes and both table planes");
+  RART_CHECK_ARG(!xs || (t->c_mid == 64 && !t->res_hi), "rart_conv3x3_tail_pair: the shortcut source is served at c_mid = 64 and takes the place of the skip pair");
+  ConvTailDev d{};
+  d.x_hi = (const uint16_t*)t->x_hi; d.x_lo = (const uint16_t*)t->x_lo; d.tx_hi = (const uint16_t*)t->tx_hi; d.tx_lo = (const uint16_t*)t->tx_lo;
   d.a_hi = (const uint16_t*)t->a_hi; d.a_lo = (const uint16_t*)t->a_lo; d.w_hi = (const uint16_t*)t->w_hi; d.w_lo = (const uint16_t*)t->w_lo;
   d.t_hi = (const uint16_t*)t->t_hi; d.t_lo = (const uint16_t*)t->t_lo;
   d.bias_mid = t->bias_mid; d.bias_out = t->bias_out;
@@ -489,7 +533,10 @@ extern "C" int rart_conv3x3_tail_pair(const rart_conv_tail_desc* t, rart_stream_
   ct_magic((uint32_t)d.H, d.h_magic, d.h_shift);
   const dim3 grid((uint32_t)((M + CT_TM - 1) / CT_TM));
   hipStream_t st = (hipStream_t)stream;
-  if (t->c_mid == 64) {
+  if (xs) {
+    if (next) hipLaunchKernelGGL((k_conv3x3_tail_pair<64, true, true>), grid, dim3(256), 0, st, d);
+    else hipLaunchKernelGGL((k_conv3x3_tail_pair<64, false, true>), grid, dim3(256), 0, st, d);
+  } else if (t->c_mid == 64) {
     if (next) hipLaunchKernelGGL((k_conv3x3_tail_pair<64, true>), grid, dim3(256), 0, st, d);
     else hipLaunchKernelGGL((k_conv3x3_tail_pair<64, false>), grid, dim3(256), 0, st, d);
   } else {

@@ -37,8 +37,12 @@ namespace {
 // (TM / WM) rows x 64 columns.  The 256-row tiles are for the K-deep, MFMA-bound products (one workgroup per CU, 48 MFMAs per wave between
 // two barriers at TN = 256); the 128-row tiles (48-96 KB of LDS: two or three workgroups per CU whose load / multiply / store phases
 // overlap) for the short-K, HBM-bound 1x1 layers and the small-M layers of ResNet-50 whose 256-row tiling would not fill 256 CUs.
-template <int TM, int TN, bool CONV>
+// SRC2 (CONV only): a second A source -- one tap at offset 0, a pixel geometry of its own -- feeds the K steps from d.kt1 on: a projection
+// shortcut accumulated in the launch of the 1x1 it is added to.  The weight table's rows hold both sources' columns side by side, so the W
+// loader walks on unchanged; the A loader picks the lane offset / resource pair by a wave-uniform compare on the step index.
+template <int TM, int TN, bool CONV, bool SRC2 = false>
 __global__ __launch_bounds__(TM * 2, 1) void k_gemm_pair(const GemmPairDev d) {
+  static_assert(CONV || !SRC2, "the second source is served by the conv instances");
   constexpr int NW = TM / 32;
   constexpr int WN = (TN / 64 < NW) ? TN / 64 : NW, WM = NW / WN, RW = TM / WM, MI = RW / 32, NJ = TN / (32 * WN);
   static_assert(NJ == 2, "a wave owns 64 columns");
@@ -119,6 +123,22 @@ __global__ __launch_bounds__(TM * 2, 1) void k_gemm_pair(const GemmPairDev d) {
       avoff[q] = ok ? (uint32_t)(((srow + d.src_off) * d.lda + csrc * 8) * 2) : RART_DMA_OOR;
     }
   }
+  uint32_t avoff2[2] = {RART_DMA_OOR, RART_DMA_OOR};
+  if (SRC2) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int r = 16 * (wave + NW * q) + (lane >> 2);
+      const int csrc = (lane & 3) ^ ((r >> 2) & 3);
+      const int m = m0 + r;
+      if (m < d.M) {      // (the host checked that every row's pixel lies inside the second source's image)
+        const uint32_t t = gp_fastdiv((uint32_t)m, d.gw_magic, d.gw_shift);
+        const int ox = (int)((uint32_t)m - t * (uint32_t)d.grid_w);
+        const int n = (int)gp_fastdiv(t, d.gh_magic, d.gh_shift);
+        const int oy = (int)(t - (uint32_t)n * (uint32_t)d.grid_h);
+        avoff2[q] = (uint32_t)(((n * d.src2_h + oy * d.sy2) * d.src2_w + ox * d.sx2) * d.lda2 * 2 + csrc * 16);
+      }
+    }
+  }
   uint32_t wvoff[BQ];
 #pragma unroll
   for (int q = 0; q < BQ; ++q) {
@@ -129,6 +149,8 @@ __global__ __launch_bounds__(TM * 2, 1) void k_gemm_pair(const GemmPairDev d) {
   }
   const rart_srd_t srd_ah = rart_dma_srd(reinterpret_cast<const char*>(a_hi) + tap_min), srd_al = rart_dma_srd(reinterpret_cast<const char*>(a_lo) + tap_min);
   const rart_srd_t srd_wh = rart_dma_srd(w_hi), srd_wl = rart_dma_srd(w_lo);
+  const rart_srd_t srd_a2h = rart_dma_srd(SRC2 ? d.a2_hi : a_hi), srd_a2l = rart_dma_srd(SRC2 ? d.a2_lo : a_lo);
+  const int kt1 = SRC2 ? d.kt1 : 0;
   const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lds;
   // GP_W_INTERLEAVED: the weight table holds, per row and K step, the 64 bytes of the hi plane followed by the 64 bytes of the lo plane
   // (one 128-byte line per row and step; w_lo = w_hi + 32 elements) instead of two planes K apart
@@ -137,7 +159,13 @@ __global__ __launch_bounds__(TM * 2, 1) void k_gemm_pair(const GemmPairDev d) {
   {                                                                                                             \
     const uint32_t st_ = lds_base + (BUF)*STAGE;                                                                \
     const int kt_ = (KT);                                                                                       \
-    if (one_tap) {                                                                                              \
+    if (SRC2 && kt_ >= kt1) {                                                                                   \
+      const uint32_t so_ = (uint32_t)(kt_ - kt1) * 64u;                                                         \
+      _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                           \
+        rart_dma_load16(avoff2[q], srd_a2h, so_, st_ + (wave + NW * q) * 1024);                                 \
+        rart_dma_load16(avoff2[q], srd_a2l, so_, st_ + GP_PLANE_A + (wave + NW * q) * 1024);                    \
+      }                                                                                                         \
+    } else if (one_tap) {                                                                                       \
       const uint32_t so_ = tap0 + (uint32_t)kt_ * 64u;                                                          \
       _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                           \
         rart_dma_load16(avoff[q], srd_ah, so_, st_ + (wave + NW * q) * 1024);                                   \
@@ -273,12 +301,15 @@ extern "C" int rart_gemm_pair_set_schedule(int mode) {
 }
 extern "C" int rart_gemm_pair_get_schedule(void) { return gp_schedule(); }
 
-extern "C" int rart_gemm_pair_bf16(const rart_gemm_pair_desc* h, rart_stream_t stream) {
+// One launch of rart_gemm_pair_bf16 (s2 == nullptr) or rart_gemm_pair2_bf16 (s2: the descriptor that carries the second A source).
+static int gp_launch(const rart_gemm_pair_desc* h, const rart_gemm_pair2_desc* s2, rart_stream_t stream) {
   RART_CHECK_ARG(h != nullptr, "rart_gemm_pair_bf16: null descriptor");
   RART_CHECK_ARG(h->a_hi && h->a_lo && h->w_hi && h->w_lo && h->dst_hi, "rart_gemm_pair_bf16: null operand plane");
   const bool conv = h->conv != 0;
-  GemmPairDev d;
+  GemmPairDev d{};
   d.M = h->M; d.K = h->K;
+  const bool src2 = s2 != nullptr;
+  RART_CHECK_ARG(!src2 || (conv && s2->a2_hi && s2->a2_lo), "rart_gemm_pair2_bf16: the second source is a pair (both planes) and is served by conv mode only");
   if (conv) {
     RART_CHECK_ARG(h->batch > 0 && h->grid_h > 0 && h->grid_w > 0 && h->src_h > 0 && h->src_w > 0 && h->dst_h > 0 && h->dst_w > 0,
                    "rart_gemm_pair_bf16 (conv): empty geometry");
@@ -295,6 +326,18 @@ extern "C" int rart_gemm_pair_bf16(const rart_gemm_pair_desc* h, rart_stream_t s
     RART_CHECK_ARG(h->lda % 8 == 0 || h->lda == 4, "rart_gemm_pair_bf16 (conv): source pixels must keep 16-byte alignment of the K chunks");
     d.M = (int)M;
     d.K = h->k_per_tap * h->n_taps;
+    if (src2) {
+      RART_CHECK_ARG(s2->k2 >= 32 && s2->k2 % GP_BK == 0, "rart_gemm_pair2_bf16: k2 must be a positive multiple of 32");
+      RART_CHECK_ARG(s2->lda2 % 8 == 0 && s2->lda2 >= s2->k2, "rart_gemm_pair2_bf16: lda2 must cover k2 and keep 16-byte alignment of the K chunks");
+      RART_CHECK_ARG(s2->src2_h > 0 && s2->src2_w > 0 && s2->sy2 > 0 && s2->sx2 > 0 && (long long)(h->grid_h - 1) * s2->sy2 < s2->src2_h &&
+                         (long long)(h->grid_w - 1) * s2->sx2 < s2->src2_w,
+                     "rart_gemm_pair2_bf16: every row's pixel must lie inside the second source's image");
+      RART_CHECK_ARG((long long)h->batch * s2->src2_h * s2->src2_w * s2->lda2 < (1ll << 30),
+                     "rart_gemm_pair2_bf16: the second source plane must stay below 2 GiB (split the batch)");
+      d.a2_hi = (const uint16_t*)s2->a2_hi; d.a2_lo = (const uint16_t*)s2->a2_lo;
+      d.lda2 = s2->lda2; d.kt1 = d.K / GP_BK; d.src2_h = s2->src2_h; d.src2_w = s2->src2_w; d.sy2 = s2->sy2; d.sx2 = s2->sx2;
+      d.K += s2->k2;
+    }
     d.grid_h = h->grid_h; d.grid_w = h->grid_w; d.src_h = h->src_h; d.src_w = h->src_w; d.sy = h->sy; d.sx = h->sx; d.n_taps = h->n_taps;
     int sh = 0;
     while ((32 << sh) < h->k_per_tap) ++sh;
@@ -363,6 +406,10 @@ extern "C" int rart_gemm_pair_bf16(const rart_gemm_pair_desc* h, rart_stream_t s
   // pad the MFMA work.  Convolutions: K <= 256 (the HBM-bound 1x1 layers: two K steps do not hide a tile's load and store phases) 256 x 64,
   // 80 KB of LDS = two workgroups per CU; K < 1024 128 x {128, 64} (64 / 48 KB: two or three per CU); K-deep wide layers 256 x 256 unless
   // that leaves fewer than 128 workgroups (layer4: 256 x 128), K-deep narrow layers (N <= 128) 128 x N.  tile_m / tile_n override.
+  // Two-source launches (a projection shortcut folded into its 1x1: K = K1 + K2) take the same policy; swept at B = 256
+  // (profiles/shortcut_fusion_tile_sweep.txt, us per launch, chosen tile first): 200704 x 384 -> 512: 308 on 224-row x 256 ping-pong (256 x 256
+  // 319, 128 x 128 349, 256 x 64 386); 50176 x 768 -> 1024: 259 on 224 x 256 (256 x 256 273, 128 x 128 289); 12544 x 1536 -> 2048: 206 on
+  // 224 x 256 (256 x 256 214, 256 x 128 258); layer1's backward 802816 x 320 -> 64: 246 on 128 x 64 (256 x 64 252).
   int tn = d.N <= 64 ? 64 : (d.N <= 128 ? 128 : 256), tm = 256;
   if (conv) {
     if (gp_schedule() >= 1 && d.N >= 256 && (d.K >= 512 || (d.K >= 256 && d.N <= 512))) {
@@ -388,7 +435,7 @@ extern "C" int rart_gemm_pair_bf16(const rart_gemm_pair_desc* h, rart_stream_t s
   hipStream_t st = (hipStream_t)stream;
   // the persistent kernel (256 x 128 tiles, deferred epilogue): one tap, no GELU epilogue, no row re-basing / batching, at least two tiles per
   // CU and a K loop with room for the 12 micro-steps of a tile's epilogue
-  if (gp_schedule() == 2 && tm == 256 && tn >= 128 && h->tile_n == 0 && h->tile_m == 0 && nz == 1 && !d.map_rows && d.src_off == 0 &&
+  if (gp_schedule() == 2 && !src2 && tm == 256 && tn >= 128 && h->tile_n == 0 && h->tile_m == 0 && nz == 1 && !d.map_rows && d.src_off == 0 &&
       (conv ? d.n_taps == 1 : true) && !(h->flags & (GP_GELU | GP_GELU_BWD | GP_GELU_KEEP)) && d.K / GP_BK >= 6) {
     const int cus = gp_cu_count();
     const long long tiles = (long long)((d.M + 255) / 256) * ((d.N + 127) / 128);
@@ -448,7 +495,7 @@ extern "C" int rart_gemm_pair_bf16(const rart_gemm_pair_desc* h, rart_stream_t s
     }
   }
   // schedule 3: launches of more than one tile per CU are WALKED by one workgroup per CU (k_gemm_pair_pp, OPT bit 1)
-  const unsigned walk_wgs = (gp_schedule() == 3 && nz == 1 && blocks > (long long)gp_cu_count()) ? (unsigned)(gp_cu_count() & ~7) : 0u;
+  const unsigned walk_wgs = (gp_schedule() == 3 && !src2 && nz == 1 && blocks > (long long)gp_cu_count()) ? (unsigned)(gp_cu_count() & ~7) : 0u;
   if (tm == 256 && tn >= 128 && gp_schedule() >= 1 && rart_gemm_pair_pp_launch(&d, tn, conv, grid.x, grid.y, st, walk_wgs)) {
     RART_CHECK_LAUNCH("rart_gemm_pair_bf16 (ping-pong)");
     return RART_OK;
@@ -465,14 +512,17 @@ extern "C" int rart_gemm_pair_bf16(const rart_gemm_pair_desc* h, rart_stream_t s
       grid2 = dim3((uint32_t)((mt2 >= 16 ? (mt2 + 7) / 8 * 8 : mt2) * n_tiles), nz);
     }
   }
-#define RART_GP_LAUNCH(TM_, TN_, CONV_) hipLaunchKernelGGL((k_gemm_pair<TM_, TN_, CONV_>), grid2, dim3(TM_ * 2), 0, st, d)
-#define RART_GP_BY_TN(TM_, CONV_)                                          \
+#define RART_GP_LAUNCH(TM_, TN_, ...) hipLaunchKernelGGL((k_gemm_pair<TM_, TN_, __VA_ARGS__>), grid2, dim3(TM_ * 2), 0, st, d)
+#define RART_GP_BY_TN(TM_, ...)                                            \
   do {                                                                     \
-    if (tn == 64) RART_GP_LAUNCH(TM_, 64, CONV_);                          \
-    else if (tn == 128) RART_GP_LAUNCH(TM_, 128, CONV_);                   \
-    else RART_GP_LAUNCH(TM_, 256, CONV_);                                  \
+    if (tn == 64) RART_GP_LAUNCH(TM_, 64, __VA_ARGS__);                    \
+    else if (tn == 128) RART_GP_LAUNCH(TM_, 128, __VA_ARGS__);             \
+    else RART_GP_LAUNCH(TM_, 256, __VA_ARGS__);                            \
   } while (0)
-  if (conv) {
+  if (src2) {
+    if (tm == 128) RART_GP_BY_TN(128, true, true);
+    else RART_GP_BY_TN(256, true, true);
+  } else if (conv) {
     if (tm == 128) RART_GP_BY_TN(128, true);
     else RART_GP_BY_TN(256, true);
   } else {
@@ -484,3 +534,13 @@ extern "C" int rart_gemm_pair_bf16(const rart_gemm_pair_desc* h, rart_stream_t s
   RART_CHECK_LAUNCH("rart_gemm_pair_bf16");
   return RART_OK;
 }
+
+extern "C" int rart_gemm_pair_bf16(const rart_gemm_pair_desc* h, rart_stream_t stream) { return gp_launch(h, nullptr, stream); }
+
+// Two A sources (include/robustart_hip.h): the launch `one` describes, and when a2_hi is set the second source's K steps after its own.
+extern "C" int rart_gemm_pair2_bf16(const rart_gemm_pair2_desc* h, rart_stream_t stream) {
+  RART_CHECK_ARG(h != nullptr, "rart_gemm_pair2_bf16: null descriptor");
+  RART_CHECK_ARG((h->a2_hi == nullptr) == (h->a2_lo == nullptr), "rart_gemm_pair2_bf16: the second source is a pair: both planes or none");
+  return gp_launch(&h->one, h->a2_hi ? h : nullptr, stream);
+}
+extern "C" int rart_gemm_pair_max_sources(void) { return 2; }

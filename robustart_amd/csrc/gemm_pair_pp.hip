@@ -75,9 +75,12 @@ __device__ unsigned long long g_pp_trace[4096][4];       // per workgroup (block
 //            K loop (K = 768).  Walking removes the first; the second shrinks because the next tile's stage 0 is requested BEFORE the
 //            epilogue (which stages through the bytes after stage 0, so the tile buffer is STAGE + staging long) and lands while the
 //            epilogue's loads and stores run.  The epilogue itself is unchanged (gp_epilogue, in order): same bits.
-template <int TN, bool CONV, int OPT>
+// SRC2 (CONV, not WALK): the second A source of k_gemm_pair's SRC2 instances -- K steps from d.kt1 on read it; the loads per phase, and with
+//            them the counted waits, are the same whichever source a step reads.
+template <int TN, bool CONV, int OPT, bool SRC2 = false>
 __global__ __launch_bounds__(512, 1) void k_gemm_pair_pp(const GemmPairDev d) {
   constexpr bool BAL = OPT & 1, WALK = OPT & 2;
+  static_assert(!SRC2 || (CONV && !WALK), "the second source is served by the conv instances that do not walk");
   constexpr int TM = 256, NW = 8, WN = TN / 64, WM = NW / WN, RW = TM / WM, MI = RW / 32, MH = MI / 2;
   static_assert(TN == 256 || TN == 128, "column tiles of 256 or 128");
   constexpr int PLANE_A = TM * 64, PLANE_B = TN * 64, STAGE = 2 * PLANE_A + 2 * PLANE_B;
@@ -149,9 +152,24 @@ __global__ __launch_bounds__(512, 1) void k_gemm_pair_pp(const GemmPairDev d) {
     const int hh = q == 0 ? og : g;
     pr[q] = (WM == 2) ? og * 128 + hh * 64 + 16 * w4 : (2 * og + (w4 >> 1)) * 64 + hh * 32 + (w4 & 1) * 16;
   }
-  uint32_t avoff[2], nok[2];
+  uint32_t avoff[2], nok[2], avoff2[2] = {PP_OOR, PP_OOR};
   int tapreg = 0, tap_min = 0;
   const bool one_tap = !CONV || d.n_taps == 1;
+  if (SRC2) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int r = pr[q] + (lane >> 2);
+      const int csrc = (lane & 3) ^ ((r >> 2) & 3);
+      const int m = m0 + r;
+      if (m < d.M && r < d.tile_rows) {      // (the host checked that every row's pixel lies inside the second source's image)
+        const uint32_t t = gp_fastdiv((uint32_t)m, d.gw_magic, d.gw_shift);
+        const int ox = (int)((uint32_t)m - t * (uint32_t)d.grid_w);
+        const int n = (int)gp_fastdiv(t, d.gh_magic, d.gh_shift);
+        const int oy = (int)(t - (uint32_t)n * (uint32_t)d.grid_h);
+        avoff2[q] = (uint32_t)(((n * d.src2_h + oy * d.sy2) * d.src2_w + ox * d.sx2) * d.lda2 * 2 + csrc * 16);
+      }
+    }
+  }
   if (CONV) {
     for (int t = 0; t < d.n_taps; ++t) tap_min = min(tap_min, (d.tap_dy[t] * d.src_w + d.tap_dx[t]) * d.lda * 2);
     if (lane < d.n_taps) tapreg = (d.tap_dy[lane] * d.src_w + d.tap_dx[lane]) * d.lda * 2 - tap_min;
@@ -200,6 +218,8 @@ __global__ __launch_bounds__(512, 1) void k_gemm_pair_pp(const GemmPairDev d) {
   RART_PP_ADDR(m0, n0)
   const pp_srd_t srd_ah = pp_make_srd(reinterpret_cast<const char*>(a_hi) + tap_min), srd_al = pp_make_srd(reinterpret_cast<const char*>(a_lo) + tap_min);
   const pp_srd_t srd_w = pp_make_srd(g ? w_lo : w_hi);
+  const pp_srd_t srd_a2h = pp_make_srd(SRC2 ? d.a2_hi : a_hi), srd_a2l = pp_make_srd(SRC2 ? d.a2_lo : a_lo);
+  const int kt1 = SRC2 ? d.kt1 : 0;
   const int w_step = (d.flags & GP_W_INTERLEAVED) ? 128 : 64;
   const uint32_t w_dst = lds_base + 2 * PLANE_A + g * PLANE_B + w4 * 1024;
   const int KT = d.K / GP_BK;
@@ -209,7 +229,11 @@ __global__ __launch_bounds__(512, 1) void k_gemm_pair_pp(const GemmPairDev d) {
   {                                                                                                              \
     const int s_ = (ST);                                                                                         \
     const uint32_t dst_ = lds_base + (s_ & 1) * STAGE + pr[Q] * 64;                                              \
-    if (one_tap) {                                                                                               \
+    if (SRC2 && s_ >= kt1) {                                                                                     \
+      const uint32_t so_ = (uint32_t)(s_ - kt1) * 64u;                                                           \
+      pp_bload(avoff2[Q], srd_a2h, so_, dst_);                                                                   \
+      pp_bload(avoff2[Q], srd_a2l, so_, dst_ + PLANE_A);                                                         \
+    } else if (one_tap) {                                                                                               \
       const uint32_t so_ = tap0 + (uint32_t)s_ * 64u;                                                            \
       pp_bload(avoff[Q], srd_ah, so_, dst_);                                                                     \
       pp_bload(avoff[Q], srd_al, so_, dst_ + PLANE_A);                                                           \
@@ -710,6 +734,13 @@ __global__ __launch_bounds__(512, 1) void k_gemm_pair_ps(const GemmPairDev d) {
 #endif
 template <int OPT>
 bool pp_launch_opt(const GemmPairDev& d, int tn, bool conv, dim3 grid, hipStream_t st, unsigned walk_wgs = 0) {
+  if (d.a2_hi) {      // two sources: conv instances, never walked (the host entry sends no walk request with a second source)
+    if (!conv || walk_wgs || (OPT & 2)) return false;
+    if (tn == 256) hipLaunchKernelGGL((k_gemm_pair_pp<256, true, OPT & 1, true>), grid, dim3(512), 0, st, d);
+    else if (tn == 128) hipLaunchKernelGGL((k_gemm_pair_pp<128, true, OPT & 1, true>), grid, dim3(512), 0, st, d);
+    else return false;
+    return true;
+  }
   if (walk_wgs && !(OPT & 2)) return pp_launch_opt<OPT | 2>(d, tn, conv, dim3(walk_wgs < grid.x ? walk_wgs : grid.x, 1), st);
   if (tn == 256) {
     if (conv) hipLaunchKernelGGL((k_gemm_pair_pp<256, true, OPT>), grid, dim3(512), 0, st, d);

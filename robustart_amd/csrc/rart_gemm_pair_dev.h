@@ -33,6 +33,10 @@ struct GemmPairDev {
   int m_begin;                                           // k_gemm_pair_pp only: the launch covers rows m_begin .. M - 1 (0 elsewhere)
   int tile_rows;                                         // k_gemm_pair_pp only: 256, or 224 = the last 32-row block of a tile is left out
   int nt;                                                // the epilogue's streams (residual / pre-activation loads, pair stores) are non-temporal
+  // SRC2 instances (CONV only): the second A source -- one tap at offset 0, pixel (oy sy2, ox sx2) of a src2_h x src2_w image, lda2 elements
+  // per pixel; K steps kt1 .. K / 32 - 1 of the launch read it (kt1 = the first source's K steps).  a2_hi == nullptr: one source
+  const uint16_t *a2_hi, *a2_lo;
+  int lda2, kt1, src2_h, src2_w, sy2, sx2;
 };
 __device__ __forceinline__ uint32_t gp_fastdiv(uint32_t n, uint32_t magic, uint32_t shift) {
   return (uint32_t)(((uint64_t)n * magic) >> shift);

@@ -43,6 +43,29 @@ def _table(build, planes, device):
     return _bf16(torch.cat(t + t[:1], 1) if len(t) == 2 else t[0]).to(device)
 
 
+def _cat_k(t1, k1, t2, k2):
+    """two [rows][hi | lo | hi] tables of `_Conv(split=True)`, K = k1 and k2, as ONE such table whose rows are [T1 | T2] along K: the
+    table of a two-source rart_gemm_pair_bf16 launch (hi = [T1_hi | T2_hi], lo = [T1_lo | T2_lo], row stride 3 (k1 + k2))"""
+    import torch
+    assert t1.shape == (t2.shape[0], 3 * k1) and t2.shape[1] == 3 * k2
+    return torch.cat([t[:, i * k:(i + 1) * k] for i in range(3) for t, k in ((t1, k1), (t2, k2))], 1).contiguous()
+
+
+def fold_shortcut_tables(ca, cc, ds):
+    """Reference precision, a Bottleneck (conv1 ca, conv3 cc) with the 1x1 projection shortcut ds: the tables that fold the shortcut into
+    the launch it is added in.  ds.w_cat = rows [W3 | Wds] and ds.bias_cat = b3 + bds: yc = relu(W3 . yb + Wds . x_strided + bias_cat) is
+    one accumulation of a two-source launch.  A stride-1 shortcut also gets ds.w_cat_bwd = rows [W1^T | Wds^T]: dx = mask(W1^T . dza +
+    Wds^T . dz).  -> whether the block has the form (1x1 convolutions, power-of-two K of the first source)."""
+    pow2 = lambda k: k >= 32 and (k & (k - 1)) == 0                      # noqa: E731
+    if not (cc.r == 1 and cc.stride == 1 and ds.r == 1 and ds.cout == cc.cout and pow2(cc.cin) and ds.cin % 32 == 0):
+        return False
+    ds.w_cat = _cat_k(cc.w_fwd, cc.cin, ds.w_fwd, ds.cin)
+    ds.bias_cat = (cc.bias + ds.bias).contiguous()
+    if ds.stride == 1 and ca.r == 1 and ca.stride == 1 and ca.cin == ds.cin and pow2(ca.cout) and ds.cout % 32 == 0:
+        ds.w_cat_bwd = _cat_k(ca.bwd[0][2], ca.cout, ds.bwd[0][2], ds.cout)
+    return True
+
+
 class _Conv:
     """One folded conv layer: forward table + backward-to-input tables, in bf16 or (split) as [hi | lo | hi] rows."""
 
@@ -127,6 +150,11 @@ class ResNet50Engine(EngineBase):
         # 20.12 -> 19.98 ms per gradient evaluation, same bits (scratch/r6/tail_channels.py)
         self.fused_tail_channels = (64,)
         self.fused_tail_pair = True      # reference-precision mode: 3x3 + 1x1 expansion of a Bottleneck as one launch (conv_tail_pair.hip); False: two launches (cross-check)
+        # reference-precision mode: the projection shortcut of a layer's first block as extra K steps of the launch it is added in (conv3's
+        # two-source launch; layer1's tail kernel; backward of layer1's stride-1 shortcut inside conv1^T's launch) -- its 4C-channel skip pair
+        # never exists in HBM.  False: its own launch, added as conv3's residual (cross-check).  The stride-2 shortcuts' BACKWARD keeps its
+        # launch on purpose: their gradient reaches one input-parity class in four
+        self.fused_shortcut_pair = True
         self.pair_gemm_kernel = True     # reference-precision mode: False = the three products as 3 x the taps of the implicit GEMM (round 3; cross-check)
         self.blocks = []
         for layer in (m.layer1, m.layer2, m.layer3, m.layer4):
@@ -170,7 +198,10 @@ class ResNet50Engine(EngineBase):
                 w = tab[:rows, pl * k:(pl + 1) * k]
                 out.append(w.reshape(rows // 32, 32, k // 64, 4, 2, 8).permute(2, 0, 3, 4, 1, 5).contiguous().view(-1))
             return torch.stack(out).contiguous()
+        two_sources = self.lib.rart_gemm_pair_max_sources() >= 2      # the library takes a second A source per pair launch
         for bi, (ca, cb, cc, ds) in enumerate(self.blocks):
+            if two_sources and ds is not None and fold_shortcut_tables(ca, cc, ds) and ds.stride == 1 and ds.cin == 64 and cc.cout == 4 * cb.cout:
+                ds.tail_x = frag(ds.w_fwd, ds.cout, ds.cin)        # layer1's first block: the shortcut inside the tail kernel
             if not (cb.r == 3 and cb.stride == 1 and cb.pad == 1 and cb.cin == cb.cout and self.lib.rart_conv3x3_tail_pair_supported(cb.cin)):
                 continue
             if cc.cin == cb.cout and cc.cout == 4 * cb.cout and cc.r == 1 and cc.stride == 1:
@@ -411,10 +442,11 @@ class ResNet50Engine(EngineBase):
     # ------------------------------------------------------------------ launches
     def _gemm(self, src, wgt, dst, batch, grid, src_hw, src_pix, k_per_tap, taps, n_cols, dst_hw, dst_pix,
               bias=None, res=None, mask=None, flags=0, stride=(1, 1), dst_stride=(1, 1), dst_off=(0, 0),
-              tap_src_off=None, sign_out=None, pair=False):
+              tap_src_off=None, sign_out=None, pair=False, src2=None):
         if pair and self.pair_gemm_kernel and len(taps) <= 16 and k_per_tap >= 32 and (k_per_tap & (k_per_tap - 1)) == 0:
             return self._gemm_pair(src, wgt, dst, batch, grid, src_hw, src_pix, k_per_tap, taps, n_cols, dst_hw, dst_pix, bias, res,
-                                   mask, flags, stride, dst_stride, dst_off, sign_out)
+                                   mask, flags, stride, dst_stride, dst_off, sign_out, src2)
+        assert src2 is None, 'a second source is served by rart_gemm_pair_bf16 only'
         dst_pair_off = res_pair_off = 0
         if pair:
             # split-bf16 tensors [2][...] (hi plane, lo plane): the three products as 3x the taps, the lo planes of dst / res
@@ -432,14 +464,15 @@ class ResNet50Engine(EngineBase):
                                     dst_org=dst_off, tap_src_off=tap_src_off, dst_pair_off=dst_pair_off, res_pair_off=res_pair_off))
 
     def _gemm_pair(self, src, wgt, dst, batch, grid, src_hw, src_pix, k_per_tap, taps, n_cols, dst_hw, dst_pix, bias, res, mask, flags,
-                   stride, dst_stride, dst_off, sign_out):
+                   stride, dst_stride, dst_off, sign_out, src2=None):
         """One convolution / product of the reference-precision mode on rart_gemm_pair_bf16 (csrc/gemm_pair.hip, conv mode): the four
         operand planes of a K step staged once, three MFMAs per fragment pair -- round 3 listed the three products as 3 x the taps of
         rart_conv_igemm_bf16, which fetched x_hi twice and ran at a quarter of this kernel's MFMA rate.  src / dst / res: pair tensors
         [2][...]; wgt: the [rows][hi | lo | hi] table of `_Conv(split=True)` (w_hi = columns 0..K, w_lo = columns K..2K, row stride 3K);
-        mask: 1-bit ReLU mask of the destination; an fp32 destination (F_OUT_F32) is a plain tensor."""
+        mask: 1-bit ReLU mask of the destination; an fp32 destination (F_OUT_F32) is a plain tensor.  src2 = (pair tensor, its hw, its
+        stride, elements per pixel, k2): a second source whose k2 channels follow in the rows of wgt (`_cat_k`)."""
         assert src.shape[0] == 2
-        k_tot = k_per_tap * len(taps)
+        k_tot = k_per_tap * len(taps) + (src2[4] if src2 is not None else 0)
         assert wgt.shape[1] == 3 * k_tot
         il = None
         if self.pair_w_interleaved:
@@ -454,17 +487,20 @@ class ResNet50Engine(EngineBase):
             rows = batch * grid[0] * grid[1]
             nbytes = 4.0 * batch * src_hw[0] * src_hw[1] * k_per_tap + 4.0 * rows * n_cols * (2 if res is not None else 1) + 4.0 * k_tot * n_cols \
                 + rows * n_cols / 8.0 * ((mask is not None) + (sign_out is not None))
+            if src2 is not None:
+                nbytes += 4.0 * batch * src2[1][0] * src2[1][1] * src2[4]
         self._launch_pair(gemm_pair_desc(src, wgt, dst, n_cols, src_pix, 3 * k_tot, dst_pix, wgt.shape[0], bias=bias, res=res, mask_bits=mask,
                                          sign_out=sign_out, flags=flags & (F_RELU | F_OUT_F32), w_lo_off=k_tot, w_il=il, batch=batch,
                                          grid=grid, src_hw=src_hw, stride=stride, k_per_tap=k_per_tap, taps=taps, dst_hw=dst_hw,
-                                         dst_stride=dst_stride, dst_org=dst_off, tile=self.pair_tile), nbytes)
+                                         dst_stride=dst_stride, dst_org=dst_off, tile=self.pair_tile, src2=src2), nbytes)
 
     def _tail(self, src, wgt, taps, tail, dst, batch, hw, c_mid, bias_mid=None, bias_out=None, res=None, mask_mid=None, mask_out=None,
-              sign_mid=None, sign_out=None, relu=False, nxt=None):
+              sign_mid=None, sign_out=None, relu=False, nxt=None, xsrc=None):
         """3x3 (c_mid -> c_mid) + point-wise step + 1x1 expansion (c_mid -> 4 c_mid) + skip pair + point-wise step of the
         reference-precision mode as ONE launch (csrc/conv_tail_pair.hip).  src / dst / res: pair tensors; wgt: the 3x3's
         [rows][hi | lo | hi] table; tail: `_pack_tail_tables`' [2][...] fragment-ordered 1x1 table.  nxt: the neighbouring block's 1x1
-        reduction of the tile in the same launch -- dict(tab, dst, bias, mask, sign, relu)."""
+        reduction of the tile in the same launch -- dict(tab, dst, bias, mask, sign, relu).  xsrc = (x pair [2][B][h][w][64], its
+        fragment-ordered table): the block's stride-1 projection shortcut as extra K steps of the 1x1 (res None, bias_out the bias sum)."""
         k_tot = 9 * c_mid
         assert src.shape[0] == 2 and wgt.shape[1] == 3 * k_tot and len(taps) == 9
         d = _lib.ConvTailDesc()
@@ -480,6 +516,9 @@ class ResNet50Engine(EngineBase):
         d.relu_mid = d.relu_out = 1 if relu else 0
         for i, (dy, dx) in enumerate(taps):
             d.tap_dy[i], d.tap_dx[i] = dy, dx
+        if xsrc is not None:
+            assert res is None and c_mid == 64 and xsrc[0].shape[-1] == 64
+            d.x_hi, d.x_lo, d.tx_hi, d.tx_lo = xsrc[0][0].data_ptr(), xsrc[0][1].data_ptr(), xsrc[1][0].data_ptr(), xsrc[1][1].data_ptr()
         if nxt is not None:
             d.n_hi, d.n_lo = nxt['tab'][0].data_ptr(), nxt['tab'][1].data_ptr()
             d.dstn_hi, d.dstn_lo = nxt['dst'][0].data_ptr(), nxt['dst'][1].data_ptr()
@@ -489,9 +528,9 @@ class ResNet50Engine(EngineBase):
         _lib.check(self.lib.rart_conv3x3_tail_pair(ctypes.byref(d), _lib.stream_ptr()))
         if ev is not None:
             px = batch * hw[0] * hw[1]
-            nbytes = 4.0 * px * c_mid * (1 + 4 + (4 if res is not None else 0) + (1 if nxt is not None else 0)) \
-                + 4.0 * c_mid * c_mid * (9 + 4 + (4 if nxt is not None else 0))
-            self._prof_end(ev, 3 * 2.0 * px * (k_tot * c_mid + (8 if nxt is not None else 4) * c_mid * c_mid), 'conv_tail_pair',
+            nx, xs = (1 if nxt is not None else 0), (1 if xsrc is not None else 0)
+            nbytes = 4.0 * px * c_mid * (1 + 4 + (4 if res is not None else 0) + nx + xs) + 4.0 * c_mid * c_mid * (9 + 4 + 4 * nx + 4 * xs)
+            self._prof_end(ev, 3 * 2.0 * px * (k_tot * c_mid + (4 + 4 * nx + 4 * xs) * c_mid * c_mid), 'conv_tail_pair',
                            nbytes)   # MFMA FLOPs issued, algorithmic bytes (every operand once)
 
     def _fc(self, a, w, out, m, n, k, bias=None):
@@ -766,22 +805,30 @@ class ResNet50Engine(EngineBase):
             ya = get('b%d_a' % bi, lead + (xhw[0], xhw[1], ca.cout))
             if not pre_a:
                 self._conv_fwd(ca, x, xhw, ya, True, sign=sa, pair=x3)
+            # reference precision: the projection shortcut rides in the launch it is added in (`fused_shortcut_pair`)
+            fold = x3 and ds is not None and self.fused_shortcut_pair and self.pair_gemm_kernel and \
+                getattr(ds, 'tail_x' if kind == 'tail' else 'w_cat', None) is not None
             if x3:               # (the pair chain launches the projection shortcut before conv2, the bf16 chain after it)
-                sk = x if ds is None else self._shortcut_fwd(bi, ds, x, xhw, ohw, B)
+                sk = x if ds is None else (None if fold else self._shortcut_fwd(bi, ds, x, xhw, ohw, B))
             if kind == 'tail':   # conv2 + relu + conv3 + skip + relu in one launch: the 3x3's output never exists in HBM
                 na = self.blocks[bi + 1][0] if bi + 1 < len(self.blocks) else None
                 if self.fused_next_pair and na is not None and getattr(na, 'next_fwd', None) is not None and cb.cout in self.fused_next_channels:
                     # ... and the next block's conv1 + relu on the output tile: that block's own read of this output disappears
                     nxt = dict(tab=na.next_fwd, bias=na.bias, relu=True, dst=get('b%d_a' % (bi + 1), lead + (ohw[0], ohw[1], na.cout)),
                                sign=get('b%d_a_sign' % (bi + 1), (B, ohw[0], ohw[1], na.cout // 8), torch.uint8) if keep else None)
-                self._tail(ya, cb.w_fwd, cb.fwd_taps, cc.tail_fwd, yc, B, ohw, cb.cout, bias_mid=cb.bias, bias_out=cc.bias, res=sk,
-                           sign_mid=sb, sign_out=sc, relu=True, nxt=nxt)
+                self._tail(ya, cb.w_fwd, cb.fwd_taps, cc.tail_fwd, yc, B, ohw, cb.cout, bias_mid=cb.bias,
+                           bias_out=ds.bias_cat if fold else cc.bias, res=sk, sign_mid=sb, sign_out=sc, relu=True, nxt=nxt,
+                           xsrc=(x, ds.tail_x) if fold else None)
             else:
                 yb = get('b%d_b' % bi, lead + (ohw[0], ohw[1], cb.cout))
                 self._conv_fwd(cb, ya, xhw, yb, True, sign=sb, pair=x3)
                 if not x3:
                     sk = x if ds is None else self._shortcut_fwd(bi, ds, x, xhw, ohw, B)
-                self._conv_fwd(cc, yb, ohw, yc, True, res=sk, sign=sc, pair=x3)
+                if fold:         # conv3 and the shortcut as one two-source launch: K = cc.cin + ds.cin
+                    self._gemm(yb, ds.w_cat, yc, B, ohw, ohw, cc.cin, cc.cin, cc.fwd_taps, cc.cout, ohw, cc.cout, bias=ds.bias_cat,
+                               flags=F_RELU, sign_out=sc, pair=True, src2=(x, xhw, (ds.stride, ds.stride), ca.cin, ds.cin))
+                else:
+                    self._conv_fwd(cc, yb, ohw, yc, True, res=sk, sign=sc, pair=x3)
         acts['b%d' % bi] = (x, xhw, ya, yb, yc, ohw)
         # the backward pass needs the activations only for their ReLU sign: the 1-bit tensors, or with `sign_bit_masks` off (bf16
         # cross-check) the activations themselves
@@ -873,6 +920,10 @@ class ResNet50Engine(EngineBase):
             self._conv_bwd(cb, dzb, ohw, dza, xhw, mask=ma, pair=x3)
             if ds is None:
                 self._conv_bwd(ca, dza, xhw, dx, xhw, res=dz, mask=mx, pair=x3)            # identity skip
+            elif x3 and self.fused_shortcut_pair and self.pair_gemm_kernel and getattr(ds, 'w_cat_bwd', None) is not None:
+                # stride-1 projection skip (layer1's first block): conv1^T and the shortcut^T as one two-source launch, dx written once
+                self._gemm(dza, ds.w_cat_bwd, dx, B, xhw, xhw, ca.cout, ca.cout, ca.bwd[0][1], ca.cin, xhw, ca.cin, mask=mx,
+                           flags=F_MASK_BITS, pair=True, src2=(dz, ohw, (1, 1), ds.cout, ds.cout))
             else:
                 self._conv_bwd(ca, dza, xhw, dx, xhw, mask=mx, pair=x3)
                 self._conv_bwd(ds, dz, ohw, dx, xhw, res=dx, mask=mx, pair=x3)             # accumulate the projection skip

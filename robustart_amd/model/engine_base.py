@@ -166,16 +166,19 @@ def conv_desc(src, wgt, dst, batch, grid, src_hw, src_pix, k_per_tap, taps, n_co
 def gemm_pair_desc(a, w, dst, N, lda, ldw, ldc, w_rows, M=0, K=0, bias=None, res=None, aux=None, mask_bits=None, sign_out=None, flags=0,
                    a_off=0, w_off=0, dst_off=0, w_lo_off=None, w_il=None, rows_per_image=0, src_rows_per_image=0, src_row_off=0,
                    dst_rows_per_image=0, dst_row_off=0, batched=None, batch=0, grid=None, src_hw=(0, 0), stride=(1, 1), k_per_tap=0,
-                   taps=(), dst_hw=(0, 0), dst_stride=(1, 1), dst_org=(0, 0), tile=(0, 0)):
+                   taps=(), dst_hw=(0, 0), dst_stride=(1, 1), dst_org=(0, 0), tile=(0, 0), src2=None):
     """rart_gemm_pair_desc: (a_hi + a_lo)[M][K] . (w_hi + w_lo)[N][K]^T -> dst, three MFMA products per contraction.
     a / res / aux / dst: pair tensors [2][...] (dst with GP_OUT_F32: a plain fp32 tensor); *_off: element offsets inside a plane.
     w: a pair tensor, or with w_lo_off one table that holds the lo plane w_lo_off elements after the hi plane; w_il: the
     interleaved copy of w's planes (`interleave_k32`), which replaces them.  batched = dict(n, inner, a=(outer, inner),
     w=(outer, inner), c=(outer, inner)).  Row form unless `grid` is given; conv form: output pixel (b, y, x) of batch x grid reads
-    source pixel (y * sy + dy, x * sx + dx) per tap (dy, dx), k_per_tap channels each (M and K follow from the geometry)."""
-    d = _lib.GemmPairDesc()
+    source pixel (y * sy + dy, x * sx + dx) per tap (dy, dx), k_per_tap channels each (M and K follow from the geometry).
+    src2 (conv form) = (pair tensor, its (h, w), (sy, sx), elements per pixel, k2): a second source read at pixel (y * sy, x * sx), whose k2
+    channels follow the first source's K in the rows of w; the result is then a rart_gemm_pair2_desc (GemmPair2Desc) around the launch."""
+    d2 = _lib.GemmPair2Desc() if src2 is not None else None
+    d = d2.one if d2 is not None else _lib.GemmPairDesc()       # (d2.one is a view: filling it fills the two-source descriptor)
     if grid is not None:
-        M, K = batch * grid[0] * grid[1], k_per_tap * len(taps)
+        M, K = batch * grid[0] * grid[1], k_per_tap * len(taps) + (src2[4] if src2 is not None else 0)
     d.a_hi, d.a_lo = a[0].data_ptr() + 2 * a_off, a[1].data_ptr() + 2 * a_off
     if w_il is not None:
         d.w_hi, d.w_lo, ldw = w_il.data_ptr(), w_il.data_ptr() + 64, 2 * K
@@ -214,6 +217,11 @@ def gemm_pair_desc(a, w, dst, N, lda, ldw, ldc, w_rows, M=0, K=0, bias=None, res
         d.dst_oy, d.dst_ox = dst_org
     d.mask_bits, d.sign_out = _addr(mask_bits), _addr(sign_out)
     d.tile_m, d.tile_n = tile
+    if d2 is not None:
+        a2, hw2, st2, lda2, k2 = src2
+        d2.a2_hi, d2.a2_lo = a2[0].data_ptr(), a2[1].data_ptr()
+        d2.lda2, d2.k2, d2.src2_h, d2.src2_w, d2.sy2, d2.sx2 = lda2, k2, hw2[0], hw2[1], st2[0], st2[1]
+        return d2
     return d
 
 
@@ -367,9 +375,14 @@ class EngineBase:
             self._prof_end(ev, 2.0 * d.batch * d.grid_h * d.grid_w * d.k_per_tap * d.n_taps * d.n_cols * max(d.n_batched, 1), 'igemm')
 
     def _launch_pair(self, d, nbytes=None):
-        """rart_gemm_pair_bf16 on descriptor d; profiled as 'gemm_pair' (MFMA FLOPs issued: three products)"""
+        """rart_gemm_pair_bf16 on descriptor d (rart_gemm_pair2_bf16 on a two-source descriptor); profiled as 'gemm_pair' (MFMA FLOPs
+        issued: three products; K of a two-source launch counts both sources)"""
         ev = self._prof_begin()
-        _lib.check(self.lib.rart_gemm_pair_bf16(ctypes.byref(d), _lib.stream_ptr()))
+        if isinstance(d, _lib.GemmPair2Desc):
+            _lib.check(self.lib.rart_gemm_pair2_bf16(ctypes.byref(d), _lib.stream_ptr()))
+            d = d.one
+        else:
+            _lib.check(self.lib.rart_gemm_pair_bf16(ctypes.byref(d), _lib.stream_ptr()))
         if ev is not None:
             self._prof_end(ev, 3 * 2.0 * max(d.n_batched, 1) * d.M * d.N * d.K, 'gemm_pair', nbytes)
 

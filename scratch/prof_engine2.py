@@ -26,6 +26,8 @@ def wrapped(src, wgt, dst, batch, grid, src_hw, src_pix, k_per_tap, taps, n_cols
     stride = kw.get('stride', (1, 1))
     # unique source bytes: the pixels the row grid touches once (taps re-read them from cache), capped by the tensor
     src_bytes = min(src.numel() * src.element_size(), M * K * 2) if len(taps) > 1 else M * K * 2
+    if kw.get('src2') is not None:      # a two-source launch (the folded projection shortcut): K = K1 + K2, both sources once
+        K += kw['src2'][4]; src_bytes += M * kw['src2'][4] * 2
     by = src_bytes + K * n_cols * 2 + M * n_cols * (4 if kw.get('flags', 0) & 2 else 2)
     if kw.get('res') is not None: by += M * n_cols * 2
     mk = kw.get('mask')
