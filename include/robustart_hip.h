@@ -1154,6 +1154,53 @@ int rart_jpeg_decode_u8(const rart_jpeg_desc* desc, const rart_jpeg_desc* desc_h
                         const uint16_t* qt, size_t qt_count, void* workspace, size_t workspace_bytes, uint8_t* out, size_t out_bytes,
                         rart_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Batched variable-size resize (csrc/resize_batch.hip): Pillow's Image.resize for 8-bit RGB for n images of DIFFERENT sizes in one
+ * call -- crop(box), resize to (resize_h, resize_w) with filter 0..5, the crop window (crop_y, crop_x, crop_h, crop_w) of the
+ * target, then an optional left-right mirror: what imagenet_s_gen.py:119-120 and torchvision's resized_crop compute.  The box is a
+ * hard boundary (the filter support never reads outside it; Image.resize(box=...) does).  Arithmetic: that of rart_pil_resize_u8
+ * for the filtered operators.
+ * Two launches per call for the filtered operators, one for NEAREST, whatever n and however the sizes mix.
+ *
+ * rart_resize_batch_plan is HOST-ONLY (no HIP call).  The caller fills src, h, w, box_* and flip of n descriptors; the plan entry
+ * writes into plan_host, a buffer of `capacity` bytes, four regions, each 16-byte aligned, behind one another:
+ *   rart_resize_plan header    : the call's parameters, the element counts and byte offsets of the regions, and workspace_bytes
+ *   n rart_resize_desc         : the caller's fields plus the derived ones
+ *   n + 1 int64 prefix         : prefix[i] = first-pass work items (= bytes of the uint8 intermediate) of the images before i;
+ *                                image i has mid_count_i * crop_w * 3 of them (vfirst: crop_h * mid_count_i * 3).  NEAREST: all zero.
+ *   table_count int32          : the coefficient tables, rows [xmin, count, k0 .. k_{ksize-1}] (22-bit fixed point), each distinct
+ *                                (in_size, out_size, filter) of the call stored once however many images share it.  NEAREST: index
+ *                                tables instead, out_size entries each = the source column / row of every output column / row,
+ *                                from Pillow's double accumulation (Geometry.c ImagingScaleAffine)
+ * `sizes` (optional) receives the same header; sizes->total_bytes is the buffer size the call needs = 80 + 64 n +
+ * 16-aligned(8 (n + 1)) + 4 table_count.  With plan_host NULL only `sizes` is filled (RART_OK); a capacity below total_bytes is
+ * RART_ERR_WORKSPACE and nothing is written.
+ * The caller moves plan_host[0 .. total_bytes) to the device in ONE copy (16-byte aligned) and passes both copies to
+ * rart_resize_batch_u8, which validates the HOST copy before any launch: the count, the filter, the crop window inside the
+ * target, every box inside its image, the region offsets, every table offset and every tap range the kernels will read, the
+ * prefix table, workspace_bytes >= header.workspace_bytes and out_bytes >= n crop_h crop_w 3 -- so no descriptor can make a kernel
+ * read or write outside the caller's buffers (RART_ERR_INVALID / RART_ERR_WORKSPACE).  out: uint8 [n][crop_h][crop_w][3]. */
+typedef struct rart_resize_desc {
+  uint64_t src;                           /* device address of the image, uint8 [h][w][3] */
+  int32_t h, w;
+  int32_t box_y, box_x, box_h, box_w;     /* the source box, inside the image */
+  int32_t flip;                           /* non-zero: mirror the output left-right */
+  /* derived by rart_resize_batch_plan */
+  int32_t mid_first, mid_count;           /* rows (vfirst: columns) of the box, relative to it, that the first pass produces */
+  int32_t tab_h, ks_h, tab_v, ks_v;       /* int32 element of the table region where the table starts; its taps per row (NEAREST: 0) */
+  int32_t vfirst;                         /* 1: vertical pass first, as PIL's resize() does when box_h > 100 box_w and the height shrinks */
+} rart_resize_desc;
+typedef struct rart_resize_plan {
+  int32_t n, filter, resize_h, resize_w, crop_y, crop_x, crop_h, crop_w;
+  int64_t desc_off, prefix_off, table_off;    /* byte offsets from the start of the buffer */
+  int64_t table_count;                        /* int32 elements */
+  int64_t workspace_bytes, total_bytes;
+} rart_resize_plan;
+int rart_resize_batch_plan(const rart_resize_desc* images_host, int n, int filter, int resize_h, int resize_w, int crop_y, int crop_x,
+                           int crop_h, int crop_w, void* plan_host, size_t capacity, rart_resize_plan* sizes);
+int rart_resize_batch_u8(const void* plan, const void* plan_host, size_t plan_bytes, void* workspace, size_t workspace_bytes,
+                         uint8_t* out, size_t out_bytes, rart_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -235,6 +235,8 @@ SIGNATURES = {
     'rart_jpeg_decode_workspace_bytes': (c_size_t, [c_void_p, c_int]),
     'rart_jpeg_decode_u8': (c_int, [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_int64, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
                                     c_size_t, c_void_p]),
+    'rart_resize_batch_plan': (c_int, [c_void_p, c_int] + [c_int] * 7 + [c_void_p, c_size_t, c_void_p]),
+    'rart_resize_batch_u8': (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
 }
 
 
@@ -275,6 +277,20 @@ class JpegDesc(ctypes.Structure):
                 ('out_off', ctypes.c_int64)] + \
                [(n, ctypes.c_int32) for n in ('height', 'width', 'ncomp', 'h_samp', 'v_samp')] + \
                [('blocks_w', ctypes.c_int32 * 3), ('blocks_h', ctypes.c_int32 * 3), ('reserved_', ctypes.c_int32)]
+
+
+class ResizeDesc(ctypes.Structure):
+    """rart_resize_desc (include/robustart_hip.h): one image of a rart_resize_batch_u8 call, 64 bytes.  The caller fills src .. flip,
+    rart_resize_batch_plan the rest."""
+    _fields_ = [('src', ctypes.c_uint64)] + \
+               [(n, ctypes.c_int32) for n in ('h', 'w', 'box_y', 'box_x', 'box_h', 'box_w', 'flip', 'mid_first', 'mid_count', 'tab_h', 'ks_h',
+                                              'tab_v', 'ks_v', 'vfirst')]
+
+
+class ResizePlan(ctypes.Structure):
+    """rart_resize_plan (include/robustart_hip.h): the header of a rart_resize_batch_plan buffer, 80 bytes."""
+    _fields_ = [(n, ctypes.c_int32) for n in ('n', 'filter', 'resize_h', 'resize_w', 'crop_y', 'crop_x', 'crop_h', 'crop_w')] + \
+               [(n, ctypes.c_int64) for n in ('desc_off', 'prefix_off', 'table_off', 'table_count', 'workspace_bytes', 'total_bytes')]
 
 
 class FixedPointInfo(ctypes.Structure):

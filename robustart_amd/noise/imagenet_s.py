@@ -7,6 +7,8 @@ rart_pil_resize_u8; the five 'opencv-*' operators run through rart_cv_resize_u8,
 (OpenCV is not installed here, so those five are parity-unpinned -- see oracle/resize_cv_np.py).  Not available in this
 build (raise NotImplementedError, loudly): the 'opencv' and 'ffmpeg' decoders and the reference's memcached reader.  Unlike the reference (which passes float sizes to Image.resize and only works on
 Python <= 3.9, imagenet_s_gen.py:129,167) sizes are converted with int().
+pil_resize_batch is the batched form of pil_resize for images of different sizes -- crop(box), resize, crop window, mirror for a whole
+batch in one rart_resize_batch_u8 call -- and image_transfer_batch the batch form of image_transfer on top of it.
 decode_batch_gpu is the batched form of the 'pil' decoder for baseline JPEG files: Huffman decoding on host threads, the arithmetic in
 rart_jpeg_decode_u8, the same bytes as Pillow; FileImageNet(reader='hip') reads through it."""
 import random
@@ -48,6 +50,69 @@ def cv_resize(batch_u8, resize_hw, interpolation, crop=None):
     ws = _lib.workspace(nb, batch_u8.device)
     _lib.check(lib.rart_cv_resize_u8(_lib.ptr(batch_u8), _lib.ptr(out), n, h, w, rh, rw, interpolation, cy, cx, ch, cw,
                                      _lib.ptr(ws), nb, _lib.stream_ptr()))
+    return out
+
+
+_plan_pinned = {}          # device -> (pinned plan buffer, the event of the last copy that read it)
+resize_batch_launches = 0  # rart_resize_batch_u8 calls made by pil_resize_batch (one per call, whatever the batch holds)
+
+
+def pil_resize_batch(images, resize_hw, filter_id, crop=None, boxes=None, flips=None, out=None):
+    """images: a list of n CUDA uint8 HxWx3 tensors of any sizes (views of decode_batch_gpu's packed buffer or separate
+    allocations) -> CUDA uint8 (n, ch, cw, 3): per image Image.crop(box).resize((rw, rh), filter), the crop window (cy, cx, ch, cw)
+    of it, then a left-right mirror where flips[k].  boxes[k] = (y, x, h, w) inside image k (None: the whole image; the box is a
+    hard boundary, unlike Image.resize(box=...)); crop=None keeps the whole resized image; out: the tensor to fill.
+    One rart_resize_batch_plan call on the host, one copy of its buffer (pinned, kept between calls), one rart_resize_batch_u8
+    call: two launches, one for NEAREST."""
+    global resize_batch_launches
+    import ctypes
+    torch = _lib.require_gpu()
+    lib = _lib.load()
+    images = list(images)
+    n = len(images)
+    rh, rw = int(resize_hw[0]), int(resize_hw[1])
+    cy, cx, ch, cw = (int(v) for v in (crop if crop is not None else (0, 0, rh, rw)))
+    if n == 0:
+        raise ValueError('pil_resize_batch: an empty list of images')
+    dev = images[0].device
+    descs = (_lib.ResizeDesc * n)()
+    for k, img in enumerate(images):
+        if not (isinstance(img, torch.Tensor) and img.is_cuda and img.device == dev and img.dtype == torch.uint8 and img.dim() == 3
+                and img.shape[2] == 3 and img.is_contiguous()):
+            raise ValueError('pil_resize_batch: image %d must be a contiguous CUDA uint8 HxWx3 tensor on %s' % (k, dev))
+        d = descs[k]
+        d.src, d.h, d.w = img.data_ptr(), img.shape[0], img.shape[1]
+        d.box_y, d.box_x, d.box_h, d.box_w = (int(v) for v in boxes[k]) if boxes is not None and boxes[k] is not None else (0, 0, d.h, d.w)
+        d.flip = int(bool(flips[k])) if flips is not None else 0
+    if out is None:
+        out = torch.empty(n, ch, cw, 3, dtype=torch.uint8, device=dev)
+    elif not (out.is_cuda and out.device == dev and out.dtype == torch.uint8 and tuple(out.shape) == (n, ch, cw, 3) and out.is_contiguous()):
+        raise ValueError('pil_resize_batch: out must be a contiguous CUDA uint8 tensor of shape %r on %s' % ((n, ch, cw, 3), dev))
+    with torch.cuda.device(dev):
+        host, ev = _plan_pinned.pop(dev, (None, None))     # taken out while in use, as decode_batch_gpu does
+        if ev is not None:
+            ev.synchronize()               # the previous call's copy has left the buffer
+        if host is None:
+            host = torch.empty(1 << 20, dtype=torch.uint8, pin_memory=True)
+        sizes = _lib.ResizePlan()
+        args = (ctypes.addressof(descs), n, filter_id, rh, rw, cy, cx, ch, cw)
+        st = lib.rart_resize_batch_plan(*args, host.data_ptr(), host.numel(), ctypes.byref(sizes))
+        if st == 3:                        # RART_ERR_WORKSPACE: `sizes` says what the plan needs
+            host = torch.empty(int(sizes.total_bytes * 1.25), dtype=torch.uint8, pin_memory=True)
+            st = lib.rart_resize_batch_plan(*args, host.data_ptr(), host.numel(), ctypes.byref(sizes))
+        _lib.check(st)
+        total = int(sizes.total_bytes)
+        plan = torch.empty(total, dtype=torch.uint8, device=dev)
+        plan.copy_(host[:total], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        ws = _lib.workspace(int(sizes.workspace_bytes), dev)
+        resize_batch_launches += 1
+        try:
+            _lib.check(lib.rart_resize_batch_u8(_lib.ptr(plan), host.data_ptr(), total, _lib.ptr(ws), int(sizes.workspace_bytes),
+                                                _lib.ptr(out), out.numel(), _lib.stream_ptr()))
+        finally:
+            _plan_pinned[dev] = (host, ev)
     return out
 
 
@@ -239,3 +304,40 @@ def image_transfer(image, decoder_type='pil', resize_type='pil-bilinear', transf
         dev = torch.from_numpy(np.ascontiguousarray(arr[y:y + h, x:x + w])[None]).cuda()
         return op(dev, size, f)[0].cpu().numpy()
     raise NotImplementedError(transform_type)
+
+
+def image_transfer_batch(items, decoder_type='pil', resize_type='pil-bilinear', transform_type='val', resize=224, num_workers=8,
+                         decoded=None):
+    """The batch form of image_transfer: items (file paths / encoded bytes) -> CUDA uint8 (n, resize, resize, 3), image k equal to
+    image_transfer(items[k], ...) (same size rule, same crop offsets; 'train' draws its boxes from the global random module in item
+    order).  decoded: the already decoded images (CUDA uint8 HxWx3 tensors, or ndarrays, which are uploaded) -- `items` is then not
+    read, so a caller decodes once and resizes many times.  'pil-*' operators run through one pil_resize_batch call; the five
+    'opencv-*' operators through cv_resize, image by image."""
+    torch = _lib.require_gpu()
+    if resize_type not in PIL_FILTERS and resize_type not in CV_MODES:
+        raise NotImplementedError(resize_type)
+    if transform_type not in ('val', 'train'):
+        raise NotImplementedError(transform_type)
+    if decoder_type != 'pil':
+        decode(b'', decoder_type)                  # raises NotImplementedError with decode's message, decoded batch or not
+    if decoded is None:
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=max(1, min(int(num_workers), MAX_DECODE_WORKERS))) as pool:
+            decoded = list(pool.map(lambda it: decode(it, 'pil'), list(items)))
+    images = [torch.from_numpy(np.ascontiguousarray(a)).cuda(non_blocking=True) if isinstance(a, np.ndarray) else a for a in decoded]
+    size = (resize, resize) if not isinstance(resize, tuple) else resize
+    if transform_type == 'val':
+        first = tuple(int(s * 8 / 7) for s in size)                    # imagenet_s_gen.py:129,139
+        th, tw = size
+        crop = (int(round((first[0] - th) / 2.)), int(round((first[1] - tw) / 2.)), th, tw)
+        boxes = [None] * len(images)
+    else:
+        first, crop = size, (0, 0, size[0], size[1])
+        boxes = [_train_params(tuple(a.shape[:2]), random) for a in images]
+    if resize_type in PIL_FILTERS:
+        return pil_resize_batch(images, first, PIL_FILTERS[resize_type], crop=crop, boxes=boxes)
+    out = torch.empty(len(images), crop[2], crop[3], 3, dtype=torch.uint8, device=images[0].device)
+    for k, (img, b) in enumerate(zip(images, boxes)):
+        src = img if b is None else img[b[0]:b[0] + b[2], b[1]:b[1] + b[3]].contiguous()
+        out[k] = cv_resize(src[None], first, CV_MODES[resize_type], crop=crop)[0]
+    return out

@@ -118,13 +118,26 @@ def read_meta_file(path):
     return out
 
 
+class _TransformName(str):
+    """FileImageNet.transform: the transform's name ('ONECROP' / 'STANDARD', what configs and callers compare it with) that can also be
+    called as the transform step, transform(decoded, indices, epoch) = FileImageNet.transform_batch."""
+
+    def __new__(cls, name, owner):
+        self = super().__new__(cls, name)
+        self.owner = owner
+        return self
+
+    def __call__(self, decoded, indices, epoch=0):
+        return self.owner.transform_batch(decoded, indices, epoch)
+
+
 class FileImageNet(torch.utils.data.Dataset):
     """`data.read_from: fs` with `data.<split>.{root_dir, meta_file, image_reader.type: pil | hip, transforms}`
     (exp/imagenet_c_loop_mini/config_vit_base.yaml:80-104; `transforms` as the mapping {type: ...} or as a list of torchvision entries,
     read_transforms): files are decoded on the host by PIL (the reference's 'pil'
     reader) and the transform's arithmetic runs on the GPU:
       ONECROP  = Resize([test_resize, test_resize]) (PIL bilinear, what torchvision applies to a PIL image) + CenterCrop(
-                 input_size) -> rart_pil_resize_u8 with the fused centre crop, bit-exact with Pillow;
+                 input_size) -> rart_resize_batch_u8 with the fused centre crop, bit-exact with Pillow;
       STANDARD = RandomResizedCrop(input_size) + RandomHorizontalFlip: the crop box / flip are drawn on the host from
                  (seed, global index) (a pure function of the sample, like every draw of this path), the resize runs in
                  the same kernel.  `flip=False` (a transform list without RandomHorizontalFlip) never flips.  `jitter` (the ranges of
@@ -134,7 +147,9 @@ class FileImageNet(torch.utils.data.Dataset):
     the engine's input kernel.
     reader='hip' (`image_reader.type: hip`, opt-in) decodes a batch's baseline JPEGs through noise.imagenet_s.decode_batch_gpu --
     Huffman decoding on `num_workers` host threads, IDCT / upsampling / colour conversion on the GPU, bit-identical to the 'pil'
-    reader -- and hands every other file to PIL as 'pil' does; `decode_stats` counts the files that took each path."""
+    reader -- and hands every other file to PIL as 'pil' does; `decode_stats` counts the files that took each path.
+    batch() = decode_indices() then transform(): a caller that scores one decoded batch under several transforms (the ImageNet-S loop)
+    calls the two steps itself."""
 
     def __init__(self, root_dir, meta_file, size=224, test_resize=256, transform='ONECROP', reader='pil', limit=None, seed=0,
                  jitter=None, flip=True, num_workers=8):
@@ -148,7 +163,7 @@ class FileImageNet(torch.utils.data.Dataset):
         self.classes = None                 # from_folder: the sorted class-folder names, label = position
         if limit:
             self.items = self.items[:int(limit)]
-        self.size, self.test_resize, self.transform, self.seed = int(size), int(test_resize), transform, int(seed)
+        self.size, self.test_resize, self.transform, self.seed = int(size), int(test_resize), _TransformName(transform, self), int(seed)
         self.n = len(self.items)
         self.jitter, self.flip = jitter, bool(flip)
 
@@ -203,37 +218,37 @@ class FileImageNet(torch.utils.data.Dataset):
         y, x, h, w = _train_params(hw, r)
         return y, x, h, w, r.random() < 0.5
 
-    def batch(self, indices, device, epoch=0):
-        from ..noise.imagenet_s import pil_resize
-        dev = torch.device(device)
+    def decode_indices(self, indices, dev):
+        """step 1 of batch(): the decoded images of `indices` as CUDA uint8 HxWx3 tensors on `dev` -- a Pillow loop plus uploads for
+        reader='pil', one decode_batch_gpu call for reader='hip'"""
+        dev = torch.device(dev)
         if dev.type != 'cuda':
             raise RuntimeError('FileImageNet: the resize / crop of the transform runs on the GPU (no CPU fallback)')
-        out = torch.empty(len(indices), self.size, self.size, 3, dtype=torch.uint8, device=dev)
-        labs = []
-        decoded = self.decode_batch(indices, dev) if self.reader == 'hip' else None
-        for k, i in enumerate(indices):
-            if decoded is not None:
-                arr, lab = decoded[k], self.items[i][1]               # already on the device
-            else:
-                arr, lab = self.decode(i)
-            labs.append(lab)
-            if self.transform == 'ONECROP':
-                r, t = self.test_resize, self.size
-                o = int(round((r - t) / 2.0))                         # torchvision CenterCrop
-                src = (arr if decoded is not None else torch.from_numpy(arr).to(dev, non_blocking=True))[None]
-                out[k] = pil_resize(src, (r, r), 1, crop=(o, o, t, t))[0]
-            else:
-                y, x, h, w, flip = self.box(i, arr.shape[:2], epoch)
-                if decoded is not None:
-                    src = arr[y:y + h, x:x + w].contiguous()[None]
-                else:
-                    src = torch.from_numpy(arr[y:y + h, x:x + w].copy()).to(dev, non_blocking=True)[None]
-                img = pil_resize(src, (self.size, self.size), 1)[0]
-                out[k] = img.flip(1) if flip and self.flip else img
-        if self.transform == 'STANDARD' and self.jitter is not None:
-            from .jitter import apply_jitter, draw_jitter
-            apply_jitter(out, [draw_jitter(self.jitter, self.seed, epoch, i) for i in indices])
-        return out, torch.tensor(labs, dtype=torch.int64, device=dev)
+        if self.reader == 'hip':
+            return self.decode_batch(indices, dev)
+        return [torch.from_numpy(self.decode(i)[0]).to(dev, non_blocking=True) for i in indices]
+
+    def transform_batch(self, decoded, indices, epoch=0):
+        """step 2 of batch() (also reachable as self.transform(...)): the transform of the decoded images in ONE pil_resize_batch call (rart_resize_batch_u8: box, resize,
+        centre crop and flip fused), then the jitter -> the uint8 (n, size, size, 3) batch"""
+        from ..noise.imagenet_s import pil_resize_batch
+        if self.transform == 'ONECROP':
+            r, t = self.test_resize, self.size
+            o = int(round((r - t) / 2.0))                             # torchvision CenterCrop
+            out = pil_resize_batch(decoded, (r, r), 1, crop=(o, o, t, t))
+        else:
+            draws = [self.box(i, tuple(img.shape[:2]), epoch) for i, img in zip(indices, decoded)]
+            out = pil_resize_batch(decoded, (self.size, self.size), 1, boxes=[d[:4] for d in draws],
+                                   flips=[d[4] and self.flip for d in draws])
+            if self.jitter is not None:
+                from .jitter import apply_jitter, draw_jitter
+                apply_jitter(out, [draw_jitter(self.jitter, self.seed, epoch, i) for i in indices])
+        return out
+
+    def batch(self, indices, device, epoch=0):
+        dev = torch.device(device)
+        out = self.transform_batch(self.decode_indices(indices, dev), indices, epoch)
+        return out, torch.tensor([self.items[i][1] for i in indices], dtype=torch.int64, device=dev)
 
 
 def _entry(e, where):
@@ -717,9 +732,106 @@ def evaluate_natural(cfg, args, rank, world, device, model=None):
     return res
 
 
+def imagenet_s_ops(spec=None):
+    """`--imagenet-s-ops a,b,...` -> the resize operators of the ImageNet-S loop, in order; None / '' -> the eleven names of
+    PIL_FILTERS then CV_MODES.  An unknown or repeated name is a ValueError."""
+    from ..noise.imagenet_s import CV_MODES, PIL_FILTERS
+    known = list(PIL_FILTERS) + list(CV_MODES)
+    if spec is None or not str(spec).strip():
+        return known
+    ops = [t.strip() for t in str(spec).split(',') if t.strip()]
+    for t in ops:
+        if t not in known:
+            raise ValueError('--imagenet-s-ops: unknown resize operator %r (%s)' % (t, ', '.join(known)))
+    if len(set(ops)) != len(ops) or not ops:
+        raise ValueError('--imagenet-s-ops: every operator once, got %r' % (spec,))
+    return ops
+
+
+def evaluate_imagenet_s(cfg, args, rank, world, device, model=None):
+    """`--evaluate --imagenet-s`: the loop of exp/imagenet_s_loop (eval.sh:23, multi_eval_decoder_resize_solver): one model scored on
+    the test set once per (decoder, resize operator) pair; the accuracies, their mean and their spread.  Per batch of sharded
+    indices the files are decoded ONCE (data.test.image_reader.type pil | hip) and every operator runs on the decoded batch through
+    image_transfer_batch(transform_type='val', resize=data.input_size): the operator under test replaces the config's Resize, so
+    only input_size is taken from the transform list (which still has to parse).  The decoder is 'pil' (the others are not in this
+    build).  `data.test.save_acc_var_neg` (with --save-dir) also writes <save_dir>/<model>/imagenet_s_summary.json; the reference
+    solver that defines this key is absent from the reference tree, so the summary's form is unpinned."""
+    ops = imagenet_s_ops(getattr(args, 'imagenet_s_ops', None))
+    dcfg = cfg.get('data', {})
+    if (getattr(args, 'attack', None) and args.attack != 'none') or getattr(args, 'corruption', None) or natural_mode(dcfg):
+        raise ValueError('--imagenet-s cannot be combined with --attack, --corruption or data.test.imagenet_a&o: no config of '
+                         'imagenet_s_loop has another noise')
+    if device.type != 'cuda':
+        raise RuntimeError('--imagenet-s runs on the GPU (the resize operators are HIP kernels; no CPU fallback)')
+    from ..metrics import ImageNetSEvaluator, ResultWriter, result_dir
+    from ..noise import imagenet_s as NS
+    bs = int(dcfg.get('batch_size', 64))
+    size = int(dcfg.get('input_size', 224))
+    ds = make_dataset(dcfg, int(dcfg.get('fake_size', dcfg.get('limit_samples', 256))), size, 'test')    # parses the transforms
+    if not isinstance(ds, FileImageNet):
+        raise ValueError('--imagenet-s needs data.read_from: fs (the loop is about decoding and resizing files)')
+    idx = shard_indices(len(ds), rank, world)
+    model = model or build_model(cfg, args)
+    model = model.to(device).eval()
+    use_hip = args.engine == 'hip'
+    if use_hip:
+        from ..model.engine import EngineModel
+        prec = getattr(args, 'precision', None) or cfg.get('engine_precision', 'bf16')
+        f_model = EngineModel(model, takes_normalized=False, precision=prec)
+    mean = torch.tensor(IMAGENET_MEAN, device=device).view(1, 3, 1, 1)
+    std = torch.tensor(IMAGENET_STD, device=device).view(1, 3, 1, 1)
+    name = getattr(args, 'src_name', None) or cfg['model']['type']
+    save_dir = getattr(args, 'save_dir', None)
+    writers = {op: ResultWriter(result_dir(save_dir, name, 'imagenet_s', 'pil_%s' % op), rank, world) for op in ops} if save_dir else {}
+    counters = {op: [0, 0] for op in ops}
+    cnt = 0
+    t0 = time.time()
+    for s in range(0, len(idx), bs):
+        items = idx[s:s + bs]
+        decoded = ds.decode_indices(items, device)                 # once per batch, whatever the number of operators
+        labels = torch.tensor([ds.items[i][1] for i in items], dtype=torch.int64, device=device)
+        cnt += len(items)
+        for op in ops:
+            imgs = NS.image_transfer_batch(None, 'pil', op, 'val', size, ds.num_workers, decoded=decoded)
+            if use_hip:
+                logits = f_model.rart_engine.logits_from_u8(imgs, IMAGENET_MEAN, IMAGENET_STD)
+            else:
+                with torch.no_grad():
+                    logits = model((imgs.permute(0, 3, 1, 2).float() / 255.0 - mean) / std)
+            a, b = topk_correct(logits.float(), labels)
+            counters[op][0] += a
+            counters[op][1] += b
+            if writers:
+                writers[op].write_batch(logits, labels, items)
+    barrier = dist.barrier if dist.is_available() and dist.is_initialized() else None
+    paths = {op: writers[op].close(barrier=barrier) for op in ops} if writers else {}
+    flat = all_reduce_counters([v for op in ops for v in counters[op]] + [cnt], device)
+    cnt = flat[-1]
+    res = None
+    if rank == 0:
+        ev = ImageNetSEvaluator()
+        for k, op in enumerate(ops):
+            if paths:
+                ev.eval(paths[op], 'pil', op)
+            else:
+                ev.metric.update({('pil', op): 100.0 * flat[2 * k] / max(cnt, 1)})
+        acc = {'%s/%s' % k: v for k, v in ev.metric.metric.items()}
+        res = {'imagenet_s': acc, 'Mean': ev.get_mean()['Mean'], 'Std.': ev.get_std()['Std.'], 'count': cnt, 'world_size': world,
+               'seconds': time.time() - t0}
+        if save_dir and bool((dcfg.get('test') or {}).get('save_acc_var_neg', False)):
+            import numpy as np
+            vals = list(acc.values())
+            with open(os.path.join(save_dir, name, 'imagenet_s_summary.json'), 'w') as f:
+                json.dump({'acc': acc, 'mean': res['Mean'], 'var': float(np.var(vals)), 'neg_std': -res['Std.']}, f)
+        print(json.dumps(res))
+    return res
+
+
 def evaluate(cfg, args, rank, world, device, model=None):
     """Clean / corrupted / attacked evaluation over the sharded dataset; returns the reduced metrics dict."""
     dcfg = cfg.get('data', {})
+    if getattr(args, 'imagenet_s', False):
+        return evaluate_imagenet_s(cfg, args, rank, world, device, model)
     if natural_mode(dcfg):
         return evaluate_natural(cfg, args, rank, world, device, model)
     n = int(dcfg.get('fake_size', dcfg.get('limit_samples', 256)))
@@ -1118,7 +1230,15 @@ def main(argv=None):
     ap.add_argument('--tgt_name', default=None, help='transfer: name of the target model (new_transfer/eval.sh:42-44)')
     ap.add_argument('--tgt-type', default=None, help='transfer: model.type of the target model; adversarial examples '
                     'are crafted on cfg.model and scored on this one')
+    ap.add_argument('--imagenet-s', action='store_true', dest='imagenet_s',
+                    help='with --evaluate: the ImageNet-S loop (exp/imagenet_s_loop): one pass per (decoder, resize operator) pair')
+    ap.add_argument('--imagenet-s-ops', default=None, dest='imagenet_s_ops',
+                    help='comma-separated resize operators of --imagenet-s (default: the six pil-* then the five opencv-*)')
     args = ap.parse_args(argv)
+    if args.imagenet_s:
+        imagenet_s_ops(args.imagenet_s_ops)           # an unknown name fails before anything is built
+        if not args.evaluate:
+            raise ValueError('--imagenet-s is an evaluation loop: pass --evaluate')
     cfg = load_config(args.config)
     rank, world, device = init_dist()
     try:
