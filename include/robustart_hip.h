@@ -478,6 +478,29 @@ typedef struct rart_gemm_pair2_desc {
 } rart_gemm_pair2_desc;
 int rart_gemm_pair2_bf16(const rart_gemm_pair2_desc* desc_host, rart_stream_t stream);
 int rart_gemm_pair_max_sources(void);
+/* Up to four CLASSES of one conv-mode pair launch in ONE grid (blockIdx.y = class): the input-parity classes of a stride-2 backward-to-input,
+ * which otherwise run as one launch each, every one quantised into passes over the CUs on its own.  `two.one` describes what the classes
+ * share: the row grid, N, the source and destination geometry and strides, k_per_tap, the planes, the mask, the flags; its tap_dy / tap_dx
+ * hold the taps of ALL classes (n_taps = how many of the sixteen slots are filled) and its dst_oy / dst_ox are not read.  A class is
+ *   taps tap_begin .. tap_begin + n_taps - 1 of those slots,
+ *   the columns k_off .. k_off + K - 1 of the rows of the weight table (K = k_per_tap * n_taps, + two.k2 with src2; k_off % 8 == 0): the
+ *     per-class tables laid out side by side in one table whose hi and lo planes are w_hi and w_lo, rows ldw apart,
+ *   the destination origin (dst_oy, dst_ox),
+ *   src2 = 1: the class also accumulates the second source `two` describes (its K steps after the class's own).  Class 0 only.
+ * Every output element is the sum of the same products in the same order as in the class's own rart_gemm_pair_bf16 / rart_gemm_pair2_bf16
+ * launch: the same bits.  The grid is ordered longest K first.  Tile policy is per launch: the tiles the longest class would choose serve
+ * all of them (measured faster than one launch per tile form).  No interleaved weight table (flag 16), no batching, no row re-basing.
+ * rart_gemm_pair_max_classes: how many classes the loaded library takes per launch (4); the engines use the entry only where it says so. */
+typedef struct rart_gemm_pair_class {
+  int tap_begin, n_taps, k_off, dst_oy, dst_ox, src2;
+} rart_gemm_pair_class;
+typedef struct rart_gemm_pair_cls_desc {
+  rart_gemm_pair2_desc two;
+  int n_classes, reserved_;
+  rart_gemm_pair_class cls[4];
+} rart_gemm_pair_cls_desc;
+int rart_gemm_pair_classes_bf16(const rart_gemm_pair_cls_desc* desc_host, rart_stream_t stream);
+int rart_gemm_pair_max_classes(void);
 /* Schedule of the 256-row tiles with 128 / 256 columns (round 6, csrc/gemm_pair_pp.hip): 1 (default; RART_PAIR_SCHEDULE in the environment
  * sets the initial value) = ping-pong -- the two halves of the workgroup alternate memory and matrix phases, counted vmcnt, no drain in the
  * steady state; 2 (opt-in: measured slower than 1, see the kernel's header) = ping-pong, and one-tap problems (1x1 convolutions, plain
@@ -723,6 +746,16 @@ int rart_engine_stem_bwd_fused(const void* dpool, const void* argmax, const void
 int rart_engine_stem_fwd_fused_pair(const void* src, int src_is_u8, const void* wgt_hi, const void* wgt_lo, const float* bias, void* p1_hi,
                                     void* p1_lo, void* argmax_out, void* sign_out, int n, int h, int w, const float* mean_host,
                                     const float* std_host, rart_stream_t stream);
+/* The same kernel, which ALSO runs the 1x1 convolution (64 -> 64) + bias + ReLU that reads the pooled pair -- conv1 of layer1's first block
+ * -- on each pooled tile before it leaves the CU: that launch's read of the pooled pair disappears.  wnext_*: the table planes [64][ldw_next]
+ * bf16 (row = output channel, 64 input channels; ldw_next >= 64, a multiple of 8); next_*: the output pair [n][h/4][w/4][64];
+ * next_sign_out: (output hi plane > 0), 1 bit per element (may be null, like bias_next).  Everything else as rart_engine_stem_fwd_fused_pair,
+ * with the same p1 / argmax / sign outputs bit for bit; next_* and next_sign_out are bit-identical to rart_gemm_pair_bf16 on p1 (one tap,
+ * K = 64, flag 1): the same products in the same order on the same rounded pair. */
+int rart_engine_stem_fwd_next_pair(const void* src, int src_is_u8, const void* wgt_hi, const void* wgt_lo, const float* bias, void* p1_hi,
+                                   void* p1_lo, void* argmax_out, void* sign_out, const void* wnext_hi, const void* wnext_lo, int ldw_next,
+                                   const float* bias_next, void* next_hi, void* next_lo, void* next_sign_out, int n, int h, int w,
+                                   const float* mean_host, const float* std_host, rart_stream_t stream);
 /* The reference-precision form (csrc/stem_pair.hip): pooled gradient and weight table as hi + lo planes of bf16, three MFMA products per
  * fragment pair; replaces rart_engine_maxpool_bwd_pair -> rart_gemm_pair_bf16 (patches, fp32) -> rart_engine_stem_col2im_f32. */
 int rart_engine_stem_bwd_fused_pair(const void* dpool_hi, const void* dpool_lo, const void* argmax, const void* wtab_hi, const void* wtab_lo,

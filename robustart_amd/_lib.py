@@ -83,6 +83,8 @@ SIGNATURES = {
     'rart_conv_igemm_bf16': (c_int, [c_void_p, c_void_p]),
     'rart_gemm_pair2_bf16': (c_int, [c_void_p, c_void_p]),
     'rart_gemm_pair_max_sources': (c_int, []),
+    'rart_gemm_pair_classes_bf16': (c_int, [c_void_p, c_void_p]),
+    'rart_gemm_pair_max_classes': (c_int, []),
     'rart_conv3x3_halo_supported': (c_int, [c_int, c_int, c_int]),
     'rart_conv3x3_pack_frag_bf16': (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     'rart_pack_frag_bf16': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
@@ -138,6 +140,8 @@ SIGNATURES = {
     'rart_conv3x3_tail_pair_supported': (c_int, [c_int]),
     'rart_conv3x3_tail_pair': (c_int, [c_void_p, c_void_p]),
     'rart_engine_stem_fwd_fused_pair': (c_int, [c_void_p, c_int] + [c_void_p] * 7 + [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'rart_engine_stem_fwd_next_pair': (c_int, [c_void_p, c_int] + [c_void_p] * 9 + [c_int] + [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p, c_void_p,
+                                               c_void_p]),
     'rart_engine_stem_bwd_fused_pair': (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_void_p, c_void_p]),
     'rart_engine_stem_bwd_fused': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'rart_engine_maxpool_pair': (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
@@ -323,6 +327,16 @@ class GemmPair2Desc(ctypes.Structure):
     """rart_gemm_pair2_desc (include/robustart_hip.h): a conv-mode pair launch `one` with a second A source."""
     _fields_ = [('one', GemmPairDesc), ('a2_hi', c_void_p), ('a2_lo', c_void_p)] + \
                [(n, ctypes.c_int32) for n in ('lda2', 'k2', 'src2_h', 'src2_w', 'sy2', 'sx2')]
+
+
+class GemmPairClass(ctypes.Structure):
+    """rart_gemm_pair_class (include/robustart_hip.h): one class of a class launch."""
+    _fields_ = [(n, ctypes.c_int32) for n in ('tap_begin', 'n_taps', 'k_off', 'dst_oy', 'dst_ox', 'src2')]
+
+
+class GemmPairClsDesc(ctypes.Structure):
+    """rart_gemm_pair_cls_desc (include/robustart_hip.h): up to four classes of the conv-mode pair launch `two.one` in one grid."""
+    _fields_ = [('two', GemmPair2Desc), ('n_classes', ctypes.c_int32), ('reserved_', ctypes.c_int32), ('cls', GemmPairClass * 4)]
 
 
 class TokmixDesc(ctypes.Structure):

@@ -40,9 +40,15 @@ namespace {
 // SRC2 (CONV only): a second A source -- one tap at offset 0, a pixel geometry of its own -- feeds the K steps from d.kt1 on: a projection
 // shortcut accumulated in the launch of the 1x1 it is added to.  The weight table's rows hold both sources' columns side by side, so the W
 // loader walks on unchanged; the A loader picks the lane offset / resource pair by a wave-uniform compare on the step index.
-template <int TM, int TN, bool CONV, bool SRC2 = false>
+// CLS (CONV + SRC2 instances): blockIdx.y selects a CLASS of the launch (d.cls): its taps, its slice of the weight rows, its K length and
+// its destination parity -- the input-parity classes of a stride-2 backward in one grid.  A tile's class is block-uniform, so the K loop,
+// the loader's scalar offsets and the epilogue are the single-class ones; a class whose kt1 == KT never reads the second source.
+template <int TM, int TN, bool CONV, bool SRC2 = false, bool CLS = false>
 __global__ __launch_bounds__(TM * 2, 1) void k_gemm_pair(const GemmPairDev d) {
   static_assert(CONV || !SRC2, "the second source is served by the conv instances");
+  static_assert(!CLS || (CONV && SRC2), "classes are served by the two-source conv instances");
+  const int ci = CLS ? (int)blockIdx.y : 0;
+  const int tap_b = CLS ? d.cls[ci].tap_begin : 0, ntap = CLS ? d.cls[ci].n_taps : d.n_taps;
   constexpr int NW = TM / 32;
   constexpr int WN = (TN / 64 < NW) ? TN / 64 : NW, WM = NW / WN, RW = TM / WM, MI = RW / 32, NJ = TN / (32 * WN);
   static_assert(NJ == 2, "a wave owns 64 columns");
@@ -89,12 +95,12 @@ __global__ __launch_bounds__(TM * 2, 1) void k_gemm_pair(const GemmPairDev d) {
   //      step where round 5's form had ~15 (which competed with the co-resident workgroups' MFMAs for the vector issue).
   uint32_t avoff[2], nok[2] = {0u, 0u};
   int tapreg = 0, tap_min = 0;
-  const bool one_tap = !CONV || d.n_taps == 1;
+  const bool one_tap = !CONV || ntap == 1;
   if (CONV) {
-    for (int t = 0; t < d.n_taps; ++t) tap_min = min(tap_min, (d.tap_dy[t] * d.src_w + d.tap_dx[t]) * d.lda * 2);
-    if (lane < d.n_taps) tapreg = (d.tap_dy[lane] * d.src_w + d.tap_dx[lane]) * d.lda * 2 - tap_min;
+    for (int t = 0; t < ntap; ++t) tap_min = min(tap_min, (d.tap_dy[tap_b + t] * d.src_w + d.tap_dx[tap_b + t]) * d.lda * 2);
+    if (lane < ntap) tapreg = (d.tap_dy[tap_b + lane] * d.src_w + d.tap_dx[tap_b + lane]) * d.lda * 2 - tap_min;
   }
-  const uint32_t tap0 = CONV ? (uint32_t)__builtin_amdgcn_readfirstlane((d.tap_dy[0] * d.src_w + d.tap_dx[0]) * d.lda * 2 - tap_min) : 0u;
+  const uint32_t tap0 = CONV ? (uint32_t)__builtin_amdgcn_readfirstlane((d.tap_dy[tap_b] * d.src_w + d.tap_dx[tap_b]) * d.lda * 2 - tap_min) : 0u;
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     const int r = 16 * (wave + NW * q) + (lane >> 2);
@@ -109,8 +115,8 @@ __global__ __launch_bounds__(TM * 2, 1) void k_gemm_pair(const GemmPairDev d) {
       const int oy = (int)(t - (uint32_t)n * (uint32_t)d.grid_h);
       const int by = oy * d.sy, bx = ox * d.sx;
       avoff[q] = (uint32_t)((n * d.src_h * d.src_w + by * d.src_w + bx) * d.lda * 2 + csrc * 16);
-      for (int t2 = 0; t2 < d.n_taps; ++t2) {
-        const int iy = by + d.tap_dy[t2], ix = bx + d.tap_dx[t2];
+      for (int t2 = 0; t2 < ntap; ++t2) {
+        const int iy = by + d.tap_dy[tap_b + t2], ix = bx + d.tap_dx[tap_b + t2];
         if (!(ok && (unsigned)iy < (unsigned)d.src_h && (unsigned)ix < (unsigned)d.src_w)) nok[q] |= 1u << t2;
       }
       if (one_tap && (nok[q] & 1u)) avoff[q] = RART_DMA_OOR;
@@ -150,7 +156,8 @@ __global__ __launch_bounds__(TM * 2, 1) void k_gemm_pair(const GemmPairDev d) {
   const rart_srd_t srd_ah = rart_dma_srd(reinterpret_cast<const char*>(a_hi) + tap_min), srd_al = rart_dma_srd(reinterpret_cast<const char*>(a_lo) + tap_min);
   const rart_srd_t srd_wh = rart_dma_srd(w_hi), srd_wl = rart_dma_srd(w_lo);
   const rart_srd_t srd_a2h = rart_dma_srd(SRC2 ? d.a2_hi : a_hi), srd_a2l = rart_dma_srd(SRC2 ? d.a2_lo : a_lo);
-  const int kt1 = SRC2 ? d.kt1 : 0;
+  const int kt1 = CLS ? d.cls[ci].kt1 : (SRC2 ? d.kt1 : 0);
+  const uint32_t w_off = CLS ? (uint32_t)d.cls[ci].w_off : 0u;       // (bytes) the class's slice of the weight rows
   const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lds;
   // GP_W_INTERLEAVED: the weight table holds, per row and K step, the 64 bytes of the hi plane followed by the 64 bytes of the lo plane
   // (one 128-byte line per row and step; w_lo = w_hi + 32 elements) instead of two planes K apart
@@ -181,7 +188,7 @@ __global__ __launch_bounds__(TM * 2, 1) void k_gemm_pair(const GemmPairDev d) {
       }                                                                                                         \
     }                                                                                                           \
     {                                                                                                           \
-      const uint32_t so_ = (uint32_t)(kt_ * w_step);                                                            \
+      const uint32_t so_ = w_off + (uint32_t)(kt_ * w_step);                                                    \
       _Pragma("unroll") for (int q = 0; q < BQ; ++q) {                                                          \
         if (NW * q + NW <= B_PIECES || wave + NW * q < B_PIECES) {   /* (first half: compile time, no branch) */  \
           rart_dma_load16(wvoff[q], srd_wh, so_, st_ + 2 * GP_PLANE_A + (wave + NW * q) * 1024);                \
@@ -205,7 +212,7 @@ __global__ __launch_bounds__(TM * 2, 1) void k_gemm_pair(const GemmPairDev d) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = bv;
   }
-  const int KT = d.K / GP_BK;
+  const int KT = CLS ? d.cls[ci].KT : d.K / GP_BK;
   const bool skip_last = wm * RW + MI * 32 > TMV;      // (wave-uniform) this wave's last row block lies past the tile's rows
   RART_GP_ISSUE(0, 0)
   rart_dma_wait<0>();
@@ -244,7 +251,7 @@ __global__ __launch_bounds__(TM * 2, 1) void k_gemm_pair(const GemmPairDev d) {
     __syncthreads();
   }
 #undef RART_GP_ISSUE
-  gp_epilogue<TM, TN, CONV, MI>(d, lds, acc, m0, n0, c_off, TMV);
+  gp_epilogue<TM, TN, CONV, MI>(d, lds, acc, m0, n0, c_off, TMV, CLS ? d.cls[ci].dst_oy : d.dst_oy, CLS ? d.cls[ci].dst_ox : d.dst_ox);
 }
 
 // 1 (default): the 256-row tiles with 128 / 256 columns run the ping-pong schedule of csrc/gemm_pair_pp.hip; 2 (opt-in, measured slower): as 1,
@@ -301,8 +308,38 @@ extern "C" int rart_gemm_pair_set_schedule(int mode) {
 }
 extern "C" int rart_gemm_pair_get_schedule(void) { return gp_schedule(); }
 
-// One launch of rart_gemm_pair_bf16 (s2 == nullptr) or rart_gemm_pair2_bf16 (s2: the descriptor that carries the second A source).
-static int gp_launch(const rart_gemm_pair_desc* h, const rart_gemm_pair2_desc* s2, rart_stream_t stream) {
+// Tile policy, from the per-shape sweep of every launch of a ResNet-50 gradient evaluation at B = 256 (scratch/r4/sweep_pair_tiles.py,
+// profiles/r04_pair_tile_sweep.txt).  Plain products (the transformer GEMMs): 256 rows x the widest of 64 / 128 / 256 columns that does not
+// pad the MFMA work.  Convolutions: K <= 256 (the HBM-bound 1x1 layers: two K steps do not hide a tile's load and store phases) 256 x 64,
+// 80 KB of LDS = two workgroups per CU; K < 1024 128 x {128, 64} (64 / 48 KB: two or three per CU); K-deep wide layers 256 x 256 unless
+// that leaves fewer than 128 workgroups (layer4: 256 x 128), K-deep narrow layers (N <= 128) 128 x N.  tile_m / tile_n override.
+// Two-source launches (a projection shortcut folded into its 1x1: K = K1 + K2) take the same policy; swept at B = 256
+// (profiles/shortcut_fusion_tile_sweep.txt, us per launch, chosen tile first): 200704 x 384 -> 512: 308 on 224-row x 256 ping-pong (256 x 256
+// 319, 128 x 128 349, 256 x 64 386); 50176 x 768 -> 1024: 259 on 224 x 256 (256 x 256 273, 128 x 128 289); 12544 x 1536 -> 2048: 206 on
+// 224 x 256 (256 x 256 214, 256 x 128 258); layer1's backward 802816 x 320 -> 64: 246 on 128 x 64 (256 x 64 252).
+// A class launch (ncls > 1 grids of the same tiles) counts its workgroups over all classes.
+static void gp_tile_policy(bool conv, int M, int N, int K, int& tm, int& tn, int ncls = 1) {
+  tn = N <= 64 ? 64 : (N <= 128 ? 128 : 256);
+  tm = 256;
+  if (conv) {
+    if (gp_schedule() >= 1 && N >= 256 && (K >= 512 || (K >= 256 && N <= 512))) {
+      // round 6 (scratch/r6/time_pair_pp.py --tiles, profiles/r06_pair_pp.json): with the ping-pong schedule the 256-row tiles win wherever
+      // the layer is at least 256 wide and 256 deep -- 256 x 256 unless that leaves fewer than 128 workgroups (layer4: 256 x 128); the one
+      // exception measured: K = 256 into >= 1024 columns (layer3's expansion: epilogue-bound, 155-165 us on 256 x 64 vs 166-176).  128-column
+      // layers (layer2's 3 x 3 once its tail kernel is off) stay on the two-stage 128 x 128 tiles: 19.97 vs 20.14 ms on 256 x 128 ping-pong
+      tm = 256;
+      tn = (long long)((M + 255) / 256) * ((N + 255) / 256) * ncls < 128 ? 128 : 256;
+    } else if (K <= 256) { tm = 256; tn = 64; }
+    else if (K < 1024 || N <= 128) { tm = 128; tn = N <= 64 ? 64 : 128; }
+    else if ((long long)((M + 255) / 256) * ((N + 255) / 256) * ncls < 128) { tm = 256; tn = 128; }
+    if (M <= 256) { tm = 128; tn = 64; }
+  }
+}
+
+// One launch of rart_gemm_pair_bf16 (s2 == nullptr), rart_gemm_pair2_bf16 (s2: the descriptor that carries the second A source) or
+// rart_gemm_pair_classes_bf16 (cd: the classes of the grid, checked by that entry; s2 = the second source of the class that has src2 set).
+static int gp_launch(const rart_gemm_pair_desc* h, const rart_gemm_pair2_desc* s2, rart_stream_t stream,
+                     const rart_gemm_pair_cls_desc* cd = nullptr) {
   RART_CHECK_ARG(h != nullptr, "rart_gemm_pair_bf16: null descriptor");
   RART_CHECK_ARG(h->a_hi && h->a_lo && h->w_hi && h->w_lo && h->dst_hi, "rart_gemm_pair_bf16: null operand plane");
   const bool conv = h->conv != 0;
@@ -348,6 +385,22 @@ static int gp_launch(const rart_gemm_pair_desc* h, const rart_gemm_pair2_desc* s
     gp_magic((uint32_t)d.grid_h, d.gh_magic, d.gh_shift);
     d.mask_bits = (const uint8_t*)h->mask_bits; d.sign_out = (uint8_t*)h->sign_out;
     RART_CHECK_ARG(!(d.sign_out && (h->flags & GP_OUT_F32)), "rart_gemm_pair_bf16 (conv): sign_out needs a pair destination");
+    if (cd) {
+      // the class table, longest K first (the dispatcher hands out blockIdx.y = 0 first); d.K = the longest, which the tile policy reads
+      const int n = cd->n_classes, k2 = src2 ? s2->k2 : 0;
+      int order[4] = {0, 1, 2, 3};
+      auto klen = [&](int i) { return h->k_per_tap * cd->cls[i].n_taps + (cd->cls[i].src2 ? k2 : 0); };
+      for (int i = 1; i < n; ++i)
+        for (int j = i; j > 0 && klen(order[j]) > klen(order[j - 1]); --j) { const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
+      d.n_cls = n;
+      for (int i = 0; i < n; ++i) {
+        const rart_gemm_pair_class& c = cd->cls[order[i]];
+        d.cls[i].tap_begin = c.tap_begin; d.cls[i].n_taps = c.n_taps; d.cls[i].w_off = c.k_off * 2;
+        d.cls[i].kt1 = h->k_per_tap * c.n_taps / GP_BK; d.cls[i].KT = klen(order[i]) / GP_BK;
+        d.cls[i].dst_oy = c.dst_oy; d.cls[i].dst_ox = c.dst_ox; d.cls[i].pad_ = 0;
+      }
+      d.K = klen(order[0]);
+    }
   } else {
     RART_CHECK_ARG(!h->mask_bits && !h->sign_out, "rart_gemm_pair_bf16: mask_bits / sign_out are served by conv mode only");
     RART_CHECK_ARG(h->lda % 8 == 0 && h->lda >= h->K, "rart_gemm_pair_bf16: lda must cover the row and keep 16-byte alignment");
@@ -401,29 +454,11 @@ static int gp_launch(const rart_gemm_pair_desc* h, const rart_gemm_pair2_desc* s
   RART_CHECK_ARG(nz <= 65535, "rart_gemm_pair_bf16: n_batched must be <= 65535");
   d.z_inner = h->z_inner > 0 ? h->z_inner : 1;
   d.a_zo = h->a_z_outer; d.a_zi = h->a_z_inner; d.w_zo = h->w_z_outer; d.w_zi = h->w_z_inner; d.c_zo = h->c_z_outer; d.c_zi = h->c_z_inner;
-  // Tile policy, from the per-shape sweep of every launch of a ResNet-50 gradient evaluation at B = 256 (scratch/r4/sweep_pair_tiles.py,
-  // profiles/r04_pair_tile_sweep.txt).  Plain products (the transformer GEMMs): 256 rows x the widest of 64 / 128 / 256 columns that does not
-  // pad the MFMA work.  Convolutions: K <= 256 (the HBM-bound 1x1 layers: two K steps do not hide a tile's load and store phases) 256 x 64,
-  // 80 KB of LDS = two workgroups per CU; K < 1024 128 x {128, 64} (64 / 48 KB: two or three per CU); K-deep wide layers 256 x 256 unless
-  // that leaves fewer than 128 workgroups (layer4: 256 x 128), K-deep narrow layers (N <= 128) 128 x N.  tile_m / tile_n override.
-  // Two-source launches (a projection shortcut folded into its 1x1: K = K1 + K2) take the same policy; swept at B = 256
-  // (profiles/shortcut_fusion_tile_sweep.txt, us per launch, chosen tile first): 200704 x 384 -> 512: 308 on 224-row x 256 ping-pong (256 x 256
-  // 319, 128 x 128 349, 256 x 64 386); 50176 x 768 -> 1024: 259 on 224 x 256 (256 x 256 273, 128 x 128 289); 12544 x 1536 -> 2048: 206 on
-  // 224 x 256 (256 x 256 214, 256 x 128 258); layer1's backward 802816 x 320 -> 64: 246 on 128 x 64 (256 x 64 252).
-  int tn = d.N <= 64 ? 64 : (d.N <= 128 ? 128 : 256), tm = 256;
-  if (conv) {
-    if (gp_schedule() >= 1 && d.N >= 256 && (d.K >= 512 || (d.K >= 256 && d.N <= 512))) {
-      // round 6 (scratch/r6/time_pair_pp.py --tiles, profiles/r06_pair_pp.json): with the ping-pong schedule the 256-row tiles win wherever
-      // the layer is at least 256 wide and 256 deep -- 256 x 256 unless that leaves fewer than 128 workgroups (layer4: 256 x 128); the one
-      // exception measured: K = 256 into >= 1024 columns (layer3's expansion: epilogue-bound, 155-165 us on 256 x 64 vs 166-176).  128-column
-      // layers (layer2's 3 x 3 once its tail kernel is off) stay on the two-stage 128 x 128 tiles: 19.97 vs 20.14 ms on 256 x 128 ping-pong
-      tm = 256;
-      tn = (long long)((d.M + 255) / 256) * ((d.N + 255) / 256) < 128 ? 128 : 256;
-    } else if (d.K <= 256) { tm = 256; tn = 64; }
-    else if (d.K < 1024 || d.N <= 128) { tm = 128; tn = d.N <= 64 ? 64 : 128; }
-    else if ((long long)((d.M + 255) / 256) * ((d.N + 255) / 256) < 128) { tm = 256; tn = 128; }
-    if (d.M <= 256) { tm = 128; tn = 64; }
-  }
+  // A class launch takes the tiles of its longest class for all of them.  Measured at B = 256 (profiles/first_block_folds_per_part.txt): the
+  // K = 640 + 3 x K = 128 classes of layer2's folded shortcut^T run 505 us as one 256 x 256 ping-pong grid against 560 us as two launches
+  // with each class on the tiles its own K would choose (622 us before the fold).
+  int tn, tm;
+  gp_tile_policy(conv, d.M, d.N, d.K, tm, tn, cd ? d.n_cls : 1);
   if (h->tile_n == 64 || h->tile_n == 128 || h->tile_n == 256) tn = h->tile_n;
   if (h->tile_m == 128 || h->tile_m == 256) tm = h->tile_m;
   if (h->tile_m == 224) tm = 256;            // the ping-pong kernel's 224-row form (below)
@@ -431,11 +466,12 @@ static int gp_launch(const rart_gemm_pair_desc* h, const rart_gemm_pair2_desc* s
   const int m_enum = m_tiles >= 16 ? (m_tiles + 7) / 8 * 8 : m_tiles;     // the XCD remap enumerates row tiles in groups of 8
   const long long blocks = (long long)m_enum * n_tiles;
   RART_CHECK_ARG(blocks < (1ll << 31), "rart_gemm_pair_bf16: grid too large");
-  const dim3 grid((uint32_t)blocks, nz);
+  const int ncls = cd ? d.n_cls : 1;            // a class launch: blockIdx.y = class (conv mode is unbatched: nz == 1)
+  const dim3 grid((uint32_t)blocks, cd ? ncls : nz);
   hipStream_t st = (hipStream_t)stream;
   // the persistent kernel (256 x 128 tiles, deferred epilogue): one tap, no GELU epilogue, no row re-basing / batching, at least two tiles per
   // CU and a K loop with room for the 12 micro-steps of a tile's epilogue
-  if (gp_schedule() == 2 && !src2 && tm == 256 && tn >= 128 && h->tile_n == 0 && h->tile_m == 0 && nz == 1 && !d.map_rows && d.src_off == 0 &&
+  if (gp_schedule() == 2 && !src2 && !cd && tm == 256 && tn >= 128 && h->tile_n == 0 && h->tile_m == 0 && nz == 1 && !d.map_rows && d.src_off == 0 &&
       (conv ? d.n_taps == 1 : true) && !(h->flags & (GP_GELU | GP_GELU_BWD | GP_GELU_KEEP)) && d.K / GP_BK >= 6) {
     const int cus = gp_cu_count();
     const long long tiles = (long long)((d.M + 255) / 256) * ((d.N + 127) / 128);
@@ -453,10 +489,15 @@ static int gp_launch(const rart_gemm_pair_desc* h, const rart_gemm_pair2_desc* s
     // loads, waits and barriers unchanged) makes 224 / 56 row tiles = 28 / 7 per XCD: the same passes, 7/8 of the matrix work per tile.
     auto passes = [&](int mt, int nt) { const int cx = gp_cu_count() / 8; return ((mt >= 16 ? (mt + 7) / 8 * nt : (mt * nt + 7) / 8) + cx - 1) / cx; };
     const int mt224 = (d.M + 223) / 224;
-    if (h->tile_m == 224 || passes(mt224, n_tiles) * 0.92 < passes(m_tiles, n_tiles) - 0.01) {
+    // A class launch streams ncls grids of unequal K through the CUs, so whole passes mean little: what 224-row tiles can still buy is the
+    // balance between the XCDs -- row tiles on the fullest one, (m_tiles + 7) / 8, against 7/8 of the work in each of (mt224 + 7) / 8 --
+    // and they cost about 6 % per unit of work (more tiles for the same rows).  Measured at B = 256: 12544 rows (49 -> 56 row tiles: 7 -> 7
+    // x 7/8) 171 -> 167 us (3x3) and 333 -> 317 us (shortcut^T); 50176 rows (25 -> 28 x 7/8) 180 -> 189 us; 200704 rows 505 -> 530 us.
+    const bool rows224 = cd ? (mt224 + 7) / 8 * 0.875 * 1.06 < (m_tiles + 7) / 8 : passes(mt224, n_tiles) * 0.92 < passes(m_tiles, n_tiles) - 0.01;
+    if (h->tile_m == 224 || rows224) {
       d.tile_rows = 224;
       const int me = mt224 >= 16 ? (mt224 + 7) / 8 * 8 : mt224;
-      if (rart_gemm_pair_pp_launch(&d, tn, conv, (unsigned)(me * n_tiles), 1, st, 0)) {
+      if (rart_gemm_pair_pp_launch(&d, tn, conv, (unsigned)(me * n_tiles), grid.y, st, 0)) {
         RART_CHECK_LAUNCH("rart_gemm_pair_bf16 (ping-pong, 224-row tiles)");
         return RART_OK;
       }
@@ -495,7 +536,7 @@ static int gp_launch(const rart_gemm_pair_desc* h, const rart_gemm_pair2_desc* s
     }
   }
   // schedule 3: launches of more than one tile per CU are WALKED by one workgroup per CU (k_gemm_pair_pp, OPT bit 1)
-  const unsigned walk_wgs = (gp_schedule() == 3 && !src2 && nz == 1 && blocks > (long long)gp_cu_count()) ? (unsigned)(gp_cu_count() & ~7) : 0u;
+  const unsigned walk_wgs = (gp_schedule() == 3 && !src2 && !cd && nz == 1 && blocks > (long long)gp_cu_count()) ? (unsigned)(gp_cu_count() & ~7) : 0u;
   if (tm == 256 && tn >= 128 && gp_schedule() >= 1 && rart_gemm_pair_pp_launch(&d, tn, conv, grid.x, grid.y, st, walk_wgs)) {
     RART_CHECK_LAUNCH("rart_gemm_pair_bf16 (ping-pong)");
     return RART_OK;
@@ -503,7 +544,7 @@ static int gp_launch(const rart_gemm_pair_desc* h, const rart_gemm_pair2_desc* s
   // the two-stage kernel: tiles that step tm - 32 rows where that saves work per pass (resident workgroups per CU by LDS: 2 x STAGE bytes each)
   d.tile_rows = tm;
   dim3 grid2 = grid;
-  if ((gp_rows224() == 2 || (gp_rows224() == 3 && d.K >= 1024)) && nz == 1 && h->tile_m == 0 && h->tile_n == 0 && gp_schedule() >= 1) {   // (3: K-deep only)
+  if ((gp_rows224() == 2 || (gp_rows224() == 3 && d.K >= 1024)) && nz == 1 && !cd && h->tile_m == 0 && h->tile_n == 0 && gp_schedule() >= 1) {   // (3: K-deep only)
     const int lds = 2 * (2 * tm * 64 + 2 * tn * 64), res = lds > 80 * 1024 ? 1 : (lds > 53 * 1024 ? 2 : 3), cx = gp_cu_count() / 8 * res;
     auto passes = [&](int mt) { return ((mt >= 16 ? (mt + 7) / 8 * n_tiles : (mt * n_tiles + 7) / 8) + cx - 1) / cx; };
     const int rows = tm - 32, mt2 = (d.M + rows - 1) / rows;
@@ -519,7 +560,10 @@ static int gp_launch(const rart_gemm_pair_desc* h, const rart_gemm_pair2_desc* s
     else if (tn == 128) RART_GP_LAUNCH(TM_, 128, __VA_ARGS__);             \
     else RART_GP_LAUNCH(TM_, 256, __VA_ARGS__);                            \
   } while (0)
-  if (src2) {
+  if (cd) {
+    if (tm == 128) RART_GP_BY_TN(128, true, true, true);
+    else RART_GP_BY_TN(256, true, true, true);
+  } else if (src2) {
     if (tm == 128) RART_GP_BY_TN(128, true, true);
     else RART_GP_BY_TN(256, true, true);
   } else if (conv) {
@@ -544,3 +588,32 @@ extern "C" int rart_gemm_pair2_bf16(const rart_gemm_pair2_desc* h, rart_stream_t
   return gp_launch(&h->one, h->a2_hi ? h : nullptr, stream);
 }
 extern "C" int rart_gemm_pair_max_sources(void) { return 2; }
+
+// Up to four classes of a conv-mode pair launch in one grid (include/robustart_hip.h): the checks, then gp_launch with the class table.
+extern "C" int rart_gemm_pair_max_classes(void) { return 4; }
+extern "C" int rart_gemm_pair_classes_bf16(const rart_gemm_pair_cls_desc* c, rart_stream_t stream) {
+  RART_CHECK_ARG(c != nullptr, "rart_gemm_pair_classes_bf16: null descriptor");
+  const rart_gemm_pair_desc& h = c->two.one;
+  RART_CHECK_ARG(c->n_classes >= 1 && c->n_classes <= 4, "rart_gemm_pair_classes_bf16: 1..4 classes");
+  RART_CHECK_ARG(h.conv != 0 && h.batch > 0 && h.grid_h > 0 && h.grid_w > 0 && h.dst_sy > 0 && h.dst_sx > 0,
+                 "rart_gemm_pair_classes_bf16: classes are served by conv mode only");
+  RART_CHECK_ARG(h.n_taps >= 1 && h.n_taps <= 16 && h.k_per_tap >= 32, "rart_gemm_pair_classes_bf16: 1..16 taps in all, k_per_tap >= 32");
+  RART_CHECK_ARG(!(h.flags & GP_W_INTERLEAVED), "rart_gemm_pair_classes_bf16: no interleaved weight table");
+  RART_CHECK_ARG((c->two.a2_hi == nullptr) == (c->two.a2_lo == nullptr), "rart_gemm_pair_classes_bf16: the second source is a pair: both planes or none");
+  const bool has2 = c->two.a2_hi != nullptr;
+  RART_CHECK_ARG(!has2 || (c->two.k2 >= 32 && c->two.k2 % GP_BK == 0), "rart_gemm_pair_classes_bf16: k2 must be a positive multiple of 32");
+  for (int i = 0; i < c->n_classes; ++i) {
+    const rart_gemm_pair_class& k = c->cls[i];
+    RART_CHECK_ARG(k.tap_begin >= 0 && k.n_taps >= 1 && k.tap_begin + k.n_taps <= 16 && k.tap_begin + k.n_taps <= h.n_taps,
+                   "rart_gemm_pair_classes_bf16: a class's taps must lie inside the filled tap slots (sixteen at most)");
+    RART_CHECK_ARG(k.src2 == 0 || (i == 0 && has2), "rart_gemm_pair_classes_bf16: the second source rides in class 0 only, and needs its planes");
+    const long long K = (long long)h.k_per_tap * k.n_taps + (k.src2 ? c->two.k2 : 0);
+    RART_CHECK_ARG(k.k_off >= 0 && k.k_off % 8 == 0 && k.k_off + K <= h.ldw,
+                   "rart_gemm_pair_classes_bf16: a class's slice must lie inside the rows of the weight table and keep 16-byte alignment");
+    RART_CHECK_ARG(k.dst_oy >= 0 && k.dst_ox >= 0 && (long long)(h.grid_h - 1) * h.dst_sy + k.dst_oy < h.dst_h &&
+                       (long long)(h.grid_w - 1) * h.dst_sx + k.dst_ox < h.dst_w,
+                   "rart_gemm_pair_classes_bf16: every row's destination pixel must lie inside the destination image");
+  }
+  RART_CHECK_ARG(!has2 || c->cls[0].src2, "rart_gemm_pair_classes_bf16: a second source needs class 0 to take it (src2 = 1)");
+  return gp_launch(&h, has2 ? &c->two : nullptr, stream, c);
+}

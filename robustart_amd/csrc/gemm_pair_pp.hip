@@ -77,10 +77,15 @@ __device__ unsigned long long g_pp_trace[4096][4];       // per workgroup (block
 //            epilogue's loads and stores run.  The epilogue itself is unchanged (gp_epilogue, in order): same bits.
 // SRC2 (CONV, not WALK): the second A source of k_gemm_pair's SRC2 instances -- K steps from d.kt1 on read it; the loads per phase, and with
 //            them the counted waits, are the same whichever source a step reads.
-template <int TN, bool CONV, int OPT, bool SRC2 = false>
+// CLS (SRC2 instances): blockIdx.y selects a class of the launch (d.cls), as in k_gemm_pair: its taps, its slice of the weight rows, its K
+//            length and its destination parity are block-uniform, so the phases, the loads per phase and the counted waits are unchanged.
+template <int TN, bool CONV, int OPT, bool SRC2 = false, bool CLS = false>
 __global__ __launch_bounds__(512, 1) void k_gemm_pair_pp(const GemmPairDev d) {
   constexpr bool BAL = OPT & 1, WALK = OPT & 2;
   static_assert(!SRC2 || (CONV && !WALK), "the second source is served by the conv instances that do not walk");
+  static_assert(!CLS || SRC2, "classes are served by the two-source conv instances");
+  const int ci = CLS ? (int)blockIdx.y : 0;
+  const int tap_b = CLS ? d.cls[ci].tap_begin : 0, ntap = CLS ? d.cls[ci].n_taps : d.n_taps;
   constexpr int TM = 256, NW = 8, WN = TN / 64, WM = NW / WN, RW = TM / WM, MI = RW / 32, MH = MI / 2;
   static_assert(TN == 256 || TN == 128, "column tiles of 256 or 128");
   constexpr int PLANE_A = TM * 64, PLANE_B = TN * 64, STAGE = 2 * PLANE_A + 2 * PLANE_B;
@@ -154,7 +159,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_pair_pp(const GemmPairDev d) {
   }
   uint32_t avoff[2], nok[2], avoff2[2] = {PP_OOR, PP_OOR};
   int tapreg = 0, tap_min = 0;
-  const bool one_tap = !CONV || d.n_taps == 1;
+  const bool one_tap = !CONV || ntap == 1;
   if (SRC2) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
@@ -171,10 +176,10 @@ __global__ __launch_bounds__(512, 1) void k_gemm_pair_pp(const GemmPairDev d) {
     }
   }
   if (CONV) {
-    for (int t = 0; t < d.n_taps; ++t) tap_min = min(tap_min, (d.tap_dy[t] * d.src_w + d.tap_dx[t]) * d.lda * 2);
-    if (lane < d.n_taps) tapreg = (d.tap_dy[lane] * d.src_w + d.tap_dx[lane]) * d.lda * 2 - tap_min;
+    for (int t = 0; t < ntap; ++t) tap_min = min(tap_min, (d.tap_dy[tap_b + t] * d.src_w + d.tap_dx[tap_b + t]) * d.lda * 2);
+    if (lane < ntap) tapreg = (d.tap_dy[tap_b + lane] * d.src_w + d.tap_dx[tap_b + lane]) * d.lda * 2 - tap_min;
   }
-  const uint32_t tap0 = CONV ? (uint32_t)__builtin_amdgcn_readfirstlane((d.tap_dy[0] * d.src_w + d.tap_dx[0]) * d.lda * 2 - tap_min) : 0u;
+  const uint32_t tap0 = CONV ? (uint32_t)__builtin_amdgcn_readfirstlane((d.tap_dy[tap_b] * d.src_w + d.tap_dx[tap_b]) * d.lda * 2 - tap_min) : 0u;
   uint32_t wvoff[WQ];
 #define RART_PP_ADDR(M0_, N0_)                                                                                   \
   {                                                                                                              \
@@ -193,8 +198,8 @@ __global__ __launch_bounds__(512, 1) void k_gemm_pair_pp(const GemmPairDev d) {
         const int oy = (int)(t - (uint32_t)n * (uint32_t)d.grid_h);                                              \
         const int by = oy * d.sy, bx = ox * d.sx;                                                                \
         avoff[q] = (uint32_t)((n * d.src_h * d.src_w + by * d.src_w + bx) * d.lda * 2 + csrc * 16);              \
-        for (int t2 = 0; t2 < d.n_taps; ++t2) {                                                                  \
-          const int iy = by + d.tap_dy[t2], ix = bx + d.tap_dx[t2];                                              \
+        for (int t2 = 0; t2 < ntap; ++t2) {                                                                      \
+          const int iy = by + d.tap_dy[tap_b + t2], ix = bx + d.tap_dx[tap_b + t2];                              \
           if (!(ok && (unsigned)iy < (unsigned)d.src_h && (unsigned)ix < (unsigned)d.src_w)) nok[q] |= 1u << t2; \
         }                                                                                                        \
         if (one_tap && (nok[q] & 1u)) avoff[q] = PP_OOR;                                                         \
@@ -219,10 +224,11 @@ __global__ __launch_bounds__(512, 1) void k_gemm_pair_pp(const GemmPairDev d) {
   const pp_srd_t srd_ah = pp_make_srd(reinterpret_cast<const char*>(a_hi) + tap_min), srd_al = pp_make_srd(reinterpret_cast<const char*>(a_lo) + tap_min);
   const pp_srd_t srd_w = pp_make_srd(g ? w_lo : w_hi);
   const pp_srd_t srd_a2h = pp_make_srd(SRC2 ? d.a2_hi : a_hi), srd_a2l = pp_make_srd(SRC2 ? d.a2_lo : a_lo);
-  const int kt1 = SRC2 ? d.kt1 : 0;
+  const int kt1 = CLS ? d.cls[ci].kt1 : (SRC2 ? d.kt1 : 0);
+  const uint32_t w_off = CLS ? (uint32_t)d.cls[ci].w_off : 0u;       // (bytes) the class's slice of the weight rows
   const int w_step = (d.flags & GP_W_INTERLEAVED) ? 128 : 64;
   const uint32_t w_dst = lds_base + 2 * PLANE_A + g * PLANE_B + w4 * 1024;
-  const int KT = d.K / GP_BK;
+  const int KT = CLS ? d.cls[ci].KT : d.K / GP_BK;
 
   // stage ST's A piece q (hi + lo): 2 loads
 #define RART_PP_ISSUE_A(Q, ST)                                                                                   \
@@ -249,7 +255,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_pair_pp(const GemmPairDev d) {
 #define RART_PP_ISSUE_W(ST, Q0, Q1)                                                                              \
   {                                                                                                              \
     const int s_ = (ST);                                                                                         \
-    const uint32_t so_ = (uint32_t)(s_ * w_step);                                                                \
+    const uint32_t so_ = w_off + (uint32_t)(s_ * w_step);                                                        \
     _Pragma("unroll") for (int q = (Q0); q < (Q1); ++q) pp_bload(wvoff[q], srd_w, so_, w_dst + (s_ & 1) * STAGE + q * 4096); \
   }
 
@@ -392,7 +398,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_pair_pp(const GemmPairDev d) {
       RART_PP_ISSUE_A(1, 0)
     }
   }
-  gp_epilogue<TM, TN, CONV, MI>(d, lds + EP_OFF, acc, m0e, n0e, c_off, TMV);
+  gp_epilogue<TM, TN, CONV, MI>(d, lds + EP_OFF, acc, m0e, n0e, c_off, TMV, CLS ? d.cls[ci].dst_oy : d.dst_oy, CLS ? d.cls[ci].dst_ox : d.dst_ox);
 #ifdef RART_PP_STAMPS
   __builtin_amdgcn_s_waitcnt(0);
   PP_T(t_exit)
@@ -734,6 +740,13 @@ __global__ __launch_bounds__(512, 1) void k_gemm_pair_ps(const GemmPairDev d) {
 #endif
 template <int OPT>
 bool pp_launch_opt(const GemmPairDev& d, int tn, bool conv, dim3 grid, hipStream_t st, unsigned walk_wgs = 0) {
+  if (d.n_cls > 0) {  // a class launch (grid.y = classes): the two-source conv instances, never walked
+    if (!conv || walk_wgs || (OPT & 2)) return false;
+    if (tn == 256) hipLaunchKernelGGL((k_gemm_pair_pp<256, true, OPT & 1, true, true>), grid, dim3(512), 0, st, d);
+    else if (tn == 128) hipLaunchKernelGGL((k_gemm_pair_pp<128, true, OPT & 1, true, true>), grid, dim3(512), 0, st, d);
+    else return false;
+    return true;
+  }
   if (d.a2_hi) {      // two sources: conv instances, never walked (the host entry sends no walk request with a second source)
     if (!conv || walk_wgs || (OPT & 2)) return false;
     if (tn == 256) hipLaunchKernelGGL((k_gemm_pair_pp<256, true, OPT & 1, true>), grid, dim3(512), 0, st, d);

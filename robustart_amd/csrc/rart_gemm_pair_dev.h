@@ -37,6 +37,11 @@ struct GemmPairDev {
   // per pixel; K steps kt1 .. K / 32 - 1 of the launch read it (kt1 = the first source's K steps).  a2_hi == nullptr: one source
   const uint16_t *a2_hi, *a2_lo;
   int lda2, kt1, src2_h, src2_w, sy2, sx2;
+  // CLS instances (CONV only): blockIdx.y selects one of n_cls classes -- the taps tap_begin .. tap_begin + n_taps - 1 of tap_dy / tap_dx,
+  // the slice of the weight rows w_off bytes in, KT K steps of which the first kt1 read the first source (kt1 == KT: one source), and the
+  // destination parity.  Everything else (row grid, N, strides, planes) is the launch's.  n_cls == 0 elsewhere
+  int n_cls;
+  struct Cls { int tap_begin, n_taps, w_off, kt1, KT, dst_oy, dst_ox, pad_; } cls[4];
 };
 __device__ __forceinline__ uint32_t gp_fastdiv(uint32_t n, uint32_t magic, uint32_t shift) {
   return (uint32_t)(((uint64_t)n * magic) >> shift);
@@ -185,10 +190,11 @@ __device__ __forceinline__ void gp_finish_segment(const GemmPairDev& d, int flag
 }
 
 // Epilogue of a TM x TN tile whose accumulators acc[MI][2] follow k_gemm_pair's wave layout (wave = (wm, wn), a wave owns RW rows x 64
-// columns).  `lds` is the workgroup's tile buffer (free after the K loop).  Must be called by every thread of the workgroup.
+// columns).  `lds` is the workgroup's tile buffer (free after the K loop).  Must be called by every thread of the workgroup.  dst_oy /
+// dst_ox: the destination origin of a CONV tile (d's, or the one of the tile's class).
 template <int TM, int TN, bool CONV, int MI>
 __device__ __forceinline__ void gp_epilogue(const GemmPairDev& d, uint8_t* lds, f32x16 (&acc)[MI][2], int m0, int n0, long long c_off,
-                                            int tile_rows = TM) {
+                                            int tile_rows, int dst_oy, int dst_ox) {
   constexpr int NW = TM / 32;
   constexpr int WN = (TN / 64 < NW) ? TN / 64 : NW, WM = NW / WN, RW = TM / WM;
   static_assert(MI == RW / 32, "accumulator blocks per wave");
@@ -209,7 +215,7 @@ __device__ __forceinline__ void gp_epilogue(const GemmPairDev& d, uint8_t* lds, 
         const int ox = (int)(m - t * (uint32_t)d.grid_w);
         const int n = (int)gp_fastdiv(t, d.gh_magic, d.gh_shift);
         const int oy = (int)(t - (uint32_t)n * (uint32_t)d.grid_h);
-        off = (uint32_t)(((n * d.dst_h + (oy * d.dst_sy + d.dst_oy)) * d.dst_w + (ox * d.dst_sx + d.dst_ox)) * d.ldc);
+        off = (uint32_t)(((n * d.dst_h + (oy * d.dst_sy + dst_oy)) * d.dst_w + (ox * d.dst_sx + dst_ox)) * d.ldc);
       }
       row_dst[tid] = off;
     }

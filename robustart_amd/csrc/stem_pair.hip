@@ -306,6 +306,14 @@ extern "C" int rart_engine_stem_bwd_fused_pair(const void* dpool_hi, const void*
 // consecutive channels of one position.  What the pair changes: both weight planes are LDS resident (2 x 29.7 KB), and the stem-output
 // tile is kept as fp32 -- the value hi + lo of the pair the unfused chain would have written, so the pool's comparisons, argmax codes and
 // outputs are bit-identical to it -- 78.6 KB: one workgroup of 512 threads per CU (138 KB of LDS).
+//
+// NEXT instances (rart_engine_stem_fwd_next_pair): layer1 block 0's conv1 (1x1, 64 -> 64) + bias + ReLU on the pooled tile before it leaves
+// the CU -- that launch (802816 x 64 -> 64 at B = 256) re-read the 205 MB pooled pair this kernel has just written.  Both planes of its
+// 64 x 64 table stay LDS resident beside the stem's (2 x 9 KB, rows of SP_NROW bytes); after the pool the tile's 64 pooled positions go to
+// LDS as the pair this kernel stores (hi, lo of the same rounding: the operand the separate launch reads), waves 0-3 run one 32 x 32 block
+// each -- accumulators start at the bias, per 16-deep K slice a_lo.w_hi, a_hi.w_lo, a_hi.w_hi: k_gemm_pair's products in k_gemm_pair's
+// order, so the output pair and its sign bits are the separate launch's bit for bit -- and the fp32 block goes through LDS to the pool's
+// thread mapping (one position x 8 channels per thread) for ReLU, the hi / lo split and 16-byte stores.  156 432 B of LDS.
 // =====================================================================================================================
 namespace {
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -332,19 +340,34 @@ constexpr int SP_NT = 3;                        // 32-position M tiles of wave r
                                                 // positions, and every SIMD holds one wave of each kind (waves w and w + 4)
 constexpr int SP_U = (SP_PH * SP_SW + 511) / 512;   // patch pixels a thread stages per tile (4)
 static_assert(SP_T_BYTES >= 2 * SP_PLANE, "the stem-output tile must cover the patch it aliases");
+// NEXT: the 64 x 64 table planes and the pooled tile's planes as rows of 64 bf16 + 16 B (conflict-free b128 fragment reads); the pooled
+// planes and the fp32 result block [64 positions][SP_YROW] alias the stem-output tile once the pool has read it
+constexpr int SP_NROW = 144;
+constexpr int SP_N_BYTES = 64 * SP_NROW;        // 9 216 per plane
+static_assert(2 * SP_N_BYTES + 64 * SP_YROW <= SP_T_BYTES, "pooled planes + result block fit the tile they alias");
+static_assert(2 * SP_W_BYTES + SP_T_BYTES + 2 * SP_N_BYTES <= 160 * 1024, "one workgroup per CU");
 
 struct StemNormP { float mean[3], istd[3]; };
 // the normalisation must round exactly like k_prep_input (engine_aux.hip): multiply, subtract, multiply -- no contraction
 #pragma clang fp contract(off)
 
-template <bool SRC_U8>
+struct StemNextP {          // NEXT: the 1x1 that follows the pool -- table planes [64][ldw] bf16, bias, output pair [pos][64], its sign bits
+  const uint16_t *w_h, *w_l;
+  const float* bias;
+  uint4 *y_h, *y_l;
+  uint8_t* sign;
+  int ldw;
+};
+
+template <bool SRC_U8, bool NEXT = false>
 __global__ __launch_bounds__(512, 1) void k_stem_fwd_pair(const void* __restrict__ src, const uint16_t* __restrict__ w_h,
                                                           const uint16_t* __restrict__ w_l, const float* __restrict__ bias,
                                                           uint4* __restrict__ p1_h, uint4* __restrict__ p1_l, uint2* __restrict__ arg,
-                                                          uint8_t* __restrict__ sign, int n, int h, int w, StemNormP nm) {
-  __shared__ __attribute__((aligned(16))) uint8_t lds[2 * SP_W_BYTES + SP_T_BYTES];
+                                                          uint8_t* __restrict__ sign, int n, int h, int w, StemNormP nm, StemNextP nx) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[2 * SP_W_BYTES + SP_T_BYTES + (NEXT ? 2 * SP_N_BYTES : 0)];
   uint8_t* sW = lds;                            // [hi | lo][64][SP_WROW]
   uint8_t* sP = lds + 2 * SP_W_BYTES;           // patch (hi plane, lo plane) / stem-output tile
+  uint8_t* sN = lds + 2 * SP_W_BYTES + SP_T_BYTES;      // NEXT: [hi | lo][64][SP_NROW]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int kq = lane >> 5;
@@ -357,6 +380,16 @@ __global__ __launch_bounds__(512, 1) void k_stem_fwd_pair(const void* __restrict
     const int pl = i / (64 * 28), j = i - pl * (64 * 28), row = j / 28, ch = j - row * 28;
     *reinterpret_cast<uint4*>(sW + pl * SP_W_BYTES + row * SP_WROW + ch * 16) =
         *reinterpret_cast<const uint4*>((pl ? w_l : w_h) + (size_t)row * 224 + ch * 8);
+  }
+  float bzn[16];
+  if (NEXT) {
+    for (int i = tid; i < 2 * 64 * 8; i += 512) {
+      const int pl = i >> 9, j = i & 511, row = j >> 3, ch = j & 7;
+      *reinterpret_cast<uint4*>(sN + pl * SP_N_BYTES + row * SP_NROW + ch * 16) =
+          *reinterpret_cast<const uint4*>((pl ? nx.w_l : nx.w_h) + (size_t)row * nx.ldw + ch * 8);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) bzn[r] = nx.bias ? nx.bias[(wave & 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kq] : 0.f;
   }
   const int mt0 = wm < 2 ? wm * SP_NT : 2 * SP_NT + (wm - 2) * (SP_NT - 1);     // first M tile of this wave row: 0, 3, 6, 8
   const int n_mt = wm < 2 ? SP_NT : SP_NT - 1;
@@ -487,6 +520,7 @@ __global__ __launch_bounds__(512, 1) void k_stem_fwd_pair(const void* __restrict
       const int c = tid & 7, q = tid >> 3;          // 64 pooled positions x 8 channel groups = 512 threads
       const int qy = q / SP_PT, qx = q - qy * SP_PT;
       const int gy = q0y + qy, gx = q0x + qx;
+      uint4 nh = make_uint4(0, 0, 0, 0), nl = nh;   // NEXT: this thread's 8 channels of the pooled pair (zeros outside the grid)
       if (gy < oh2 && gx < ow2) {
         float m[8];
         uint32_t code[8];
@@ -515,6 +549,7 @@ __global__ __launch_bounds__(512, 1) void k_stem_fwd_pair(const void* __restrict
         }
         p1_h[o] = make_uint4(hv[0], hv[1], hv[2], hv[3]);
         p1_l[o] = make_uint4(lv[0], lv[1], lv[2], lv[3]);
+        if (NEXT) { nh = make_uint4(hv[0], hv[1], hv[2], hv[3]); nl = make_uint4(lv[0], lv[1], lv[2], lv[3]); }
         uint32_t sb = 0;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -523,6 +558,53 @@ __global__ __launch_bounds__(512, 1) void k_stem_fwd_pair(const void* __restrict
         if (sign) sign[o] = (uint8_t)sb;
         if (arg) arg[o] = make_uint2(code[0] | (code[1] << 8) | (code[2] << 16) | (code[3] << 24),
                                      code[4] | (code[5] << 8) | (code[6] << 16) | (code[7] << 24));
+      }
+      if (NEXT) {
+        // ---- the 1x1 that follows: y = relu(W . p1 + b) on the tile's 64 pooled positions
+        __syncthreads();                                             // every thread is done reading the stem-output tile
+        *reinterpret_cast<uint4*>(sP + q * SP_NROW + c * 16) = nh;
+        *reinterpret_cast<uint4*>(sP + SP_N_BYTES + q * SP_NROW + c * 16) = nl;
+        __syncthreads();
+        float* const sY = reinterpret_cast<float*>(sP + 2 * SP_N_BYTES);
+        if (wave < 4) {                                              // 2 x 2 blocks of 32 positions x 32 channels
+          const int pm = wave >> 1, pn = wave & 1;
+          const uint8_t* ap = sP + (pm * 32 + (lane & 31)) * SP_NROW + kq * 16;
+          const uint8_t* wp = sN + (pn * 32 + (lane & 31)) * SP_NROW + kq * 16;
+          f32x16 an;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) an[r] = bzn[r];
+#pragma unroll
+          for (int ks = 0; ks < 4; ++ks) {
+            const bf16x8 wh = *reinterpret_cast<const bf16x8*>(wp + ks * 32), wl = *reinterpret_cast<const bf16x8*>(wp + SP_N_BYTES + ks * 32);
+            const bf16x8 ah = *reinterpret_cast<const bf16x8*>(ap + ks * 32), al = *reinterpret_cast<const bf16x8*>(ap + SP_N_BYTES + ks * 32);
+            an = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, al, an, 0, 0, 0);
+            an = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, ah, an, 0, 0, 0);
+            an = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, ah, an, 0, 0, 0);
+          }
+#pragma unroll
+          for (int g4 = 0; g4 < 4; ++g4)
+            *reinterpret_cast<float4*>(reinterpret_cast<uint8_t*>(sY) + (pm * 32 + (lane & 31)) * SP_YROW + (pn * 32 + 8 * g4 + 4 * kq) * 4) =
+                make_float4(an[4 * g4], an[4 * g4 + 1], an[4 * g4 + 2], an[4 * g4 + 3]);
+        }
+        __syncthreads();
+        if (gy < oh2 && gx < ow2) {
+          const float* yp = reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(sY) + q * SP_YROW) + c * 8;
+          const float4 v0 = *reinterpret_cast<const float4*>(yp), v1 = *reinterpret_cast<const float4*>(yp + 4);
+          const float f[8] = {fmaxf(v0.x, 0.f), fmaxf(v0.y, 0.f), fmaxf(v0.z, 0.f), fmaxf(v0.w, 0.f),
+                              fmaxf(v1.x, 0.f), fmaxf(v1.y, 0.f), fmaxf(v1.z, 0.f), fmaxf(v1.w, 0.f)};
+          uint32_t hv[4], lv[4], sb = 0;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            hv[k] = sp_pack2(f[2 * k], f[2 * k + 1]);
+            lv[k] = sp_pack2(f[2 * k] - __uint_as_float(hv[k] << 16), f[2 * k + 1] - __uint_as_float(hv[k] & 0xFFFF0000u));
+            sb |= ((short)(hv[k] & 0xFFFFu) > 0 ? 1u : 0u) << (2 * k);          // (hi plane > 0), as the pair GEMM's epilogue writes it
+            sb |= ((short)(hv[k] >> 16) > 0 ? 1u : 0u) << (2 * k + 1);
+          }
+          const size_t o = (((size_t)img * oh2 + gy) * ow2 + gx) * 8 + c;
+          nx.y_h[o] = make_uint4(hv[0], hv[1], hv[2], hv[3]);
+          nx.y_l[o] = make_uint4(lv[0], lv[1], lv[2], lv[3]);
+          if (nx.sign) nx.sign[o] = (uint8_t)sb;
+        }
       }
     }
     SP_T(t5)
@@ -538,9 +620,9 @@ __global__ __launch_bounds__(512, 1) void k_stem_fwd_pair(const void* __restrict
 #pragma clang fp contract(fast)
 }  // namespace
 
-extern "C" int rart_engine_stem_fwd_fused_pair(const void* src, int src_is_u8, const void* wgt_hi, const void* wgt_lo, const float* bias,
-                                               void* p1_hi, void* p1_lo, void* argmax_out, void* sign_out, int n, int h, int w,
-                                               const float* mean_host, const float* std_host, rart_stream_t stream) {
+static int stem_fwd_pair_launch(const void* src, int src_is_u8, const void* wgt_hi, const void* wgt_lo, const float* bias, void* p1_hi,
+                                void* p1_lo, void* argmax_out, void* sign_out, int n, int h, int w, const float* mean_host,
+                                const float* std_host, rart_stream_t stream, const StemNextP* next) {
   RART_CHECK_ARG(src && wgt_hi && wgt_lo && p1_hi && p1_lo && n > 0 && h % 4 == 0 && w % 4 == 0 && h >= 4 && w >= 4,
                  "rart_engine_stem_fwd_fused_pair: bad arguments (h, w multiples of 4)");
   StemNormP nm;
@@ -550,14 +632,42 @@ extern "C" int rart_engine_stem_fwd_fused_pair(const void* src, int src_is_u8, c
   }
   const long long tiles = (long long)n * ((h / 4 + SP_PT - 1) / SP_PT) * ((w / 4 + SP_PT - 1) / SP_PT);
   const int grid = (int)(tiles < 256 ? tiles : 256);              // persistent: one workgroup per CU
-  if (src_is_u8)
-    hipLaunchKernelGGL(k_stem_fwd_pair<true>, dim3(grid), dim3(512), 0, (hipStream_t)stream, src, (const uint16_t*)wgt_hi,
-                       (const uint16_t*)wgt_lo, bias, (uint4*)p1_hi, (uint4*)p1_lo, (uint2*)argmax_out, (uint8_t*)sign_out, n, h, w, nm);
-  else
-    hipLaunchKernelGGL(k_stem_fwd_pair<false>, dim3(grid), dim3(512), 0, (hipStream_t)stream, src, (const uint16_t*)wgt_hi,
-                       (const uint16_t*)wgt_lo, bias, (uint4*)p1_hi, (uint4*)p1_lo, (uint2*)argmax_out, (uint8_t*)sign_out, n, h, w, nm);
+#define RART_STEM_LAUNCH(U8_, NEXT_)                                                                                         \
+  hipLaunchKernelGGL((k_stem_fwd_pair<U8_, NEXT_>), dim3(grid), dim3(512), 0, (hipStream_t)stream, src, (const uint16_t*)wgt_hi, \
+                     (const uint16_t*)wgt_lo, bias, (uint4*)p1_hi, (uint4*)p1_lo, (uint2*)argmax_out, (uint8_t*)sign_out, n, h, w, nm, nx)
+  const StemNextP nx = next ? *next : StemNextP{};
+  if (next) {
+    if (src_is_u8) RART_STEM_LAUNCH(true, true);
+    else RART_STEM_LAUNCH(false, true);
+  } else {
+    if (src_is_u8) RART_STEM_LAUNCH(true, false);
+    else RART_STEM_LAUNCH(false, false);
+  }
+#undef RART_STEM_LAUNCH
   RART_CHECK_LAUNCH("rart_engine_stem_fwd_fused_pair");
   return RART_OK;
+}
+
+extern "C" int rart_engine_stem_fwd_fused_pair(const void* src, int src_is_u8, const void* wgt_hi, const void* wgt_lo, const float* bias,
+                                               void* p1_hi, void* p1_lo, void* argmax_out, void* sign_out, int n, int h, int w,
+                                               const float* mean_host, const float* std_host, rart_stream_t stream) {
+  return stem_fwd_pair_launch(src, src_is_u8, wgt_hi, wgt_lo, bias, p1_hi, p1_lo, argmax_out, sign_out, n, h, w, mean_host, std_host, stream,
+                              nullptr);
+}
+
+// ... and the 1x1 convolution (64 -> 64) + bias + ReLU that reads the pooled pair, on the tile before it leaves the CU (NEXT instances).
+extern "C" int rart_engine_stem_fwd_next_pair(const void* src, int src_is_u8, const void* wgt_hi, const void* wgt_lo, const float* bias,
+                                              void* p1_hi, void* p1_lo, void* argmax_out, void* sign_out, const void* wnext_hi,
+                                              const void* wnext_lo, int ldw_next, const float* bias_next, void* next_hi, void* next_lo,
+                                              void* next_sign_out, int n, int h, int w, const float* mean_host, const float* std_host,
+                                              rart_stream_t stream) {
+  RART_CHECK_ARG(wnext_hi && wnext_lo && next_hi && next_lo && ldw_next >= 64 && ldw_next % 8 == 0,
+                 "rart_engine_stem_fwd_next_pair: the next 1x1 needs both table planes ([64][ldw_next], ldw_next >= 64, a multiple of 8) and "
+                 "both output planes");
+  const StemNextP nx = {(const uint16_t*)wnext_hi, (const uint16_t*)wnext_lo, bias_next, (uint4*)next_hi, (uint4*)next_lo,
+                        (uint8_t*)next_sign_out, ldw_next};
+  return stem_fwd_pair_launch(src, src_is_u8, wgt_hi, wgt_lo, bias, p1_hi, p1_lo, argmax_out, sign_out, n, h, w, mean_host, std_host, stream,
+                              &nx);
 }
 
 #ifdef RART_STEM_STAMPS

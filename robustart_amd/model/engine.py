@@ -20,7 +20,7 @@ import os as _os
 
 from .. import _lib
 from .engine_base import (F_MASK_BITS, F_OUT_F32, F_PAIR, F_RELU, EngineBase, cints as _cints, conv_desc, conv_tap_classes,
-                          gemm_pair_desc, interleave_k32, k32, lo_off, pad_k, pad_rows, rows_mult, pair, split_hi_lo, stem_rows)
+                          gemm_pair_cls_desc, gemm_pair_desc, interleave_k32, k32, lo_off, pad_k, pad_rows, rows_mult, pair, split_hi_lo, stem_rows)
 
 
 def _bf16(t):
@@ -64,6 +64,32 @@ def fold_shortcut_tables(ca, cc, ds):
     if ds.stride == 1 and ca.r == 1 and ca.stride == 1 and ca.cin == ds.cin and pow2(ca.cout) and ds.cout % 32 == 0:
         ds.w_cat_bwd = _cat_k(ca.bwd[0][2], ca.cout, ds.bwd[0][2], ds.cout)
     return True
+
+
+def _cat_classes(tabs):
+    """[rows][hi | lo | hi] tables of `_Conv(split=True)` with K = k_0, k_1, ... -> (ONE such table whose rows hold the slices side by side
+    along K, class by class: hi = [T0_hi | T1_hi | ...], lo likewise, row stride 3 sum(k); the first column of every slice): the table of a
+    rart_gemm_pair_classes_bf16 launch"""
+    import torch
+    ks = [t.shape[1] // 3 for t in tabs]
+    assert all(t.shape == (tabs[0].shape[0], 3 * k) for t, k in zip(tabs, ks))
+    tab = torch.cat([t[:, i * k:(i + 1) * k] for i in range(3) for t, k in zip(tabs, ks)], 1).contiguous()
+    return tab, [sum(ks[:i]) for i in range(len(ks))]
+
+
+def class_tables(ca, cb, ds):
+    """Reference precision, the class-ordered tables of a stride-2 first block (conv1 ca, 3x3 cb, projection shortcut ds), for launches
+    that run the four input-parity classes of a stride-2 backward in one grid.  cb.cls_bwd = (table, [(taps, k_off, parity)]): the four
+    per-class tables of cb.bwd as one.  ds.cls_bwd = the same for dx = mask(W1^T . dza + Wds^T . dz): conv1^T read at the four parities of
+    dza, the class (0, 0) with the shortcut^T as its second source (rows [W1^T | Wds^T]); the other three slices are W1^T again."""
+    pow2 = lambda k: k >= 32 and (k & (k - 1)) == 0                      # noqa: E731
+    if cb.stride == 2 and all(taps and tab is not None for _, taps, tab in cb.bwd) and sum(len(t) for _, t, _ in cb.bwd) <= 16 and pow2(cb.cout):
+        tab, offs = _cat_classes([t for _, _, t in cb.bwd])
+        cb.cls_bwd = (tab, [(taps, off, parity) for (parity, taps, _), off in zip(cb.bwd, offs)])
+    if ds is not None and ds.stride == 2 and ds.r == 1 and ca.r == 1 and ca.stride == 1 and ca.cin == ds.cin and pow2(ca.cout) and ds.cout % 32 == 0:
+        w1, wd = ca.bwd[0][2], ds.bwd[0][2]
+        tab, offs = _cat_classes([_cat_k(w1, ca.cout, wd, ds.cout), w1, w1, w1])
+        ds.cls_bwd = (tab, [([(ph, pw)], off, (ph, pw)) for (ph, pw), off in zip(((0, 0), (0, 1), (1, 0), (1, 1)), offs)])
 
 
 class _Conv:
@@ -152,9 +178,25 @@ class ResNet50Engine(EngineBase):
         self.fused_tail_pair = True      # reference-precision mode: 3x3 + 1x1 expansion of a Bottleneck as one launch (conv_tail_pair.hip); False: two launches (cross-check)
         # reference-precision mode: the projection shortcut of a layer's first block as extra K steps of the launch it is added in (conv3's
         # two-source launch; layer1's tail kernel; backward of layer1's stride-1 shortcut inside conv1^T's launch) -- its 4C-channel skip pair
-        # never exists in HBM.  False: its own launch, added as conv3's residual (cross-check).  The stride-2 shortcuts' BACKWARD keeps its
-        # launch on purpose: their gradient reaches one input-parity class in four
+        # never exists in HBM.  False: its own launch, added as conv3's residual (cross-check).  The stride-2 shortcuts' BACKWARD, whose
+        # gradient reaches one input-parity class in four, rides in conv1^T's class launch (`pair_class_launch` below)
         self.fused_shortcut_pair = True
+        # reference-precision mode: the input-parity classes of a stride-2 backward-to-input as ONE launch (rart_gemm_pair_classes_bf16)
+        # instead of one launch per class, for 3x3 convolutions of these widths; False / () : a launch per class (cross-check).  With
+        # `fused_shortcut_pair` the stride-2 shortcuts' backward rides in conv1^T's class launch for shortcut inputs of
+        # `class_shortcut_channels`: dx = mask(W1^T . dza) on the parities (0, 1) (1, 0) (1, 1), mask(W1^T . dza + Wds^T . dz) on (0, 0),
+        # written once and never read.  Honoured only where the library serves four classes (the query is made once, here)
+        self.pair_class_launch = True
+        self.class_3x3_channels = (128, 256, 512)
+        self.class_shortcut_channels = (256, 512, 1024)
+        self.pair_classes = self.lib.rart_gemm_pair_max_classes() if split else 0
+        # reference-precision mode: layer1 block 0's conv1 + bias + ReLU inside the fused stem forward (rart_engine_stem_fwd_next_pair): the
+        # pooled pair is not re-read by a launch of its own.  False: its own launch (cross-check).  Same bits either way.  Per source form,
+        # by its own measurement at B = 256 (profiles/first_block_folds_per_part.txt): uint8 sources 549 -> 496 us for stem + conv1; fp32
+        # sources 485 -> 478 us, inside the run-to-run spread, so the fold stays off for them.  Honoured only where the library answers
+        # rart_gemm_pair_max_classes (the entry came with it)
+        self.fused_stem_next_pair = True
+        self.fused_stem_next_sources = ('u8',)
         self.pair_gemm_kernel = True     # reference-precision mode: False = the three products as 3 x the taps of the implicit GEMM (round 3; cross-check)
         self.blocks = []
         for layer in (m.layer1, m.layer2, m.layer3, m.layer4):
@@ -200,6 +242,8 @@ class ResNet50Engine(EngineBase):
             return torch.stack(out).contiguous()
         two_sources = self.lib.rart_gemm_pair_max_sources() >= 2      # the library takes a second A source per pair launch
         for bi, (ca, cb, cc, ds) in enumerate(self.blocks):
+            if self.pair_classes >= 4:
+                class_tables(ca, cb, ds)
             if two_sources and ds is not None and fold_shortcut_tables(ca, cc, ds) and ds.stride == 1 and ds.cin == 64 and cc.cout == 4 * cb.cout:
                 ds.tail_x = frag(ds.w_fwd, ds.cout, ds.cin)        # layer1's first block: the shortcut inside the tail kernel
             if not (cb.r == 3 and cb.stride == 1 and cb.pad == 1 and cb.cin == cb.cout and self.lib.rart_conv3x3_tail_pair_supported(cb.cin)):
@@ -494,6 +538,32 @@ class ResNet50Engine(EngineBase):
                                          grid=grid, src_hw=src_hw, stride=stride, k_per_tap=k_per_tap, taps=taps, dst_hw=dst_hw,
                                          dst_stride=dst_stride, dst_org=dst_off, tile=self.pair_tile, src2=src2), nbytes)
 
+    def _classes_ok(self, tabs):
+        """whether a launch with the class-ordered tables `tabs` = (table, classes) goes out as one class launch"""
+        return tabs is not None and self.pair_class_launch and self.pair_classes >= len(tabs[1]) and self.pair_gemm_kernel and \
+            not self.pair_w_interleaved
+
+    def _gemm_pair_classes(self, src, tabs, dst, batch, grid, src_hw, src_pix, k_per_tap, n_cols, dst_hw, dst_pix, res=None, mask=None,
+                           stride=(1, 1), dst_stride=(2, 2), src2=None):
+        """The classes of tabs = (table, [(taps, k_off, dst_org)]) (`class_tables`) as one rart_gemm_pair_classes_bf16 launch: class i reads
+        its taps of src and the slice of the table's rows from column k_off on, and writes the destination pixels of origin dst_org.  src2
+        (as in `_gemm_pair`): a second source accumulated by class 0."""
+        wgt, classes = tabs
+        k_tot = wgt.shape[1] // 3
+        assert src.shape[0] == 2 and k_tot == k_per_tap * sum(len(c[0]) for c in classes) + (src2[4] if src2 is not None else 0)
+        nbytes = None
+        if self.profile is not None:
+            rows = batch * grid[0] * grid[1] * len(classes)
+            nbytes = 4.0 * batch * src_hw[0] * src_hw[1] * k_per_tap + 4.0 * rows * n_cols * (2 if res is not None else 1) + 4.0 * k_tot * n_cols \
+                + rows * n_cols / 8.0 * (mask is not None)
+            if src2 is not None:
+                nbytes += 4.0 * batch * src2[1][0] * src2[1][1] * src2[4]
+        d = gemm_pair_cls_desc(src, wgt, dst, n_cols, src_pix, 3 * k_tot, dst_pix, wgt.shape[0],
+                               [(taps, off, org, src2 is not None and i == 0) for i, (taps, off, org) in enumerate(classes)], res=res,
+                               mask_bits=mask, w_lo_off=k_tot, batch=batch, grid=grid, src_hw=src_hw, stride=stride, k_per_tap=k_per_tap,
+                               dst_hw=dst_hw, dst_stride=dst_stride, tile=self.pair_tile, src2=src2)
+        self._launch_pair_classes(d, nbytes)
+
     def _tail(self, src, wgt, taps, tail, dst, batch, hw, c_mid, bias_mid=None, bias_out=None, res=None, mask_mid=None, mask_out=None,
               sign_mid=None, sign_out=None, relu=False, nxt=None, xsrc=None):
         """3x3 (c_mid -> c_mid) + point-wise step + 1x1 expansion (c_mid -> 4 c_mid) + skip pair + point-wise step of the
@@ -672,6 +742,11 @@ class ResNet50Engine(EngineBase):
         assert not pair or mask is None or fl, 'the split-bf16 mode reads ReLU masks as 1-bit tensors only'
         if not pair and res is None and (mask is None or fl) and self._halo_ok(c, dx_hw, B):
             return self._halo(dz, c.w_bwd_frag, dx, B, dx_hw, c.cin, c.bwd[0][1], mask=mask)
+        if pair and c.r == 3 and c.cin in self.class_3x3_channels and self._classes_ok(getattr(c, 'cls_bwd', None)) and \
+                dx_hw[0] % 2 == 0 and dx_hw[1] % 2 == 0:
+            # stride-2 3x3: the four input-parity classes (1 / 2 / 2 / 4 taps) in one grid
+            return self._gemm_pair_classes(dz, c.cls_bwd, dx, B, (dx_hw[0] // 2, dx_hw[1] // 2), dz_hw, c.cout, c.cout, c.cin, dx_hw, c.cin,
+                                           res=res, mask=mask)
         for parity, taps, w in c.bwd:
             if parity is None:
                 self._gemm(dz, w, dx, B, dx_hw, dz_hw, c.cout, c.cout, taps, c.cin, dx_hw, c.cin, res=res, mask=mask,
@@ -703,7 +778,7 @@ class ResNet50Engine(EngineBase):
         bits = keep and (self.x3 or self.sign_bit_masks)
         acts = {'in_shape': (B, H, W)}
         x, xhw, xs = self._stem_fwd(src, src_is_u8, mean, std, B, H, W, keep, bits, acts)
-        pre_a = False            # this block's conv1 was already computed by the previous block's launch
+        pre_a = acts['stem_next']      # this block's conv1 was already computed by the previous block's launch (block 0: by the stem's)
         for bi in range(len(self.blocks)):
             x, xhw, xs, pre_a = self._block_fwd(bi, x, xhw, xs, B, keep, bits, pre_a, acts)
         acts['last'], acts['last_sign'] = (x, xhw), xs
@@ -729,7 +804,23 @@ class ResNet50Engine(EngineBase):
         parg = self._get('p1_argmax', (B, h2, w2, 64), torch.uint8) if keep else None
         xs = self._get('p1_sign', (B, h2, w2, 8), torch.uint8) if bits else None
         y1 = None
-        if self.fused_stem_fwd and x3:        # one persistent kernel (stem_pair.hip)
+        ca = self.blocks[0][0]
+        nxt = self.fused_stem_fwd and x3 and self.fused_stem_next_pair and ('u8' if src_is_u8 else 'f32') in self.fused_stem_next_sources and \
+            self.pair_classes >= 4 and self.pair_gemm_kernel and ca.r == 1 and ca.stride == 1 and ca.cin == 64 and ca.cout == 64
+        acts['stem_next'] = bool(nxt)        # block 0 starts with its conv1 done
+        if nxt:                               # ... with layer1 block 0's conv1 + ReLU on the pooled tile
+            ya = self._act('b0_a', (B, h2, w2, 64))
+            sa = self._get('b0_a_sign', (B, h2, w2, 8), torch.uint8) if bits else None
+            ev = self._prof_begin()
+            _lib.check(lib.rart_engine_stem_fwd_next_pair(_lib.ptr(src), u8, _lib.ptr(self.stem_w_pair[0]), _lib.ptr(self.stem_w_pair[1]),
+                                                          _lib.ptr(self.stem.bias), *self._hl(p1), _lib.ptr(parg), _lib.ptr(xs),
+                                                          ctypes.c_void_p(ca.w_fwd.data_ptr()), ctypes.c_void_p(ca.w_fwd.data_ptr() + 2 * 64),
+                                                          ca.w_fwd.shape[1], _lib.ptr(ca.bias), *self._hl(ya), _lib.ptr(sa), B, H, W,
+                                                          meanf, stdf, sp))
+            if ev is not None:   # the stem's products + 3 x 64 x 64 per pooled position; bytes: image + pooled pair + conv1's output pair
+                self._prof_end(ev, 3 * 2.0 * B * (h1 * w1 * 224 + h2 * w2 * 64) * 64, 'stem_pair',
+                               B * H * W * 3 * (1 if src_is_u8 else 4) + 8.0 * B * h2 * w2 * 64)
+        elif self.fused_stem_fwd and x3:      # one persistent kernel (stem_pair.hip)
             ev = self._prof_begin()
             _lib.check(lib.rart_engine_stem_fwd_fused_pair(_lib.ptr(src), u8, _lib.ptr(self.stem_w_pair[0]), _lib.ptr(self.stem_w_pair[1]),
                                                            _lib.ptr(self.stem.bias), *self._hl(p1), _lib.ptr(parg), _lib.ptr(xs), B, H, W,
@@ -924,6 +1015,12 @@ class ResNet50Engine(EngineBase):
                 # stride-1 projection skip (layer1's first block): conv1^T and the shortcut^T as one two-source launch, dx written once
                 self._gemm(dza, ds.w_cat_bwd, dx, B, xhw, xhw, ca.cout, ca.cout, ca.bwd[0][1], ca.cin, xhw, ca.cin, mask=mx,
                            flags=F_MASK_BITS, pair=True, src2=(dz, ohw, (1, 1), ds.cout, ds.cout))
+            elif x3 and self.fused_shortcut_pair and ds.cin in self.class_shortcut_channels and self._classes_ok(getattr(ds, 'cls_bwd', None)) \
+                    and xhw[0] % 2 == 0 and xhw[1] % 2 == 0:
+                # stride-2 projection skip: conv1^T per input parity in one class launch, the shortcut^T as the second source of the class
+                # (0, 0) -- the only one its gradient reaches -- so dx is written once and never read
+                self._gemm_pair_classes(dza, ds.cls_bwd, dx, B, ohw, xhw, ca.cout, ca.cout, ca.cin, xhw, ca.cin, mask=mx, stride=(2, 2),
+                                        src2=(dz, ohw, (1, 1), ds.cout, ds.cout))
             else:
                 self._conv_bwd(ca, dza, xhw, dx, xhw, mask=mx, pair=x3)
                 self._conv_bwd(ds, dz, ohw, dx, xhw, res=dx, mask=mx, pair=x3)             # accumulate the projection skip

@@ -225,6 +225,24 @@ def gemm_pair_desc(a, w, dst, N, lda, ldw, ldc, w_rows, M=0, K=0, bias=None, res
     return d
 
 
+def gemm_pair_cls_desc(a, w, dst, N, lda, ldw, ldc, w_rows, classes, **kw):
+    """rart_gemm_pair_cls_desc: the conv-form launch `gemm_pair_desc(a, w, dst, ..., **kw)` would describe, as up to four classes in one grid.
+    classes = [(taps, k_off, dst_org, src2)]: the (dy, dx) taps of the class, the first column of its slice in the rows of w, its
+    destination origin and whether it also accumulates the second source kw['src2'] (class 0 only).  kw carries no taps / dst_org."""
+    taps = [t for c in classes for t in c[0]]
+    src2 = kw.pop('src2', None)
+    one = gemm_pair_desc(a, w, dst, N, lda, ldw, ldc, w_rows, taps=taps, src2=src2, **kw)
+    d = _lib.GemmPairClsDesc()
+    ctypes.memmove(ctypes.byref(d.two), ctypes.byref(one), ctypes.sizeof(one))
+    d.n_classes = len(classes)
+    at = 0
+    for i, (ctaps, k_off, org, s2) in enumerate(classes):
+        c = d.cls[i]
+        c.tap_begin, c.n_taps, c.k_off, c.dst_oy, c.dst_ox, c.src2 = at, len(ctaps), k_off, org[0], org[1], int(bool(s2))
+        at += len(ctaps)
+    return d
+
+
 def tokmix_desc(a, x, dst, M, N, K, batch, x_stride, c_stride, ldx=None, ldc=None, bias=None, res=None, aux=None, flags=0, pair=False):
     """rart_tokmix_desc of MLP-Mixer's token-mixing GEMM: C_b[m][n] = sum_k A[m][k] X_b[k][n] for images b < batch.  a: the weight table
     [M][lda] (K padded with zero columns; a pair [2][M][lda] when `pair`); x / dst / res / aux: per-image slabs x_stride / c_stride
@@ -385,6 +403,15 @@ class EngineBase:
             _lib.check(self.lib.rart_gemm_pair_bf16(ctypes.byref(d), _lib.stream_ptr()))
         if ev is not None:
             self._prof_end(ev, 3 * 2.0 * max(d.n_batched, 1) * d.M * d.N * d.K, 'gemm_pair', nbytes)
+
+    def _launch_pair_classes(self, d, nbytes=None):
+        """rart_gemm_pair_classes_bf16 on descriptor d; profiled as 'gemm_pair' (MFMA FLOPs issued over all classes)"""
+        ev = self._prof_begin()
+        _lib.check(self.lib.rart_gemm_pair_classes_bf16(ctypes.byref(d), _lib.stream_ptr()))
+        if ev is not None:
+            one = d.two.one
+            k = sum(one.k_per_tap * d.cls[i].n_taps + (d.two.k2 if d.cls[i].src2 else 0) for i in range(d.n_classes))
+            self._prof_end(ev, 3 * 2.0 * one.M * one.N * k, 'gemm_pair', nbytes)
 
     def _launch_tokmix(self, d, pair):
         """rart_tokmix_{bf16,pair} on descriptor d; profiled as 'tokmix' (MFMA FLOPs issued: three products in pair form)"""

@@ -94,7 +94,17 @@ def wrapped_tail(src, wgt, taps, tail, dst, batch, hw, c_mid, **kw):
     e0.record(); r = orig_tail(src, wgt, taps, tail, dst, batch, hw, c_mid, **kw); e1.record()
     rows.append(((M, 9 * c_mid + 4 * c_mid, c_mid, 92), 2.0 * M * c_mid * (9 * c_mid + 4 * c_mid), by, e0, e1))   # taps column 92 = 3x3 + 1x1 expansion, one launch (fp32x)
     return r
+orig_cls = eng._gemm_pair_classes
+def wrapped_cls(src, tabs, dst, batch, grid, src_hw, src_pix, k_per_tap, n_cols, dst_hw, dst_pix, **kw):
+    M = batch * grid[0] * grid[1]
+    k_taps = k_per_tap * sum(len(c[0]) for c in tabs[1]); k2 = kw['src2'][4] if kw.get('src2') is not None else 0
+    by = batch * src_hw[0] * src_hw[1] * k_per_tap * 4 + M * k2 * 4 + (k_taps + k2) * n_cols * 4 + len(tabs[1]) * M * n_cols * (4 * (2 if kw.get('res') is not None else 1) + (0.125 if kw.get('mask') is not None else 0))
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(); r = orig_cls(src, tabs, dst, batch, grid, src_hw, src_pix, k_per_tap, n_cols, dst_hw, dst_pix, **kw); e1.record()
+    rows.append(((M, k_taps + k2, n_cols, 91), 2.0 * M * (k_taps + k2) * n_cols, by, e0, e1))   # taps column 91 = the parity classes of a stride-2 backward, one launch: M rows per class, K summed over the classes
+    return r
 for _ in range(2): eng.forward_backward(x, MEAN, STD, y, 0)
+eng._gemm_pair_classes = wrapped_cls
 eng._tail = wrapped_tail
 eng._bneck_image = wrapped_b14
 eng._bneck_s2_bwd = wrapped_s2b
@@ -107,6 +117,7 @@ rows.clear()
 eng.forward_backward(x, MEAN, STD, y, 0)
 torch.cuda.synchronize()
 eng._gemm = orig
+eng._gemm_pair_classes = orig_cls
 eng._tail = orig_tail
 eng._halo = orig_halo
 eng._bneck = orig_bneck
@@ -123,7 +134,7 @@ for key, (us, cnt, fl, by) in sorted(agg.items(), key=lambda kv: -kv[1][0]):
     floor = max(fl / PEAK_F, by / PEAK_B) * 1e6
     tot += us; totf += floor
     print('%9d %6d %6d %4d %4d %9.1f %8.1f %8.1f %9.1f %6.3f' % (*key, cnt, us, fl / us / 1e6, by / us / 1e3, floor, floor / us))
-print('(taps 99 = the LDS-resident 3x3 kernels, 98 / 97 / 96 / 95 = the fused Bottleneck kernels of layer1 / layer3 / layer2 / layer4: one row = 1x1 + 3x3 + 1x1; 94 / 93 = the fused stride-2 first blocks of layer2 / layer3, forward / backward; 92 = 3x3 + 1x1 expansion of the fp32x engine, one launch)')
+print('(taps 99 = the LDS-resident 3x3 kernels, 98 / 97 / 96 / 95 = the fused Bottleneck kernels of layer1 / layer3 / layer2 / layer4: one row = 1x1 + 3x3 + 1x1; 94 / 93 = the fused stride-2 first blocks of layer2 / layer3, forward / backward; 92 = 3x3 + 1x1 expansion of the fp32x engine, one launch; 91 = the parity classes of a stride-2 backward in one launch (fp32x): M rows per class, K summed over the classes)')
 print('conv launches %d: measured %.1f us, roofline floor %.1f us, fraction of the per-layer floor %.3f' %
       (len(rows), tot, totf, totf / tot))
 for name, fn in (('fwd+bwd', lambda: eng.forward_backward(x, MEAN, STD, y, 0)), ('fwd', lambda: eng.logits(x, MEAN, STD))):
