@@ -1234,6 +1234,69 @@ int rart_resize_batch_plan(const rart_resize_desc* images_host, int n, int filte
 int rart_resize_batch_u8(const void* plan, const void* plan_host, size_t plan_bytes, void* workspace, size_t workspace_bytes,
                          uint8_t* out, size_t out_bytes, rart_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Batched variable-size resize, OpenCV family (csrc/resize_cv_batch.hip): cv2.resize for 8-bit 3-channel images for n images of
+ * DIFFERENT sizes in one call -- the box of each image, cv2.resize to (resize_w, resize_h) with interpolation 0..4 (INTER_NEAREST,
+ * LINEAR, CUBIC, AREA, LANCZOS4), the crop window of the target, then an optional left-right mirror.  Image k of `out` holds the
+ * bytes rart_cv_resize_u8 gives for the box of image k alone; the box is a hard boundary (edge taps replicate the box's border,
+ * not the image's) and the row stride is the image's width.  The counterpart of the rart_resize_batch_* pair above, with the same
+ * shape: a host-only plan entry, one buffer that crosses the bus in one copy, validation of the host copy before any launch.
+ * At most two launches per call, whatever n and however the sizes mix; one when no image of the batch takes the two-pass path.
+ *
+ * cv2.resize chooses its code from the source size and the target, so the PATH is a field of the descriptor, not of the call:
+ *   RART_CV_PATH_NEAREST   : gather; tables = the source column / row of every target column / row, min(floor(d * scale), size - 1)
+ *   RART_CV_PATH_TWO_PASS  : LINEAR / CUBIC / LANCZOS4, and AREA with an up-scaling axis (area-mode coordinates): horizontal pass
+ *                            into an int32 intermediate, vertical pass with OpenCV's fixed-point casts.  Table rows
+ *                            [first tap (may lie outside: taps clamp to the box), k0 .. k_{ks-1}], ks = 2, 4 or 8
+ *   RART_CV_PATH_AREA_FLOAT: AREA, both scales >= 1, fractional: float accumulation in OpenCV's order.  Table rows
+ *                            [count, (source index, alpha as float bits) x ks], ks = the largest count of the table
+ *   RART_CV_PATH_AREA_INT  : AREA with integer scales, and LINEAR with an exact 2 x 2 decimation (cv2 executes it as AREA): no
+ *                            tables; ks_x / ks_y hold the integer scales, (a+b+c+d+2)>>2 for 2 x 2, rintf(sum * (1.f / area)) otherwise
+ *
+ * rart_cv_resize_batch_plan is HOST-ONLY (no HIP call).  The caller fills src, h, w, box_* and flip of n descriptors; the plan
+ * entry writes into plan_host, a buffer of `capacity` bytes, four regions, each 16-byte aligned, behind one another:
+ *   rart_cv_resize_plan header : the call's parameters, the element counts and byte offsets of the regions, and workspace_bytes
+ *   n rart_cv_resize_desc      : the caller's fields plus the derived ones
+ *   n + 1 int64 prefix         : prefix[i] = int32 samples of the intermediates of the images before i; a two-pass image has
+ *                                mid_count_i * crop_w * 3 of them (the rows of its box that the crop window's vertical taps read, the
+ *                                crop window's columns), every other image none
+ *   table_count int32          : the tables, each distinct (source size, target size, interpolation, axis) of the call stored once
+ *                                however many images share it
+ * `sizes` (optional) receives the same header; sizes->total_bytes is the buffer size the call needs = 80 + 64 n +
+ * 16-aligned(8 (n + 1)) + 4 table_count, and sizes->workspace_bytes = 256-aligned(4 prefix[n]).  With plan_host NULL only `sizes`
+ * is filled (RART_OK); a capacity below total_bytes is RART_ERR_WORKSPACE and nothing is written.
+ * The caller moves plan_host[0 .. total_bytes) to the device in ONE copy (16-byte aligned) and passes both copies to
+ * rart_cv_resize_batch_u8, which validates the HOST copy before any launch: the count, the interpolation, the crop window inside
+ * the target, the region offsets, every box inside its image, every path code, every table offset and row inside the table region,
+ * every tap and area index the kernels will form (after the clamp they apply) inside the box, the intermediate ranges, the prefix
+ * table, plan_bytes, workspace_bytes >= header.workspace_bytes and out_bytes >= n crop_h crop_w 3 -- so no descriptor can make a
+ * kernel read or write outside the caller's buffers (RART_ERR_INVALID / RART_ERR_WORKSPACE).  src may be any byte address (the
+ * kernels read it byte by byte).  out: uint8 [n][crop_h][crop_w][3]. */
+#define RART_CV_PATH_NEAREST 0
+#define RART_CV_PATH_TWO_PASS 1
+#define RART_CV_PATH_AREA_FLOAT 2
+#define RART_CV_PATH_AREA_INT 3
+typedef struct rart_cv_resize_desc {
+  uint64_t src;                           /* device address of the image, uint8 [h][w][3] */
+  int32_t h, w;
+  int32_t box_y, box_x, box_h, box_w;     /* the source box, inside the image */
+  int32_t flip;                           /* non-zero: mirror the output left-right */
+  /* derived by rart_cv_resize_batch_plan */
+  int32_t path;                           /* RART_CV_PATH_* */
+  int32_t tab_x, ks_x, tab_y, ks_y;       /* int32 element of the table region where the table starts, and ks as the path defines it */
+  int32_t mid_first, mid_count;           /* two-pass: rows of the box, relative to it, that the horizontal pass produces; else 0 */
+} rart_cv_resize_desc;
+typedef struct rart_cv_resize_plan {
+  int32_t n, interpolation, resize_h, resize_w, crop_y, crop_x, crop_h, crop_w;
+  int64_t desc_off, prefix_off, table_off;    /* byte offsets from the start of the buffer */
+  int64_t table_count;                        /* int32 elements */
+  int64_t workspace_bytes, total_bytes;
+} rart_cv_resize_plan;
+int rart_cv_resize_batch_plan(const rart_cv_resize_desc* images_host, int n, int interpolation, int resize_h, int resize_w, int crop_y,
+                              int crop_x, int crop_h, int crop_w, void* plan_host, size_t capacity, rart_cv_resize_plan* sizes);
+int rart_cv_resize_batch_u8(const void* plan, const void* plan_host, size_t plan_bytes, void* workspace, size_t workspace_bytes,
+                            uint8_t* out, size_t out_bytes, rart_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

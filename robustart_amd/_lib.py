@@ -241,6 +241,8 @@ SIGNATURES = {
                                     c_size_t, c_void_p]),
     'rart_resize_batch_plan': (c_int, [c_void_p, c_int] + [c_int] * 7 + [c_void_p, c_size_t, c_void_p]),
     'rart_resize_batch_u8': (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    'rart_cv_resize_batch_plan': (c_int, [c_void_p, c_int] + [c_int] * 7 + [c_void_p, c_size_t, c_void_p]),
+    'rart_cv_resize_batch_u8': (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
 }
 
 
@@ -294,6 +296,23 @@ class ResizeDesc(ctypes.Structure):
 class ResizePlan(ctypes.Structure):
     """rart_resize_plan (include/robustart_hip.h): the header of a rart_resize_batch_plan buffer, 80 bytes."""
     _fields_ = [(n, ctypes.c_int32) for n in ('n', 'filter', 'resize_h', 'resize_w', 'crop_y', 'crop_x', 'crop_h', 'crop_w')] + \
+               [(n, ctypes.c_int64) for n in ('desc_off', 'prefix_off', 'table_off', 'table_count', 'workspace_bytes', 'total_bytes')]
+
+
+CV_PATHS = ('nearest', 'two-pass', 'area-float', 'area-int')      # RART_CV_PATH_* of include/robustart_hip.h, by code
+
+
+class CvResizeDesc(ctypes.Structure):
+    """rart_cv_resize_desc (include/robustart_hip.h): one image of a rart_cv_resize_batch_u8 call, 64 bytes.  The caller fills
+    src .. flip, rart_cv_resize_batch_plan the rest."""
+    _fields_ = [('src', ctypes.c_uint64)] + \
+               [(n, ctypes.c_int32) for n in ('h', 'w', 'box_y', 'box_x', 'box_h', 'box_w', 'flip', 'path', 'tab_x', 'ks_x', 'tab_y',
+                                              'ks_y', 'mid_first', 'mid_count')]
+
+
+class CvResizePlan(ctypes.Structure):
+    """rart_cv_resize_plan (include/robustart_hip.h): the header of a rart_cv_resize_batch_plan buffer, 80 bytes."""
+    _fields_ = [(n, ctypes.c_int32) for n in ('n', 'interpolation', 'resize_h', 'resize_w', 'crop_y', 'crop_x', 'crop_h', 'crop_w')] + \
                [(n, ctypes.c_int64) for n in ('desc_off', 'prefix_off', 'table_off', 'table_count', 'workspace_bytes', 'total_bytes')]
 
 

@@ -8,7 +8,8 @@ rart_pil_resize_u8; the five 'opencv-*' operators run through rart_cv_resize_u8,
 build (raise NotImplementedError, loudly): the 'opencv' and 'ffmpeg' decoders and the reference's memcached reader.  Unlike the reference (which passes float sizes to Image.resize and only works on
 Python <= 3.9, imagenet_s_gen.py:129,167) sizes are converted with int().
 pil_resize_batch is the batched form of pil_resize for images of different sizes -- crop(box), resize, crop window, mirror for a whole
-batch in one rart_resize_batch_u8 call -- and image_transfer_batch the batch form of image_transfer on top of it.
+batch in one rart_resize_batch_u8 call -- cv_resize_batch the same for cv_resize through rart_cv_resize_batch_u8 (each
+image takes the code cv2.resize chooses for its size), and image_transfer_batch the batch form of image_transfer on top of the two.
 decode_batch_gpu is the batched form of the 'pil' decoder for baseline JPEG files: Huffman decoding on host threads, the arithmetic in
 rart_jpeg_decode_u8, the same bytes as Pillow; FileImageNet(reader='hip') reads through it."""
 import random
@@ -64,42 +65,70 @@ def pil_resize_batch(images, resize_hw, filter_id, crop=None, boxes=None, flips=
     hard boundary, unlike Image.resize(box=...)); crop=None keeps the whole resized image; out: the tensor to fill.
     One rart_resize_batch_plan call on the host, one copy of its buffer (pinned, kept between calls), one rart_resize_batch_u8
     call: two launches, one for NEAREST."""
-    global resize_batch_launches
+    return _resize_batch('pil_resize_batch', images, resize_hw, filter_id, crop, boxes, flips, out)
+
+
+cv_resize_batch_launches = 0   # rart_cv_resize_batch_u8 calls made by cv_resize_batch (one per call, whatever the batch holds)
+
+
+def cv_resize_batch(images, resize_hw, interpolation, crop=None, boxes=None, flips=None, out=None):
+    """The batched form of cv_resize for images of different sizes, the counterpart of pil_resize_batch (same arguments):
+    -> CUDA uint8 (n, ch, cw, 3), image k equal to cv_resize(images[k][box][None], resize_hw, interpolation, crop)[0], mirrored
+    left-right where flips[k].  boxes[k] = (y, x, h, w) inside image k (None: the whole image) is a hard boundary: edge taps
+    replicate the box's border.  cv2.resize chooses its code from the source size, so the images of one call may each take
+    another path (nearest, two-pass, float area, integer area).
+    One rart_cv_resize_batch_plan call on the host, one copy of its buffer (pinned, kept between calls), one
+    rart_cv_resize_batch_u8 call: two launches, one when no image takes the two-pass path."""
+    return _resize_batch('cv_resize_batch', images, resize_hw, interpolation, crop, boxes, flips, out)
+
+
+# who -> (descriptor, plan header, plan entry, device entry, the module counter of device-entry calls)
+_BATCH_ENTRIES = {
+    'pil_resize_batch': ('ResizeDesc', 'ResizePlan', 'rart_resize_batch_plan', 'rart_resize_batch_u8', 'resize_batch_launches'),
+    'cv_resize_batch': ('CvResizeDesc', 'CvResizePlan', 'rart_cv_resize_batch_plan', 'rart_cv_resize_batch_u8', 'cv_resize_batch_launches'),
+}
+
+
+def _resize_batch(who, images, resize_hw, mode, crop, boxes, flips, out):
+    """pil_resize_batch / cv_resize_batch: the two entry pairs take the same arguments and the same plan buffer."""
     import ctypes
     torch = _lib.require_gpu()
     lib = _lib.load()
+    desc_t, plan_t, plan_fn, run_fn, counter = _BATCH_ENTRIES[who]
+    plan_fn, run_fn = getattr(lib, plan_fn), getattr(lib, run_fn)
     images = list(images)
     n = len(images)
     rh, rw = int(resize_hw[0]), int(resize_hw[1])
     cy, cx, ch, cw = (int(v) for v in (crop if crop is not None else (0, 0, rh, rw)))
     if n == 0:
-        raise ValueError('pil_resize_batch: an empty list of images')
+        raise ValueError('%s: an empty list of images' % who)
     dev = images[0].device
-    descs = (_lib.ResizeDesc * n)()
+    descs = (getattr(_lib, desc_t) * n)()
     for k, img in enumerate(images):
         if not (isinstance(img, torch.Tensor) and img.is_cuda and img.device == dev and img.dtype == torch.uint8 and img.dim() == 3
                 and img.shape[2] == 3 and img.is_contiguous()):
-            raise ValueError('pil_resize_batch: image %d must be a contiguous CUDA uint8 HxWx3 tensor on %s' % (k, dev))
+            raise ValueError('%s: image %d must be a contiguous CUDA uint8 HxWx3 tensor on %s' % (who, k, dev))
         d = descs[k]
         d.src, d.h, d.w = img.data_ptr(), img.shape[0], img.shape[1]
         d.box_y, d.box_x, d.box_h, d.box_w = (int(v) for v in boxes[k]) if boxes is not None and boxes[k] is not None else (0, 0, d.h, d.w)
         d.flip = int(bool(flips[k])) if flips is not None else 0
     if out is None:
         out = torch.empty(n, ch, cw, 3, dtype=torch.uint8, device=dev)
-    elif not (out.is_cuda and out.device == dev and out.dtype == torch.uint8 and tuple(out.shape) == (n, ch, cw, 3) and out.is_contiguous()):
-        raise ValueError('pil_resize_batch: out must be a contiguous CUDA uint8 tensor of shape %r on %s' % ((n, ch, cw, 3), dev))
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev and out.dtype == torch.uint8
+              and tuple(out.shape) == (n, ch, cw, 3) and out.is_contiguous()):
+        raise ValueError('%s: out must be a contiguous CUDA uint8 tensor of shape %r on %s' % (who, (n, ch, cw, 3), dev))
     with torch.cuda.device(dev):
         host, ev = _plan_pinned.pop(dev, (None, None))     # taken out while in use, as decode_batch_gpu does
         if ev is not None:
             ev.synchronize()               # the previous call's copy has left the buffer
         if host is None:
             host = torch.empty(1 << 20, dtype=torch.uint8, pin_memory=True)
-        sizes = _lib.ResizePlan()
-        args = (ctypes.addressof(descs), n, filter_id, rh, rw, cy, cx, ch, cw)
-        st = lib.rart_resize_batch_plan(*args, host.data_ptr(), host.numel(), ctypes.byref(sizes))
+        sizes = getattr(_lib, plan_t)()
+        args = (ctypes.addressof(descs), n, mode, rh, rw, cy, cx, ch, cw)
+        st = plan_fn(*args, host.data_ptr(), host.numel(), ctypes.byref(sizes))
         if st == 3:                        # RART_ERR_WORKSPACE: `sizes` says what the plan needs
             host = torch.empty(int(sizes.total_bytes * 1.25), dtype=torch.uint8, pin_memory=True)
-            st = lib.rart_resize_batch_plan(*args, host.data_ptr(), host.numel(), ctypes.byref(sizes))
+            st = plan_fn(*args, host.data_ptr(), host.numel(), ctypes.byref(sizes))
         _lib.check(st)
         total = int(sizes.total_bytes)
         plan = torch.empty(total, dtype=torch.uint8, device=dev)
@@ -107,10 +136,10 @@ def pil_resize_batch(images, resize_hw, filter_id, crop=None, boxes=None, flips=
         ev = torch.cuda.Event()
         ev.record()
         ws = _lib.workspace(int(sizes.workspace_bytes), dev)
-        resize_batch_launches += 1
+        globals()[counter] += 1
         try:
-            _lib.check(lib.rart_resize_batch_u8(_lib.ptr(plan), host.data_ptr(), total, _lib.ptr(ws), int(sizes.workspace_bytes),
-                                                _lib.ptr(out), out.numel(), _lib.stream_ptr()))
+            _lib.check(run_fn(_lib.ptr(plan), host.data_ptr(), total, _lib.ptr(ws), int(sizes.workspace_bytes), _lib.ptr(out),
+                              out.numel(), _lib.stream_ptr()))
         finally:
             _plan_pinned[dev] = (host, ev)
     return out
@@ -311,8 +340,8 @@ def image_transfer_batch(items, decoder_type='pil', resize_type='pil-bilinear', 
     """The batch form of image_transfer: items (file paths / encoded bytes) -> CUDA uint8 (n, resize, resize, 3), image k equal to
     image_transfer(items[k], ...) (same size rule, same crop offsets; 'train' draws its boxes from the global random module in item
     order).  decoded: the already decoded images (CUDA uint8 HxWx3 tensors, or ndarrays, which are uploaded) -- `items` is then not
-    read, so a caller decodes once and resizes many times.  'pil-*' operators run through one pil_resize_batch call; the five
-    'opencv-*' operators through cv_resize, image by image."""
+    read, so a caller decodes once and resizes many times.  'pil-*' operators run through one pil_resize_batch call, the five
+    'opencv-*' operators through one cv_resize_batch call: no per-image call and no copy of a box for either family."""
     torch = _lib.require_gpu()
     if resize_type not in PIL_FILTERS and resize_type not in CV_MODES:
         raise NotImplementedError(resize_type)
@@ -336,8 +365,4 @@ def image_transfer_batch(items, decoder_type='pil', resize_type='pil-bilinear', 
         boxes = [_train_params(tuple(a.shape[:2]), random) for a in images]
     if resize_type in PIL_FILTERS:
         return pil_resize_batch(images, first, PIL_FILTERS[resize_type], crop=crop, boxes=boxes)
-    out = torch.empty(len(images), crop[2], crop[3], 3, dtype=torch.uint8, device=images[0].device)
-    for k, (img, b) in enumerate(zip(images, boxes)):
-        src = img if b is None else img[b[0]:b[0] + b[2], b[1]:b[1] + b[3]].contiguous()
-        out[k] = cv_resize(src[None], first, CV_MODES[resize_type], crop=crop)[0]
-    return out
+    return cv_resize_batch(images, first, CV_MODES[resize_type], crop=crop, boxes=boxes)
