@@ -554,6 +554,12 @@ typedef struct rart_conv_tail_desc {
 } rart_conv_tail_desc;
 int rart_conv3x3_tail_pair_supported(int c_mid);
 int rart_conv3x3_tail_pair(const rart_conv_tail_desc* desc_host, rart_stream_t stream);
+/* How rart_conv3x3_tail_pair brings the 3x3's input to LDS.  1 (default): launches with c_mid = 64, w <= 59 and taps within the 3 x 3
+ * neighbourhood stage the positions a 128-position tile reads over all nine taps ONCE per tile (a slab of 128 + 2 (w + 1) rows) and mask
+ * out-of-image taps per lane; 0: every launch stages 128 rows per tap, as the c_mid = 128 launches always do.  Outputs are bit-identical
+ * (same products, same order).  RART_TAIL_STAGING in the environment sets the initial value. */
+int rart_conv3x3_tail_pair_set_staging(int mode);
+int rart_conv3x3_tail_pair_get_staging(void);
 
 /* Row / elementwise kernels of the reference-precision ViT-B/16 engine (csrc/vit_pair.hip): every tensor a pair of bf16 planes, the
  * arithmetic in fp32 as the fp32 module (timm ViT-B/16, RobustART/model/__init__.py:1 -> absent submodule) does it.

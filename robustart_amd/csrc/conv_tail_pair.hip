@@ -43,6 +43,10 @@ constexpr int CT_PLANE_A = CT_TM * 64;           // one position plane of a stag
 constexpr int CT_NLD = 144;                      // NEXT: row stride (bytes) of a 32 x 64 bf16 plane of the chunk: ds_read_b128 conflict free
 constexpr int CT_WREG = 2 * 32 * CT_NLD;         // a wave's private LDS region (9 216 B >= the 32 x 68 fp32 staging)
 static_assert(CT_WREG >= 32 * CT_LDE * 4, "the staging must fit the wave's region");
+// SLAB instances (C = 64): the 3x3's input of a tile is staged ONCE, as the flat positions m0 - (W + 1) .. m0 - (W + 1) + CT_SLAB_ROWS - 1,
+// instead of once per tap (constants and lane maps mirrored by tests/test_tail_slab_cpu.py)
+constexpr int CT_SLAB_ROWS = 248;                // 128 + 2 (W + 1) rows: serves W <= 59
+constexpr int CT_SLAB_IMG = CT_SLAB_ROWS * 64;   // one image of the slab: a 32-channel K half of one plane, 64 B per row
 
 struct ConvTailDev {
   const uint16_t *a_hi, *a_lo, *w_hi, *w_lo, *t_hi, *t_lo;
@@ -153,9 +157,17 @@ __device__ __forceinline__ void ct_pointwise_frags(const f32x16* acc, const uint
 // plane and K step, no LDS); its table is a second fragment-ordered table.  The skip pair the shortcut's own launch wrote and this kernel
 // re-read (822 MB each way in layer1's first block at B = 256) never exists.
 // (XS without NEXT sits 2 registers above the 168 of three workgroups per CU: it is built for two, like the NEXT instances.)
-template <int C, bool NEXT, bool XS = false>
-__global__ __launch_bounds__(256, (C == 64 && !NEXT && !XS) ? 3 : 2) void k_conv3x3_tail_pair(const ConvTailDev d) {
+//
+// SLAB (C = 64): a flat tile of 128 consecutive positions reads, over its nine taps, only the positions m0 - (W + 1) .. m0 + 127 + (W + 1):
+// 242 rows at W = 56 where per-tap staging brings 9 x 128.  The prologue stages them once as four images [K half][hi / lo][row][64 B] in the
+// same lane-linear, XOR-swizzled format (62 pieces of 1 KiB per tile instead of 288); the main loop stages only the weights and reads tap
+// t's B fragments at slab row 32 wave + fr + (dy_t + 1) W + (dx_t + 1).  Where a tap leaves the image the slab holds a NEIGHBOURING pixel,
+// so every lane keeps the nine-bit mask of its own fragment position and replaces what it read with zeros.  Same products, same order:
+// bit-identical outputs.  63 488 + 16 384 B of LDS: two workgroups per CU.
+template <int C, bool NEXT, bool XS = false, bool SLAB = false>
+__global__ __launch_bounds__(256, (C == 64 && !NEXT && !XS && !SLAB) ? 3 : 2) void k_conv3x3_tail_pair(const ConvTailDev d) {
   static_assert(!XS || C == 64, "the shortcut source is built for layer1's first block: 64 input channels");
+  static_assert(!SLAB || C == 64, "the slab is sized for 64 channels (124 KB at 128)");
   constexpr int KX = 4;                          // XS: 16-deep K steps of the shortcut (64 input channels)
   constexpr int NJ = C / 32;                     // 32-channel blocks of the 3x3's output
   constexpr int KS = C / 16;                     // 16-deep K steps of the 1x1
@@ -164,8 +176,10 @@ __global__ __launch_bounds__(256, (C == 64 && !NEXT && !XS) ? 3 : 2) void k_conv
   constexpr int KT = 9 << TPT_SHIFT;
   constexpr int PLANE_B = C * 64, STAGE = 2 * CT_PLANE_A + 2 * PLANE_B;
   constexpr int BQ = (C / 16) / 4;               // 1 KiB pieces of a weight plane per wave
-  static_assert(4 * CT_WREG <= 2 * STAGE, "the waves' epilogue regions must fit the tile buffers");
-  __shared__ __attribute__((aligned(16))) uint8_t lds[2 * STAGE];
+  constexpr int SLAB_W = 4 * CT_SLAB_IMG;         // SLAB: the two weight stages follow the slab
+  constexpr int LDS_BYTES = SLAB ? SLAB_W + 4 * PLANE_B : 2 * STAGE;
+  static_assert(4 * CT_WREG <= (SLAB ? SLAB_W : 2 * STAGE), "the waves' epilogue regions must fit the tile buffers");
+  __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_BYTES];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // vertically adjacent row tiles share input rows: keep neighbours on one XCD (its L2 serves the overlap)
@@ -175,57 +189,6 @@ __global__ __launch_bounds__(256, (C == 64 && !NEXT && !XS) ? 3 : 2) void k_conv
     tile = (xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q) + slot;
   }
   const int m0 = (int)tile * CT_TM;
-
-  // ---- loader (see k_gemm_pair): a plane goes to LDS in 1 KiB pieces (16 rows x 64 B); lane -> row (lane >> 2), LDS chunk (lane & 3)
-  //      <- the row's chunk (lane & 3) ^ ((row >> 2) & 3).  Round 6 (rart_lds_dma.h): buffer_load ... lds with one constant per-lane byte
-  //      offset per piece; the tap and the K step move the scalar offset (resource base shifted down by the most negative tap offset); a
-  //      pixel outside the image for tap t has bit t of `nok` set and its offset ORed with RART_DMA_OOR (zero-filled by the range check)
-  uint32_t avoff[2], nok[2] = {0u, 0u};
-  int tap_min = 0;
-  for (int t = 0; t < 9; ++t) tap_min = min(tap_min, (d.tap_dy[t] * d.W + d.tap_dx[t]) * (C * 2));
-  const int tapreg = lane < 9 ? (d.tap_dy[lane] * d.W + d.tap_dx[lane]) * (C * 2) - tap_min : 0;
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int r = 16 * (wave + 4 * q) + (lane >> 2);
-    const int cs = ((lane & 3) ^ ((r >> 2) & 3)) * 16;
-    const int m = m0 + r;
-    const bool ok = m < d.M;
-    const uint32_t mm = ok ? (uint32_t)m : 0u;
-    const uint32_t t = ct_fastdiv(mm, d.w_magic, d.w_shift);
-    const int ax = (int)(mm - t * (uint32_t)d.W);
-    const int n = (int)ct_fastdiv(t, d.h_magic, d.h_shift);
-    const int ay = (int)(t - (uint32_t)n * (uint32_t)d.H);
-    avoff[q] = (uint32_t)((n * d.H * d.W + ay * d.W + ax) * (C * 2) + cs);
-    for (int t2 = 0; t2 < 9; ++t2) {
-      const int iy = ay + d.tap_dy[t2], ix = ax + d.tap_dx[t2];
-      if (!(ok && (unsigned)iy < (unsigned)d.H && (unsigned)ix < (unsigned)d.W)) nok[q] |= 1u << t2;
-    }
-  }
-  uint32_t wvoff[BQ];
-#pragma unroll
-  for (int q = 0; q < BQ; ++q) {
-    const int r = 16 * (wave + 4 * q) + (lane >> 2);
-    wvoff[q] = (uint32_t)((r * d.ldw + (((lane & 3) ^ ((r >> 2) & 3)) * 8)) * 2);
-  }
-  const rart_srd_t srd_ah = rart_dma_srd(reinterpret_cast<const char*>(d.a_hi) + tap_min), srd_al = rart_dma_srd(reinterpret_cast<const char*>(d.a_lo) + tap_min);
-  const rart_srd_t srd_wh = rart_dma_srd(d.w_hi), srd_wl = rart_dma_srd(d.w_lo);
-  const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lds;
-#define RART_CT_ISSUE(KT_, BUF)                                                                                 \
-  {                                                                                                             \
-    const uint32_t st_ = lds_base + (BUF)*STAGE;                                                                \
-    const int kt_ = (KT_);                                                                                      \
-    const int tap_ = kt_ >> TPT_SHIFT;                                                                          \
-    const uint32_t so_ = (uint32_t)(__builtin_amdgcn_readlane(tapreg, tap_) + (kt_ - (tap_ << TPT_SHIFT)) * 64); \
-    _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                             \
-      const uint32_t vo_ = avoff[q] | ((uint32_t)__builtin_amdgcn_sbfe(nok[q], tap_, 1) & RART_DMA_OOR);        \
-      rart_dma_load16(vo_, srd_ah, so_, st_ + (wave + 4 * q) * 1024);                                           \
-      rart_dma_load16(vo_, srd_al, so_, st_ + CT_PLANE_A + (wave + 4 * q) * 1024);                              \
-    }                                                                                                           \
-    _Pragma("unroll") for (int q = 0; q < BQ; ++q) {                                                            \
-      rart_dma_load16(wvoff[q], srd_wh, (uint32_t)kt_ * 64u, st_ + 2 * CT_PLANE_A + (wave + 4 * q) * 1024);     \
-      rart_dma_load16(wvoff[q], srd_wl, (uint32_t)kt_ * 64u, st_ + 2 * CT_PLANE_A + PLANE_B + (wave + 4 * q) * 1024); \
-    }                                                                                                           \
-  }
   const int fr = lane & 31, h = lane >> 5;
   uint32_t xo[2];
 #pragma unroll
@@ -240,32 +203,177 @@ __global__ __launch_bounds__(256, (C == 64 && !NEXT && !XS) ? 3 : 2) void k_conv
       if (d.bias_mid) bv = *reinterpret_cast<const float4*>(d.bias_mid + j * 32 + 8 * g + 4 * h);
       acc[j][4 * g] = bv.x; acc[j][4 * g + 1] = bv.y; acc[j][4 * g + 2] = bv.z; acc[j][4 * g + 3] = bv.w;
     }
-  RART_CT_ISSUE(0, 0)
-  rart_dma_wait<0>();
-  __syncthreads();
-  for (int kt = 0; kt < KT; ++kt) {
-    const int buf = kt & 1;
-    if (kt + 1 < KT) RART_CT_ISSUE(kt + 1, buf ^ 1)
-    const uint8_t* Pb = lds + buf * STAGE + (wave * 32) * 64;
-    const uint8_t* Wb = lds + buf * STAGE + 2 * CT_PLANE_A;
+
+  if constexpr (SLAB) {
+    // ---- slab loader: image (kh, plane) of the slab goes to LDS in 1 KiB pieces of 16 rows; lane -> row-in-piece (lane >> 2), LDS chunk
+    //      (lane & 3) <- source chunk (lane & 3) ^ ((row >> 2) & 3): 16 rows per piece leave that key to the lane alone.  Bounds: slab row s
+    //      is flat position m0 - (W + 1) + s; a position before 0 (compared UNSIGNED, so a negative one counts as large) or past M - 1
+    //      gets the offset RART_DMA_OOR, and the resources here carry the plane's TRUE size M * 128 B in num_records, so such a lane -- and any
+    //      lane at all beyond the plane -- is zero-filled by the range check.  Everything that varies sits in the per-lane offset (the scalar
+    //      offset is 0): the form "voffset >= num_records -> zeros" that rart_lds_dma.h records.  An in-range lane reads bytes
+    //      pos * 128 + [0, 128) with pos <= M - 1.  The last piece of an image has 8 rows: its lanes 32 .. 63 stay out of the load.
+    rart_srd_t srd_ah = rart_dma_srd(d.a_hi), srd_al = rart_dma_srd(d.a_lo);
+    srd_ah[2] = srd_al[2] = (uint32_t)d.M * (uint32_t)(C * 2);
+    const rart_srd_t srd_wh = rart_dma_srd(d.w_hi), srd_wl = rart_dma_srd(d.w_lo);
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lds;
+    const int halo = d.W + 1;
+    const uint32_t lane_off = (uint32_t)((((lane & 3) ^ ((lane >> 4) & 3)) << 4));
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const bf16x8 ph = *reinterpret_cast<const bf16x8*>(Pb + xo[ks]);
-      const bf16x8 pl = *reinterpret_cast<const bf16x8*>(Pb + CT_PLANE_A + xo[ks]);
+    for (int q = 0; q < 4; ++q) {
+      const int piece = wave + 4 * q;
+      const int srow = 16 * piece + (lane >> 2);
+      const int pos = m0 - halo + srow;
+      const uint32_t vo = (uint32_t)pos < (uint32_t)d.M ? (uint32_t)pos * (uint32_t)(C * 2) + lane_off : RART_DMA_OOR;
+      if (srow < CT_SLAB_ROWS) {
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const bf16x8 wh = *reinterpret_cast<const bf16x8*>(Wb + j * 32 * 64 + xo[ks]);
-        const bf16x8 wl = *reinterpret_cast<const bf16x8*>(Wb + PLANE_B + j * 32 * 64 + xo[ks]);
-        // the two small products first (x_lo . w_hi, x_hi . w_lo), the large one last, as in k_gemm_pair
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, pl, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, ph, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, ph, acc[j], 0, 0, 0);
+        for (int kh = 0; kh < 2; ++kh) {
+          rart_dma_load16(vo + kh * 64, srd_ah, 0u, lds_base + (2 * kh) * CT_SLAB_IMG + piece * 1024);
+          rart_dma_load16(vo + kh * 64, srd_al, 0u, lds_base + (2 * kh + 1) * CT_SLAB_IMG + piece * 1024);
+        }
       }
     }
-    rart_dma_wait<0>();                     // the next stage has landed in LDS
-    __syncthreads();
+    // the weights of a K step: two stages after the slab, one piece per wave and plane (see the per-tap loader below)
+    const int wr = 16 * wave + (lane >> 2);
+    const uint32_t wvoff = (uint32_t)((wr * d.ldw + (((lane & 3) ^ ((wr >> 2) & 3)) * 8)) * 2);
+#define RART_CT_ISSUE_W(KT_, BUF)                                                              \
+  {                                                                                            \
+    const uint32_t st_ = lds_base + SLAB_W + (BUF) * 2 * PLANE_B + wave * 1024;                \
+    rart_dma_load16(wvoff, srd_wh, (uint32_t)(KT_) * 64u, st_);                                \
+    rart_dma_load16(wvoff, srd_wl, (uint32_t)(KT_) * 64u, st_ + PLANE_B);                      \
   }
+    RART_CT_ISSUE_W(0, 0)
+    // bit t of nokf: tap t of THIS lane's fragment position leaves the image (or the position lies past M)
+    uint32_t nokf = 0u;
+    {
+      const int m = m0 + wave * 32 + fr;
+      const bool ok = m < d.M;
+      const uint32_t mm = ok ? (uint32_t)m : 0u;
+      const uint32_t t = ct_fastdiv(mm, d.w_magic, d.w_shift);
+      const int ax = (int)(mm - t * (uint32_t)d.W);
+      const int ay = (int)(t - ct_fastdiv(t, d.h_magic, d.h_shift) * (uint32_t)d.H);
+      for (int t2 = 0; t2 < 9; ++t2) {
+        const int iy = ay + d.tap_dy[t2], ix = ax + d.tap_dx[t2];
+        if (!(ok && (unsigned)iy < (unsigned)d.H && (unsigned)ix < (unsigned)d.W)) nokf |= 1u << t2;
+      }
+    }
+    const int tapreg = lane < 9 ? d.tap_dy[lane] * d.W + d.tap_dx[lane] : 0;   // tap t: slab rows relative to the centre tap
+    const int rbase = wave * 32 + fr + halo;
+    rart_dma_wait<0>();
+    __syncthreads();
+    // the compiler does not see that wait: left alone it waits for the bias loads at the loop's first MFMA with its own vmcnt(0), which
+    // also waits for the weight stage issued just before.  A use of the accumulators here moves its wait in front of the loop.
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) asm volatile("" : "+v"(acc[j]));
+#pragma unroll 1
+    for (int tap = 0; tap < 9; ++tap) {
+      const int R = rbase + __builtin_amdgcn_readlane(tapreg, tap);
+      const bool zero = ((nokf >> tap) & 1u) != 0u;
+      uint32_t so[2];
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) so[ks] = (uint32_t)(R * 64 + (((2 * ks + h) ^ ((R >> 2) & 3)) << 4));
+#pragma unroll
+      for (int kh = 0; kh < 2; ++kh) {               // K step kt = 2 tap + kh, weight stage kh
+        if (2 * tap + kh + 1 < KT) RART_CT_ISSUE_W(2 * tap + kh + 1, kh ^ 1)
+        const uint8_t* Pb = lds + (2 * kh) * CT_SLAB_IMG;
+        const uint8_t* Wb = lds + SLAB_W + kh * 2 * PLANE_B;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          uint4 vh = *reinterpret_cast<const uint4*>(Pb + so[ks]);
+          uint4 vl = *reinterpret_cast<const uint4*>(Pb + CT_SLAB_IMG + so[ks]);
+          if (zero) vh = vl = make_uint4(0u, 0u, 0u, 0u);
+          const bf16x8 ph = __builtin_bit_cast(bf16x8, vh), pl = __builtin_bit_cast(bf16x8, vl);
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) {
+            const bf16x8 wh = *reinterpret_cast<const bf16x8*>(Wb + j * 32 * 64 + xo[ks]);
+            const bf16x8 wl = *reinterpret_cast<const bf16x8*>(Wb + PLANE_B + j * 32 * 64 + xo[ks]);
+            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, pl, acc[j], 0, 0, 0);
+            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, ph, acc[j], 0, 0, 0);
+            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, ph, acc[j], 0, 0, 0);
+          }
+        }
+        rart_dma_wait<0>();                     // the next weight stage has landed in LDS
+        __syncthreads();
+      }
+    }
+#undef RART_CT_ISSUE_W
+  } else {
+    // ---- loader (see k_gemm_pair): a plane goes to LDS in 1 KiB pieces (16 rows x 64 B); lane -> row (lane >> 2), LDS chunk (lane & 3)
+    //      <- the row's chunk (lane & 3) ^ ((row >> 2) & 3).  Round 6 (rart_lds_dma.h): buffer_load ... lds with one constant per-lane byte
+    //      offset per piece; the tap and the K step move the scalar offset (resource base shifted down by the most negative tap offset); a
+    //      pixel outside the image for tap t has bit t of `nok` set and its offset ORed with RART_DMA_OOR (zero-filled by the range check)
+    uint32_t avoff[2], nok[2] = {0u, 0u};
+    int tap_min = 0;
+    for (int t = 0; t < 9; ++t) tap_min = min(tap_min, (d.tap_dy[t] * d.W + d.tap_dx[t]) * (C * 2));
+    const int tapreg = lane < 9 ? (d.tap_dy[lane] * d.W + d.tap_dx[lane]) * (C * 2) - tap_min : 0;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int r = 16 * (wave + 4 * q) + (lane >> 2);
+      const int cs = ((lane & 3) ^ ((r >> 2) & 3)) * 16;
+      const int m = m0 + r;
+      const bool ok = m < d.M;
+      const uint32_t mm = ok ? (uint32_t)m : 0u;
+      const uint32_t t = ct_fastdiv(mm, d.w_magic, d.w_shift);
+      const int ax = (int)(mm - t * (uint32_t)d.W);
+      const int n = (int)ct_fastdiv(t, d.h_magic, d.h_shift);
+      const int ay = (int)(t - (uint32_t)n * (uint32_t)d.H);
+      avoff[q] = (uint32_t)((n * d.H * d.W + ay * d.W + ax) * (C * 2) + cs);
+      for (int t2 = 0; t2 < 9; ++t2) {
+        const int iy = ay + d.tap_dy[t2], ix = ax + d.tap_dx[t2];
+        if (!(ok && (unsigned)iy < (unsigned)d.H && (unsigned)ix < (unsigned)d.W)) nok[q] |= 1u << t2;
+      }
+    }
+    uint32_t wvoff[BQ];
+#pragma unroll
+    for (int q = 0; q < BQ; ++q) {
+      const int r = 16 * (wave + 4 * q) + (lane >> 2);
+      wvoff[q] = (uint32_t)((r * d.ldw + (((lane & 3) ^ ((r >> 2) & 3)) * 8)) * 2);
+    }
+    const rart_srd_t srd_ah = rart_dma_srd(reinterpret_cast<const char*>(d.a_hi) + tap_min), srd_al = rart_dma_srd(reinterpret_cast<const char*>(d.a_lo) + tap_min);
+    const rart_srd_t srd_wh = rart_dma_srd(d.w_hi), srd_wl = rart_dma_srd(d.w_lo);
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lds;
+#define RART_CT_ISSUE(KT_, BUF)                                                                                 \
+    {                                                                                                             \
+      const uint32_t st_ = lds_base + (BUF)*STAGE;                                                                \
+      const int kt_ = (KT_);                                                                                      \
+      const int tap_ = kt_ >> TPT_SHIFT;                                                                          \
+      const uint32_t so_ = (uint32_t)(__builtin_amdgcn_readlane(tapreg, tap_) + (kt_ - (tap_ << TPT_SHIFT)) * 64); \
+      _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                             \
+        const uint32_t vo_ = avoff[q] | ((uint32_t)__builtin_amdgcn_sbfe(nok[q], tap_, 1) & RART_DMA_OOR);        \
+        rart_dma_load16(vo_, srd_ah, so_, st_ + (wave + 4 * q) * 1024);                                           \
+        rart_dma_load16(vo_, srd_al, so_, st_ + CT_PLANE_A + (wave + 4 * q) * 1024);                              \
+      }                                                                                                           \
+      _Pragma("unroll") for (int q = 0; q < BQ; ++q) {                                                            \
+        rart_dma_load16(wvoff[q], srd_wh, (uint32_t)kt_ * 64u, st_ + 2 * CT_PLANE_A + (wave + 4 * q) * 1024);     \
+        rart_dma_load16(wvoff[q], srd_wl, (uint32_t)kt_ * 64u, st_ + 2 * CT_PLANE_A + PLANE_B + (wave + 4 * q) * 1024); \
+      }                                                                                                           \
+    }
+    RART_CT_ISSUE(0, 0)
+    rart_dma_wait<0>();
+    __syncthreads();
+    for (int kt = 0; kt < KT; ++kt) {
+      const int buf = kt & 1;
+      if (kt + 1 < KT) RART_CT_ISSUE(kt + 1, buf ^ 1)
+      const uint8_t* Pb = lds + buf * STAGE + (wave * 32) * 64;
+      const uint8_t* Wb = lds + buf * STAGE + 2 * CT_PLANE_A;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const bf16x8 ph = *reinterpret_cast<const bf16x8*>(Pb + xo[ks]);
+        const bf16x8 pl = *reinterpret_cast<const bf16x8*>(Pb + CT_PLANE_A + xo[ks]);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          const bf16x8 wh = *reinterpret_cast<const bf16x8*>(Wb + j * 32 * 64 + xo[ks]);
+          const bf16x8 wl = *reinterpret_cast<const bf16x8*>(Wb + PLANE_B + j * 32 * 64 + xo[ks]);
+          // the two small products first (x_lo . w_hi, x_hi . w_lo), the large one last, as in k_gemm_pair
+          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, pl, acc[j], 0, 0, 0);
+          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, ph, acc[j], 0, 0, 0);
+          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, ph, acc[j], 0, 0, 0);
+        }
+      }
+      rart_dma_wait<0>();                     // the next stage has landed in LDS
+      __syncthreads();
+    }
 #undef RART_CT_ISSUE
+  }
 
   // ---- point-wise step of the intermediate, in registers: ReLU or the 1-bit mask, hi + lo split, then lanes l and l + 32 exchange
   //      halves so that lane half h owns the whole 8-channel chunk 2s + h of K step s: the B-operand fragments of the 1x1
@@ -497,7 +605,26 @@ void ct_magic(uint32_t dv, uint32_t& mg, uint32_t& sh) {   // exact for dividend
   sh = 31 + l;
   mg = (uint32_t)(((1ull << sh) + dv - 1) / dv);
 }
+
+// 1 (default): the c_mid = 64 instances stage the 3x3's input once per tile (SLAB); 0: once per tap everywhere (the A/B switch of
+// tests/test_tail_slab_gpu.py and scratch/time_tail_staging.py).  Bit-identical outputs.  RART_TAIL_STAGING in the environment sets the
+// initial value.
+int g_tail_staging = -1;
+int ct_staging() {
+  if (g_tail_staging < 0) {
+    const char* e = getenv("RART_TAIL_STAGING");
+    g_tail_staging = (e && atoi(e) == 0) ? 0 : 1;
+  }
+  return g_tail_staging;
+}
 }  // namespace
+
+extern "C" int rart_conv3x3_tail_pair_set_staging(int mode) {
+  RART_CHECK_ARG(mode == 0 || mode == 1, "rart_conv3x3_tail_pair_set_staging: mode must be 0 (input staged per tap) or 1 (input slab staged once per tile)");
+  g_tail_staging = mode;
+  return RART_OK;
+}
+extern "C" int rart_conv3x3_tail_pair_get_staging(void) { return ct_staging(); }
 
 extern "C" int rart_conv3x3_tail_pair_supported(int c_mid) { return (c_mid == 64 || c_mid == 128) ? 1 : 0; }
 
@@ -533,7 +660,18 @@ extern "C" int rart_conv3x3_tail_pair(const rart_conv_tail_desc* t, rart_stream_
   ct_magic((uint32_t)d.H, d.h_magic, d.h_shift);
   const dim3 grid((uint32_t)((M + CT_TM - 1) / CT_TM));
   hipStream_t st = (hipStream_t)stream;
-  if (xs) {
+  // the slab serves 64 channels, rows no wider than its halo allows, and taps inside the 3 x 3 neighbourhood (its rows and the lanes' masks)
+  bool slab = ct_staging() == 1 && t->c_mid == 64 && CT_TM + 2 * (t->w + 1) <= CT_SLAB_ROWS;
+  for (int i = 0; i < 9; ++i) slab = slab && t->tap_dy[i] >= -1 && t->tap_dy[i] <= 1 && t->tap_dx[i] >= -1 && t->tap_dx[i] <= 1;
+  if (slab) {
+    if (xs) {
+      if (next) hipLaunchKernelGGL((k_conv3x3_tail_pair<64, true, true, true>), grid, dim3(256), 0, st, d);
+      else hipLaunchKernelGGL((k_conv3x3_tail_pair<64, false, true, true>), grid, dim3(256), 0, st, d);
+    } else {
+      if (next) hipLaunchKernelGGL((k_conv3x3_tail_pair<64, true, false, true>), grid, dim3(256), 0, st, d);
+      else hipLaunchKernelGGL((k_conv3x3_tail_pair<64, false, false, true>), grid, dim3(256), 0, st, d);
+    }
+  } else if (xs) {
     if (next) hipLaunchKernelGGL((k_conv3x3_tail_pair<64, true, true>), grid, dim3(256), 0, st, d);
     else hipLaunchKernelGGL((k_conv3x3_tail_pair<64, false, true>), grid, dim3(256), 0, st, d);
   } else if (t->c_mid == 64) {
