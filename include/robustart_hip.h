@@ -560,6 +560,13 @@ int rart_conv3x3_tail_pair(const rart_conv_tail_desc* desc_host, rart_stream_t s
  * (same products, same order).  RART_TAIL_STAGING in the environment sets the initial value. */
 int rart_conv3x3_tail_pair_set_staging(int mode);
 int rart_conv3x3_tail_pair_get_staging(void);
+/* How the launches that take the slab path above read the fragment table of the 1x1 expansion.  1 (default): each 64-output-channel
+ * chunk of the table reaches LDS once per workgroup (LDS DMA into the bytes the slab leaves free, two buffers) and all four waves read
+ * their fragments from there; 0: every wave loads every fragment from L2 itself.  The tables of the neighbour's reduction and of the
+ * shortcut always come from L2; launches off the slab path always use direct loads.  Outputs are bit-identical (same products, same
+ * order).  RART_TAIL_TABLES in the environment sets the initial value. */
+int rart_conv3x3_tail_pair_set_tables(int mode);
+int rart_conv3x3_tail_pair_get_tables(void);
 
 /* Row / elementwise kernels of the reference-precision ViT-B/16 engine (csrc/vit_pair.hip): every tensor a pair of bf16 planes, the
  * arithmetic in fp32 as the fp32 module (timm ViT-B/16, RobustART/model/__init__.py:1 -> absent submodule) does it.

@@ -141,6 +141,8 @@ SIGNATURES = {
     'rart_conv3x3_tail_pair': (c_int, [c_void_p, c_void_p]),
     'rart_conv3x3_tail_pair_set_staging': (c_int, [c_int]),
     'rart_conv3x3_tail_pair_get_staging': (c_int, []),
+    'rart_conv3x3_tail_pair_set_tables': (c_int, [c_int]),
+    'rart_conv3x3_tail_pair_get_tables': (c_int, []),
     'rart_engine_stem_fwd_fused_pair': (c_int, [c_void_p, c_int] + [c_void_p] * 7 + [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'rart_engine_stem_fwd_next_pair': (c_int, [c_void_p, c_int] + [c_void_p] * 9 + [c_int] + [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p, c_void_p,
                                                c_void_p]),

@@ -18,8 +18,9 @@
 // positions the B operand -- so a lane ends up with 4 consecutive channels of ONE position: bias / ReLU / mask / hi + lo split happen in
 // registers, one v_permlane32_swap per register pair turns the results into the B-operand fragments of the 1x1 (the intermediate
 // stays in registers, as in csrc/bottleneck_fused.hip), and its sign bits leave as whole bytes.  The 1x1's table comes straight from
-// L2 in MFMA fragment order (1 KiB contiguous per fragment load), 64 output channels at a time; each 32 x 64 result is transposed
-// through the wave's private LDS region so that the skip loads and the stores are 128-byte row segments per plane.
+// L2 in MFMA fragment order (1 KiB contiguous per fragment load; the TLDS instances below: through LDS, once per workgroup), 64 output
+// channels at a time; each 32 x 64 result is transposed through the wave's private LDS region so that the skip loads and the stores
+// are 128-byte row segments per plane.
 //
 // NEXT instances also run the 1x1 REDUCTION of the neighbouring block on the tile they just produced (a 1x1 convolution is
 // position-local): forward, conv1 + bias + ReLU of the NEXT block on `out`; backward, conv3^T + mask of the PREVIOUS block on dx.  Each
@@ -47,6 +48,11 @@ static_assert(CT_WREG >= 32 * CT_LDE * 4, "the staging must fit the wave's regio
 // instead of once per tap (constants and lane maps mirrored by tests/test_tail_slab_cpu.py)
 constexpr int CT_SLAB_ROWS = 248;                // 128 + 2 (W + 1) rows: serves W <= 59
 constexpr int CT_SLAB_IMG = CT_SLAB_ROWS * 64;   // one image of the slab: a 32-channel K half of one plane, 64 B per row
+// TLDS instances (SLAB only): the expansion's fragment table reaches LDS once per workgroup, a 64-output-channel chunk at a time, in two
+// 16 KiB buffers behind the waves' regions: [hi / lo][8 fragments][1 KiB lane-linear] (map mirrored by tests/test_tail_tables_cpu.py)
+constexpr int CT_TBL = 4 * CT_WREG;              // first byte after the waves' regions
+constexpr int CT_TBL_PLANE = 8 * 1024;           // one plane of a chunk: 2 blocks x 4 K steps of 1 KiB fragments
+constexpr int CT_TBL_BYTES = 2 * CT_TBL_PLANE;   // a chunk of a table
 
 struct ConvTailDev {
   const uint16_t *a_hi, *a_lo, *w_hi, *w_lo, *t_hi, *t_lo;
@@ -164,10 +170,24 @@ __device__ __forceinline__ void ct_pointwise_frags(const f32x16* acc, const uint
 // t's B fragments at slab row 32 wave + fr + (dy_t + 1) W + (dx_t + 1).  Where a tap leaves the image the slab holds a NEIGHBOURING pixel,
 // so every lane keeps the nine-bit mask of its own fragment position and replaces what it read with zeros.  Same products, same order:
 // bit-identical outputs.  63 488 + 16 384 B of LDS: two workgroups per CU.
-template <int C, bool NEXT, bool XS = false, bool SLAB = false>
+//
+// TLDS (SLAB instances): after the 3x3 loop's last barrier the slab and the weight stages are dead, and the waves' regions take only bytes
+// [0, 36 864) of the 79 872.  Direct, each of the four waves loads every fragment of the expansion table itself from L2 (16 loads of 1 KiB
+// per wave and chunk: 256 wave-instructions per tile for identical bytes); here each wave brings a quarter of a chunk with rart_dma_load16
+// (lane-linear = fragment order) and all four read their A fragments with ds_read_b128 at fragment * 1024 + lane * 16: 64 per tile.  Two
+// buffers: chunk c + 1 is issued behind the barrier that publishes chunk c, so it lands under chunk c's MFMAs, transposes and stores, and
+// the chunk loop takes ONE barrier per chunk.  That barrier follows every wave's last read of chunk c - 1, whose buffer the refill
+// overwrites; a landed buffer is published by s_waitcnt vmcnt(0) + barrier.  The chunk loop has a constant trip count and no wave leaves
+// the kernel early, so the barrier is legal.  The neighbour's table (NEXT) and the shortcut's (XS) stay on direct loads: a second table in
+// LDS has no second buffer (16 KiB each, 43 008 B free), so its refill needs a second barrier per chunk, and that form measured slower
+// (DESIGN 4.4).  hipcc does not count the inline-asm DMAs: its counted wait for a load OLDER than a pending DMA also waits for that DMA,
+// so the bias loads of a chunk are issued in front of the barrier's full wait and an empty asm that uses the accumulators sits behind it.
+// Same MFMAs in the same order: bit-identical outputs.
+template <int C, bool NEXT, bool XS = false, bool SLAB = false, bool TLDS = false>
 __global__ __launch_bounds__(256, (C == 64 && !NEXT && !XS && !SLAB) ? 3 : 2) void k_conv3x3_tail_pair(const ConvTailDev d) {
   static_assert(!XS || C == 64, "the shortcut source is built for layer1's first block: 64 input channels");
   static_assert(!SLAB || C == 64, "the slab is sized for 64 channels (124 KB at 128)");
+  static_assert(!TLDS || SLAB, "the table buffers live in what the slab leaves free");
   constexpr int KX = 4;                          // XS: 16-deep K steps of the shortcut (64 input channels)
   constexpr int NJ = C / 32;                     // 32-channel blocks of the 3x3's output
   constexpr int KS = C / 16;                     // 16-deep K steps of the 1x1
@@ -179,6 +199,7 @@ __global__ __launch_bounds__(256, (C == 64 && !NEXT && !XS && !SLAB) ? 3 : 2) vo
   constexpr int SLAB_W = 4 * CT_SLAB_IMG;         // SLAB: the two weight stages follow the slab
   constexpr int LDS_BYTES = SLAB ? SLAB_W + 4 * PLANE_B : 2 * STAGE;
   static_assert(4 * CT_WREG <= (SLAB ? SLAB_W : 2 * STAGE), "the waves' epilogue regions must fit the tile buffers");
+  static_assert(!TLDS || (CT_TBL + 2 * CT_TBL_BYTES <= LDS_BYTES && KS == 4 && NJ == 2), "two table buffers behind the waves' regions");
   __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_BYTES];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -377,6 +398,24 @@ __global__ __launch_bounds__(256, (C == 64 && !NEXT && !XS && !SLAB) ? 3 : 2) vo
 
   // ---- point-wise step of the intermediate, in registers: ReLU or the 1-bit mask, hi + lo split, then lanes l and l + 32 exchange
   //      halves so that lane half h owns the whole 8-channel chunk 2s + h of K step s: the B-operand fragments of the 1x1
+  // TLDS: a chunk of the table is 8 fragments of 1 KiB per plane, contiguous in memory; wave w brings fragments w and w + 4 of both planes.
+  // The resources carry the planes' true size (NOUT x C bf16), every offset below stays inside it.
+  rart_srd_t srd_th = {0u, 0u, 0u, 0u}, srd_tl = srd_th;
+  const uint32_t tbl_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lds + CT_TBL;
+  const uint32_t tbl_voff = (uint32_t)lane * 16u;
+  if constexpr (TLDS) {
+    srd_th = rart_dma_srd(d.t_hi); srd_tl = rart_dma_srd(d.t_lo);
+    srd_th[2] = srd_tl[2] = (uint32_t)(NOUT * C * 2);
+  }
+#define RART_CT_ISSUE_TBL(CHUNK, BUF)                                                                           \
+  _Pragma("unroll") for (int q_ = 0; q_ < 2; ++q_) {                                                            \
+    const uint32_t k_ = (uint32_t)(wave + 4 * q_);                                                              \
+    const uint32_t so_ = ((uint32_t)(CHUNK) * 8u + k_) * 1024u;                                                 \
+    const uint32_t la_ = tbl_lds + (uint32_t)(BUF) * (uint32_t)CT_TBL_BYTES + k_ * 1024u;                       \
+    rart_dma_load16(tbl_voff, srd_th, so_, la_);                                                                \
+    rart_dma_load16(tbl_voff, srd_tl, so_, la_ + (uint32_t)CT_TBL_PLANE);                                       \
+  }
+  if constexpr (TLDS) { RART_CT_ISSUE_TBL(0, 0) }            // chunk 0 lands under the point-wise step and the sign stores
   const int p = m0 + wave * 32 + fr;
   const bool p_ok = p < d.M;
   bf16x8 a2h[KS], a2l[KS];
@@ -432,43 +471,62 @@ __global__ __launch_bounds__(256, (C == 64 && !NEXT && !XS && !SLAB) ? 3 : 2) vo
   const uint4* txh_base = reinterpret_cast<const uint4*>(XS ? d.tx_hi : d.t_hi) + lane;
   const uint4* txl_base = reinterpret_cast<const uint4*>(XS ? d.tx_lo : d.t_lo) + lane;
   const bool relu_out = d.relu_out != 0;
+  // the skip operands and the biases of chunk c: requested at the chunk top (direct) or around the chunk's barrier (TLDS, see above)
+#define RART_CT_LOAD_SKIP                                                  \
+  _Pragma("unroll") for (int q = 0; q < 4; ++q) {                          \
+    const int pp = m0 + wave * 32 + q * 8 + rw;                            \
+    eo[q] = -1;                                                            \
+    rh[q] = rl[q] = make_uint4(0, 0, 0, 0);                                \
+    mb[q] = 0xFFu;                                                         \
+    if (pp < d.M) {                                                        \
+      const int e = pp * NOUT + c * 64 + cw * 8;                           \
+      eo[q] = e;                                                           \
+      if (d.res_hi) {                                                      \
+        rh[q] = ct_nt_load(d.res_hi + e);                                  \
+        rl[q] = ct_nt_load(d.res_lo + e);                                  \
+      }                                                                    \
+      if (d.mask_out) mb[q] = d.mask_out[e >> 3];                          \
+    }                                                                      \
+  }
+#define RART_CT_BIAS_ACC2(B_)                                                                                             \
+  _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                                         \
+    float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);                                                                          \
+    if (d.bias_out) bv = *reinterpret_cast<const float4*>(d.bias_out + c * 64 + (B_) * 32 + 8 * g + 4 * h);               \
+    acc2[B_][4 * g] = bv.x; acc2[B_][4 * g + 1] = bv.y; acc2[B_][4 * g + 2] = bv.z; acc2[B_][4 * g + 3] = bv.w;           \
+  }
 #pragma unroll 1
   for (int c = 0; c < NC; ++c) {
     int eo[4];                 // element offsets stay below 2^31 (checked on the host)
     uint4 rh[4], rl[4];
     uint32_t mb[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int pp = m0 + wave * 32 + q * 8 + rw;
-      eo[q] = -1;
-      rh[q] = rl[q] = make_uint4(0, 0, 0, 0);
-      mb[q] = 0xFFu;
-      if (pp < d.M) {
-        const int e = pp * NOUT + c * 64 + cw * 8;
-        eo[q] = e;
-        if (d.res_hi) {
-          rh[q] = ct_nt_load(d.res_hi + e);
-          rl[q] = ct_nt_load(d.res_lo + e);
-        }
-        if (d.mask_out) mb[q] = d.mask_out[e >> 3];
-      }
-    }
+    if constexpr (!TLDS) { RART_CT_LOAD_SKIP }
     f32x16 acc2[2];
+    const uint8_t* tbuf = lds;                               // TLDS: this chunk of the expansion table, at the lane's 16 bytes
+    if constexpr (TLDS) {
+      RART_CT_BIAS_ACC2(0)
+      RART_CT_BIAS_ACC2(1)
+      rart_dma_wait<0>();                    // chunk c has landed; every wave is past its reads of chunk c - 1, which the refill overwrites
+      __syncthreads();
+      asm volatile("" : "+v"(acc2[0]), "+v"(acc2[1]));
+      tbuf = lds + CT_TBL + lane * 16 + (c & 1) * CT_TBL_BYTES;
+      if (c + 1 < NC) { RART_CT_ISSUE_TBL(c + 1, (c + 1) & 1) }
+      RART_CT_LOAD_SKIP
+    }
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (d.bias_out) bv = *reinterpret_cast<const float4*>(d.bias_out + c * 64 + b * 32 + 8 * g + 4 * h);
-        acc2[b][4 * g] = bv.x; acc2[b][4 * g + 1] = bv.y; acc2[b][4 * g + 2] = bv.z; acc2[b][4 * g + 3] = bv.w;
-      }
+      if constexpr (!TLDS) { RART_CT_BIAS_ACC2(b) }
 #pragma unroll
       for (int sg = 0; sg < KS; sg += 4) {          // four K steps of table fragments in flight (32 registers)
         uint4 th[4], tl[4];
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-          th[s] = th_base[((c * 2 + b) * KS + sg + s) * 64];
-          tl[s] = tl_base[((c * 2 + b) * KS + sg + s) * 64];
+          if constexpr (TLDS) {
+            th[s] = *reinterpret_cast<const uint4*>(tbuf + (b * KS + sg + s) * 1024);
+            tl[s] = *reinterpret_cast<const uint4*>(tbuf + CT_TBL_PLANE + (b * KS + sg + s) * 1024);
+          } else {
+            th[s] = th_base[((c * 2 + b) * KS + sg + s) * 64];
+            tl[s] = tl_base[((c * 2 + b) * KS + sg + s) * 64];
+          }
         }
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
@@ -576,6 +634,9 @@ __global__ __launch_bounds__(256, (C == 64 && !NEXT && !XS && !SLAB) ? 3 : 2) vo
       __builtin_amdgcn_wave_barrier();       // the fragment reads are done before the next chunk's staging
     }
   }
+#undef RART_CT_LOAD_SKIP
+#undef RART_CT_BIAS_ACC2
+#undef RART_CT_ISSUE_TBL
   if (NEXT) {
     // ---- point-wise step of the neighbour's reduction and its stores: a lane owns 16-byte segments of its position's row
     uint32_t mw[NJ];
@@ -617,7 +678,25 @@ int ct_staging() {
   }
   return g_tail_staging;
 }
+// 1 (default): the SLAB instances bring the expansion's fragment table to LDS once per workgroup (TLDS); 0: every wave loads it from
+// L2 itself (the A/B switch of tests/test_tail_tables_gpu.py and scratch/time_tail_tables.py).  Bit-identical outputs.  RART_TAIL_TABLES in
+// the environment sets the initial value.  A launch that does not take the slab path has direct tables whatever the mode.
+int g_tail_tables = -1;
+int ct_tables() {
+  if (g_tail_tables < 0) {
+    const char* e = getenv("RART_TAIL_TABLES");
+    g_tail_tables = (e && atoi(e) == 0) ? 0 : 1;
+  }
+  return g_tail_tables;
+}
 }  // namespace
+
+extern "C" int rart_conv3x3_tail_pair_set_tables(int mode) {
+  RART_CHECK_ARG(mode == 0 || mode == 1, "rart_conv3x3_tail_pair_set_tables: mode must be 0 (table fragments loaded by every wave) or 1 (staged in LDS once per workgroup)");
+  g_tail_tables = mode;
+  return RART_OK;
+}
+extern "C" int rart_conv3x3_tail_pair_get_tables(void) { return ct_tables(); }
 
 extern "C" int rart_conv3x3_tail_pair_set_staging(int mode) {
   RART_CHECK_ARG(mode == 0 || mode == 1, "rart_conv3x3_tail_pair_set_staging: mode must be 0 (input staged per tap) or 1 (input slab staged once per tile)");
@@ -663,7 +742,15 @@ extern "C" int rart_conv3x3_tail_pair(const rart_conv_tail_desc* t, rart_stream_
   // the slab serves 64 channels, rows no wider than its halo allows, and taps inside the 3 x 3 neighbourhood (its rows and the lanes' masks)
   bool slab = ct_staging() == 1 && t->c_mid == 64 && CT_TM + 2 * (t->w + 1) <= CT_SLAB_ROWS;
   for (int i = 0; i < 9; ++i) slab = slab && t->tap_dy[i] >= -1 && t->tap_dy[i] <= 1 && t->tap_dx[i] >= -1 && t->tap_dx[i] <= 1;
-  if (slab) {
+  if (slab && ct_tables() == 1) {
+    if (xs) {
+      if (next) hipLaunchKernelGGL((k_conv3x3_tail_pair<64, true, true, true, true>), grid, dim3(256), 0, st, d);
+      else hipLaunchKernelGGL((k_conv3x3_tail_pair<64, false, true, true, true>), grid, dim3(256), 0, st, d);
+    } else {
+      if (next) hipLaunchKernelGGL((k_conv3x3_tail_pair<64, true, false, true, true>), grid, dim3(256), 0, st, d);
+      else hipLaunchKernelGGL((k_conv3x3_tail_pair<64, false, false, true, true>), grid, dim3(256), 0, st, d);
+    }
+  } else if (slab) {
     if (xs) {
       if (next) hipLaunchKernelGGL((k_conv3x3_tail_pair<64, true, true, true>), grid, dim3(256), 0, st, d);
       else hipLaunchKernelGGL((k_conv3x3_tail_pair<64, false, true, true>), grid, dim3(256), 0, st, d);
