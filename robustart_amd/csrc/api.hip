@@ -4,6 +4,7 @@
 #include <stdarg.h>
 #include <string.h>
 #include "rart_common.h"
+#include "rart_bf16_helpers.h"
 #include <map>
 #include <mutex>
 #include <utility>
@@ -166,12 +167,6 @@ __global__ __launch_bounds__(kBlock) void k_fill_normal(float* __restrict__ out,
   }
 }
 
-__device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
-  uint32_t u = __float_as_uint(f);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
 // (x/255 - mean)/std, layouts NCHW / NHWC, dtypes fp32 / bf16.  One thread per pixel.
 template <typename T, bool NHWC>
 __global__ __launch_bounds__(kBlock) void k_u8_to_norm(const uint8_t* __restrict__ in, T* __restrict__ out,
@@ -185,7 +180,7 @@ __global__ __launch_bounds__(kBlock) void k_u8_to_norm(const uint8_t* __restrict
     for (int c = 0; c < 3; ++c) {
       const float v = ((float)in[p * 3 + c] * (1.0f / 255.0f) - mean[c]) * istd[c];
       const size_t o = NHWC ? p * 3 + c : (img * 3 + c) * hw + pix;
-      if constexpr (sizeof(T) == 4) out[o] = v; else out[o] = f32_to_bf16_rne(v);
+      if constexpr (sizeof(T) == 4) out[o] = v; else out[o] = rart_bf16::f2bf(v);
     }
   }
 }

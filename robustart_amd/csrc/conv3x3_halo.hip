@@ -15,9 +15,7 @@
 // robustart_amd/model/resnet_torch.py) inside the forward / autograd of each attack iteration
 // (RobustART/noise/utils/adv/attack.py:21-22, Attacks/autoattack/autopgd_base.py:271-289).
 #include "rart_common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
+#include "rart_bf16_helpers.h"
 
 struct RartHaloDesc {
   const uint16_t* src;
@@ -37,29 +35,9 @@ struct RartHaloDesc {
 };
 
 namespace {
+using namespace rart_bf16;
 __device__ __forceinline__ uint32_t fastdiv(uint32_t n, uint32_t magic, uint32_t shift) {
   return (uint32_t)(((uint64_t)n * magic) >> shift);
-}
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-typedef __attribute__((ext_vector_type(2))) short i16x2_t;
-__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
-  f32x2_t f = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, bf16x2_t));
-}
-__device__ __forceinline__ uint32_t relu_bf16x2(uint32_t w) {
-  const i16x2_t z = {0, 0};
-  return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(i16x2_t, w), z));
-}
-__device__ __forceinline__ uint32_t halves_from_bits(uint32_t byte, int pair) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_sbfe(byte, 2 * pair, 1);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_sbfe(byte, 2 * pair + 1, 1);
-  return __builtin_amdgcn_perm(hi, lo, 0x07060100u);
-}
-__device__ __forceinline__ uint32_t bits_from_halves(uint32_t w) {
-  const i16x2_t z = {0, 0}, one = {1, 1};
-  const uint32_t t = __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_elementwise_max(__builtin_bit_cast(i16x2_t, w), z), one));
-  return (t | (t >> 15)) & 3u;
 }
 
 template <int C>

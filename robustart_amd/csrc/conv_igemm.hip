@@ -25,11 +25,9 @@
 // Most ResNet-50 layers are HBM-bound at bf16 (K = 64..512), so the kernel is built around wide coalesced traffic first
 // and MFMA issue second (DESIGN.md 4.3 has the measured breakdown).
 #include "rart_common.h"
+#include "rart_bf16_helpers.h"
 #include "rart_lds_dma.h"
 #include <type_traits>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 struct RartConvDescDev {
   const uint16_t* src;
@@ -66,36 +64,13 @@ struct RartConvDescDev {
 };
 
 namespace {
+using namespace rart_bf16;
 constexpr int BM = 128;
 constexpr int kThreads = 256;
 enum { F_RELU = 1, F_OUT_F32 = 2, F_GELU = 4, F_GELU_BWD = 8, F_MASK_BITS = 16, F_PAIR = 32, F_GELU_KEEP = 64, F_MASK_RES = 128 };
 
 __device__ __forceinline__ uint32_t fastdiv(uint32_t n, uint32_t magic, uint32_t shift) {
   return (uint32_t)(((uint64_t)n * magic) >> shift);
-}
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-typedef __attribute__((ext_vector_type(2))) short i16x2_t;
-__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {   // round to nearest even
-  f32x2_t f = {lo, hi};
-  bf16x2_t b = __builtin_convertvector(f, bf16x2_t);
-  return __builtin_bit_cast(uint32_t, b);
-}
-__device__ __forceinline__ uint32_t relu_bf16x2(uint32_t w) {           // sign bit set -> 0 (also -0.0)
-  const i16x2_t z = {0, 0};
-  return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(i16x2_t, w), z));
-}
-// two mask bits (bit 0 -> low half, bit 1 -> high half) -> 0xFFFF per selected bf16 half
-__device__ __forceinline__ uint32_t halves_from_bits(uint32_t byte, int pair) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_sbfe(byte, 2 * pair, 1);        // 0 or 0xFFFFFFFF
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_sbfe(byte, 2 * pair + 1, 1);
-  return __builtin_amdgcn_perm(hi, lo, 0x07060100u);                              // {hi.b3, hi.b2, lo.b1, lo.b0}
-}
-// packed pair of non-negative-or-zero bf16 (after ReLU) or any bf16 -> 2 bits (half > 0)
-__device__ __forceinline__ uint32_t bits_from_halves(uint32_t w) {
-  const i16x2_t z = {0, 0}, one = {1, 1};
-  const uint32_t t = __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_elementwise_max(__builtin_bit_cast(i16x2_t, w), z), one));
-  return (t | (t >> 15)) & 3u;
 }
 __device__ __forceinline__ uint32_t positive_lanes_i16(uint32_t w) {    // 0xFFFF per half whose int16 is > 0
   const i16x2_t z = {0, 0}, one = {1, 1}, full = {-1, -1};
@@ -126,12 +101,6 @@ __device__ __forceinline__ float gelu_grad_erf(float u) {
   const float e = __expf(-x * x);                         // exp(-u^2 / 2)
   const float erf_abs = 1.0f - p * t * e;
   return fmaf(u * 0.3989422804014327f, e, 0.5f * (1.0f + copysignf(erf_abs, u)));
-}
-__device__ __forceinline__ float bf2f(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
-__device__ __forceinline__ uint16_t f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  u += 0x7FFFu + ((u >> 16) & 1u);  // round to nearest even (inputs are finite)
-  return (uint16_t)(u >> 16);
 }
 
 // Per-thread row of the A tile for the buffer loads of k_conv_igemm_bf16: vo = byte offset of the row's pixel at tap (0, 0) inside a source

@@ -32,12 +32,11 @@
 // robustart_amd/model/resnet_torch.py) and its autograd inside every attack iteration, in fp32
 // (RobustART/noise/utils/adv/attack.py:20-23, Attacks/autoattack/autopgd_base.py:271-289).
 #include "rart_common.h"
+#include "rart_bf16_helpers.h"
 #include "rart_lds_dma.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
 namespace {
+using namespace rart_bf16;
 constexpr int CT_TM = 128;                       // positions per workgroup
 constexpr int CT_LDE = 68;                       // epilogue staging row (floats): 64 columns + 4
 constexpr int CT_PLANE_A = CT_TM * 64;           // one position plane of a stage: 128 rows x 64 B
@@ -87,30 +86,6 @@ __device__ __forceinline__ void ct_nt_store(uint16_t* p, const uint4& v) {
 }
 __device__ __forceinline__ uint32_t ct_fastdiv(uint32_t n, uint32_t magic, uint32_t shift) { return (uint32_t)(((uint64_t)n * magic) >> shift); }
 
-__device__ __forceinline__ uint32_t ct_pack_bf16x2(float lo, float hi) {   // round to nearest even (v_cvt_pk_bf16_f32)
-  typedef __attribute__((ext_vector_type(2))) float f2_t;
-  typedef __attribute__((ext_vector_type(2))) __bf16 b2_t;
-  f2_t f = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, b2_t));
-}
-__device__ __forceinline__ void ct_split8(const float* v, uint4& hi, uint4& lo) {
-  uint32_t h[4], l[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    h[j] = ct_pack_bf16x2(v[2 * j], v[2 * j + 1]);
-    l[j] = ct_pack_bf16x2(v[2 * j] - __uint_as_float(h[j] << 16), v[2 * j + 1] - __uint_as_float(h[j] & 0xFFFF0000u));
-  }
-  hi = make_uint4(h[0], h[1], h[2], h[3]);
-  lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
-__device__ __forceinline__ void ct_join8(const uint4& hi, const uint4& lo, float* v) {
-  const uint32_t h[4] = {hi.x, hi.y, hi.z, hi.w}, l[4] = {lo.x, lo.y, lo.z, lo.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    v[2 * j] = __uint_as_float(h[j] << 16) + __uint_as_float(l[j] << 16);
-    v[2 * j + 1] = __uint_as_float(h[j] & 0xFFFF0000u) + __uint_as_float(l[j] & 0xFFFF0000u);
-  }
-}
 // (element > 0) of the 8 bf16 values of a 16-byte chunk as one byte: a bf16 is > 0 exactly when its bits, read as int16, are > 0
 __device__ __forceinline__ uint32_t ct_sign_byte(const uint4& v) {
   const uint32_t hw[4] = {v.x, v.y, v.z, v.w};
@@ -144,10 +119,10 @@ __device__ __forceinline__ void ct_pointwise_frags(const f32x16* acc, const uint
           if (!((mw[j] >> (8 * ge + 4 * h + 2 * w + i)) & 1u)) ve[i] = 0.f;
           if (!((mw[j] >> (8 * ge + 8 + 4 * h + 2 * w + i)) & 1u)) vo[i] = 0.f;
         }
-        eh[w] = ct_pack_bf16x2(ve[0], ve[1]);
-        el[w] = ct_pack_bf16x2(ve[0] - __uint_as_float(eh[w] << 16), ve[1] - __uint_as_float(eh[w] & 0xFFFF0000u));
-        oh[w] = ct_pack_bf16x2(vo[0], vo[1]);
-        ol[w] = ct_pack_bf16x2(vo[0] - __uint_as_float(oh[w] << 16), vo[1] - __uint_as_float(oh[w] & 0xFFFF0000u));
+        eh[w] = pack_bf16x2(ve[0], ve[1]);
+        el[w] = pack_bf16x2(ve[0] - __uint_as_float(eh[w] << 16), ve[1] - __uint_as_float(eh[w] & 0xFFFF0000u));
+        oh[w] = pack_bf16x2(vo[0], vo[1]);
+        ol[w] = pack_bf16x2(vo[0] - __uint_as_float(oh[w] << 16), vo[1] - __uint_as_float(oh[w] & 0xFFFF0000u));
         const auto sh = __builtin_amdgcn_permlane32_swap(eh[w], oh[w], false, false);
         eh[w] = sh[0]; oh[w] = sh[1];
         const auto sl = __builtin_amdgcn_permlane32_swap(el[w], ol[w], false, false);
@@ -574,7 +549,7 @@ __global__ __launch_bounds__(256, (C == 64 && !NEXT && !XS && !SLAB) ? 3 : 2) vo
         float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
         if (d.res_hi) {
           float rv[8];
-          ct_join8(rh[q], rl[q], rv);
+          join8(rh[q], rl[q], rv);
 #pragma unroll
           for (int j = 0; j < 8; ++j) v[j] += rv[j];
         }
@@ -586,7 +561,7 @@ __global__ __launch_bounds__(256, (C == 64 && !NEXT && !XS && !SLAB) ? 3 : 2) vo
           for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
         }
         uint4 ph, pl;
-        ct_split8(v, ph, pl);
+        split8(v, ph, pl);
         ct_nt_store(d.dst_hi + e, ph);
         ct_nt_store(d.dst_lo + e, pl);
         if (d.sign_out) d.sign_out[e >> 3] = (uint8_t)ct_sign_byte(ph);

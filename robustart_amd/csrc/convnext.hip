@@ -21,19 +21,15 @@
 // Reference: timm's ConvNeXt block (conv_dw -> LayerNorm eps 1e-6 -> fc1 -> GELU -> fc2 -> gamma -> residual), restated in
 // robustart_amd/model/convnext_torch.py.
 #include "rart_common.h"
+#include "rart_bf16_helpers.h"
 
 namespace {
+using namespace rart_bf16;
 constexpr int kBlock = 256;
 constexpr int kRun = 4;                         // output pixels per thread item along a row
 constexpr int kVec = 4;                         // channels per thread item (8-byte loads per plane)
 constexpr int kMaxRowElems = 16384;             // w * c of the LDS row (64 KB fp32)
 
-__device__ __forceinline__ float bf2f(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
-__device__ __forceinline__ uint16_t f2bf(float f) {       // round to nearest even
-  uint32_t u = __float_as_uint(f);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
 template <bool PAIR>
 __device__ __forceinline__ float ldv(const uint16_t* __restrict__ h, const uint16_t* __restrict__ l, size_t i) {
   const float v = bf2f(h[i]);

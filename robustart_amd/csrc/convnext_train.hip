@@ -21,8 +21,10 @@
 // Reference: torch autograd through timm's ConvNeXt block (conv_dw, LayerNorm, fc1, GELU, fc2, gamma, residual), restated in
 // robustart_amd/model/convnext_torch.py; the adversarial-training configs exprs/nips_benchmark/{pgd,new}_adv_train/convnext_base.
 #include "rart_common.h"
+#include "rart_bf16_helpers.h"
 
 namespace {
+using namespace rart_bf16;
 constexpr int kBlock = 256;
 constexpr int kSlice = 32;                      // channels per workgroup of the depthwise weight gradient
 constexpr int kTaps = 49;
@@ -30,13 +32,6 @@ constexpr int kDwRows = kTaps + 1;              // partial rows per workgroup: 4
 constexpr int kStripRows = 14;                  // output rows per strip (at most)
 constexpr int kMaxW = 128;                      // LDS window: (7 * (w + 6) + w) * 32 * 2 bytes = 68 KB at w = 128
 constexpr int kTargetWgs = 1024;
-
-__device__ __forceinline__ float bf2f(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
-__device__ __forceinline__ uint16_t f2bf(float f) {       // round to nearest even
-  uint32_t u = __float_as_uint(f);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
 
 struct DwGeom {
   int strip_rows, strips, imgs_per_wg, groups, slices;

@@ -22,49 +22,17 @@
 // partials to a workspace ([n][2][c] fp32), and k_grn_param_fold adds them over the images in a fixed order.  `a` keeps the bits of
 // rart_cnx_grn_bwd_reduce_bf16 (same FMAs, same order), so rart_cnx_grn_bwd_apply_bf16 consumes it unchanged.
 // Reference: timm's GlobalResponseNorm (channels-last) inside GlobalResponseNormMlp, restated in robustart_amd/model/convnext_torch.py.
-#include "rart_gemm_pair_dev.h"
+#include "rart_bf16_helpers.h"
+#include "rart_gemm_pair_dev.h"   // gp_gelu_grad
 
 namespace {
+using namespace rart_bf16;
 constexpr int kBlock = 256;
 constexpr int kSliceLanes = 16;                         // lanes across channels in the reductions: 16 x 8 = 128 channels
 constexpr int kSlice = kSliceLanes * 8;
 constexpr int kRows = kBlock / kSliceLanes;             // pixel rows per pass
 constexpr int kMaxC = 4096;                             // per-channel factors in LDS: 2 x C x 4 bytes <= 32 KB
 constexpr int kTileElems = 32768;                       // elements per workgroup of the per-pixel kernels
-
-// eight consecutive channels of one pixel: one 16-byte load per plane
-template <bool PAIR>
-__device__ __forceinline__ void ld8(const uint16_t* h, const uint16_t* l, size_t i, float* v) {
-  const uint4 a = *reinterpret_cast<const uint4*>(h + i);
-  const uint32_t aw[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    v[2 * j] = __uint_as_float(aw[j] << 16);
-    v[2 * j + 1] = __uint_as_float(aw[j] & 0xFFFF0000u);
-  }
-  if (PAIR) {
-    const uint4 b = *reinterpret_cast<const uint4*>(l + i);
-    const uint32_t bw[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[2 * j] += __uint_as_float(bw[j] << 16);
-      v[2 * j + 1] += __uint_as_float(bw[j] & 0xFFFF0000u);
-    }
-  }
-}
-// eight values -> bf16 (round to nearest even), or hi + lo planes
-template <bool PAIR>
-__device__ __forceinline__ void st8(uint16_t* h, uint16_t* l, size_t i, const float* v) {
-  if (PAIR) {
-    uint4 hi, lo;
-    gp_split8(v, hi, lo);
-    *reinterpret_cast<uint4*>(h + i) = hi;
-    *reinterpret_cast<uint4*>(l + i) = lo;
-  } else {
-    *reinterpret_cast<uint4*>(h + i) = make_uint4(gp_pack_bf16x2(v[0], v[1]), gp_pack_bf16x2(v[2], v[3]), gp_pack_bf16x2(v[4], v[5]),
-                                                  gp_pack_bf16x2(v[6], v[7]));
-  }
-}
 
 // sum of one value per thread over the workgroup, the same fixed order in every workgroup; s_red: kBlock / 64 floats
 __device__ __forceinline__ float block_sum(float v, float* s_red) {

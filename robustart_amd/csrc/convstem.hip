@@ -20,44 +20,17 @@
 //                           the 2 x 2 pixel block of one patch position and sums, in a fixed order, the one, two or four patch entries that
 //                           cover each pixel; no atomics, every pixel written once.
 // GELU is the erfc form of the pair GEMM's epilogue (rart_gemm_pair_dev.h: |error| 3.8e-7 in fp32) in both precisions.
-#include "rart_gemm_pair_dev.h"
+#include "rart_bf16_helpers.h"
+#include "rart_gemm_pair_dev.h"   // gp_gelu, gp_gelu_grad
 
 namespace {
+using namespace rart_bf16;
 constexpr int kBlock = 256;
 
 struct Norm3 {
   float mean[3], istd[3];
 };
 
-__device__ __forceinline__ float cs_bf(uint32_t w, int half) { return __uint_as_float(half ? (w & 0xFFFF0000u) : (w << 16)); }
-
-// eight consecutive elements of a bf16 row (or of a pair: hi + lo), one 16-byte load per plane
-template <bool PAIR>
-__device__ __forceinline__ void cs_ld8(const uint16_t* __restrict__ h, const uint16_t* __restrict__ l, size_t i, float* v) {
-  const uint4 a = *reinterpret_cast<const uint4*>(h + i);
-  const uint32_t aw[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    v[2 * j] = cs_bf(aw[j], 0);
-    v[2 * j + 1] = cs_bf(aw[j], 1);
-  }
-  if (PAIR) {
-    const uint4 b = *reinterpret_cast<const uint4*>(l + i);
-    const uint32_t bw[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[2 * j] += cs_bf(bw[j], 0);
-      v[2 * j + 1] += cs_bf(bw[j], 1);
-    }
-  }
-}
-template <bool PAIR>
-__device__ __forceinline__ void cs_st8(uint16_t* __restrict__ h, uint16_t* __restrict__ l, size_t i, const float* v) {
-  uint4 hi, lo;
-  gp_split8(v, hi, lo);
-  *reinterpret_cast<uint4*>(h + i) = hi;
-  if (PAIR) *reinterpret_cast<uint4*>(l + i) = lo;
-}
 template <bool PAIR>
 __device__ __forceinline__ void cs_zero8(uint16_t* __restrict__ h, uint16_t* __restrict__ l, size_t i) {
   *reinterpret_cast<uint4*>(h + i) = make_uint4(0, 0, 0, 0);
@@ -98,7 +71,7 @@ __global__ __launch_bounds__(kBlock) void k_ln_gelu(const uint16_t* __restrict__
     for (int c = 0; c < NCH; ++c) {
       const int q = c * LPR + sub;
       if (live && q < n8) {
-        cs_ld8<PAIR>(xh, xl, (size_t)(r * ld_x) + (size_t)q * 8, v[c]);
+        ld8<PAIR>(xh, xl, (size_t)(r * ld_x) + (size_t)q * 8, v[c]);
       } else {
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[c][j] = 0.f;
@@ -129,7 +102,7 @@ __global__ __launch_bounds__(kBlock) void k_ln_gelu(const uint16_t* __restrict__
           cs_ldf8(b + q * 8, bv);
 #pragma unroll
           for (int j = 0; j < 8; ++j) y[j] = gp_gelu(fmaf(v[c][j] * rstd, gv[j], bv[j]));
-          cs_st8<PAIR>(oh, ol, (size_t)(r * ld_out) + (size_t)q * 8, y);
+          st8<PAIR>(oh, ol, (size_t)(r * ld_out) + (size_t)q * 8, y);
         }
       }
     } else {
@@ -143,7 +116,7 @@ __global__ __launch_bounds__(kBlock) void k_ln_gelu(const uint16_t* __restrict__
           float gv[8], bv[8], dy[8];
           cs_ldf8(g + q * 8, gv);
           cs_ldf8(b + q * 8, bv);
-          cs_ld8<PAIR>(dyh, dyl, (size_t)(r * ld_dy) + (size_t)q * 8, dy);
+          ld8<PAIR>(dyh, dyl, (size_t)(r * ld_dy) + (size_t)q * 8, dy);
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
             const float xhat = v[c][j] * rstd;
@@ -165,7 +138,7 @@ __global__ __launch_bounds__(kBlock) void k_ln_gelu(const uint16_t* __restrict__
           float y[8];
 #pragma unroll
           for (int j = 0; j < 8; ++j) y[j] = rstd * (dh[c][j] - m1 - v[c][j] * m2);
-          cs_st8<PAIR>(oh, ol, (size_t)(r * ld_out) + (size_t)q * 8, y);
+          st8<PAIR>(oh, ol, (size_t)(r * ld_out) + (size_t)q * 8, y);
         }
       }
     }
@@ -233,7 +206,7 @@ __global__ __launch_bounds__(kBlock) void k_cvst_im2col(const void* __restrict__
       }
     }
     uint4 hv, lv;
-    gp_split8(v, hv, lv);
+    split8(v, hv, lv);
     reinterpret_cast<uint4*>(hi)[i] = hv;
     if (lo) reinterpret_cast<uint4*>(lo)[i] = lv;
   }

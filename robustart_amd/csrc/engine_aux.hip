@@ -4,32 +4,11 @@
 // fp32 image) and an fp32 -> padded bf16 row converter.  All HBM-bound elementwise/gather work on
 // NHWC bf16 tensors, 16-byte (8-channel) vectors per lane.
 #include "rart_common.h"
+#include "rart_bf16_helpers.h"
 
 namespace {
+using namespace rart_bf16;
 constexpr int kBlock = 256;
-
-__device__ __forceinline__ float bf2f(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
-__device__ __forceinline__ uint16_t f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-__device__ __forceinline__ void unpack8(const uint4 v, float* f) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    f[2 * j] = bf2f((uint16_t)(w[j] & 0xFFFF));
-    f[2 * j + 1] = bf2f((uint16_t)(w[j] >> 16));
-  }
-}
-__device__ __forceinline__ uint4 pack8(const float* f) {
-  uint4 o;
-  o.x = f2bf(f[0]) | ((uint32_t)f2bf(f[1]) << 16);
-  o.y = f2bf(f[2]) | ((uint32_t)f2bf(f[3]) << 16);
-  o.z = f2bf(f[4]) | ((uint32_t)f2bf(f[5]) << 16);
-  o.w = f2bf(f[6]) | ((uint32_t)f2bf(f[7]) << 16);
-  return o;
-}
 
 struct Norm3 {
   float mean[3], istd[3];
@@ -273,8 +252,6 @@ int grid_for(size_t items) { return rart_grid_for(items, kBlock, 256 * 16); }
 // 1 GFLOP).  Here a workgroup owns ONE 32 x 32 output tile (8 x 32 = 256 of them for the head) and its four waves split K; the operands
 // are used once per workgroup, so the MFMA fragments come straight from global memory (A is 1 MB, W 4 MB: L2 resident), 16 bytes per
 // lane, and the four partial tiles are summed through LDS in a fixed order.
-typedef __attribute__((ext_vector_type(8))) __bf16 sm_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float sm_f32x16;
 __global__ __launch_bounds__(kBlock) void k_gemm_small_m(const uint16_t* __restrict__ a, int lda, const uint16_t* __restrict__ wgt, int ldw,
                                                          const float* __restrict__ bias, void* __restrict__ out, int ldo, int out_f32,
                                                          int M, int N, int K) {
@@ -285,12 +262,12 @@ __global__ __launch_bounds__(kBlock) void k_gemm_small_m(const uint16_t* __restr
   const int kq = K / 4;                                                        // host: K % 64 == 0
   const uint16_t* pa = a + (size_t)row_a * lda + wave * kq + hh * 8;
   const uint16_t* pw = wgt + (size_t)row_w * ldw + wave * kq + hh * 8;
-  sm_f32x16 acc;
+  f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   for (int k = 0; k < kq; k += 16) {
     const uint4 av = *reinterpret_cast<const uint4*>(pa + k), wv = *reinterpret_cast<const uint4*>(pw + k);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(sm_bf16x8, av), __builtin_bit_cast(sm_bf16x8, wv), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av), __builtin_bit_cast(bf16x8, wv), acc, 0, 0, 0);
   }
   // acc[r] = partial C[m0 + (r&3) + 8*(r>>2) + 4*hh][n0 + l31]
 #pragma unroll

@@ -8,16 +8,12 @@
 // hi + lo is exact in fp32 (two 8-bit significands, |lo| <= half an ulp of hi), so every kernel unpacks to fp32,
 // computes as the bf16 kernels of engine_aux.hip do, and splits again.
 #include "rart_common.h"
+#include "rart_bf16_helpers.h"
 
 namespace {
+using namespace rart_bf16;
 constexpr int kBlock = 256;
 
-__device__ __forceinline__ float bf2f(uint32_t v16) { return __uint_as_float(v16 << 16); }
-__device__ __forceinline__ uint32_t f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  u += 0x7FFFu + ((u >> 16) & 1u);   // round to nearest even (finite inputs)
-  return u >> 16;
-}
 // value = hi + lo of the 8 channels of one 16-byte vector per plane; lo_off in uint4 units
 __device__ __forceinline__ void load_pair8(const uint4* __restrict__ hi, size_t lo_off, size_t i, float* f) {
   const uint4 a = hi[i], b = hi[i + lo_off];

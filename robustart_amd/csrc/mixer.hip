@@ -21,9 +21,11 @@
 // value rounded to the stored u, so a forward-only run and the kept forward agree), GELU with u kept in aux, or x GELU'(aux);
 // bf16 / pair or fp32 output.
 #include "rart_common.h"
-#include "rart_gemm_pair_dev.h"
+#include "rart_bf16_helpers.h"
+#include "rart_gemm_pair_dev.h"   // gp_gelu, gp_gelu_grad
 
 namespace {
+using namespace rart_bf16;
 typedef __attribute__((ext_vector_type(4))) short tm_s16x4;
 typedef __attribute__((ext_vector_type(8))) short tm_s16x8;
 
@@ -60,9 +62,8 @@ __device__ __forceinline__ bf16x8 tm_x_frag(const uint8_t* tile, int k0, int col
 __device__ __forceinline__ bf16x8 tm_a_frag(const uint8_t* tile, int row, int c) {
   return *reinterpret_cast<const bf16x8*>(tile + row * 64 + 16 * (c ^ ((row >> 2) & 3)));
 }
-__device__ __forceinline__ float tm_bf(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
-__device__ __forceinline__ uint16_t tm_rne(float v) {           // round to nearest even, the hardware conversion of gp_pack_bf16x2
-  return (uint16_t)(gp_pack_bf16x2(v, 0.f) & 0xFFFFu);
+__device__ __forceinline__ uint16_t tm_rne(float v) {           // round to nearest even, the hardware conversion of pack_bf16x2
+  return (uint16_t)(pack_bf16x2(v, 0.f) & 0xFFFFu);
 }
 
 template <bool PAIR>
@@ -169,23 +170,23 @@ __global__ __launch_bounds__(256) void k_tokmix(const TokmixDev d) {
         const long long e = coff + (long long)row * d.ldc + col;
         float v = acc[i][j][r];
         if (d.bias) v += d.bias[row];
-        if (d.res_hi) v += PAIR ? tm_bf(d.res_hi[e]) + tm_bf(d.res_lo[e]) : tm_bf(d.res_hi[e]);
+        if (d.res_hi) v += PAIR ? bf2f(d.res_hi[e]) + bf2f(d.res_lo[e]) : bf2f(d.res_hi[e]);
         if (flags & (TM_GELU | TM_GELU_KEEP)) {
           const uint16_t uh = tm_rne(v);
-          const uint16_t ul = PAIR ? tm_rne(v - tm_bf(uh)) : 0;
+          const uint16_t ul = PAIR ? tm_rne(v - bf2f(uh)) : 0;
           if (flags & TM_GELU_KEEP) {
             d.aux_hi[e] = uh;
             if (PAIR) d.aux_lo[e] = ul;
           }
-          v = gp_gelu(PAIR ? tm_bf(uh) + tm_bf(ul) : tm_bf(uh));
+          v = gp_gelu(PAIR ? bf2f(uh) + bf2f(ul) : bf2f(uh));
         }
-        if (flags & TM_GELU_BWD) v *= gp_gelu_grad(PAIR ? tm_bf(d.aux_hi[e]) + tm_bf(d.aux_lo[e]) : tm_bf(d.aux_hi[e]));
+        if (flags & TM_GELU_BWD) v *= gp_gelu_grad(PAIR ? bf2f(d.aux_hi[e]) + bf2f(d.aux_lo[e]) : bf2f(d.aux_hi[e]));
         if (flags & TM_OUT_F32) {
           reinterpret_cast<float*>(d.dst_hi)[e] = v;
         } else {
           const uint16_t oh = tm_rne(v);
           d.dst_hi[e] = oh;
-          if (PAIR) d.dst_lo[e] = tm_rne(v - tm_bf(oh));
+          if (PAIR) d.dst_lo[e] = tm_rne(v - bf2f(oh));
         }
       }
     }

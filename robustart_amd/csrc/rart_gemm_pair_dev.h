@@ -1,14 +1,13 @@
 // Device-side pieces shared by the split-bf16 ("fp32x") GEMM kernels: csrc/gemm_pair.hip (k_gemm_pair) and csrc/conv3x3_res_pair.hip
-// (k_conv3x3_res_pair, the 3x3 convolution with the input chunk resident in LDS): the device descriptor, the hi + lo helpers and the
+// (k_conv3x3_res_pair, the 3x3 convolution with the input chunk resident in LDS): the device descriptor, the GELU forms and the
 // epilogue (per wave, 32 rows x 64 columns at a time through LDS: bias is already in the accumulators; residual PAIR, GELU forms, 1-bit
 // masks and sign bits, ReLU, then hi / lo as two coalesced 16-byte stores, or fp32).  Moved out of gemm_pair.hip in round 5, unchanged.
 #pragma once
 #include "rart_common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
+#include "rart_bf16_helpers.h"
 
 namespace {
+using namespace rart_bf16;
 enum { GP_OUT_F32 = 2, GP_GELU = 4, GP_GELU_BWD = 8, GP_GELU_KEEP = 64, GP_RELU = 1, GP_W_INTERLEAVED = 16 };
 constexpr int GP_BK = 32;
 constexpr int GP_LDE = 68;                         // epilogue staging row (floats): 64 columns + 4
@@ -46,13 +45,6 @@ struct GemmPairDev {
 __device__ __forceinline__ uint32_t gp_fastdiv(uint32_t n, uint32_t magic, uint32_t shift) {
   return (uint32_t)(((uint64_t)n * magic) >> shift);
 }
-
-__device__ __forceinline__ uint32_t gp_pack_bf16x2(float lo, float hi) {   // round to nearest even (v_cvt_pk_bf16_f32)
-  typedef __attribute__((ext_vector_type(2))) float f2_t;
-  typedef __attribute__((ext_vector_type(2))) __bf16 b2_t;
-  f2_t f = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, b2_t));
-}
 // exact (erf) GELU, timm's nn.GELU default, at fp32 accuracy without libm's erff.  Round 6: the per-workgroup trace of the ping-pong
 // kernel (scratch/r6/vit_pp_trace.py) put the epilogue of ViT's fc1 tiles at 50 k cycles (forward, GELU) and 74 k (backward, GELU') against
 // 15 k for a plain tile and 95 k for the whole K loop -- erff (and expf) of libm are ~45 instructions with divergent range branches, 128
@@ -84,16 +76,6 @@ __device__ __forceinline__ float gp_gelu_grad(float u) {
   const float hc = gp_half_erfc_abs(u, e);
   return fmaf(u * 0.3989422804014327f, e, u < 0.f ? hc : 1.0f - hc);
 }
-__device__ __forceinline__ void gp_split8(const float* v, uint4& hi, uint4& lo) {
-  uint32_t h[4], l[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    h[j] = gp_pack_bf16x2(v[2 * j], v[2 * j + 1]);
-    l[j] = gp_pack_bf16x2(v[2 * j] - __uint_as_float(h[j] << 16), v[2 * j + 1] - __uint_as_float(h[j] & 0xFFFF0000u));
-  }
-  hi = make_uint4(h[0], h[1], h[2], h[3]);
-  lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
 // Round 6: the epilogue's residual / pre-activation loads and its pair stores are NON-TEMPORAL accesses (streams of 100-800 MB per launch that
 // the producing kernel never touches again and that do not fit the 4 MB L2 of an XCD): reference-precision ResNet-50 gradient evaluation
 // 19.50 -> 19.13 ms, ViT-B/16 65.73 -> 65.09 ms (same-box A/B of lab builds, together with the tail kernel's streams).
@@ -106,15 +88,6 @@ __device__ __forceinline__ void gp_nt_store(uint16_t* p, const uint4& v) {
   gp_u4 w = {v.x, v.y, v.z, v.w};
   __builtin_nontemporal_store(w, reinterpret_cast<gp_u4*>(p));
 }
-// hi + lo is exact in fp32 (two 8-bit significands, lo below half an ulp of hi)
-__device__ __forceinline__ void gp_join8(const uint4& hi, const uint4& lo, float* v) {
-  const uint32_t h[4] = {hi.x, hi.y, hi.z, hi.w}, l[4] = {lo.x, lo.y, lo.z, lo.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    v[2 * j] = __uint_as_float(h[j] << 16) + __uint_as_float(l[j] << 16);
-    v[2 * j + 1] = __uint_as_float(h[j] & 0xFFFF0000u) + __uint_as_float(l[j] & 0xFFFF0000u);
-  }
-}
 
 
 // The point-wise tail of one 8-column row segment (element offset e, CONV or plain): v = the fp32 accumulator values of the segment; residual
@@ -125,14 +98,14 @@ __device__ __forceinline__ void gp_finish_segment(const GemmPairDev& d, int flag
                                             const uint4& rl_q, const uint4& uh_q, const uint4& ul_q, uint32_t mb_q) {
   if (d.res_hi) {
     float rv[8];
-    gp_join8(rh_q, rl_q, rv);
+    join8(rh_q, rl_q, rv);
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] += rv[j];
   }
   if (GELU && (flags & GP_GELU)) {     // gelu of the value the PAIR of the pre-activation represents: the same result as GELU_KEEP's, so a forward-only
     uint4 ph, pl;            // evaluation and the forward of a gradient evaluation agree bit for bit
-    gp_split8(v, ph, pl);
-    gp_join8(ph, pl, v);
+    split8(v, ph, pl);
+    join8(ph, pl, v);
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = gp_gelu(v[j]);
   }
@@ -140,16 +113,16 @@ __device__ __forceinline__ void gp_finish_segment(const GemmPairDev& d, int flag
     // two outputs: the pre-activation pair u goes to `aux` (the backward's GELU' operand); dst receives gelu of the value the
     // pair REPRESENTS, so forward and backward see the same u
     uint4 ph, pl;
-    gp_split8(v, ph, pl);
+    split8(v, ph, pl);
     gp_nt_store(d.aux_hi + e, ph);
     gp_nt_store(d.aux_lo + e, pl);
-    gp_join8(ph, pl, v);
+    join8(ph, pl, v);
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = gp_gelu(v[j]);
   }
   if (GELU && (flags & GP_GELU_BWD)) {
     float u[8];
-    gp_join8(uh_q, ul_q, u);
+    join8(uh_q, ul_q, u);
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] *= gp_gelu_grad(u[j]);
   }
@@ -168,7 +141,7 @@ __device__ __forceinline__ void gp_finish_segment(const GemmPairDev& d, int flag
     *reinterpret_cast<float4*>(o + 4) = make_float4(v[4], v[5], v[6], v[7]);
   } else {
     uint4 ph, pl;
-    gp_split8(v, ph, pl);
+    split8(v, ph, pl);
     if (d.nt) {
       gp_nt_store(d.dst_hi + e, ph);
       gp_nt_store(d.dst_lo + e, pl);

@@ -18,11 +18,10 @@
 // global memory, one tap row (8 fragments) ahead.  Epilogue: the 16 x 16 x 12 results are transposed through LDS to
 // [c][32][32] and leave as 128-byte rows of the NCHW fp32 gradient, scaled by 1/std[c].
 #include "rart_common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+#include "rart_bf16_helpers.h"
 
 namespace {
+using namespace rart_bf16;
 constexpr int T = 16;                     // positions per tile side
 constexpr int HT = T + 3;                 // halo tile side (dp, dq in -1..2)
 constexpr int NPOS_PAD = 368;             // multiple of 16: chunk planes start on a 256-byte bank row
@@ -30,14 +29,6 @@ constexpr int PT = T / 2 + 3;             // pooled positions per side that reac
 constexpr int NPOOL = PT * PT;            // 121
 constexpr int OT = 2 * T;                 // image pixels per tile side (32)
 constexpr int OLD = OT + 1;               // padded fp32 output row in LDS
-
-__device__ __forceinline__ float bf2f(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) {
-  typedef __attribute__((ext_vector_type(2))) float f2;
-  typedef __attribute__((ext_vector_type(2))) __bf16 b2;
-  f2 f = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, b2));
-}
 
 
 // the halo positions whose stem row has parity EY and whose stem column has parity EX (tile origins are multiples of 16, so
@@ -83,7 +74,7 @@ __device__ __forceinline__ void pool_bwd_class(uint4* sDz1, const uint4* sDp, co
         }
       }
     }
-    sDz1[c * NPOS_PAD + hy * HT + hx] = make_uint4(pack2(g[0], g[1]), pack2(g[2], g[3]), pack2(g[4], g[5]), pack2(g[6], g[7]));
+    sDz1[c * NPOS_PAD + hy * HT + hx] = make_uint4(pack_bf16x2(g[0], g[1]), pack_bf16x2(g[2], g[3]), pack_bf16x2(g[4], g[5]), pack_bf16x2(g[6], g[7]));
   }
 }
 
@@ -218,7 +209,6 @@ extern "C" int rart_engine_stem_bwd_fused(const void* dpool, const void* argmax,
 // with 8-byte writes; the pool reads 16-byte channel groups from it and writes p1, the argmax codes and the sign bits.
 // =====================================================================================================================
 namespace {
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 constexpr int SF_PT = 8;                        // pooled tile side
 constexpr int SF_R = 2 * SF_PT + 1;             // stem-output region side (17)
 constexpr int SF_NPOS = SF_R * SF_R;            // 289
@@ -234,12 +224,6 @@ static_assert(SF_T_BYTES >= 2 * SF_PLANE, "the stem-output tile must cover the p
 struct StemNorm { float mean[3], istd[3]; };
 // the normalisation must round exactly like k_prep_input (engine_aux.hip): multiply, subtract, multiply -- no contraction
 #pragma clang fp contract(off)
-
-__device__ __forceinline__ uint16_t sf_f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
 
 template <bool SRC_U8>
 __global__ __launch_bounds__(256, 2) void k_stem_fwd_fused(const void* __restrict__ src, const uint16_t* __restrict__ wgt,
@@ -313,8 +297,8 @@ __global__ __launch_bounds__(256, 2) void k_stem_fwd_fused(const void* __restric
           for (int c = 0; c < 3; ++c) {
             const float x01 = SRC_U8 ? v01[u][c] * (1.0f / 255.0f) : v01[u][c];
             const float v = (x01 - nm.mean[c]) * nm.istd[c];
-            hv[c] = sf_f2bf(v);
-            lv[c] = sf_f2bf(v - __uint_as_float((uint32_t)hv[c] << 16));
+            hv[c] = f2bf(v);
+            lv[c] = f2bf(v - __uint_as_float((uint32_t)hv[c] << 16));
           }
         }
         *reinterpret_cast<uint2*>(sP + i * 8) = make_uint2(hv[0] | ((uint32_t)hv[1] << 16), hv[2]);
@@ -349,8 +333,8 @@ __global__ __launch_bounds__(256, 2) void k_stem_fwd_fused(const void* __restric
       if (p < SF_NPOS) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const uint32_t lo2 = pack2(fmaxf(acc[i][4 * q], 0.f), fmaxf(acc[i][4 * q + 1], 0.f));
-          const uint32_t hi2 = pack2(fmaxf(acc[i][4 * q + 2], 0.f), fmaxf(acc[i][4 * q + 3], 0.f));
+          const uint32_t lo2 = pack_bf16x2(fmaxf(acc[i][4 * q], 0.f), fmaxf(acc[i][4 * q + 1], 0.f));
+          const uint32_t hi2 = pack_bf16x2(fmaxf(acc[i][4 * q + 2], 0.f), fmaxf(acc[i][4 * q + 3], 0.f));
           *reinterpret_cast<uint2*>(sP + p * SF_YROW + (wn * 32 + 8 * q + 4 * kq) * 2) = make_uint2(lo2, hi2);
         }
       }
@@ -382,7 +366,7 @@ __global__ __launch_bounds__(256, 2) void k_stem_fwd_fused(const void* __restric
         }
       }
       const size_t o = (((size_t)img * oh2 + gy) * ow2 + gx) * 8 + c;
-      p1[o] = make_uint4(pack2(m[0], m[1]), pack2(m[2], m[3]), pack2(m[4], m[5]), pack2(m[6], m[7]));
+      p1[o] = make_uint4(pack_bf16x2(m[0], m[1]), pack_bf16x2(m[2], m[3]), pack_bf16x2(m[4], m[5]), pack_bf16x2(m[6], m[7]));
       uint32_t sb = 0;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {

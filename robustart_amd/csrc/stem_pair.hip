@@ -18,11 +18,9 @@
 // Attacks/autoattack/autopgd_base.py:271-289, fp32) through conv1 / bn1 / relu / maxpool of the public ResNet-50
 // (RobustART/model/__init__.py:1 -> absent submodule; robustart_amd/model/resnet_torch.py states it).
 #include "rart_common.h"
+#include "rart_bf16_helpers.h"
 
 #include <type_traits>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 // Lab builds only: -DRART_STEM_STAMPS sums s_memtime intervals per phase and wave into g_sp_stamps ([0] backward: stage, pool backward,
 // weights + taps, epilogue, whole kernel, waves; [1] forward: stage, row taps, barrier after them, ReLU + tile store, pool + global store,
@@ -41,6 +39,7 @@ __device__ unsigned long long g_sp_stamps[2][8];
 #endif
 
 namespace {
+using namespace rart_bf16;
 constexpr int T = 16;                     // positions per tile side
 constexpr int HT = T + 3;                 // halo tile side (dp, dq in -1..2)
 constexpr int NPOS_PAD = 368;             // 361 rounded up to a multiple of 16: chunk planes start on a 256-byte bank row
@@ -61,13 +60,6 @@ constexpr int W_BYTES = 2 * 16 * 64 * 16;             // the weight fragments of
 constexpr int RW_BYTES = W_BYTES;                     // one region: raw pooled tile, then the half's weights, at the end the output tile
 static_assert(DP_BYTES + ARG_BYTES <= RW_BYTES && 3 * OPL * 4 <= RW_BYTES, "raw pooled tile and output tile must fit the weight region");
 static_assert(2 * (DZ_BYTES + RW_BYTES) <= 160 * 1024, "two workgroups per CU");
-
-__device__ __forceinline__ uint32_t sp_pack2(float lo, float hi) {
-  typedef __attribute__((ext_vector_type(2))) float f2;
-  typedef __attribute__((ext_vector_type(2))) __bf16 b2;
-  f2 f = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, b2));
-}
 
 // the halo positions whose stem row has parity EY and whose stem column has parity EX (see pool_bwd_class in stem_fused.hip): one
 // window per even coordinate, two per odd; the gradient of a position is the fp32 sum of the pair VALUES of its matching windows
@@ -118,8 +110,8 @@ __device__ __forceinline__ void pool_bwd_class_pair(uint4* sDz1, const uint4* sD
     uint32_t hv[4], lv[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      hv[k] = sp_pack2(g[2 * k], g[2 * k + 1]);
-      lv[k] = sp_pack2(g[2 * k] - __uint_as_float(hv[k] << 16), g[2 * k + 1] - __uint_as_float(hv[k] & 0xFFFF0000u));
+      hv[k] = pack_bf16x2(g[2 * k], g[2 * k + 1]);
+      lv[k] = pack_bf16x2(g[2 * k] - __uint_as_float(hv[k] << 16), g[2 * k + 1] - __uint_as_float(hv[k] & 0xFFFF0000u));
     }
     sDz1[c * NPOS_PAD + hy * HT + hx] = make_uint4(hv[0], hv[1], hv[2], hv[3]);
     sDz1[(4 + c) * NPOS_PAD + hy * HT + hx] = make_uint4(lv[0], lv[1], lv[2], lv[3]);
@@ -316,7 +308,6 @@ extern "C" int rart_engine_stem_bwd_fused_pair(const void* dpool_hi, const void*
 // thread mapping (one position x 8 channels per thread) for ReLU, the hi / lo split and 16-byte stores.  156 432 B of LDS.
 // =====================================================================================================================
 namespace {
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 constexpr int SP_PT = 8;                        // pooled tile side
 constexpr int SP_R = 2 * SP_PT + 1;             // stem-output region side (17)
 constexpr int SP_NPOS = SP_R * SP_R;            // 289
@@ -456,8 +447,8 @@ __global__ __launch_bounds__(512, 1) void k_stem_fwd_pair(const void* __restrict
         for (int c = 0; c < 3; ++c) {
           const float x01 = SRC_U8 ? v01[u][c] * (1.0f / 255.0f) : v01[u][c];
           const float v = (x01 - nm.mean[c]) * nm.istd[c];
-          hv[c] = sp_pack2(v, 0.f) & 0xFFFFu;
-          lv[c] = sp_pack2(v - __uint_as_float(hv[c] << 16), 0.f) & 0xFFFFu;
+          hv[c] = pack_bf16x2(v, 0.f) & 0xFFFFu;
+          lv[c] = pack_bf16x2(v - __uint_as_float(hv[c] << 16), 0.f) & 0xFFFFu;
         }
       }
       *reinterpret_cast<uint2*>(sP + po) = make_uint2(hv[0] | (hv[1] << 16), hv[2]);
@@ -504,9 +495,9 @@ __global__ __launch_bounds__(512, 1) void k_stem_fwd_pair(const void* __restrict
           float v[4];
 #pragma unroll
           for (int k = 0; k < 4; ++k) v[k] = fmaxf(acc[i][4 * q + k], 0.f);
-          const uint32_t h0 = sp_pack2(v[0], v[1]), h1 = sp_pack2(v[2], v[3]);
-          const uint32_t l0 = sp_pack2(v[0] - __uint_as_float(h0 << 16), v[1] - __uint_as_float(h0 & 0xFFFF0000u));
-          const uint32_t l1 = sp_pack2(v[2] - __uint_as_float(h1 << 16), v[3] - __uint_as_float(h1 & 0xFFFF0000u));
+          const uint32_t h0 = pack_bf16x2(v[0], v[1]), h1 = pack_bf16x2(v[2], v[3]);
+          const uint32_t l0 = pack_bf16x2(v[0] - __uint_as_float(h0 << 16), v[1] - __uint_as_float(h0 & 0xFFFF0000u));
+          const uint32_t l1 = pack_bf16x2(v[2] - __uint_as_float(h1 << 16), v[3] - __uint_as_float(h1 & 0xFFFF0000u));
           *reinterpret_cast<float4*>(sP + p * SP_YROW + (wn * 32 + 8 * q + 4 * kq) * 4) =
               make_float4(__uint_as_float(h0 << 16) + __uint_as_float(l0 << 16), __uint_as_float(h0 & 0xFFFF0000u) + __uint_as_float(l0 & 0xFFFF0000u),
                           __uint_as_float(h1 << 16) + __uint_as_float(l1 << 16), __uint_as_float(h1 & 0xFFFF0000u) + __uint_as_float(l1 & 0xFFFF0000u));
@@ -544,8 +535,8 @@ __global__ __launch_bounds__(512, 1) void k_stem_fwd_pair(const void* __restrict
         uint32_t hv[4], lv[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          hv[k] = sp_pack2(m[2 * k], m[2 * k + 1]);
-          lv[k] = sp_pack2(m[2 * k] - __uint_as_float(hv[k] << 16), m[2 * k + 1] - __uint_as_float(hv[k] & 0xFFFF0000u));
+          hv[k] = pack_bf16x2(m[2 * k], m[2 * k + 1]);
+          lv[k] = pack_bf16x2(m[2 * k] - __uint_as_float(hv[k] << 16), m[2 * k + 1] - __uint_as_float(hv[k] & 0xFFFF0000u));
         }
         p1_h[o] = make_uint4(hv[0], hv[1], hv[2], hv[3]);
         p1_l[o] = make_uint4(lv[0], lv[1], lv[2], lv[3]);
@@ -595,8 +586,8 @@ __global__ __launch_bounds__(512, 1) void k_stem_fwd_pair(const void* __restrict
           uint32_t hv[4], lv[4], sb = 0;
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            hv[k] = sp_pack2(f[2 * k], f[2 * k + 1]);
-            lv[k] = sp_pack2(f[2 * k] - __uint_as_float(hv[k] << 16), f[2 * k + 1] - __uint_as_float(hv[k] & 0xFFFF0000u));
+            hv[k] = pack_bf16x2(f[2 * k], f[2 * k + 1]);
+            lv[k] = pack_bf16x2(f[2 * k] - __uint_as_float(hv[k] << 16), f[2 * k + 1] - __uint_as_float(hv[k] & 0xFFFF0000u));
             sb |= ((short)(hv[k] & 0xFFFFu) > 0 ? 1u : 0u) << (2 * k);          // (hi plane > 0), as the pair GEMM's epilogue writes it
             sb |= ((short)(hv[k] >> 16) > 0 ? 1u : 0u) << (2 * k + 1);
           }

@@ -15,33 +15,13 @@
 // Reference arithmetic: torch.nn.BatchNorm2d / conv2d autograd (the reference trains with PyTorch:
 // cifar10/code/train.py:96-127; model RobustART/model/__init__.py:1 -> public ResNet-50).
 #include "rart_common.h"
+#include "rart_bf16_helpers.h"
 #include <cstdlib>
 
 namespace {
+using namespace rart_bf16;
 constexpr int kBlock = 256;
 
-__device__ __forceinline__ float bf2f(uint32_t v16) { return __uint_as_float(v16 << 16); }
-__device__ __forceinline__ uint32_t f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return u >> 16;
-}
-__device__ __forceinline__ void unpack8(const uint4& v, float* f) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    f[2 * j] = __uint_as_float(w[j] << 16);
-    f[2 * j + 1] = __uint_as_float(w[j] & 0xFFFF0000u);
-  }
-}
-__device__ __forceinline__ uint4 pack8(const float* f) {
-  uint4 o;
-  o.x = f2bf(f[0]) | (f2bf(f[1]) << 16);
-  o.y = f2bf(f[2]) | (f2bf(f[3]) << 16);
-  o.z = f2bf(f[4]) | (f2bf(f[5]) << 16);
-  o.w = f2bf(f[6]) | (f2bf(f[7]) << 16);
-  return o;
-}
 // 8 per-channel "keep" flags from a post-ReLU activation vector: bits > 0 as int16
 __device__ __forceinline__ void keep8(const uint4& v, bool* k) {
   const uint32_t w[4] = {v.x, v.y, v.z, v.w};

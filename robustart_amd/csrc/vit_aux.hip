@@ -4,15 +4,11 @@
 // -> absent submodule; `vit_base` = timm ViT-B/16 (jx_vit_base_p16_224): 12 blocks, width 768,
 // 12 heads, qkv bias, LayerNorm eps 1e-6, exact GELU.
 #include "rart_common.h"
+#include "rart_bf16_helpers.h"
 
 namespace {
+using namespace rart_bf16;
 constexpr int kBlock = 256;
-__device__ __forceinline__ float bf2f(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
-__device__ __forceinline__ uint16_t f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
 struct Norm3 {
   float mean[3], istd[3];
 };
@@ -75,28 +71,6 @@ __global__ __launch_bounds__(kBlock) void k_add_pos_cls(uint16_t* __restrict__ x
 
 // ---- row kernels: one wave per row, the row lives in registers as 16-byte vectors (lane l holds vectors l and l + 64),
 //      so every tensor is read exactly once with coalesced 16-byte loads.  Rows of up to 1024 elements, multiple of 8.
-__device__ __forceinline__ void unpack8(const uint4& v, float* f) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    f[2 * j] = __uint_as_float(w[j] << 16);
-    f[2 * j + 1] = __uint_as_float(w[j] & 0xFFFF0000u);
-  }
-}
-__device__ __forceinline__ uint4 pack8(const float* f) {
-  return make_uint4(f2bf(f[0]) | ((uint32_t)f2bf(f[1]) << 16), f2bf(f[2]) | ((uint32_t)f2bf(f[3]) << 16),
-                    f2bf(f[4]) | ((uint32_t)f2bf(f[5]) << 16), f2bf(f[6]) | ((uint32_t)f2bf(f[7]) << 16));
-}
-// loads the row's vectors v (< nv) into r[2][8] (zeros elsewhere)
-__device__ __forceinline__ void load_row(const uint16_t* row, int nv, int lane, float r[2][8]) {
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int v = lane + 64 * k;
-    uint4 q = make_uint4(0, 0, 0, 0);
-    if (v < nv) q = *reinterpret_cast<const uint4*>(row + (size_t)v * 8);
-    unpack8(q, r[k]);
-  }
-}
 
 // LayerNorm over the last dim, fp32 two-pass statistics.  (Round 5, scratch/r5/time_layernorm.py: 36.4 us per launch on [256 x 197][768] = 4.25 TB/s on
 // input + output; a wave walking eight rows with gamma / beta in registers and the next row prefetched was SLOWER, 49.2 us: one row per wave
@@ -214,16 +188,7 @@ int grid_for(size_t items) { return rart_grid_for(items, kBlock, 256 * 16); }
 // rescaling).  The normalised probabilities are packed to bf16 and fed straight back as the A operand of
 // O = P . V: the MFMA's k index is only a summation label, so instead of re-laying P through LDS the V operand
 // is read from LDS (stored transposed) in the key order the accumulator registers already have.
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 constexpr int ATT_HD = 64, ATT_LDK = ATT_HD + 8;
-
-__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {   // round to nearest even (v_cvt_pk_bf16_f32)
-  typedef __attribute__((ext_vector_type(2))) float f2_t;
-  typedef __attribute__((ext_vector_type(2))) __bf16 b2_t;
-  f2_t f = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, b2_t));
-}
 
 // Round 5 measured the launch alone (scratch/r5/time_attention.py, B = 256, 12 heads, 197 tokens).  One workgroup of 4 waves per (image, head), two
 // resident per CU: 122 us = 2.5 TB/s on q, k, v, out, 250 TFLOP/s -- the CU idle ~70 % of the launch between 75 KB staging phases; the interleaved

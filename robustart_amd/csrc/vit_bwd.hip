@@ -5,15 +5,11 @@
 // S = Q K^T) -- run on rart_conv_igemm_bf16 as batched problems; transposed operands come from
 // rart_transpose_gather_bf16 / rart_vit_transpose_v.  HBM-bound row / elementwise kernels, bf16 storage, fp32 math.
 #include "rart_common.h"
+#include "rart_bf16_helpers.h"
 
 namespace {
+using namespace rart_bf16;
 constexpr int kBlock = 256;
-__device__ __forceinline__ float bf2f(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
-__device__ __forceinline__ uint16_t f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
 __device__ __forceinline__ float gelu_f(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
 __device__ __forceinline__ float gelu_grad_f(float v) {
   // d/dv [v * Phi(v)] = Phi(v) + v * phi(v)
@@ -46,28 +42,6 @@ __global__ __launch_bounds__(kBlock) void k_gelu(const uint4* __restrict__ a, co
       o[j] = f2bf(r0) | ((uint32_t)f2bf(r1) << 16);
     }
     out[i] = make_uint4(o[0], o[1], o[2], o[3]);
-  }
-}
-
-__device__ __forceinline__ void unpack8(const uint4& v, float* f) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    f[2 * j] = __uint_as_float(w[j] << 16);
-    f[2 * j + 1] = __uint_as_float(w[j] & 0xFFFF0000u);
-  }
-}
-__device__ __forceinline__ uint4 pack8(const float* f) {
-  return make_uint4(f2bf(f[0]) | ((uint32_t)f2bf(f[1]) << 16), f2bf(f[2]) | ((uint32_t)f2bf(f[3]) << 16),
-                    f2bf(f[4]) | ((uint32_t)f2bf(f[5]) << 16), f2bf(f[6]) | ((uint32_t)f2bf(f[7]) << 16));
-}
-__device__ __forceinline__ void load_row(const uint16_t* row, int nv, int lane, float r[2][8]) {
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int v = lane + 64 * k;
-    uint4 q = make_uint4(0, 0, 0, 0);
-    if (v < nv) q = *reinterpret_cast<const uint4*>(row + (size_t)v * 8);
-    unpack8(q, r[k]);
   }
 }
 

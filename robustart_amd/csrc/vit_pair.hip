@@ -6,36 +6,14 @@
 // (exprs/exp/imagenet_c_loop_mini/config_vit_base.yaml:1-9: no precision key; adv/attack.py:20-23; autopgd_base.py:271-289); model
 // `vit_base` = timm ViT-B/16 (RobustART/model/__init__.py:1 -> absent submodule; robustart_amd/model/vit_torch.py).
 #include "rart_common.h"
+#include "rart_bf16_helpers.h"
 #include <stdlib.h>
 #include "rart_lds_dma.h"
 
 namespace {
+using namespace rart_bf16;
 constexpr int kBlock = 256;
 
-__device__ __forceinline__ uint32_t pk2(float lo, float hi) {   // round to nearest even (v_cvt_pk_bf16_f32)
-  typedef __attribute__((ext_vector_type(2))) float f2_t;
-  typedef __attribute__((ext_vector_type(2))) __bf16 b2_t;
-  f2_t f = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, b2_t));
-}
-__device__ __forceinline__ void split8(const float* v, uint4& hi, uint4& lo) {
-  uint32_t h[4], l[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    h[j] = pk2(v[2 * j], v[2 * j + 1]);
-    l[j] = pk2(v[2 * j] - __uint_as_float(h[j] << 16), v[2 * j + 1] - __uint_as_float(h[j] & 0xFFFF0000u));
-  }
-  hi = make_uint4(h[0], h[1], h[2], h[3]);
-  lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
-__device__ __forceinline__ void join8(const uint4& hi, const uint4& lo, float* v) {
-  const uint32_t h[4] = {hi.x, hi.y, hi.z, hi.w}, l[4] = {lo.x, lo.y, lo.z, lo.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    v[2 * j] = __uint_as_float(h[j] << 16) + __uint_as_float(l[j] << 16);
-    v[2 * j + 1] = __uint_as_float(h[j] & 0xFFFF0000u) + __uint_as_float(l[j] & 0xFFFF0000u);
-  }
-}
 // one wave per row, the row in registers as 16-byte vectors (lane l holds vectors l and l + 64): rows of up to 1024 elements
 template <bool NT = false>
 __device__ __forceinline__ void load_row_pair(const uint16_t* hi, const uint16_t* lo, int nv, int lane, float r[2][8]) {
@@ -182,13 +160,6 @@ __global__ __launch_bounds__(kBlock) void k_layernorm_bwd_pair(const uint16_t* _
   }
 }
 
-__device__ __forceinline__ void split4(const float* v, uint2& hi, uint2& lo) {
-  const uint32_t h0 = pk2(v[0], v[1]), h1 = pk2(v[2], v[3]);
-  hi = make_uint2(h0, h1);
-  lo = make_uint2(pk2(v[0] - __uint_as_float(h0 << 16), v[1] - __uint_as_float(h0 & 0xFFFF0000u)),
-                  pk2(v[2] - __uint_as_float(h1 << 16), v[3] - __uint_as_float(h1 & 0xFFFF0000u)));
-}
-
 // P[row][0..n_valid) = softmax(scale * S[row][0..n_valid)) as a pair, P[row][n_valid..ld_out) = 0; S fp32 (the pair GEMM's fp32
 // output).  One wave per row, four consecutive columns per lane (rows of up to 256 columns)
 __global__ __launch_bounds__(kBlock) void k_softmax_rows_pair(const float* __restrict__ sm, uint16_t* __restrict__ ph,
@@ -284,8 +255,6 @@ __global__ __launch_bounds__(kBlock) void k_unpatchify_from_f32(const float* __r
 // B operand of O^T = V^T P^T in the key order the accumulator registers already have; O is scaled by 1 / sum and written as a pair.
 // Replaces, per layer and forward pass, the batched S = Q K^T product (fp32 scores, 0.5 GB at B = 256), the soft-max row kernel, two
 // V transposes and the batched P V product of the unfused path (ViTEngine.fused_attention = False keeps that path as the cross-check).
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 constexpr int PATT_HD = 64, PATT_LDK = PATT_HD + 8;
 // Round 6: EIGHT waves per workgroup (512 threads) instead of four.  The LDS images keep these kernels at one workgroup per CU, so with four
 // waves every SIMD held ONE wave -- nothing ran beside its soft-max VALU work, its LDS gathers or its K / V staging, the matrix pipes were
@@ -404,8 +373,8 @@ __global__ __launch_bounds__(kAttBlock, 1) void k_vit_attention_pair(const uint1
         const float e0 = __builtin_amdgcn_exp2f(fmaf(sacc[kt][2 * j], scale_log2e, mneg));
         const float e1 = __builtin_amdgcn_exp2f(fmaf(sacc[kt][2 * j + 1], scale_log2e, mneg));
         sum += e0 + e1;
-        ph[j] = pk2(e0, e1);
-        pl[j] = pk2(e0 - __uint_as_float(ph[j] << 16), e1 - __uint_as_float(ph[j] & 0xFFFF0000u));
+        ph[j] = pack_bf16x2(e0, e1);
+        pl[j] = pack_bf16x2(e0 - __uint_as_float(ph[j] << 16), e1 - __uint_as_float(ph[j] & 0xFFFF0000u));
       }
 #pragma unroll
       for (int kb2 = 0; kb2 < 2; ++kb2) {
@@ -587,8 +556,8 @@ __global__ __launch_bounds__(kAttBlock, 1) void k_vit_attention_pair_walk(const 
           const float e0 = __builtin_amdgcn_exp2f(fmaf(sacc[kt][2 * j], scale_log2e, mneg));
           const float e1 = __builtin_amdgcn_exp2f(fmaf(sacc[kt][2 * j + 1], scale_log2e, mneg));
           sum += e0 + e1;
-          ph[j] = pk2(e0, e1);
-          pl[j] = pk2(e0 - __uint_as_float(ph[j] << 16), e1 - __uint_as_float(ph[j] & 0xFFFF0000u));
+          ph[j] = pack_bf16x2(e0, e1);
+          pl[j] = pack_bf16x2(e0 - __uint_as_float(ph[j] << 16), e1 - __uint_as_float(ph[j] & 0xFFFF0000u));
         }
 #pragma unroll
         for (int kb2 = 0; kb2 < 2; ++kb2) {

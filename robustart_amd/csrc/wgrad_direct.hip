@@ -20,10 +20,9 @@
 // Reference step: loss.backward() of the adversarial-training loop (RobustART/training/cls_solver.py:183-215 -> torch autograd through
 // every convolution; exprs/nips_benchmark/pgd_adv_train/resnet50/config.yaml:1-33).
 #include "rart_common.h"
+#include "rart_bf16_helpers.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 namespace {
 struct WgradDev {
