@@ -1200,6 +1200,62 @@ int rart_jpeg_decode_u8(const rart_jpeg_desc* desc, const rart_jpeg_desc* desc_h
                         const uint16_t* qt, size_t qt_count, void* workspace, size_t workspace_bytes, uint8_t* out, size_t out_bytes,
                         rart_stream_t stream);
 
+/* Entropy decoding on the device (csrc/jpeg_entropy_par.h + csrc/jpeg_entropy_gpu.hip): a self-synchronising
+ * parallel Huffman decoder, one workgroup per image, whose coefficients are those of rart_jpeg_entropy_decode element for
+ * element.  The scan is cut into subsequences of subseq_bytes raw bytes (a power of two from 4 up; 0 = the default); all of them
+ * decode from a guessed state, then rounds re-decode those whose entry changed until a round changes nothing; prefix sums over the
+ * subsequences place the blocks and the DC predictors, and a last pass writes the coefficients.  An image that has not converged
+ * after max_rounds rounds (0 = the default) gets status RART_ERR_UNSUPPORTED ("decode it with rart_jpeg_entropy_decode"), a
+ * truncated or corrupt stream RART_ERR_INVALID, exactly where rart_jpeg_entropy_decode returns it; never a guess.
+ *
+ * rart_jpeg_scan_plan is HOST-ONLY.  From a file and its probe it fills *scan_host -- all but the four offsets the caller owns --
+ * and writes the image's distinct Huffman tables (ntab <= RART_JPEG_MAX_TABLES, RART_JPEG_HUFF_PITCH bytes each, a device-ready
+ * image of the decoder's own table) to tabs_host (capacity in bytes; RART_ERR_INVALID when too small).  host_path = 1 marks a file
+ * the sequential decoder has to take: a restart interval, a scan of more than RART_JPEG_MAX_SUBSEQ subsequences or 2^19 - 2
+ * bytes, more than four distinct tables; its scan_len, nsub and ntab are 0.  What the image needs of the staging buffers:
+ * scan_len bytes of `scans` (the file's bytes from scan_pos on) and ntab * RART_JPEG_HUFF_PITCH bytes of `tabs`.
+ *
+ * rart_jpeg_entropy_decode_gpu: scan / scan_host hold the same n descriptors on the device and on the host.  Host-path images
+ * come first and are skipped (status RART_OK, rounds_used 0, their coefficients untouched: the caller put them there); the
+ * coefficients of all others are zeroed and written.  block_start numbers an image's first block as rart_jpeg_desc.block_start[0]
+ * does, sub_start counts the subsequences of the images before it.  Every offset and size of the host copy is checked against
+ * scans_bytes, tabs_bytes, total_blocks and workspace_bytes BEFORE any launch; in the kernel every byte read is checked against
+ * the image's scan_len, every store against its block total, every loop is bounded by a count fixed at launch, and no workgroup
+ * waits for another.  status / rounds_used: device int32[n].  One memset + one launch.
+ *
+ * rart_jpeg_entropy_emulate is HOST-ONLY: the same rounds, cap, prefix sums and write pass from the same source on the CPU, for
+ * one file (a host-path file goes through the sequential decoder, rounds_used 0).  Statuses as above; coef_host as
+ * rart_jpeg_entropy_decode writes it (written for RART_OK / RART_ERR_INVALID only). */
+#define RART_JPEG_DEFAULT_SUBSEQ_BYTES 512
+#define RART_JPEG_DEFAULT_MAX_ROUNDS 14
+#define RART_JPEG_MAX_SUBSEQ 4096
+#define RART_JPEG_MAX_TABLES 4
+#define RART_JPEG_HUFF_PITCH 1504
+typedef struct rart_jpeg_scan {
+  int64_t scan_off;               /* caller: byte of `scans` where the image's scan_len bytes start */
+  int64_t tab_off;                /* caller: byte of `tabs` where its ntab tables start, a multiple of 16 */
+  int64_t block_start;            /* caller: the image's first block in `coef` */
+  int64_t sub_start;              /* caller: subsequences of the images before it (indexes the workspace) */
+  int64_t scan_pos;               /* plan: byte of the file where the entropy-coded segment starts */
+  int32_t scan_len;               /* plan: bytes from scan_pos to the first marker or the end of the file */
+  int32_t nsub;                   /* plan: ceil(scan_len / subseq_bytes) */
+  int32_t host_path, ntab;
+  int32_t dc_tab[3], ac_tab[3];   /* plan: each component's tables, as indices into the image's ntab tables */
+  int32_t ncomp, h_samp, v_samp;  /* luma's sampling factors */
+  int32_t mcux, mcuy;
+  int32_t blocks_w[3], blocks_h[3];
+  int32_t reserved_;
+} rart_jpeg_scan;
+int rart_jpeg_scan_plan(const uint8_t* data_host, size_t len, const rart_jpeg_info* info_host, int subseq_bytes,
+                        rart_jpeg_scan* scan_host, void* tabs_host, size_t tabs_capacity);
+size_t rart_jpeg_entropy_workspace_bytes(const rart_jpeg_scan* scan_host, int n);
+int rart_jpeg_entropy_decode_gpu(const rart_jpeg_scan* scan, const rart_jpeg_scan* scan_host, int n, const uint8_t* scans,
+                                 size_t scans_bytes, const uint8_t* tabs, size_t tabs_bytes, int16_t* coef, int64_t total_blocks,
+                                 int subseq_bytes, int max_rounds, int32_t* status, int32_t* rounds_used, void* workspace,
+                                 size_t workspace_bytes, rart_stream_t stream);
+int rart_jpeg_entropy_emulate(const uint8_t* data_host, size_t len, const rart_jpeg_info* info_host, int subseq_bytes,
+                              int max_rounds, int16_t* coef_host, size_t capacity, int32_t* rounds_used);
+
 /* ---------------------------------------------------------------------------------------
  * Batched variable-size resize (csrc/resize_batch.hip): Pillow's Image.resize for 8-bit RGB for n images of DIFFERENT sizes in one
  * call -- crop(box), resize to (resize_h, resize_w) with filter 0..5, the crop window (crop_y, crop_x, crop_h, crop_w) of the

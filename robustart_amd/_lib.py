@@ -243,6 +243,11 @@ SIGNATURES = {
     'rart_jpeg_decode_workspace_bytes': (c_size_t, [c_void_p, c_int]),
     'rart_jpeg_decode_u8': (c_int, [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_int64, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
                                     c_size_t, c_void_p]),
+    'rart_jpeg_scan_plan': (c_int, [ctypes.c_char_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t]),
+    'rart_jpeg_entropy_workspace_bytes': (c_size_t, [c_void_p, c_int]),
+    'rart_jpeg_entropy_decode_gpu': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, ctypes.c_int64,
+                                             c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'rart_jpeg_entropy_emulate': (c_int, [ctypes.c_char_p, c_size_t, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     'rart_resize_batch_plan': (c_int, [c_void_p, c_int] + [c_int] * 7 + [c_void_p, c_size_t, c_void_p]),
     'rart_resize_batch_u8': (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     'rart_cv_resize_batch_plan': (c_int, [c_void_p, c_int] + [c_int] * 7 + [c_void_p, c_size_t, c_void_p]),
@@ -286,6 +291,20 @@ class JpegDesc(ctypes.Structure):
     _fields_ = [('block_start', ctypes.c_int64 * 3), ('plane_off', ctypes.c_int64 * 3), ('qt_off', ctypes.c_int64),
                 ('out_off', ctypes.c_int64)] + \
                [(n, ctypes.c_int32) for n in ('height', 'width', 'ncomp', 'h_samp', 'v_samp')] + \
+               [('blocks_w', ctypes.c_int32 * 3), ('blocks_h', ctypes.c_int32 * 3), ('reserved_', ctypes.c_int32)]
+
+
+JPEG_HUFF_PITCH, JPEG_MAX_TABLES, JPEG_MAX_SUBSEQ = 1504, 4, 4096       # RART_JPEG_HUFF_PITCH / _MAX_TABLES / _MAX_SUBSEQ
+JPEG_DEFAULT_SUBSEQ_BYTES, JPEG_DEFAULT_MAX_ROUNDS = 512, 14             # RART_JPEG_DEFAULT_SUBSEQ_BYTES / _MAX_ROUNDS
+
+
+class JpegScan(ctypes.Structure):
+    """rart_jpeg_scan (include/robustart_hip.h): one image of a rart_jpeg_entropy_decode_gpu batch, 128 bytes.  rart_jpeg_scan_plan
+    fills all but scan_off, tab_off, block_start and sub_start."""
+    _fields_ = [(n, ctypes.c_int64) for n in ('scan_off', 'tab_off', 'block_start', 'sub_start', 'scan_pos')] + \
+               [(n, ctypes.c_int32) for n in ('scan_len', 'nsub', 'host_path', 'ntab')] + \
+               [('dc_tab', ctypes.c_int32 * 3), ('ac_tab', ctypes.c_int32 * 3)] + \
+               [(n, ctypes.c_int32) for n in ('ncomp', 'h_samp', 'v_samp', 'mcux', 'mcuy')] + \
                [('blocks_w', ctypes.c_int32 * 3), ('blocks_h', ctypes.c_int32 * 3), ('reserved_', ctypes.c_int32)]
 
 

@@ -17,6 +17,13 @@
 
 #include "../../include/robustart_hip.h"
 
+// what the device half of the parallel entropy decoder (csrc/jpeg_entropy_par.h, csrc/jpeg_entropy_gpu.hip) compiles too
+#if defined(__HIPCC__)
+#define RART_JPEG_HD __host__ __device__
+#else
+#define RART_JPEG_HD
+#endif
+
 namespace rart_jpeg {
 
 constexpr int64_t kMaxPixels = (int64_t)1 << 26;   // larger frames are left to Pillow (and its decompression-bomb check)
@@ -249,6 +256,26 @@ inline Result probe(const uint8_t* data, size_t len, rart_jpeg_info* info) {
   return r;
 }
 
+// The code at the head of `look` (16 bits, zero-padded past the end of the data) -> its length 1..16 and symbol; 0 = no code of
+// the table starts these bits.
+RART_JPEG_HD inline int huff_lookup(const Huff& h, uint32_t look, int* sym) {
+  int l = h.fast_len[look >> 7];
+  if (l) {
+    *sym = h.fast_sym[look >> 7];
+    return l;
+  }
+  for (l = 10; l <= 16; ++l) {
+    const int32_t code = (int32_t)(look >> (16 - l));
+    if (h.maxcode[l] >= 0 && code <= h.maxcode[l]) {
+      const int idx = h.valptr[l] + code - h.mincode[l];
+      if (idx < 0 || idx >= h.nvals || idx >= 256) return 0;
+      *sym = h.vals[idx];
+      return l;
+    }
+  }
+  return 0;
+}
+
 // The bit reader of one entropy-coded segment.  `acc` holds the next bits left-aligned; bits past `nbits` are zero.  It stops
 // feeding at a marker (FF followed by anything but 00) and at the end of the data: asking for more bits than remain is an error.
 struct Bits {
@@ -293,21 +320,8 @@ struct Bits {
   bool symbol(const Huff& h, int* sym) {
     if (nbits < 16) fill();
     const uint32_t look = (uint32_t)(acc >> 48);   // 16 bits, zero-padded past the end
-    int l = h.fast_len[look >> 7];
-    if (l) {
-      *sym = h.fast_sym[look >> 7];
-    } else {
-      for (l = 10; l <= 16; ++l) {
-        const int32_t code = (int32_t)(look >> (16 - l));
-        if (h.maxcode[l] >= 0 && code <= h.maxcode[l]) {
-          const int idx = h.valptr[l] + code - h.mincode[l];
-          if (idx < 0 || idx >= h.nvals) return false;
-          *sym = h.vals[idx];
-          break;
-        }
-      }
-      if (l > 16) return false;
-    }
+    const int l = huff_lookup(h, look, sym);
+    if (!l) return false;
     if (nbits < l) return false;
     acc <<= l;
     nbits -= l;
@@ -315,7 +329,7 @@ struct Bits {
   }
 };
 
-inline int extend(uint32_t v, int s) { return v < (1u << (s - 1)) ? (int)v - (1 << s) + 1 : (int)v; }
+RART_JPEG_HD inline int extend(uint32_t v, int s) { return v < (1u << (s - 1)) ? (int)v - (1 << s) + 1 : (int)v; }
 
 inline Result entropy_decode(const uint8_t* data, size_t len, const rart_jpeg_info* info, int16_t* coef, size_t capacity) {
   if (!info || !coef) return {RART_ERR_INVALID, "null info / coef"};

@@ -11,7 +11,8 @@ pil_resize_batch is the batched form of pil_resize for images of different sizes
 batch in one rart_resize_batch_u8 call -- cv_resize_batch the same for cv_resize through rart_cv_resize_batch_u8 (each
 image takes the code cv2.resize chooses for its size), and image_transfer_batch the batch form of image_transfer on top of the two.
 decode_batch_gpu is the batched form of the 'pil' decoder for baseline JPEG files: Huffman decoding on host threads, the arithmetic in
-rart_jpeg_decode_u8, the same bytes as Pillow; FileImageNet(reader='hip') reads through it."""
+rart_jpeg_decode_u8, the same bytes as Pillow; FileImageNet(reader='hip') reads through it.  entropy='gpu' moves the
+Huffman decoding to the GPU too (rart_jpeg_entropy_decode_gpu), bit-identical to the host decoder; 'host' is the default."""
 import random
 
 import numpy as np
@@ -186,23 +187,242 @@ MAX_DECODE_WORKERS = 16
 decode_launches = 0        # rart_jpeg_decode_u8 calls made by decode_batch_gpu (one per batch that has a GPU-decodable file)
 
 
-def decode_batch_gpu(items, num_workers=8, timings=None):
+entropy_launches = 0       # rart_jpeg_entropy_decode_gpu calls made by decode_batch_gpu(entropy='gpu'): one per batch that has a
+#                            file for the device entropy decoder
+entropy_stats = {'gpu': 0, 'host_dri': 0, 'host_not_converged': 0, 'invalid': 0}   # images by who decoded their entropy data
+ENTROPY_MODES = ('host', 'gpu')
+entropy_params = {'subseq_bytes': 0, 'max_rounds': 0}   # what decode_batch_gpu(entropy='gpu') uses where its caller passes 0
+#                                                         (FileImageNet does); 0 = the library's defaults
+
+
+def check_entropy_mode(entropy):
+    if entropy not in ENTROPY_MODES:
+        raise ValueError("entropy must be 'host' or 'gpu', got %r" % (entropy,))
+    return entropy
+
+
+def jpeg_scan_plan(data, info, subseq_bytes=0):
+    """rart_jpeg_scan_plan (host only) -> (_lib.JpegScan, the image's Huffman tables as a ctypes byte array of
+    JPEG_MAX_TABLES * JPEG_HUFF_PITCH bytes, of which scan.ntab * JPEG_HUFF_PITCH are written)"""
+    import ctypes
+    scan = _lib.JpegScan()
+    tabs = (ctypes.c_ubyte * (_lib.JPEG_MAX_TABLES * _lib.JPEG_HUFF_PITCH))()
+    _lib.check(_lib.load().rart_jpeg_scan_plan(data, len(data), ctypes.byref(info), subseq_bytes, ctypes.byref(scan), tabs, len(tabs)))
+    return scan, tabs
+
+
+def jpeg_entropy_emulate(data, info, coef, subseq_bytes=0, max_rounds=0):
+    """rart_jpeg_entropy_emulate (host only): the device entropy decoder's rounds, prefix sums and write pass on the CPU.
+    coef as for jpeg_entropy_decode.  -> (status, rounds_used)"""
+    import ctypes
+    assert coef.dtype == np.int16 and coef.flags['C_CONTIGUOUS']
+    used = ctypes.c_int32(0)
+    st = _lib.load().rart_jpeg_entropy_emulate(data, len(data), ctypes.byref(info), subseq_bytes, max_rounds, coef.ctypes.data, coef.size,
+                                               ctypes.byref(used))
+    return st, used.value
+
+
+def _fill_jpeg_descs(descs, infos):
+    """the rart_jpeg_desc of each probed image, in the order given -> (blocks, pixels)"""
+    blk = pix = plane = 0
+    for j, info in enumerate(infos):
+        d = descs[j]
+        d.height, d.width, d.ncomp = info.height, info.width, info.ncomp
+        d.h_samp, d.v_samp = info.h_samp[0], info.v_samp[0]
+        d.qt_off, d.out_off = j * 192, 3 * pix
+        for c in range(3):
+            bw, bh = (info.blocks_w[c], info.blocks_h[c]) if c < info.ncomp else (0, 0)
+            d.blocks_w[c], d.blocks_h[c], d.block_start[c] = bw, bh, blk
+            d.plane_off[c] = plane
+            blk += bw * bh
+            plane += (bw * bh * 64 + 15) // 16 * 16
+        pix += info.height * info.width
+    return blk, pix
+
+
+def _align16(v):
+    return (v + 15) // 16 * 16
+
+
+def _pool_map(pool, fn, seq, workers):
+    """pool.map(fn, seq) in slices of about a quarter of a worker's share: the per-file steps of the GPU entropy path are tens of
+    microseconds each, less than what one future costs"""
+    seq = list(seq)
+    step = max(1, -(-len(seq) // (4 * workers)))
+    parts = pool.map(lambda part: [fn(x) for x in part], [seq[i:i + step] for i in range(0, len(seq), step)])
+    return [r for part in parts for r in part]
+
+
+def _decode_batch_gpu_entropy(items, workers, timings, subseq_bytes, max_rounds):
+    """decode_batch_gpu(entropy='gpu'): the pool reads, probes and plans; one pinned buffer holds descriptors | scan descriptors |
+    quantisation tables | Huffman tables | scan bytes | the coefficients of host-path images (restart intervals, scans beyond the
+    kernel's limits), which come first in the batch's block numbering; one copy moves it; rart_jpeg_entropy_decode_gpu fills the
+    other images' coefficients behind them; the status array comes back (the batch's one synchronisation); images that have
+    not converged are decoded by rart_jpeg_entropy_decode into their slots; rart_jpeg_decode_u8 finishes the whole batch."""
+    global decode_launches, entropy_launches
+    import ctypes
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    torch = _lib.require_gpu()
+    lib = _lib.load()
+    n = len(items)
+    t0 = time.perf_counter()
+
+    def probe(item):
+        data = _read_bytes(item)
+        info = jpeg_probe(data)
+        return (data, info) + (jpeg_scan_plan(data, info, subseq_bytes) if info.status == 0 else (None, None))
+
+    images, used = [None] * n, [False] * n
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        probed = _pool_map(pool, probe, items, workers)
+        ok_ids = [k for k in range(n) if probed[k][1].status == 0]
+        ids = [k for k in ok_ids if probed[k][2].host_path] + [k for k in ok_ids if not probed[k][2].host_path]
+        if ids:
+            m = len(ids)
+            m_host = sum(1 for k in ids if probed[k][2].host_path)
+            descs = (_lib.JpegDesc * m)()
+            scans = (_lib.JpegScan * m)()
+            blk, pix = _fill_jpeg_descs(descs, [probed[k][1] for k in ids])
+            host_blk = descs[m_host].block_start[0] if m_host < m else blk
+            tab_bytes = scan_bytes = sub = 0
+            for j, k in enumerate(ids):
+                s = scans[j]
+                ctypes.memmove(ctypes.addressof(s), ctypes.addressof(probed[k][2]), ctypes.sizeof(s))
+                s.block_start, s.sub_start, s.tab_off, s.scan_off = descs[j].block_start[0], sub, tab_bytes, scan_bytes
+                sub += s.nsub
+                tab_bytes += s.ntab * _lib.JPEG_HUFF_PITCH
+                scan_bytes += _align16(s.scan_len)
+            # staging: descriptors | scan descriptors | quantisation tables | Huffman tables | scan bytes | host-path coefficients;
+            # on the device the other images' coefficients, then status and rounds_used, follow.  Each region 16-byte aligned.
+            o_scan = _align16(ctypes.sizeof(descs))
+            o_qt = o_scan + _align16(ctypes.sizeof(scans))
+            o_tab = o_qt + m * 192 * 2
+            o_bytes = o_tab + max(tab_bytes, 16)
+            o_coef = o_bytes + max(scan_bytes, 16)
+            staged = o_coef + host_blk * 128
+            o_status = o_coef + blk * 128
+            total = o_status + _align16(8 * m)
+            dev = torch.device('cuda', torch.cuda.current_device())
+            host, ev = _pinned.pop(dev, (None, None))
+            if ev is not None:
+                ev.synchronize()
+            if host is None or host.numel() < staged:
+                host = torch.empty(int(staged * 1.25), dtype=torch.uint8, pin_memory=True)
+            hnp = host.numpy()
+            ctypes.memmove(hnp.ctypes.data, ctypes.addressof(descs), ctypes.sizeof(descs))
+            ctypes.memmove(hnp.ctypes.data + o_scan, ctypes.addressof(scans), ctypes.sizeof(scans))
+            qt = hnp[o_qt:o_tab].view(np.uint16).reshape(m, 3, 64)
+            coef = hnp[o_coef:staged].view(np.int16)
+
+            def stage(j):
+                data, info, _, tabs = probed[ids[j]]
+                s = scans[j]
+                qt[j] = np.ctypeslib.as_array(info.qt)
+                if s.host_path:
+                    lo = descs[j].block_start[0] * 64
+                    return jpeg_entropy_decode(data, info, coef[lo:lo + info.coef_count])
+                nt = s.ntab * _lib.JPEG_HUFF_PITCH
+                ctypes.memmove(hnp.ctypes.data + o_tab + s.tab_off, tabs, nt)
+                hnp[o_bytes + s.scan_off:o_bytes + s.scan_off + s.scan_len] = np.frombuffer(data, np.uint8, s.scan_len, s.scan_pos)
+                return 0
+
+            status = _pool_map(pool, stage, range(m), workers)
+            if timings is not None:
+                timings['host_s'] = time.perf_counter() - t0
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+            dbuf = torch.empty(total, dtype=torch.uint8, device=dev)
+            dbuf[:staged].copy_(host[:staged], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            _pinned[dev] = (host, ev)
+            if timings is not None:
+                torch.cuda.synchronize()
+                timings['copy_s'] = time.perf_counter() - t0
+                t0 = time.perf_counter()
+            base = dbuf.data_ptr()
+            if m_host < m:
+                nb = lib.rart_jpeg_entropy_workspace_bytes(ctypes.addressof(scans), m)
+                ws = _lib.workspace(nb, dev)
+                entropy_launches += 1
+                if timings is not None:
+                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    ev0.record()
+                _lib.check(lib.rart_jpeg_entropy_decode_gpu(base + o_scan, ctypes.addressof(scans), m, base + o_bytes, max(scan_bytes, 16),
+                                                            base + o_tab, max(tab_bytes, 16), base + o_coef, blk, subseq_bytes, max_rounds,
+                                                            base + o_status, base + o_status + 4 * m, _lib.ptr(ws), nb, _lib.stream_ptr()))
+                if timings is not None:
+                    ev1.record()
+                dev_status = dbuf[o_status:o_status + 4 * m].view(torch.int32).cpu().tolist()   # the batch's one synchronisation
+                if timings is not None:
+                    timings['entropy_kernel_s'] = 1e-3 * ev0.elapsed_time(ev1)         # the memset + the launch, by device events
+                redo = [j for j in range(m_host, m) if dev_status[j] == 2]
+
+                def fallback(j):
+                    data, info = probed[ids[j]][:2]
+                    tmp = np.empty(info.coef_count, np.int16)
+                    return jpeg_entropy_decode(data, info, tmp), tmp
+
+                for j, (st, tmp) in zip(redo, pool.map(fallback, redo)):
+                    lo = o_coef + descs[j].block_start[0] * 128
+                    dbuf[lo:lo + tmp.nbytes].copy_(torch.from_numpy(tmp).view(torch.uint8))
+                    dev_status[j] = st
+                for j in range(m_host, m):
+                    status[j] = dev_status[j]
+                entropy_stats['host_not_converged'] += len(redo)
+                entropy_stats['gpu'] += sum(1 for j in range(m_host, m) if status[j] == 0) - sum(1 for j in redo if status[j] == 0)
+            entropy_stats['host_dri'] += m_host
+            entropy_stats['invalid'] += sum(1 for j in range(m) if status[j] != 0)
+            if timings is not None:
+                torch.cuda.synchronize()
+                timings['entropy_s'] = time.perf_counter() - t0
+                t0 = time.perf_counter()
+            out = torch.empty(3 * pix, dtype=torch.uint8, device=dev)
+            nb = lib.rart_jpeg_decode_workspace_bytes(ctypes.addressof(descs), m)
+            ws = _lib.workspace(nb, dev)
+            decode_launches += 1
+            _lib.check(lib.rart_jpeg_decode_u8(base, ctypes.addressof(descs), m, base + o_coef, blk, base + o_qt, m * 192, _lib.ptr(ws), nb,
+                                               _lib.ptr(out), out.numel(), _lib.stream_ptr()))
+            if timings is not None:
+                torch.cuda.synchronize()
+                timings['device_s'] = time.perf_counter() - t0
+            for j, k in enumerate(ids):
+                if status[j] == 0:
+                    d = descs[j]
+                    images[k] = out[d.out_off:d.out_off + 3 * d.height * d.width].view(d.height, d.width, 3)
+                    used[k] = True
+    for k in range(n):
+        if images[k] is None:
+            images[k] = torch.from_numpy(decode(probed[k][0], 'pil')).cuda(non_blocking=True)
+    return images, used
+
+
+def decode_batch_gpu(items, num_workers=8, timings=None, entropy='host', subseq_bytes=0, max_rounds=0):
     """items: file paths or encoded bytes -> (images, used_gpu): a list of CUDA uint8 HxWx3 tensors equal to decode(item, 'pil')
     bit for bit, and a bool per item.  Baseline JPEGs (jpeg_probe) are entropy-decoded on the host by a pool of
     min(num_workers, 16) threads (ctypes releases the GIL) into one pinned buffer, cross the bus in one copy together with their
     tables and descriptors, and are finished by rart_jpeg_decode_u8 in two launches for the whole batch; their images are views
     of one packed buffer.  Every other file (used_gpu False) is decoded by decode(item, 'pil') and uploaded, as the 'pil' reader
     does; what Pillow raises propagates.  timings: a dict that receives 'host_s', 'copy_s', 'device_s' (each phase is then
-    followed by a synchronize: a measurement aid)."""
+    followed by a synchronize: a measurement aid).
+    entropy='gpu' (opt-in; the default stays 'host'): the file bytes cross the bus instead of the coefficients and
+    rart_jpeg_entropy_decode_gpu decodes them, bit-identical to the host decoder (_decode_batch_gpu_entropy; subseq_bytes and
+    max_rounds are its parameters, 0 = entropy_params, there 0 = the library's defaults); timings gains 'entropy_s' (launch, status
+    read-back and host fallbacks) and 'entropy_kernel_s' (the memset and the kernel, by device events)."""
     global decode_launches
     import ctypes
     import time
     from concurrent.futures import ThreadPoolExecutor
+    check_entropy_mode(entropy)
     torch = _lib.require_gpu()
     lib = _lib.load()
     items = list(items)
     n = len(items)
     workers = max(1, min(int(num_workers), MAX_DECODE_WORKERS))
+    if entropy == 'gpu':
+        return _decode_batch_gpu_entropy(items, workers, timings, int(subseq_bytes) or entropy_params['subseq_bytes'],
+                                         int(max_rounds) or entropy_params['max_rounds'])
     t0 = time.perf_counter()
 
     def probe(item):
@@ -216,19 +436,7 @@ def decode_batch_gpu(items, num_workers=8, timings=None):
         if gpu_ids:
             m = len(gpu_ids)
             descs = (_lib.JpegDesc * m)()
-            blk = pix = plane = 0
-            for j, k in enumerate(gpu_ids):
-                info, d = probed[k][1], descs[j]
-                d.height, d.width, d.ncomp = info.height, info.width, info.ncomp
-                d.h_samp, d.v_samp = info.h_samp[0], info.v_samp[0]
-                d.qt_off, d.out_off = j * 192, 3 * pix
-                for c in range(3):
-                    bw, bh = (info.blocks_w[c], info.blocks_h[c]) if c < info.ncomp else (0, 0)
-                    d.blocks_w[c], d.blocks_h[c], d.block_start[c] = bw, bh, blk
-                    d.plane_off[c] = plane
-                    blk += bw * bh
-                    plane += (bw * bh * 64 + 15) // 16 * 16
-                pix += info.height * info.width
+            blk, pix = _fill_jpeg_descs(descs, [probed[k][1] for k in gpu_ids])
             # one staging buffer: descriptors | quantisation tables | coefficients, each region 16-byte aligned
             desc_bytes = (ctypes.sizeof(descs) + 15) // 16 * 16
             qt_bytes = m * 192 * 2

@@ -148,14 +148,18 @@ class FileImageNet(torch.utils.data.Dataset):
     reader='hip' (`image_reader.type: hip`, opt-in) decodes a batch's baseline JPEGs through noise.imagenet_s.decode_batch_gpu --
     Huffman decoding on `num_workers` host threads, IDCT / upsampling / colour conversion on the GPU, bit-identical to the 'pil'
     reader -- and hands every other file to PIL as 'pil' does; `decode_stats` counts the files that took each path.
+    entropy='gpu' (`image_reader.entropy: gpu`, opt-in, with reader='hip') moves the Huffman decoding to the GPU as well
+    (decode_batch_gpu(entropy='gpu')): the same images, the same `decode_stats`.
     batch() = decode_indices() then transform(): a caller that scores one decoded batch under several transforms (the ImageNet-S loop)
     calls the two steps itself."""
 
     def __init__(self, root_dir, meta_file, size=224, test_resize=256, transform='ONECROP', reader='pil', limit=None, seed=0,
-                 jitter=None, flip=True, num_workers=8):
+                 jitter=None, flip=True, num_workers=8, entropy='host'):
         if reader not in ('pil', 'hip'):
             raise NotImplementedError("image_reader.type %r: 'pil' and 'hip' are available in this build" % (reader,))
-        self.reader, self.num_workers = reader, int(num_workers)
+        if entropy not in ('host', 'gpu'):
+            raise ValueError("image_reader.entropy %r: 'host' and 'gpu' are available" % (entropy,))
+        self.reader, self.num_workers, self.entropy = reader, int(num_workers), entropy
         self.decode_stats = {'gpu': 0, 'fallback': 0}          # reader='hip': files decoded on the GPU / by PIL
         if transform not in ('ONECROP', 'STANDARD'):
             raise NotImplementedError('transforms.type %r (ONECROP / STANDARD)' % (transform,))
@@ -168,14 +172,15 @@ class FileImageNet(torch.utils.data.Dataset):
         self.jitter, self.flip = jitter, bool(flip)
 
     @classmethod
-    def from_folder(cls, root_dir, size=224, test_resize=256, transform='ONECROP', reader='pil', limit=None, seed=0, num_workers=8):
+    def from_folder(cls, root_dir, size=224, test_resize=256, transform='ONECROP', reader='pil', limit=None, seed=0, num_workers=8,
+                    entropy='host'):
         """An image-folder set `<root>/<class folder>/<file>` (imagenet-a, imagenet-o and the in-distribution folder of
         exp/imagenet-a_o-loop): class folders sorted by name, files sorted by name inside each, label = the position of the folder --
         torchvision's ImageFolder order.  `classes` keeps the folder names.  Entries of the root that are not directories (ImageNet-A
         ships a README.txt) are skipped; decode, ONECROP and the resize are FileImageNet's."""
         if not os.path.isdir(root_dir):
             raise ValueError('image folder %r is not a directory' % (root_dir,))
-        self = cls(root_dir, None, size, test_resize, transform, reader, None, seed, num_workers=num_workers)
+        self = cls(root_dir, None, size, test_resize, transform, reader, None, seed, num_workers=num_workers, entropy=entropy)
         self.classes = sorted(d for d in os.listdir(root_dir) if os.path.isdir(os.path.join(root_dir, d)))
         for lab, d in enumerate(self.classes):
             for f in sorted(os.listdir(os.path.join(root_dir, d))):
@@ -199,7 +204,8 @@ class FileImageNet(torch.utils.data.Dataset):
         """reader='hip': the decoded images of `indices` as CUDA uint8 HxWx3 tensors (one decode_batch_gpu call)"""
         from ..noise.imagenet_s import decode_batch_gpu
         with torch.cuda.device(dev):
-            images, used = decode_batch_gpu([os.path.join(self.root, self.items[i][0]) for i in indices], self.num_workers)
+            images, used = decode_batch_gpu([os.path.join(self.root, self.items[i][0]) for i in indices], self.num_workers,
+                                            entropy=self.entropy)
         self.decode_stats['gpu'] += sum(used)
         self.decode_stats['fallback'] += len(used) - sum(used)
         return images
@@ -364,7 +370,8 @@ def make_dataset(dcfg, n, size, split='test'):
         t = read_transforms(dcfg, split)
         return FileImageNet(sec['root_dir'], sec['meta_file'], size, t['test_resize'], t['type'],
                             (sec.get('image_reader') or {}).get('type', 'pil'), dcfg.get('limit_samples'),
-                            int(dcfg.get('seed', 0)), jitter=t['jitter'], flip=t['flip'], num_workers=int(dcfg.get('num_workers') or 8))
+                            int(dcfg.get('seed', 0)), jitter=t['jitter'], flip=t['flip'], num_workers=int(dcfg.get('num_workers') or 8),
+                            entropy=(sec.get('image_reader') or {}).get('entropy', 'host'))
     if rf != 'fake':
         raise NotImplementedError("data.read_from %r ('fake', 'structured', 'fs')" % (rf,))
     return FakeImageNet(n, size)
@@ -655,7 +662,8 @@ def natural_datasets(cfg):
         if not tcfg.get(name):
             raise ValueError('data.test: imagenet_a&o needs data.test.%s' % name)
         sets[key] = FileImageNet.from_folder(tcfg[name], size, t['test_resize'], t['type'], (tcfg.get('image_reader') or {}).get('type', 'pil'),
-                                             dcfg.get('limit_samples'), int(dcfg.get('seed', 0)), num_workers=int(dcfg.get('num_workers') or 8))
+                                             dcfg.get('limit_samples'), int(dcfg.get('seed', 0)), num_workers=int(dcfg.get('num_workers') or 8),
+                                             entropy=(tcfg.get('image_reader') or {}).get('entropy', 'host'))
     if sets['o_in'].classes != sets['o_out'].classes:
         raise ValueError('data.test.imagenet_o_folder must hold exactly the class folders of imagenet_o_root_dir: %d vs %d folders, '
                          'differing in %s' % (len(sets['o_in'].classes), len(sets['o_out'].classes),
