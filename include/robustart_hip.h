@@ -919,6 +919,28 @@ int rart_color_jitter_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, 
 int rart_logit_confidence_f32(const float* logits, int64_t rows, int classes, int64_t ld, const int32_t* subset, int n_subset,
                               const int64_t* labels, int32_t* pred, float* conf, uint8_t* correct, rart_stream_t stream);
 
+/* ---- Prediction, label rank and top-k hit counters (csrc/topk_score.hip; robustart_amd/metrics/confidence.py: topk_score) ----------
+ * What the ImageNet-C loop keeps of a batch.  logits: fp32 [rows][ld], ld >= classes, no alignment assumed (16-byte loads are used
+ * when the base is 16-byte aligned and ld a multiple of 4, element loads otherwise).  labels: int64 [rows] on the device.  With
+ * y = labels[r] and z the first `classes` values of row r:
+ *   rank[r] = #{j : z_j > z_y} + #{j < y : z_j == z_y}: the position of the label in a stable descending sort of z, ties to the lower
+ *             class index (what torch.topk(sorted) returns on the CPU and metrics.evaluators._topk_acc restates).  A label outside
+ *             [0, classes) or a NaN z_y gives rank = classes.  The compares are IEEE: a NaN elsewhere never outranks the label, +inf
+ *             and -inf need no special case.
+ *   pred[r] = the LOWEST index that attains max z; if the row holds a NaN, the index of the first NaN (numpy.argmax, the rule of
+ *             rart_logit_confidence_f32)
+ *   hits[i] += #{r : rank[r] < ks[i] and rank[r] < classes} for i < n_k, 0 <= n_k <= 8: rank = classes is a miss for EVERY k, also
+ *             for a k above classes.  ks: HOST array, copied into the launch arguments, every entry >= 1.  hits: int64 on the DEVICE;
+ *             the entry ADDS and never clears (the caller passes hits + 2 * slot to keep a pair of counters per slot), with one
+ *             64-bit atomic add per workgroup and k after a register + LDS reduction.  The sums are integers: no order dependence.
+ * pred, rank and hits may each be NULL to skip that output (hits == NULL or n_k == 0 skips the counting).  One launch, no workspace;
+ * one wave per row, rows (64-bit) walked with a grid stride of at most 8192 rows per trip; a row is read once whatever `classes` is
+ * (no ceiling).  A row's pred and rank depend on that row alone.  rows == 0 returns RART_OK and launches nothing; rows < 0,
+ * classes < 1, ld < classes, n_k outside [0, 8], NULL ks with n_k > 0, a ks[i] < 1, or NULL logits / labels with rows > 0 is
+ * RART_ERR_INVALID, decided before any HIP call. */
+int rart_topk_score_f32(const float* logits, int64_t rows, int classes, int64_t ld, const int64_t* labels, int32_t* pred, int32_t* rank,
+                        const int* ks, int n_k, int64_t* hits, rart_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * Train-mode conv + BatchNorm support (cls_solver training step): the contractions run on
  * rart_conv_igemm_bf16; these are the HBM-bound kernels around it.  Activations are bf16 [rows][channels]

@@ -225,6 +225,8 @@ SIGNATURES = {
     'rart_color_jitter_u8': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'rart_logit_confidence_f32': (c_int, [c_void_p, ctypes.c_int64, c_int, ctypes.c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p]),
+    'rart_topk_score_f32': (c_int, [c_void_p, ctypes.c_int64, c_int, ctypes.c_int64, c_void_p, c_void_p, c_void_p,
+                                    ctypes.POINTER(c_int), c_int, c_void_p, c_void_p]),
     'rart_bn_workspace_bytes': (c_size_t, [c_size_t, c_int]),
     'rart_bn_train_forward_bf16': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,

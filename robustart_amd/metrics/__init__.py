@@ -13,6 +13,8 @@ Mirrors RobustART/metrics/ (names, arguments, printed quantities):
     calib_err, aurra, fpr_at_recall, get_measures   RobustART/metrics/calibration_tools.py:26-63,138-191, numpy fp64, no sklearn
     class_subset, subset_confidence   prediction / confidence / correctness over a class subset on the GPU (metrics/confidence.py,
                                       rart_logit_confidence_f32); ConfidenceWriter writes them, 9 bytes per sample off the device
+    topk_score           prediction, label rank and device-resident top-k counters of the ImageNet-C loop (rart_topk_score_f32);
+                         RankWriter writes `rank` lines, 8 bytes per sample off the device, which ImageNetCEvaluator reads as well
 and writes the JSON-lines `results.txt.all` files they read (one line per sample, `prediction` first, `label`
 second: AR/WCAR/transfer parse the first two values of a line).
 
@@ -30,8 +32,8 @@ Departures from the reference as written (each one is a defect there, SURVEY.md 
 Not mirrored: tune_temp, soft_f1, the decoding of ImageNet-P's sequences.
 """
 from .calibration import aurra, calib_err, fpr_at_recall, get_measures                 # noqa: F401
-from .confidence import class_subset, subset_confidence                               # noqa: F401
+from .confidence import class_subset, subset_confidence, topk_score                   # noqa: F401
 from .evaluators import (AdvRobustEvaluator, ImageNetAEvaluator, ImageNetCEvaluator,   # noqa: F401
                          ImageNetOEvaluator, ImageNetPEvaluator, ImageNetSEvaluator,
                          WorstCaseAdvRobustEvaluator, parse_line, transfer_rate)
-from .writer import ConfidenceWriter, ResultWriter, result_dir                        # noqa: F401
+from .writer import ConfidenceWriter, RankWriter, ResultWriter, result_dir            # noqa: F401

@@ -4,7 +4,12 @@ ImageNet-A and ImageNet-O score a 1000-class model on 200 of its classes (imagen
 prediction inside the subset, the largest soft-max probability over the subset and whether the prediction is right.
 rart_logit_confidence_f32 (csrc/logit_confidence.hip) computes the three in one launch, so 9 bytes per sample reach the host instead
 of the score vector.
+
+The ImageNet-C loop scores the same model on all classes once per (corruption, severity): topk_score (rart_topk_score_f32,
+csrc/topk_score.hip) gives the prediction and the label's rank per sample and adds the top-k hits to counters that stay on the device.
 """
+import ctypes
+
 import torch
 
 
@@ -65,3 +70,45 @@ def subset_confidence(logits, subset=None, labels=None):
                                                  _lib.ptr(labels), pred.data_ptr(), conf.data_ptr(), correct.data_ptr(),
                                                  _lib.stream_ptr()))
     return pred, conf, correct
+
+
+def topk_score(logits, labels, ks=(1, 5), hits=None, pred=True, rank=True):
+    """(pred int32 [b] or None, rank int32 [b] or None) of fp32 CUDA logits [b, classes], which may be a row-strided view (unit stride
+    along the classes), and int64 CUDA labels [b].  rank is the label's position in a stable descending sort of the row (ties to the
+    lower class index; `classes` for a label outside [0, classes) or a NaN at the label), pred the lowest index of the maximum: the
+    definition is rart_topk_score_f32's (include/robustart_hip.h).  hits: None, or a contiguous int64 CUDA vector of at least
+    len(ks) entries to which the number of rows with rank < ks[i] is ADDED (never cleared: pass counters[2 * slot:] to keep one pair
+    per slot).  pred / rank False skips that output.  No device-to-host read and no allocation beyond the outputs asked for; there is
+    no CPU path."""
+    from .. import _lib
+    if not isinstance(logits, torch.Tensor) or logits.device.type != 'cuda':
+        raise RuntimeError('topk_score: logits must be a CUDA tensor (the row reduction is a HIP kernel; there is no CPU fallback)')
+    if logits.dtype != torch.float32 or logits.dim() != 2:
+        raise ValueError('topk_score: logits must be fp32 [rows, classes], got %s %s' % (logits.dtype, tuple(logits.shape)))
+    rows, classes = logits.shape
+    if classes < 1:
+        raise ValueError('topk_score: logits have no classes')
+    if classes > 1 and logits.stride(1) != 1:
+        raise ValueError('topk_score: the classes of a row must be contiguous (stride %d)' % logits.stride(1))
+    ld = logits.stride(0) if rows > 1 else classes
+    if ld < classes:
+        raise ValueError('topk_score: row stride %d is shorter than the %d classes' % (ld, classes))
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or labels.shape != (rows,) or labels.device != logits.device \
+            or not labels.is_contiguous():
+        raise ValueError('topk_score: labels must be a contiguous int64 vector [rows] on the logits\' device')
+    ks = [int(k) for k in ks]
+    if len(ks) > 8 or any(k < 1 for k in ks):
+        raise ValueError('topk_score: at most 8 values of k, each at least 1, got %r' % (ks,))
+    if hits is not None:
+        if not isinstance(hits, torch.Tensor) or hits.dtype != torch.int64 or hits.dim() != 1 or hits.device != logits.device \
+                or not hits.is_contiguous() or hits.numel() < len(ks):
+            raise ValueError('topk_score: hits must be a contiguous int64 vector of at least %d entries on the logits\' device' % len(ks))
+    dev = logits.device
+    p = torch.empty(rows, dtype=torch.int32, device=dev) if pred else None
+    r = torch.empty(rows, dtype=torch.int32, device=dev) if rank else None
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        _lib.check(lib.rart_topk_score_f32(logits.data_ptr(), rows, classes, ld, _lib.ptr(labels), _lib.ptr(p), _lib.ptr(r),
+                                           (ctypes.c_int * max(len(ks), 1))(*ks), len(ks) if hits is not None else 0, _lib.ptr(hits),
+                                           _lib.stream_ptr()))
+    return p, r

@@ -79,7 +79,13 @@ class ImageNetCEvaluator(object):
 
     def eval(self, res_file):
         res = self.load_res(res_file)
-        acc = _topk_acc(res['score'], res['label'], self.topk)
+        if 'rank' in res and 'score' not in res:
+            # a RankWriter file: `rank` is the label's position in the order _topk_acc sorts the scores into, so the label is among
+            # the first k exactly when rank < k -- top-k = 100 * mean(rank < k), summed the way _topk_acc sums
+            rank = np.asarray(res['rank']).reshape(-1)
+            acc = {k: float((rank < k).sum() * (100.0 / len(rank))) for k in self.topk}
+        else:
+            acc = _topk_acc(res['score'], res['label'], self.topk)
         metric = Metric({'top%d' % k: acc[k] for k in self.topk})
         metric.set_cmp_key('top%d' % self.topk[0])
         with open(res_file.replace('results.txt.all', 'metric'), 'w') as f:

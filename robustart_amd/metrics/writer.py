@@ -9,6 +9,10 @@ ConfidenceWriter (the ImageNet-A / ImageNet-O evaluation) keeps the sharding and
 {"confidence": [c], "correct": [b], "num_correct": b, "prediction": p, "label": y, "index": i}: the key set the reference's
 ImageNetOEvaluator reads (imageneto_evaluator.py:36-50 concatenates the `confidence` / `correct` lists of the lines and sums
 `num_correct`, so it reads this file unchanged), one sample per line so that the file is the same for every batch size too.
+
+RankWriter (the ImageNet-C loop) keeps the sharding and the merge too and writes {"prediction": p, "label": y, "rank": r, "index": i}:
+the label's rank in the stable descending order of the scores instead of the scores, a few bytes per sample where a `score` line
+of a 1000-class model is some 20 KB.  ImageNetCEvaluator reads either form.
 """
 import json
 import os
@@ -73,3 +77,20 @@ class ConfidenceWriter(ResultWriter):
             b = int(correct[j])
             self.f.write(json.dumps({'confidence': [conf[j]], 'correct': [b], 'num_correct': b, 'prediction': int(pred[j]),
                                      'label': int(lab[j]), 'index': int(indices[j])}) + '\n')
+
+
+class RankWriter(ResultWriter):
+    """Compact result files of the ImageNet-C loop (metrics/confidence.py: topk_score): same shards, same merge by global index as
+    ResultWriter."""
+
+    def __init__(self, save_dir, rank=0, world=1):
+        super().__init__(save_dir, rank, world, with_score=False)
+
+    def write_batch(self, pred, rank, labels, indices):
+        """pred / rank int32: the two outputs of topk_score, [b] on any device -- 8 bytes per sample cross to the host.  labels: (b,)
+        tensor or sequence.  indices: global sample indices."""
+        pred, rank = pred.tolist(), rank.tolist()
+        lab = labels.tolist() if hasattr(labels, 'tolist') else list(labels)
+        for j in range(len(pred)):
+            self.f.write(json.dumps({'prediction': int(pred[j]), 'label': int(lab[j]), 'rank': int(rank[j]),
+                                     'index': int(indices[j])}) + '\n')

@@ -835,9 +835,204 @@ def evaluate_imagenet_s(cfg, args, rank, world, device, model=None):
     return res
 
 
+def _once_each(spec, what):
+    toks = [t.strip() for t in str(spec).split(',') if t.strip()]
+    if not toks:
+        raise ValueError('%s: an empty list' % what)
+    if len(set(toks)) != len(toks):
+        raise ValueError('%s: every entry once, got %r' % (what, spec))
+    return toks
+
+
+def imagenet_c_names(spec=None):
+    """`--imagenet-c-names a,b,...` -> (corruption names in order, named explicitly?).  None: the 15 standard corruptions,
+    CORRUPTION_NAMES[:15]; 'all': these and the four extras; both name frost only implicitly.  An unknown or repeated name or an empty
+    list is a ValueError."""
+    from ..noise.imagenet_c import CORRUPTION_NAMES
+    if spec is None:
+        return list(CORRUPTION_NAMES[:15]), False
+    if str(spec).strip() == 'all':
+        return list(CORRUPTION_NAMES), False
+    names = _once_each(spec, '--imagenet-c-names')
+    for t in names:
+        if t not in CORRUPTION_NAMES:
+            raise ValueError('--imagenet-c-names: unknown corruption %r (%s)' % (t, ', '.join(CORRUPTION_NAMES)))
+    return names, True
+
+
+def imagenet_c_severities(spec=None):
+    """`--imagenet-c-severities 1,2,...` -> severities in order; None: 1..5.  Anything outside 1..5, a repeat or an empty list is a
+    ValueError."""
+    if spec is None:
+        return [1, 2, 3, 4, 5]
+    out = []
+    for t in _once_each(spec, '--imagenet-c-severities'):
+        if t not in ('1', '2', '3', '4', '5'):
+            raise ValueError('--imagenet-c-severities: %r is not a severity (1..5)' % (t,))
+        out.append(int(t))
+    return out
+
+
+def read_frost_textures(path):
+    """The photographs of a folder as uint8 HxWx3 arrays, read with Pillow in sorted file order (the order decides which photograph
+    a sample draws)."""
+    import numpy as np
+    from PIL import Image
+    if not os.path.isdir(path):
+        raise ValueError('the frost folder %r is not a directory' % (path,))
+    out = []
+    for fn in sorted(os.listdir(path)):
+        p = os.path.join(path, fn)
+        if os.path.isfile(p):
+            with Image.open(p) as im:
+                out.append(np.array(im.convert('RGB')))
+    if not out:
+        raise ValueError('the frost folder %r holds no photographs' % (path,))
+    return out
+
+
+def imagenet_c_plan(cfg, args):
+    """Everything `--imagenet-c` decides from the arguments and the config alone, before a model, a dataset or the device is
+    looked at -> {'names', 'severities', 'skipped', 'frost_dir'}.  Frost needs photographs (--imagenet-c-frost-dir, the key
+    data.test.imagenet_c_frost_dir, or an earlier set_frost_textures): without them a frost that only the default list or 'all'
+    names is left out and listed under 'skipped'; a frost named explicitly is a ValueError."""
+    from ..noise import imagenet_c as C
+    names, explicit = imagenet_c_names(getattr(args, 'imagenet_c_names', None))
+    sevs = imagenet_c_severities(getattr(args, 'imagenet_c_severities', None))
+    dcfg = cfg.get('data', {}) or {}
+    if (getattr(args, 'attack', None) and args.attack != 'none') or getattr(args, 'corruption', None) or getattr(args, 'imagenet_s', False) \
+            or natural_mode(dcfg):
+        raise ValueError('--imagenet-c cannot be combined with --attack, --corruption, --imagenet-s or data.test.imagenet_a&o: the loop '
+                         'applies every corruption itself and no config of imagenet_c_loop_mini has another noise')
+    if getattr(args, 'imagenet_c_scores', False) and not getattr(args, 'save_dir', None):
+        raise ValueError('--imagenet-c-scores writes the full result files: it needs --save-dir')
+    frost_dir = getattr(args, 'imagenet_c_frost_dir', None) or (dcfg.get('test') or {}).get('imagenet_c_frost_dir')
+    skipped = []
+    if 'frost' in names and not frost_dir and not C._frost_textures:
+        if explicit:
+            raise ValueError('--imagenet-c-names names frost, which needs photographs: pass --imagenet-c-frost-dir (or '
+                             'data.test.imagenet_c_frost_dir)')
+        names = [t for t in names if t != 'frost']
+        skipped = ['frost']
+    return {'names': names, 'severities': sevs, 'skipped': skipped, 'frost_dir': frost_dir}
+
+
+def evaluate_imagenet_c(cfg, args, rank, world, device, model=None):
+    """`--evaluate --imagenet-c`: the loop of exp/imagenet_c_loop_mini: one model scored on every (corruption, severity) pair in one
+    pass over the test set.  Per batch of sharded indices the dataset is read ONCE (any data.read_from); every pair corrupts that
+    batch into one scratch buffer (the source batch is never written), the engine turns it into logits and rart_topk_score_f32 adds
+    the top-1 / top-5 hits to the pair's two counters, which stay on the device: nothing is read on the host inside the loop, and
+    one all_reduce and one read end it.  gaussian_noise and speckle_noise run all their severities in one noise_severities_ launch
+    (bit-identical to the per-severity calls).  Seed and sample offset are those of a single `--corruption NAME --severity S` run,
+    so a pair's inputs, logits and result directory <save_dir>/<model>/<corruption>_<severity>/ are that run's.  With --save-dir a
+    pair's file holds RankWriter lines (prediction, label, rank: 8 bytes per sample off the device), or the full ResultWriter lines
+    under --imagenet-c-scores; rank 0 evaluates every file with ImageNetCEvaluator.  Accuracies are percentages, as the evaluator's.
+    The reference's multi_eval_solver, which defines this loop's summary, is absent from the reference tree: the form of the
+    printed line ('imagenet_c' per pair, 'error' = mean top-1 error per corruption over the severities run, 'Mean' of those, 'skipped')
+    is unpinned."""
+    plan = imagenet_c_plan(cfg, args)
+    if device.type != 'cuda':
+        raise RuntimeError('--imagenet-c runs on the GPU (the corruptions and the scorer are HIP kernels; no CPU fallback)')
+    from ..metrics import ImageNetCEvaluator, RankWriter, ResultWriter, result_dir, topk_score
+    from ..noise import imagenet_c as C
+    if plan['frost_dir'] and 'frost' in plan['names']:
+        C.set_frost_textures(read_frost_textures(plan['frost_dir']))
+    names, sevs = plan['names'], plan['severities']
+    dcfg = cfg.get('data', {})
+    bs = int(dcfg.get('batch_size', 64))
+    size = int(dcfg.get('input_size', 224))
+    ds = make_dataset(dcfg, int(dcfg.get('fake_size', dcfg.get('limit_samples', 256))), size, 'test')
+    idx = shard_indices(len(ds), rank, world)
+    model = model or build_model(cfg, args)
+    model = model.to(device).eval()
+    use_hip = args.engine == 'hip'
+    if use_hip:
+        from ..model.engine import EngineModel
+        prec = getattr(args, 'precision', None) or cfg.get('engine_precision', 'bf16')
+        f_model = EngineModel(model, takes_normalized=False, precision=prec)
+    mean = torch.tensor(IMAGENET_MEAN, device=device).view(1, 3, 1, 1)
+    std = torch.tensor(IMAGENET_STD, device=device).view(1, 3, 1, 1)
+    name = getattr(args, 'src_name', None) or cfg['model']['type']
+    save_dir = getattr(args, 'save_dir', None)
+    full = bool(getattr(args, 'imagenet_c_scores', False))
+    pairs = [(c, s) for c in names for s in sevs]
+    slot = {p: k for k, p in enumerate(pairs)}
+    writers = {}
+    if save_dir:
+        writers = {p: (ResultWriter if full else RankWriter)(result_dir(save_dir, name, p[0], '%d' % p[1]), rank, world) for p in pairs}
+    counters = torch.zeros(2 * len(pairs) + 1, dtype=torch.int64, device=device)      # (top-1, top-5) per pair, then the sample count
+    fused = [c for c in ('gaussian_noise', 'speckle_noise') if c in names and len(sevs) > 1]
+    scratch = []
+    cnt = 0
+    t0 = time.time()
+
+    def score(x, pair, labels, lab_host, items):
+        if use_hip:
+            logits = f_model.rart_engine.logits_from_u8(x, IMAGENET_MEAN, IMAGENET_STD)
+        else:
+            with torch.no_grad():
+                logits = model((x.permute(0, 3, 1, 2).float() / 255.0 - mean) / std)
+        w = writers.get(pair)
+        keep = w is not None and not full
+        p, r = topk_score(logits.float(), labels, ks=(1, 5), hits=counters[2 * slot[pair]:], pred=keep, rank=keep)
+        if keep:
+            w.write_batch(p, r, lab_host, items)
+        elif w is not None:
+            w.write_batch(logits, labels, items)
+
+    for s in range(0, len(idx), bs):
+        items = idx[s:s + bs]
+        imgs, labels = ds.batch(items, device)                    # once per batch, whatever the number of pairs
+        first = items[0]                                          # global index of the batch's first sample
+        cnt += len(items)
+        lab_host = labels.tolist() if writers and not full else None
+        if not scratch or scratch[0].shape != imgs.shape:
+            scratch = [torch.empty_like(imgs) for _ in range(len(sevs) if fused else 1)]
+        for c in names:
+            cid = C.CORRUPTION_NAMES.index(c)
+            if c in fused:
+                C.noise_severities_(imgs, scratch, sevs, seeds=[args.seed] * len(sevs), sample_offset=first, corruption_id=cid)
+                for k, sv in enumerate(sevs):
+                    score(scratch[k], (c, sv), labels, lab_host, items)
+            else:
+                for sv in sevs:
+                    C.corrupt_batch_(imgs, cid, sv, seed=args.seed, sample_offset=first, out=scratch[0])
+                    score(scratch[0], (c, sv), labels, lab_host, items)
+    barrier = dist.barrier if dist.is_available() and dist.is_initialized() else None
+    paths = {}
+    if writers:
+        for w in writers.values():
+            w.f.close()
+        if barrier is not None:
+            barrier()                                             # one for all the files: every shard is on disk before rank 0 merges
+        paths = {p: writers[p].close() for p in pairs}
+    counters[-1] = cnt
+    if dist.is_available() and dist.is_initialized():
+        dist.all_reduce(counters)
+    flat = counters.tolist()                                      # the loop's only read of a counter
+    cnt = int(flat[-1])
+    res = None
+    if rank == 0:
+        ev = ImageNetCEvaluator(topk=(1, 5))
+        acc = {}
+        for k, p in enumerate(pairs):
+            if paths:
+                m = ev.eval(paths[p]).metric
+                acc['%s/%d' % p] = {'top1': m['top1'], 'top5': m['top5']}
+            else:
+                acc['%s/%d' % p] = {'top1': float(flat[2 * k] * (100.0 / max(cnt, 1))), 'top5': float(flat[2 * k + 1] * (100.0 / max(cnt, 1)))}
+        error = {c: 100.0 - sum(acc['%s/%d' % (c, sv)]['top1'] for sv in sevs) / len(sevs) for c in names}
+        res = {'imagenet_c': acc, 'error': error, 'Mean': sum(error.values()) / len(error) if error else None,
+               'skipped': plan['skipped'], 'count': cnt, 'world_size': world, 'seconds': time.time() - t0}
+        print(json.dumps(res))
+    return res
+
+
 def evaluate(cfg, args, rank, world, device, model=None):
     """Clean / corrupted / attacked evaluation over the sharded dataset; returns the reduced metrics dict."""
     dcfg = cfg.get('data', {})
+    if getattr(args, 'imagenet_c', False):
+        return evaluate_imagenet_c(cfg, args, rank, world, device, model)
     if getattr(args, 'imagenet_s', False):
         return evaluate_imagenet_s(cfg, args, rank, world, device, model)
     if natural_mode(dcfg):
@@ -1242,7 +1437,24 @@ def main(argv=None):
                     help='with --evaluate: the ImageNet-S loop (exp/imagenet_s_loop): one pass per (decoder, resize operator) pair')
     ap.add_argument('--imagenet-s-ops', default=None, dest='imagenet_s_ops',
                     help='comma-separated resize operators of --imagenet-s (default: the six pil-* then the five opencv-*)')
+    ap.add_argument('--imagenet-c', action='store_true', dest='imagenet_c',
+                    help='with --evaluate: the ImageNet-C loop (exp/imagenet_c_loop_mini): every corruption at every severity in one '
+                         'pass over the test set')
+    ap.add_argument('--imagenet-c-names', default=None, dest='imagenet_c_names',
+                    help="comma-separated corruptions of --imagenet-c (default: the 15 standard ones; 'all' adds the four extras)")
+    ap.add_argument('--imagenet-c-severities', default=None, dest='imagenet_c_severities',
+                    help='comma-separated severities of --imagenet-c (default: 1,2,3,4,5)')
+    ap.add_argument('--imagenet-c-frost-dir', default=None, dest='imagenet_c_frost_dir',
+                    help='folder of frost photographs, read in sorted order (also data.test.imagenet_c_frost_dir); without it the '
+                         'default list leaves frost out')
+    ap.add_argument('--imagenet-c-scores', action='store_true', dest='imagenet_c_scores',
+                    help='with --imagenet-c and --save-dir: write the full score lines instead of the compact rank lines')
     args = ap.parse_args(argv)
+    if args.imagenet_c:
+        if not args.evaluate:
+            raise ValueError('--imagenet-c is an evaluation loop: pass --evaluate')
+        imagenet_c_names(args.imagenet_c_names)       # an unknown name or severity fails before the config is read
+        imagenet_c_severities(args.imagenet_c_severities)
     if args.imagenet_s:
         imagenet_s_ops(args.imagenet_s_ops)           # an unknown name fails before anything is built
         if not args.evaluate:
