@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import _topk_score_ref as T
+from _tiny_eval_model import tiny_eval_model
 
 pytestmark = pytest.mark.gpu
 
@@ -47,27 +48,6 @@ def _args(**kw):
 
 def _cfg(model):
     return {'model': model, 'data': {'fake_size': N, 'batch_size': BS, 'input_size': 224, 'read_from': 'fake'}}
-
-
-def _tiny_model():
-    """The tiny model of the solver's distributed test, with the biases of the eight samples' label classes lifted to the top of
-    the logits in steps: the images are noise, so every sample sees nearly the same logits, and the eight labels then sit at ranks
-    around 0 .. 7 -- on both sides of k = 1 and k = 5 -- instead of all being misses."""
-    from robustart_amd.train import cls_solver as S
-    torch.manual_seed(0)
-    m = torch.nn.Sequential(torch.nn.Conv2d(3, 4, 3, stride=4), torch.nn.ReLU(), torch.nn.AdaptiveAvgPool2d(1), torch.nn.Flatten(),
-                            torch.nn.Linear(4, 1000)).eval()
-    x, y = S.FakeImageNet(N, 224).batch(range(N), 'cpu')
-    mean, std = torch.tensor(S.IMAGENET_MEAN).view(1, 3, 1, 1), torch.tensor(S.IMAGENET_STD).view(1, 3, 1, 1)
-    with torch.no_grad():
-        lg = m((x.permute(0, 3, 1, 2).float() / 255.0 - mean) / std)
-        top, spread = lg.max(), lg.std()
-        for i, lab in enumerate(y.tolist()):
-            m[-1].bias[lab] += (top - lg[:, lab].mean()) + spread * (0.3 - 0.1 * i)
-    assert len(set(y.tolist())) == N
-    for p in m.parameters():
-        p.requires_grad_(False)
-    return m
 
 
 def _quiet(fn, *a, **k):
@@ -113,7 +93,7 @@ def tiny(tmp_path_factory):
     from robustart_amd.train import cls_solver as S
     C.set_frost_textures([])                              # whatever an earlier test registered: this fixture runs without photographs
     root = tmp_path_factory.mktemp('imagenet_c_tiny')
-    model = _tiny_model()
+    model = tiny_eval_model(N)
     cfg = _cfg({'type': 'tiny_imagenet_c_test'})
     names = [n for n in C.CORRUPTION_NAMES[:15] if n != 'frost']
     pairs = [(c, s) for c in names for s in (1, 2, 3, 4, 5)]
