@@ -568,8 +568,10 @@ int rart_conv3x3_tail_pair_get_staging(void);
 int rart_conv3x3_tail_pair_set_tables(int mode);
 int rart_conv3x3_tail_pair_get_tables(void);
 
-/* Row / elementwise kernels of the reference-precision ViT-B/16 engine (csrc/vit_pair.hip): every tensor a pair of bf16 planes, the
- * arithmetic in fp32 as the fp32 module (timm ViT-B/16, RobustART/model/__init__.py:1 -> absent submodule) does it.
+/* Row / elementwise kernels of the reference-precision ViT-B/16 engine (soft-max rows, unpatchify: csrc/vit_pair.hip; layernorm
+ * and its backward: csrc/row_norm.hip, one kernel per direction for this storage and for bf16; add_pos_cls: csrc/vit_aux.hip,
+ * likewise): every tensor a pair of bf16 planes, the arithmetic in fp32 as the fp32 module (timm ViT-B/16,
+ * RobustART/model/__init__.py:1 -> absent submodule) does it.
  * add_pos_cls: x[b][0][:] = cls_pos0, x[b][t][:] += pos[t].  layernorm: eps inside the root, biased variance; rows of dim <= 1024.
  * layernorm_bwd: dx = rstd (g - mean(g) - xhat mean(g xhat)) [+ res pair], g = dy gamma.  softmax_rows: P = softmax(scale S) of fp32
  * scores (the pair GEMM's fp32 output), zero beyond n_valid up to ld_out (<= 256 columns).  softmax_bwd_rows: dS = scale P (dP - <P, dP>),

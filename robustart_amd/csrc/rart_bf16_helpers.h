@@ -89,6 +89,12 @@ __device__ __forceinline__ void split4(const float* v, uint2& hi, uint2& lo) {
   lo = make_uint2(pack_bf16x2(v[0] - __uint_as_float(h0 << 16), v[1] - __uint_as_float(h0 & 0xFFFF0000u)),
                   pack_bf16x2(v[2] - __uint_as_float(h1 << 16), v[3] - __uint_as_float(h1 & 0xFFFF0000u)));
 }
+__device__ __forceinline__ void join4(const uint2& hi, const uint2& lo, float* v) {
+  v[0] = __uint_as_float(hi.x << 16) + __uint_as_float(lo.x << 16);
+  v[1] = __uint_as_float(hi.x & 0xFFFF0000u) + __uint_as_float(lo.x & 0xFFFF0000u);
+  v[2] = __uint_as_float(hi.y << 16) + __uint_as_float(lo.y << 16);
+  v[3] = __uint_as_float(hi.y & 0xFFFF0000u) + __uint_as_float(lo.y & 0xFFFF0000u);
+}
 __device__ __forceinline__ void join8(const uint4& hi, const uint4& lo, float* v) {
   const uint32_t h[4] = {hi.x, hi.y, hi.z, hi.w}, l[4] = {lo.x, lo.y, lo.z, lo.w};
 #pragma unroll

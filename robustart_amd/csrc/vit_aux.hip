@@ -1,10 +1,11 @@
 // Non-GEMM kernels of the ViT-B/16 forward engine (gfx950): patch extraction (+normalise, bf16 hi/lo split),
-// class-token / position-embedding add, LayerNorm, attention soft-max rows and the V transpose that lets
-// P.V run on the implicit-GEMM kernel.  bf16 storage, fp32 statistics.  Reference: RobustART/model/__init__.py:1
-// -> absent submodule; `vit_base` = timm ViT-B/16 (jx_vit_base_p16_224): 12 blocks, width 768,
+// class-token / position-embedding add (bf16 and pair storage), attention soft-max rows and the V transpose that lets
+// P.V run on the implicit-GEMM kernel.  bf16 storage, fp32 statistics.  (LayerNorm: csrc/row_norm.hip.)
+// Reference: RobustART/model/__init__.py:1 -> absent submodule; `vit_base` = timm ViT-B/16 (jx_vit_base_p16_224): 12 blocks, width 768,
 // 12 heads, qkv bias, LayerNorm eps 1e-6, exact GELU.
 #include "rart_common.h"
 #include "rart_bf16_helpers.h"
+#include "rart_row_norm.h"
 
 namespace {
 using namespace rart_bf16;
@@ -49,71 +50,27 @@ __global__ __launch_bounds__(kBlock) void k_patchify(const void* __restrict__ sr
   }
 }
 
-// x[b][0][:] = cls_pos0; x[b][t][:] += pos[t] (t >= 1); eight channels per thread (d % 8 == 0)
-__global__ __launch_bounds__(kBlock) void k_add_pos_cls(uint16_t* __restrict__ x, const float* __restrict__ cls_pos0,
-                                                        const float* __restrict__ pos, int n, int t, int d) {
+// x[b][0][:] = cls_pos0; x[b][t][:] += pos[t] (t >= 1); eight channels per thread (d % 8 == 0).  bf16 storage (xl unused) or a pair
+template <bool PAIR>
+__global__ __launch_bounds__(kBlock) void k_add_pos_cls(uint16_t* __restrict__ xh, uint16_t* __restrict__ xl,
+                                                        const float* __restrict__ cls_pos0, const float* __restrict__ pos, int n,
+                                                        int t, int d) {
   const uint32_t d8 = (uint32_t)d / 8, total = (uint32_t)n * t * d8;
   for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < total; i += gridDim.x * kBlock) {
     const uint32_t c8 = i % d8, tok = (i / d8) % (uint32_t)t;
     const float* add = tok == 0 ? cls_pos0 + c8 * 8 : pos + (size_t)tok * d + c8 * 8;
     const float4 a0 = reinterpret_cast<const float4*>(add)[0], a1 = reinterpret_cast<const float4*>(add)[1];
     const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-    uint4 xv = reinterpret_cast<uint4*>(x)[i];
-    uint32_t xw[4] = {xv.x, xv.y, xv.z, xv.w};
+    float v[8];
+    row_load8<PAIR>(xh, xl, (size_t)i * 8, v);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float b0 = tok == 0 ? 0.f : __uint_as_float(xw[j] << 16), b1 = tok == 0 ? 0.f : __uint_as_float(xw[j] & 0xFFFF0000u);
-      xw[j] = (uint32_t)f2bf(b0 + av[2 * j]) | ((uint32_t)f2bf(b1 + av[2 * j + 1]) << 16);
-    }
-    reinterpret_cast<uint4*>(x)[i] = make_uint4(xw[0], xw[1], xw[2], xw[3]);
+    for (int j = 0; j < 8; ++j) v[j] = (tok == 0 ? 0.f : v[j]) + av[j];
+    row_store8<PAIR>(xh, xl, (size_t)i * 8, v);
   }
 }
 
 // ---- row kernels: one wave per row, the row lives in registers as 16-byte vectors (lane l holds vectors l and l + 64),
 //      so every tensor is read exactly once with coalesced 16-byte loads.  Rows of up to 1024 elements, multiple of 8.
-
-// LayerNorm over the last dim, fp32 two-pass statistics.  (Round 5, scratch/r5/time_layernorm.py: 36.4 us per launch on [256 x 197][768] = 4.25 TB/s on
-// input + output; a wave walking eight rows with gamma / beta in registers and the next row prefetched was SLOWER, 49.2 us: one row per wave
-// keeps far more rows in flight, and the 6 KB of gamma / beta per row are L1 hits.)
-__global__ __launch_bounds__(kBlock) void k_layernorm(const uint16_t* __restrict__ x, const float* __restrict__ g,
-                                                      const float* __restrict__ b, uint16_t* __restrict__ out,
-                                                      int rows, int d, long long in_stride, long long out_stride,
-                                                      float eps) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int nv = d / 8;
-  float xr[2][8];
-  load_row(x + (size_t)row * in_stride, nv, lane, xr);
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s += xr[k][j];                   // padding vectors are zero
-  const float mean = rart_wave_sum(s) / (float)d;
-  float v = 0.f;
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-    if (lane + 64 * k < nv) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float t = xr[k][j] - mean;
-        v += t * t;
-      }
-    }
-  const float rstd = rsqrtf(rart_wave_sum(v) / (float)d + eps);
-  uint16_t* o = out + (size_t)row * out_stride;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int vi = lane + 64 * k;
-    if (vi < nv) {
-      float r[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) r[j] = (xr[k][j] - mean) * rstd * g[vi * 8 + j] + b[vi * 8 + j];
-      *reinterpret_cast<uint4*>(o + (size_t)vi * 8) = pack8(r);
-    }
-  }
-}
 
 // P[row][0..n_valid) = softmax(scale * S[row][0..n_valid)), P[row][n_valid..ld_out) = 0
 __global__ __launch_bounds__(kBlock) void k_softmax_rows(const uint16_t* __restrict__ sm, uint16_t* __restrict__ pm,
@@ -638,21 +595,19 @@ int rart_vit_add_pos_cls(void* x, const float* cls_pos0, const float* pos, int n
                          rart_stream_t stream) {
   RART_CHECK_ARG(x && cls_pos0 && pos && n > 0 && tokens > 0 && dim > 0 && dim % 8 == 0 && (size_t)n * tokens * dim / 8 < (1ull << 32),
                  "rart_vit_add_pos_cls: bad arguments (dim must be a multiple of 8)");
-  hipLaunchKernelGGL(k_add_pos_cls, dim3(grid_for((size_t)n * tokens * dim / 8)), dim3(kBlock), 0, (hipStream_t)stream,
-                     (uint16_t*)x, cls_pos0, pos, n, tokens, dim);
+  hipLaunchKernelGGL(k_add_pos_cls<false>, dim3(grid_for((size_t)n * tokens * dim / 8)), dim3(kBlock), 0, (hipStream_t)stream,
+                     (uint16_t*)x, (uint16_t*)nullptr, cls_pos0, pos, n, tokens, dim);
   RART_CHECK_LAUNCH("rart_vit_add_pos_cls");
   return RART_OK;
 }
 
-int rart_layernorm_bf16(const void* x, const float* gamma, const float* beta, void* out, int rows, int dim,
-                        int64_t in_row_stride, int64_t out_row_stride, float eps, rart_stream_t stream) {
-  RART_CHECK_ARG(x && gamma && beta && out && rows > 0 && dim > 0, "rart_layernorm_bf16: bad arguments");
-  RART_CHECK_ARG(dim % 8 == 0 && dim <= 1024 && in_row_stride % 8 == 0 && out_row_stride % 8 == 0,
-                 "rart_layernorm_bf16: dim must be a multiple of 8, at most 1024; row strides multiples of 8");
-  hipLaunchKernelGGL(k_layernorm, dim3((rows + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, (hipStream_t)stream,
-                     (const uint16_t*)x, gamma, beta, (uint16_t*)out, rows, dim, (long long)in_row_stride,
-                     (long long)out_row_stride, eps);
-  RART_CHECK_LAUNCH("rart_layernorm_bf16");
+int rart_vit_add_pos_cls_pair(void* x_hi, void* x_lo, const float* cls_pos0, const float* pos, int n, int tokens, int dim,
+                              rart_stream_t stream) {
+  RART_CHECK_ARG(x_hi && x_lo && cls_pos0 && pos && n > 0 && tokens > 0 && dim > 0 && dim % 8 == 0 &&
+                     (size_t)n * tokens * dim / 8 < (1ull << 32), "rart_vit_add_pos_cls_pair: bad arguments");
+  hipLaunchKernelGGL(k_add_pos_cls<true>, dim3(grid_for((size_t)n * tokens * dim / 8)), dim3(kBlock), 0, (hipStream_t)stream,
+                     (uint16_t*)x_hi, (uint16_t*)x_lo, cls_pos0, pos, n, tokens, dim);
+  RART_CHECK_LAUNCH("rart_vit_add_pos_cls_pair");
   return RART_OK;
 }
 

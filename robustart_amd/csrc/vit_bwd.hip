@@ -4,8 +4,10 @@
 // products of the attention backward (dP = dO V^T, dQ = dS K, dK = dS^T Q, dV = P^T dO, and the recomputed
 // S = Q K^T) -- run on rart_conv_igemm_bf16 as batched problems; transposed operands come from
 // rart_transpose_gather_bf16 / rart_vit_transpose_v.  HBM-bound row / elementwise kernels, bf16 storage, fp32 math.
+// (The LayerNorm backward to the input alone: csrc/row_norm.hip.)
 #include "rart_common.h"
 #include "rart_bf16_helpers.h"
+#include "rart_row_norm.h"
 
 namespace {
 using namespace rart_bf16;
@@ -42,70 +44,6 @@ __global__ __launch_bounds__(kBlock) void k_gelu(const uint4* __restrict__ a, co
       o[j] = f2bf(r0) | ((uint32_t)f2bf(r1) << 16);
     }
     out[i] = make_uint4(o[0], o[1], o[2], o[3]);
-  }
-}
-
-// LayerNorm backward to the input, one wave per row, rows held in registers as 16-byte vectors (every tensor is read
-// once); statistics recomputed from x in fp32:
-//   xhat = (x - mean) * rstd;  g = dy * gamma;  dx = rstd * (g - mean(g) - xhat * mean(g * xhat)) [+ res]
-__global__ __launch_bounds__(kBlock) void k_layernorm_bwd(const uint16_t* __restrict__ dy, const uint16_t* __restrict__ x,
-                                                          const float* __restrict__ gamma, const uint16_t* __restrict__ res,
-                                                          uint16_t* __restrict__ dx, int rows, int d, long long dy_stride,
-                                                          long long x_stride, long long res_stride, long long dx_stride,
-                                                          float eps) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int nv = d / 8;
-  float xr[2][8], gr[2][8];
-  load_row(x + (size_t)row * x_stride, nv, lane, xr);
-  load_row(dy + (size_t)row * dy_stride, nv, lane, gr);
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s += xr[k][j];
-  const float mean = rart_wave_sum(s) / (float)d;
-  float v = 0.f;
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-    if (lane + 64 * k < nv) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float t = xr[k][j] - mean;
-        v += t * t;
-      }
-    }
-  const float rstd = rsqrtf(rart_wave_sum(v) / (float)d + eps);
-  float sg = 0.f, sgx = 0.f;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int vi = lane + 64 * k;
-    if (vi < nv) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        gr[k][j] *= gamma[vi * 8 + j];
-        xr[k][j] = (xr[k][j] - mean) * rstd;                     // xhat
-        sg += gr[k][j];
-        sgx += gr[k][j] * xr[k][j];
-      }
-    }
-  }
-  const float mg = rart_wave_sum(sg) / (float)d, mgx = rart_wave_sum(sgx) / (float)d;
-  uint16_t* o = dx + (size_t)row * dx_stride;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int vi = lane + 64 * k;
-    if (vi < nv) {
-      float r[8], rs[8];
-      if (res) unpack8(*reinterpret_cast<const uint4*>(res + (size_t)row * res_stride + (size_t)vi * 8), rs);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        r[j] = rstd * (gr[k][j] - mg - xr[k][j] * mgx);
-        if (res) r[j] += rs[j];
-      }
-      *reinterpret_cast<uint4*>(o + (size_t)vi * 8) = pack8(r);
-    }
   }
 }
 
@@ -180,19 +118,6 @@ int rart_gelu_bwd_bf16(const void* dh, const void* u, void* du, size_t n, rart_s
   return RART_OK;
 }
 
-int rart_layernorm_bwd_bf16(const void* dy, const void* x, const float* gamma, const void* res, void* dx, int rows, int dim,
-                            int64_t dy_row_stride, int64_t x_row_stride, int64_t res_row_stride, int64_t dx_row_stride,
-                            float eps, rart_stream_t stream) {
-  RART_CHECK_ARG(dy && x && gamma && dx && rows > 0 && dim > 0, "rart_layernorm_bwd_bf16: bad arguments");
-  RART_CHECK_ARG(dim % 8 == 0 && dim <= 1024 && dy_row_stride % 8 == 0 && x_row_stride % 8 == 0 && res_row_stride % 8 == 0 &&
-                     dx_row_stride % 8 == 0, "rart_layernorm_bwd_bf16: dim a multiple of 8, at most 1024; strides multiples of 8");
-  hipLaunchKernelGGL(k_layernorm_bwd, dim3((rows + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, (hipStream_t)stream,
-                     (const uint16_t*)dy, (const uint16_t*)x, gamma, (const uint16_t*)res, (uint16_t*)dx, rows, dim,
-                     (long long)dy_row_stride, (long long)x_row_stride, (long long)res_row_stride, (long long)dx_row_stride, eps);
-  RART_CHECK_LAUNCH("rart_layernorm_bwd_bf16");
-  return RART_OK;
-}
-
 int rart_softmax_bwd_rows_bf16(const void* probs, const void* dprobs, void* dscores, int64_t rows, int n_valid, int ld_p,
                                int ld_dp, int ld_out, float scale, rart_stream_t stream) {
   RART_CHECK_ARG(probs && dprobs && dscores && rows > 0 && n_valid > 0 && ld_p >= n_valid && ld_dp >= n_valid &&
@@ -225,7 +150,8 @@ int rart_vit_unpatchify_f32(const void* dpatches, float* grad, int n, int h, int
 // ---- parameter-gradient reductions for ViT training (LayerNorm gamma / beta, Linear biases, position embedding) ----
 namespace {
 // LayerNorm backward to the input AND per-wave partial sums of dgamma = sum_rows dy*xhat, dbeta = sum_rows dy:
-// a wave walks rows (grid stride), so its 2 x 8 column slots accumulate in registers; partial[wave][2][d] fp32.
+// a wave walks rows (grid stride), so its 2 x 8 column slots accumulate in registers; partial[wave][2][d] fp32.  Load, statistics
+// and the dx write are rart_row_norm.h's; the middle loop is its own (gamma in registers, ag / ab taken before the gamma multiply).
 __global__ __launch_bounds__(kBlock) void k_layernorm_bwd_full(const uint16_t* __restrict__ dy, const uint16_t* __restrict__ x,
                                                                const float* __restrict__ gamma, const uint16_t* __restrict__ res,
                                                                uint16_t* __restrict__ dx, int rows, int d, long long dy_stride,
@@ -244,26 +170,10 @@ __global__ __launch_bounds__(kBlock) void k_layernorm_bwd_full(const uint16_t* _
       gm[k][j] = vi < nv ? gamma[vi * 8 + j] : 0.f;
     }
   for (int row = wave_g; row < rows; row += n_waves) {
-    float xr[2][8], gr[2][8];
-    load_row(x + (size_t)row * x_stride, nv, lane, xr);
-    load_row(dy + (size_t)row * dy_stride, nv, lane, gr);
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s += xr[k][j];
-    const float mean = rart_wave_sum(s) / (float)d;
-    float v = 0.f;
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-      if (lane + 64 * k < nv) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float t = xr[k][j] - mean;
-          v += t * t;
-        }
-      }
-    const float rstd = rsqrtf(rart_wave_sum(v) / (float)d + eps);
+    float xr[2][8], gr[2][8], mean, rstd;
+    row_load<false>(x + (size_t)row * x_stride, nullptr, nv, lane, xr);
+    row_load<false>(dy + (size_t)row * dy_stride, nullptr, nv, lane, gr);
+    ln_row_stats<false>(xr, nv, lane, d, eps, mean, rstd);
     float sg = 0.f, sgx = 0.f;
 #pragma unroll
     for (int k = 0; k < 2; ++k)
@@ -285,14 +195,9 @@ __global__ __launch_bounds__(kBlock) void k_layernorm_bwd_full(const uint16_t* _
       for (int k = 0; k < 2; ++k) {
         const int vi = lane + 64 * k;
         if (vi < nv) {
-          float r[8], rs[8];
-          if (res) unpack8(*reinterpret_cast<const uint4*>(res + (size_t)row * res_stride + (size_t)vi * 8), rs);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            r[j] = rstd * (gr[k][j] - mg - xr[k][j] * mgx);
-            if (res) r[j] += rs[j];
-          }
-          *reinterpret_cast<uint4*>(o + (size_t)vi * 8) = pack8(r);
+          float rs[8];
+          if (res) row_load8<false>(res + (size_t)row * res_stride, nullptr, (size_t)vi * 8, rs);
+          ln_store_dx8<false>(gr[k], xr[k], rstd, mg, mgx, res != nullptr, rs, o, nullptr, (size_t)vi * 8);
         }
       }
     }

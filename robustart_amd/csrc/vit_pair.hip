@@ -1,9 +1,9 @@
 // Non-GEMM kernels of the REFERENCE-PRECISION ("fp32x" / "bf16x3") ViT-B/16 engine for gfx950: every activation and gradient is a
 // PAIR of bf16 planes (value = hi + lo, 16 significand bits; exact in fp32), every contraction runs on rart_gemm_pair_bf16
-// (csrc/gemm_pair.hip), and what is left -- class-token / position add, LayerNorm forward and backward-to-input, the attention
-// soft-max rows and their backward -- are the HBM-bound row kernels below: read the pair, compute in fp32 exactly as the fp32 module
-// does (two-pass LayerNorm statistics, max-subtracted soft-max with libm's expf), write the pair.  The reference runs ViT in fp32
-// (exprs/exp/imagenet_c_loop_mini/config_vit_base.yaml:1-9: no precision key; adv/attack.py:20-23; autopgd_base.py:271-289); model
+// (csrc/gemm_pair.hip), and what is left here -- the attention soft-max rows and their backward -- are the HBM-bound row kernels
+// below: read the pair, compute in fp32 exactly as the fp32 module does (max-subtracted soft-max with libm's expf), write the pair.
+// (LayerNorm forward and backward-to-input: csrc/row_norm.hip; the class-token / position add: csrc/vit_aux.hip.)  The reference runs
+// ViT in fp32 (exprs/exp/imagenet_c_loop_mini/config_vit_base.yaml:1-9: no precision key; adv/attack.py:20-23; autopgd_base.py:271-289); model
 // `vit_base` = timm ViT-B/16 (RobustART/model/__init__.py:1 -> absent submodule; robustart_amd/model/vit_torch.py).
 #include "rart_common.h"
 #include "rart_bf16_helpers.h"
@@ -13,152 +13,6 @@
 namespace {
 using namespace rart_bf16;
 constexpr int kBlock = 256;
-
-// one wave per row, the row in registers as 16-byte vectors (lane l holds vectors l and l + 64): rows of up to 1024 elements
-template <bool NT = false>
-__device__ __forceinline__ void load_row_pair(const uint16_t* hi, const uint16_t* lo, int nv, int lane, float r[2][8]) {
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int v = lane + 64 * k;
-    uint4 qh = make_uint4(0, 0, 0, 0), ql = make_uint4(0, 0, 0, 0);
-    if (v < nv) {
-      qh = NT ? rart_nt_load16(hi + (size_t)v * 8) : *reinterpret_cast<const uint4*>(hi + (size_t)v * 8);
-      ql = NT ? rart_nt_load16(lo + (size_t)v * 8) : *reinterpret_cast<const uint4*>(lo + (size_t)v * 8);
-    }
-    join8(qh, ql, r[k]);
-  }
-}
-#define RART_LNB_LOAD load_row_pair<true>      // the LayerNorm backward reads its inputs for the last time: non-temporal (65.63 -> 65.34 ms)
-
-// x[b][0][:] = cls_pos0; x[b][t][:] += pos[t] (t >= 1); eight channels per thread (d % 8 == 0)
-__global__ __launch_bounds__(kBlock) void k_add_pos_cls_pair(uint16_t* __restrict__ xh, uint16_t* __restrict__ xl,
-                                                             const float* __restrict__ cls_pos0, const float* __restrict__ pos, int n,
-                                                             int t, int d) {
-  const uint32_t d8 = (uint32_t)d / 8, total = (uint32_t)n * t * d8;
-  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < total; i += gridDim.x * kBlock) {
-    const uint32_t c8 = i % d8, tok = (i / d8) % (uint32_t)t;
-    const float* add = tok == 0 ? cls_pos0 + c8 * 8 : pos + (size_t)tok * d + c8 * 8;
-    const float4 a0 = reinterpret_cast<const float4*>(add)[0], a1 = reinterpret_cast<const float4*>(add)[1];
-    float v[8];
-    join8(reinterpret_cast<const uint4*>(xh)[i], reinterpret_cast<const uint4*>(xl)[i], v);
-    const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (tok == 0 ? 0.f : v[j]) + av[j];
-    uint4 oh, ol;
-    split8(v, oh, ol);
-    reinterpret_cast<uint4*>(xh)[i] = oh;
-    reinterpret_cast<uint4*>(xl)[i] = ol;
-  }
-}
-
-// LayerNorm over the last dim, fp32 two-pass statistics (torch's layer_norm: biased variance, eps inside the root)
-__global__ __launch_bounds__(kBlock) void k_layernorm_pair(const uint16_t* __restrict__ xh, const uint16_t* __restrict__ xl,
-                                                           const float* __restrict__ g, const float* __restrict__ b,
-                                                           uint16_t* __restrict__ oh, uint16_t* __restrict__ ol, int rows, int d,
-                                                           long long in_stride, long long out_stride, float eps) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int nv = d / 8;
-  float xr[2][8];
-  load_row_pair(xh + (size_t)row * in_stride, xl + (size_t)row * in_stride, nv, lane, xr);
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s += xr[k][j];                   // padding vectors are zero
-  const float mean = rart_wave_sum(s) / (float)d;
-  float v = 0.f;
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-    if (lane + 64 * k < nv) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float t = xr[k][j] - mean;
-        v += t * t;
-      }
-    }
-  const float rstd = 1.0f / sqrtf(rart_wave_sum(v) / (float)d + eps);
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int vi = lane + 64 * k;
-    if (vi < nv) {
-      float r[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) r[j] = (xr[k][j] - mean) * rstd * g[vi * 8 + j] + b[vi * 8 + j];
-      uint4 ph, pl;
-      split8(r, ph, pl);
-      *reinterpret_cast<uint4*>(oh + (size_t)row * out_stride + (size_t)vi * 8) = ph;
-      *reinterpret_cast<uint4*>(ol + (size_t)row * out_stride + (size_t)vi * 8) = pl;
-    }
-  }
-}
-
-// LayerNorm backward to the input: xhat = (x - mean) rstd; g = dy gamma; dx = rstd (g - mean(g) - xhat mean(g xhat)) [+ res]
-__global__ __launch_bounds__(kBlock) void k_layernorm_bwd_pair(const uint16_t* __restrict__ dyh, const uint16_t* __restrict__ dyl,
-                                                               const uint16_t* __restrict__ xh, const uint16_t* __restrict__ xl,
-                                                               const float* __restrict__ gamma, const uint16_t* __restrict__ rh,
-                                                               const uint16_t* __restrict__ rl, uint16_t* __restrict__ oh,
-                                                               uint16_t* __restrict__ ol, int rows, int d, long long dy_stride,
-                                                               long long x_stride, long long res_stride, long long dx_stride, float eps) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int nv = d / 8;
-  float xr[2][8], gr[2][8];
-  RART_LNB_LOAD(xh + (size_t)row * x_stride, xl + (size_t)row * x_stride, nv, lane, xr);
-  RART_LNB_LOAD(dyh + (size_t)row * dy_stride, dyl + (size_t)row * dy_stride, nv, lane, gr);
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s += xr[k][j];
-  const float mean = rart_wave_sum(s) / (float)d;
-  float v = 0.f;
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-    if (lane + 64 * k < nv) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float t = xr[k][j] - mean;
-        v += t * t;
-      }
-    }
-  const float rstd = 1.0f / sqrtf(rart_wave_sum(v) / (float)d + eps);
-  float sg = 0.f, sgx = 0.f;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int vi = lane + 64 * k;
-    if (vi < nv) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        gr[k][j] *= gamma[vi * 8 + j];
-        xr[k][j] = (xr[k][j] - mean) * rstd;                     // xhat
-        sg += gr[k][j];
-        sgx += gr[k][j] * xr[k][j];
-      }
-    }
-  }
-  const float mg = rart_wave_sum(sg) / (float)d, mgx = rart_wave_sum(sgx) / (float)d;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int vi = lane + 64 * k;
-    if (vi < nv) {
-      float r[8], rs[8];
-      if (rh) join8(*reinterpret_cast<const uint4*>(rh + (size_t)row * res_stride + (size_t)vi * 8),
-                    *reinterpret_cast<const uint4*>(rl + (size_t)row * res_stride + (size_t)vi * 8), rs);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        r[j] = rstd * (gr[k][j] - mg - xr[k][j] * mgx);
-        if (rh) r[j] += rs[j];
-      }
-      uint4 ph, pl;
-      split8(r, ph, pl);
-      *reinterpret_cast<uint4*>(oh + (size_t)row * dx_stride + (size_t)vi * 8) = ph;
-      *reinterpret_cast<uint4*>(ol + (size_t)row * dx_stride + (size_t)vi * 8) = pl;
-    }
-  }
-}
 
 // P[row][0..n_valid) = softmax(scale * S[row][0..n_valid)) as a pair, P[row][n_valid..ld_out) = 0; S fp32 (the pair GEMM's fp32
 // output).  One wave per row, four consecutive columns per lane (rows of up to 256 columns)
@@ -204,13 +58,7 @@ __global__ __launch_bounds__(kBlock) void k_softmax_bwd_rows_pair(const uint16_t
   if (row >= rows) return;
   const int c0 = lane * 4;
   float p[4] = {0.f, 0.f, 0.f, 0.f}, g[4] = {0.f, 0.f, 0.f, 0.f};
-  if (c0 < ld_p) {
-    const uint2 h = *reinterpret_cast<const uint2*>(ph + row * ld_p + c0), l = *reinterpret_cast<const uint2*>(pl + row * ld_p + c0);
-    p[0] = __uint_as_float(h.x << 16) + __uint_as_float(l.x << 16);
-    p[1] = __uint_as_float(h.x & 0xFFFF0000u) + __uint_as_float(l.x & 0xFFFF0000u);
-    p[2] = __uint_as_float(h.y << 16) + __uint_as_float(l.y << 16);
-    p[3] = __uint_as_float(h.y & 0xFFFF0000u) + __uint_as_float(l.y & 0xFFFF0000u);
-  }
+  if (c0 < ld_p) join4(*reinterpret_cast<const uint2*>(ph + row * ld_p + c0), *reinterpret_cast<const uint2*>(pl + row * ld_p + c0), p);
   if (c0 < ld_dp) {
     const float4 gv = *reinterpret_cast<const float4*>(dp + row * ld_dp + c0);
     g[0] = gv.x; g[1] = gv.y; g[2] = gv.z; g[3] = gv.w;
@@ -1254,43 +1102,6 @@ int grid_for(size_t items) { return rart_grid_for(items, kBlock, 256 * 16); }
 }  // namespace
 
 extern "C" {
-
-int rart_vit_add_pos_cls_pair(void* x_hi, void* x_lo, const float* cls_pos0, const float* pos, int n, int tokens, int dim,
-                              rart_stream_t stream) {
-  RART_CHECK_ARG(x_hi && x_lo && cls_pos0 && pos && n > 0 && tokens > 0 && dim > 0 && dim % 8 == 0 &&
-                     (size_t)n * tokens * dim / 8 < (1ull << 32), "rart_vit_add_pos_cls_pair: bad arguments");
-  hipLaunchKernelGGL(k_add_pos_cls_pair, dim3(grid_for((size_t)n * tokens * dim / 8)), dim3(kBlock), 0, (hipStream_t)stream,
-                     (uint16_t*)x_hi, (uint16_t*)x_lo, cls_pos0, pos, n, tokens, dim);
-  RART_CHECK_LAUNCH("rart_vit_add_pos_cls_pair");
-  return RART_OK;
-}
-
-int rart_layernorm_pair(const void* x_hi, const void* x_lo, const float* gamma, const float* beta, void* out_hi, void* out_lo, int rows,
-                        int dim, int64_t in_row_stride, int64_t out_row_stride, float eps, rart_stream_t stream) {
-  RART_CHECK_ARG(x_hi && x_lo && gamma && beta && out_hi && out_lo && rows > 0 && dim > 0, "rart_layernorm_pair: bad arguments");
-  RART_CHECK_ARG(dim % 8 == 0 && dim <= 1024 && in_row_stride % 8 == 0 && out_row_stride % 8 == 0,
-                 "rart_layernorm_pair: dim a multiple of 8, at most 1024; strides multiples of 8");
-  hipLaunchKernelGGL(k_layernorm_pair, dim3((rows + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, (hipStream_t)stream,
-                     (const uint16_t*)x_hi, (const uint16_t*)x_lo, gamma, beta, (uint16_t*)out_hi, (uint16_t*)out_lo, rows, dim,
-                     (long long)in_row_stride, (long long)out_row_stride, eps);
-  RART_CHECK_LAUNCH("rart_layernorm_pair");
-  return RART_OK;
-}
-
-int rart_layernorm_bwd_pair(const void* dy_hi, const void* dy_lo, const void* x_hi, const void* x_lo, const float* gamma,
-                            const void* res_hi, const void* res_lo, void* dx_hi, void* dx_lo, int rows, int dim, int64_t dy_row_stride,
-                            int64_t x_row_stride, int64_t res_row_stride, int64_t dx_row_stride, float eps, rart_stream_t stream) {
-  RART_CHECK_ARG(dy_hi && dy_lo && x_hi && x_lo && gamma && dx_hi && dx_lo && rows > 0 && dim > 0 && ((res_hi == nullptr) == (res_lo == nullptr)),
-                 "rart_layernorm_bwd_pair: bad arguments");
-  RART_CHECK_ARG(dim % 8 == 0 && dim <= 1024 && dy_row_stride % 8 == 0 && x_row_stride % 8 == 0 && res_row_stride % 8 == 0 &&
-                     dx_row_stride % 8 == 0, "rart_layernorm_bwd_pair: dim a multiple of 8, at most 1024; strides multiples of 8");
-  hipLaunchKernelGGL(k_layernorm_bwd_pair, dim3((rows + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, (hipStream_t)stream,
-                     (const uint16_t*)dy_hi, (const uint16_t*)dy_lo, (const uint16_t*)x_hi, (const uint16_t*)x_lo, gamma,
-                     (const uint16_t*)res_hi, (const uint16_t*)res_lo, (uint16_t*)dx_hi, (uint16_t*)dx_lo, rows, dim,
-                     (long long)dy_row_stride, (long long)x_row_stride, (long long)res_row_stride, (long long)dx_row_stride, eps);
-  RART_CHECK_LAUNCH("rart_layernorm_bwd_pair");
-  return RART_OK;
-}
 
 int rart_softmax_rows_pair(const float* scores, void* probs_hi, void* probs_lo, int64_t rows, int n_valid, int ld_in, int ld_out,
                            float scale, rart_stream_t stream) {

@@ -9,7 +9,8 @@ GEMMs carry GELU' in their epilogue, the LayerNorm backward adds the residual gr
 'bf16': bf16 storage, fp32 accumulation and statistics: rart_conv_igemm_bf16, rart_layernorm[_bwd]_bf16, rart_vit_attention[_bwd],
 csrc/vit_aux.hip, csrc/vit_bwd.hip.  'bf16x3' (alias 'fp32x'), the reference-precision mode: every activation, gradient and weight a
 hi + lo pair of bf16 planes, rart_gemm_pair_bf16 (three MFMA products per contraction), rart_layernorm[_bwd]_pair,
-rart_vit_attention[_bwd]_pair, soft-max and GELU in fp32 on hi + lo (csrc/vit_pair.hip).
+rart_vit_attention[_bwd]_pair, soft-max and GELU in fp32 on hi + lo (csrc/vit_pair.hip).  The LayerNorm entries of both precisions
+are one kernel per direction (csrc/row_norm.hip), and so is the class-token / position add (csrc/vit_aux.hip).
 A module whose patch embedding is a ConvStem (`vit_base_cvst`) runs the chain of convstem_engine.py in place of patch extraction + patch GEMM.
 Reference module: robustart_amd/model/vit_torch.py."""
 import os

@@ -1,6 +1,7 @@
 """fp64 references, fp32 mirrors, input generators and bounds for the plain row kernels every engine calls through engine_base.py
 (_rows, _ln, _ln_bwd, _fc1_gelu): rart_layernorm[_bwd]_{bf16,pair}, rart_softmax[_bwd]_rows_{bf16,pair} and rart_gelu[_bwd]_bf16
-(csrc/vit_aux.hip, csrc/vit_bwd.hip, csrc/vit_pair.hip).  Nothing of the library is imported here.
+(LayerNorm: csrc/row_norm.hip; soft-max: csrc/vit_aux.hip, csrc/vit_bwd.hip, csrc/vit_pair.hip; GELU: csrc/vit_bwd.hip).  Nothing of
+the library is imported here.
 tests/test_row_kernel_refs_cpu.py shows without a GPU that a plain fp32 implementation meets every bound and that a list of wrong
 implementations does not; tests/test_row_kernels_gpu.py holds the kernels to the bounds.
 

@@ -1,6 +1,7 @@
 """The plain row kernels every engine calls through engine_base.py (_rows, _ln, _ln_bwd, _fc1_gelu), each against the fp64
 reference of the same operation on the MI355X: rart_layernorm[_bwd]_{bf16,pair}, rart_softmax[_bwd]_rows_{bf16,pair},
-rart_gelu[_bwd]_bf16 (csrc/vit_aux.hip, csrc/vit_bwd.hip, csrc/vit_pair.hip).  References, inputs and bounds are in
+rart_gelu[_bwd]_bf16 (LayerNorm: csrc/row_norm.hip, one kernel per direction for both storages; soft-max: csrc/vit_aux.hip,
+csrc/vit_bwd.hip, csrc/vit_pair.hip; GELU: csrc/vit_bwd.hip).  References, inputs and bounds are in
 tests/_row_kernels_ref.py; tests/test_row_kernel_refs_cpu.py shows on the CPU that a plain fp32 implementation meets the bounds
 and that the listed wrong ones do not.
 
@@ -28,8 +29,9 @@ cases, beside the fp32 mirror's figure from the CPU test:
   rart_softmax_bwd_rows_bf16   0.4895   0.4895        rart_softmax_bwd_rows_pair    0.2248   0.2248
   rart_gelu_bf16               0.4876   0.4876        rart_gelu_bwd_bf16            0.4967   0.4967
 (the worst element of each is decided by the rounding of the stored result, which the kernel and the mirror share).  Every exact
-check holds.  Against a build of the three sources with ten deliberate, memory-safe mistakes (variance / (d - 1) in k_layernorm, the
-mean without slot 1 in k_layernorm_bwd, eps outside the root in k_layernorm_pair, no xhat term in k_layernorm_bwd_pair, <= n_valid
+check holds.  Against a build of the sources with ten deliberate, memory-safe mistakes, made when the bf16 and the pair kernels were
+still separate copies (variance / (d - 1) in what is now k_layernorm<false>, the mean without slot 1 in k_layernorm_bwd<false>, eps
+outside the root in k_layernorm<true>, no xhat term in k_layernorm_bwd<true>, <= n_valid
 in both soft-max forwards, the mask multiplied in instead of selected in k_softmax_bwd_rows, the dot over ld_p in
 k_softmax_bwd_rows_pair, tanh GELU, GELU' without v phi, a grid stride one too long in k_gelu) 114 of the 137 cases fail; the 23
 that pass are the ones those mistakes do not reach: the eight soft-max cases without slack columns, the thirteen bf16 LayerNorm

@@ -4,7 +4,7 @@ The reference evaluates and attacks ViT in fp32 (exprs/exp/imagenet_c_loop_mini/
 RobustART/noise/utils/adv/attack.py:20-23; Attacks/autoattack/autopgd_base.py:271-289) and the north star asks for logits within
 1e-4 of it; the bf16 engine is ~3e-3 away.  This mode keeps every activation / gradient / weight as a hi + lo pair of bf16 planes,
 forms every contraction as lo.hi + hi.lo + hi.hi on the bf16 MFMA with fp32 accumulation (rart_gemm_pair_bf16) and evaluates
-LayerNorm / soft-max / GELU in fp32 on hi + lo (csrc/vit_pair.hip).  Tolerances stated here:
+LayerNorm / soft-max / GELU in fp32 on hi + lo (csrc/row_norm.hip, csrc/vit_pair.hip).  Tolerances stated here:
   * the pair GEMM vs fp64 of the same pair operands: <= 1e-5 of the output scale (fp32 out), 2.5e-5 (pair out: the output split);
   * logits vs the fp32 torch module AND vs an fp64 evaluation: <= 1e-4 of the logit scale;
   * gradient w.r.t. the input vs fp64 autograd through the module: relative L2 <= 5e-4 (GELU is smooth: no decision flips).
@@ -198,8 +198,9 @@ def test_gemm_pair_row_rebasing_and_batched_products():
 
 
 def test_pair_row_kernels_vs_fp64():
-    """LayerNorm forward / backward-to-input, soft-max rows forward / backward, class-token + position add, un-patchify from fp32:
-    csrc/vit_pair.hip against torch fp64 on the values the pairs represent."""
+    """LayerNorm forward / backward-to-input (csrc/row_norm.hip), class-token + position add (csrc/vit_aux.hip), soft-max rows
+    forward / backward and un-patchify from fp32 (csrc/vit_pair.hip): the pair entries against torch fp64 on the values the pairs
+    represent."""
     from robustart_amd import _lib
     lib = _lib.load()
     sp = _lib.stream_ptr()
