@@ -528,7 +528,7 @@ def test_walking_pair_attention_backward_is_bit_identical(B, T, monkeypatch):
     monkeypatch.setenv('RART_ATT_WALK', '0')
     want, wstats = run()
     assert torch.isfinite(want.float()).all()
-    monkeypatch.setenv('RART_ATT_WALK', '2')          # 2 (= the default with the variable unset): backward-q AND backward-kv walk; 1: backward-q alone
+    monkeypatch.setenv('RART_ATT_WALK', '2')          # any value but 0 (= the default with the variable unset): backward-q and backward-kv walk
     hog_stream, hog = torch.cuda.Stream(), torch.empty(64 << 20, dtype=torch.float32, device='cuda')
     for rep in range(4):
         if rep >= 2:
