@@ -436,7 +436,7 @@ int rart_gemm256_supported(long long rows, int k, int n_cols, int src_ld, int ds
  * Row re-basing (0 = none): output row m of image m / rows_per_image reads source row img * src_rows_per_image + m % rows_per_image +
  * src_row_off and writes destination row img * dst_rows_per_image + m % rows_per_image + dst_row_off (ViT's class-token slot).
  * Batched (n_batched > 1, blockIdx.y = z -> zo = z / z_inner, zi = z % z_inner): element offsets zo * *_z_outer + zi * *_z_inner are
- * added to a_* / w_* / (dst, res, aux). */
+ * added to a_* / w_* / (dst, res, aux).  rart_gemm_pair_plan_bf16 (below) describes the launches this entry makes for a descriptor. */
 typedef struct rart_gemm_pair_desc {
   const void *a_hi, *a_lo, *w_hi, *w_lo;
   const float* bias;
@@ -470,7 +470,7 @@ int rart_gemm_pair_bf16(const rart_gemm_pair_desc* desc_host, rart_stream_t stre
  * of the second, and the weight table's rows are [W1 | W2] along K (one.ldw covers both).  a2_hi null: exactly rart_gemm_pair_bf16(&one).
  * Served under schedules 0 and 1 (224-row tiles included); under the opt-in schedules 2 and 3 such a launch takes the ping-pong kernel.
  * A descriptor of its own, so that every caller of rart_gemm_pair_bf16 keeps its layout.  rart_gemm_pair_max_sources: how many A sources
- * the loaded library takes per launch (2); the engines fold a shortcut only where it says so. */
+ * the loaded library takes per launch (2); the engines fold a shortcut only where it says so.  rart_gemm_pair_plan_bf16 describes its launches. */
 typedef struct rart_gemm_pair2_desc {
   rart_gemm_pair_desc one;
   const void *a2_hi, *a2_lo;
@@ -490,7 +490,8 @@ int rart_gemm_pair_max_sources(void);
  * Every output element is the sum of the same products in the same order as in the class's own rart_gemm_pair_bf16 / rart_gemm_pair2_bf16
  * launch: the same bits.  The grid is ordered longest K first.  Tile policy is per launch: the tiles the longest class would choose serve
  * all of them (measured faster than one launch per tile form).  No interleaved weight table (flag 16), no batching, no row re-basing.
- * rart_gemm_pair_max_classes: how many classes the loaded library takes per launch (4); the engines use the entry only where it says so. */
+ * rart_gemm_pair_max_classes: how many classes the loaded library takes per launch (4); the engines use the entry only where it says so.
+ * rart_gemm_pair_plan_bf16 describes its launches. */
 typedef struct rart_gemm_pair_class {
   int tap_begin, n_taps, k_off, dst_oy, dst_ox, src2;
 } rart_gemm_pair_class;
@@ -513,6 +514,23 @@ int rart_gemm_pair_max_classes(void);
  * all of these (same products, same order, same point-wise code). */
 int rart_gemm_pair_set_schedule(int mode);
 int rart_gemm_pair_get_schedule(void);
+/* What rart_gemm_pair_bf16 / rart_gemm_pair2_bf16 / rart_gemm_pair_classes_bf16 would launch for a descriptor, without touching the device:
+ * the descriptor is checked as those entries check it (same status, same error string), then planned under the current schedule and lab
+ * variables for a device of `cus` compute units (<= 0: the current device's, 256 where there is none).  n_classes == 0: no class table
+ * (two.a2_hi null: one source).  No operand is read.  A plan is one launch, or two for the remainder split: launch[1] starts where
+ * launch[0] ends.  A launch covers rows m_begin .. M - 1 in tiles of tile_m x tile_n that step tile_rows rows (tile_m, or tile_m - 32:
+ * the tile's last 32-row block is left out); grid_x x grid_y workgroups of `block` threads.  walk_wgs > 0: the grid_x = min(walk_wgs,
+ * tiles) workgroups walk the tiles (ping-pong, schedule 3) or each a run of them (persistent, schedule 2), grid_y == 1. */
+enum { RART_GP_TWO_STAGE = 0 /* k_gemm_pair */, RART_GP_PING_PONG = 1 /* k_gemm_pair_pp */, RART_GP_PERSISTENT = 2 /* k_gemm_pair_ps */ };
+typedef struct rart_gemm_pair_launch_rec {
+  int family, tile_m, tile_n, tile_rows, m_begin, M;
+  unsigned grid_x, grid_y, walk_wgs, block;
+} rart_gemm_pair_launch_rec;
+typedef struct rart_gemm_pair_plan {
+  int n_launches, reserved_;
+  rart_gemm_pair_launch_rec launch[2];
+} rart_gemm_pair_plan;
+int rart_gemm_pair_plan_bf16(const rart_gemm_pair_cls_desc* desc_host, int cus, rart_gemm_pair_plan* out);
 
 /* The second half of a ResNet Bottleneck of the reference-precision engine as ONE launch (csrc/conv_tail_pair.hip): 3x3 stride-1 pad-1
  * convolution (c_mid -> c_mid channels, c_mid = 64 or 128) + point-wise step + the 1x1 expansion (c_mid -> 4 c_mid) + skip pair +

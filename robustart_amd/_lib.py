@@ -116,6 +116,7 @@ SIGNATURES = {
     'rart_copy_calibration': (c_int, [c_void_p, c_void_p, ctypes.c_size_t, c_int, c_void_p]),
     'rart_gemm_pair_set_schedule': (c_int, [c_int]),
     'rart_gemm_pair_get_schedule': (c_int, []),
+    'rart_gemm_pair_plan_bf16': (c_int, [c_void_p, c_int, c_void_p]),
     'rart_pack_jobs_bf16': (c_int, [c_void_p, c_int, c_int, c_void_p]),
     'rart_vit_add_pos_cls_pair': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     'rart_layernorm_pair': (c_int, [c_void_p] * 6 + [c_int, c_int, ctypes.c_int64, ctypes.c_int64, c_float, c_void_p]),
@@ -381,6 +382,17 @@ class GemmPairClass(ctypes.Structure):
 class GemmPairClsDesc(ctypes.Structure):
     """rart_gemm_pair_cls_desc (include/robustart_hip.h): up to four classes of the conv-mode pair launch `two.one` in one grid."""
     _fields_ = [('two', GemmPair2Desc), ('n_classes', ctypes.c_int32), ('reserved_', ctypes.c_int32), ('cls', GemmPairClass * 4)]
+
+
+class GemmPairLaunchRec(ctypes.Structure):
+    """rart_gemm_pair_launch_rec (include/robustart_hip.h): one launch of a pair GEMM plan."""
+    _fields_ = [(n, ctypes.c_int32) for n in ('family', 'tile_m', 'tile_n', 'tile_rows', 'm_begin', 'M')] + \
+               [(n, ctypes.c_uint32) for n in ('grid_x', 'grid_y', 'walk_wgs', 'block')]
+
+
+class GemmPairPlan(ctypes.Structure):
+    """rart_gemm_pair_plan (include/robustart_hip.h): what rart_gemm_pair_plan_bf16 reports for a descriptor."""
+    _fields_ = [('n_launches', ctypes.c_int32), ('reserved_', ctypes.c_int32), ('launch', GemmPairLaunchRec * 2)]
 
 
 class TokmixDesc(ctypes.Structure):

@@ -259,21 +259,25 @@ __global__ __launch_bounds__(TM * 2, 1) void k_gemm_pair(const GemmPairDev d) {
 // A/B switch of tests/test_engine_x3_gpu.py and scratch/r6/).  Bit-identical outputs under all three.  RART_PAIR_SCHEDULE in the environment
 // sets the initial value.
 int g_pair_schedule = -1;
+long long gp_env(const char* name, long long unset) {
+  const char* e = getenv(name);
+  return e ? atoll(e) : unset;
+}
 int gp_schedule() {
-  if (g_pair_schedule < 0) {
-    const char* e = getenv("RART_PAIR_SCHEDULE");
-    g_pair_schedule = e ? atoi(e) : 1;
-  }
+  if (g_pair_schedule < 0) g_pair_schedule = (int)gp_env("RART_PAIR_SCHEDULE", 1);
   return g_pair_schedule;
 }
 
-int gp_rows224() {          // lab switch of the 224-row tiles below (default on)
-  const char* e = getenv("RART_PAIR_ROWS224");
-  return e ? atoi(e) : 1;
-}
-int gp_split() {            // lab switch of the remainder split below (default on)
-  const char* e = getenv("RART_PAIR_SPLIT");
-  return e ? atoi(e) : 1;
+// The schedule and the lab switches of one call.  The environment is read here and nowhere else, once per variable and on EVERY call: the
+// tests flip RART_PAIR_ROWS224 / RART_PAIR_SPLIT inside one process.
+struct GpLab {
+  int schedule;             // above
+  int rows224;              // RART_PAIR_ROWS224: tiles that leave their last 32-row block out (default 1: the ping-pong kernel's 224-row tiles; 2 / 3: the two-stage kernel's too, 3 for K >= 1024 only)
+  int split;                // RART_PAIR_SPLIT: the remainder split (default on)
+  long long nt_min_mb;      // RART_PAIR_NT_MIN_MB: non-temporal epilogue streams for output pairs of at least this size (default 0: all)
+};
+GpLab gp_read_lab() {
+  return GpLab{gp_schedule(), (int)gp_env("RART_PAIR_ROWS224", 1), (int)gp_env("RART_PAIR_SPLIT", 1), gp_env("RART_PAIR_NT_MIN_MB", 0)};
 }
 
 void gp_magic(uint32_t dv, uint32_t& mg, uint32_t& sh) {   // exact for dividends < 2^31
@@ -284,7 +288,8 @@ void gp_magic(uint32_t dv, uint32_t& mg, uint32_t& sh) {   // exact for dividend
 }
 }  // namespace
 
-bool rart_gemm_pair_pp_launch(const void* dev_desc, int tn, bool conv, unsigned grid_x, unsigned grid_y, hipStream_t st, unsigned walk_wgs);   // gemm_pair_pp.hip
+bool rart_gemm_pair_pp_has(int tn, bool conv, bool src2, bool cls, bool walk);   // gemm_pair_pp.hip
+bool rart_gemm_pair_pp_launch(const void* dev_desc, int tn, bool conv, unsigned grid_x, unsigned grid_y, hipStream_t st, unsigned walk_wgs);
 void rart_gemm_pair_ps_launch(const void* dev_desc, bool conv, unsigned wgs, hipStream_t st);
 
 namespace {
@@ -318,11 +323,11 @@ extern "C" int rart_gemm_pair_get_schedule(void) { return gp_schedule(); }
 // 319, 128 x 128 349, 256 x 64 386); 50176 x 768 -> 1024: 259 on 224 x 256 (256 x 256 273, 128 x 128 289); 12544 x 1536 -> 2048: 206 on
 // 224 x 256 (256 x 256 214, 256 x 128 258); layer1's backward 802816 x 320 -> 64: 246 on 128 x 64 (256 x 64 252).
 // A class launch (ncls > 1 grids of the same tiles) counts its workgroups over all classes.
-static void gp_tile_policy(bool conv, int M, int N, int K, int& tm, int& tn, int ncls = 1) {
+static void gp_tile_policy(bool conv, int M, int N, int K, int schedule, int& tm, int& tn, int ncls = 1) {
   tn = N <= 64 ? 64 : (N <= 128 ? 128 : 256);
   tm = 256;
   if (conv) {
-    if (gp_schedule() >= 1 && N >= 256 && (K >= 512 || (K >= 256 && N <= 512))) {
+    if (schedule >= 1 && N >= 256 && (K >= 512 || (K >= 256 && N <= 512))) {
       // round 6 (scratch/r6/time_pair_pp.py --tiles, profiles/r06_pair_pp.json): with the ping-pong schedule the 256-row tiles win wherever
       // the layer is at least 256 wide and 256 deep -- 256 x 256 unless that leaves fewer than 128 workgroups (layer4: 256 x 128); the one
       // exception measured: K = 256 into >= 1024 columns (layer3's expansion: epilogue-bound, 155-165 us on 256 x 64 vs 166-176).  128-column
@@ -336,14 +341,24 @@ static void gp_tile_policy(bool conv, int M, int N, int K, int& tm, int& tn, int
   }
 }
 
-// One launch of rart_gemm_pair_bf16 (s2 == nullptr), rart_gemm_pair2_bf16 (s2: the descriptor that carries the second A source) or
-// rart_gemm_pair_classes_bf16 (cd: the classes of the grid, checked by that entry; s2 = the second source of the class that has src2 set).
-static int gp_launch(const rart_gemm_pair_desc* h, const rart_gemm_pair2_desc* s2, rart_stream_t stream,
-                     const rart_gemm_pair_cls_desc* cd = nullptr) {
+// A checked problem: the device descriptor and what the caller's descriptor says beside it.  A second source shows as d.a2_hi, a class
+// table as d.n_cls > 0.
+struct GpProblem {
+  GemmPairDev d;
+  bool conv;
+  int nz;                   // batched problems (blockIdx.y of a launch without classes)
+  int tile_m, tile_n;       // the caller's overrides (0: the tile policy's choice)
+};
+
+// Step 1 of gp_launch: the argument checks and the device descriptor, complete but for what a launch record sets (M, m_begin, tile_rows:
+// here the whole problem on full 256-row tiles).  s2 / cd: see gp_launch.
+static int gp_check_and_fill(const rart_gemm_pair_desc* h, const rart_gemm_pair2_desc* s2, const rart_gemm_pair_cls_desc* cd, const GpLab& lab,
+                             GpProblem& p) {
   RART_CHECK_ARG(h != nullptr, "rart_gemm_pair_bf16: null descriptor");
   RART_CHECK_ARG(h->a_hi && h->a_lo && h->w_hi && h->w_lo && h->dst_hi, "rart_gemm_pair_bf16: null operand plane");
   const bool conv = h->conv != 0;
-  GemmPairDev d{};
+  GemmPairDev& d = p.d;
+  d = GemmPairDev{};
   d.M = h->M; d.K = h->K;
   const bool src2 = s2 != nullptr;
   RART_CHECK_ARG(!src2 || (conv && s2->a2_hi && s2->a2_lo), "rart_gemm_pair2_bf16: the second source is a pair (both planes) and is served by conv mode only");
@@ -444,154 +459,209 @@ static int gp_launch(const rart_gemm_pair_desc* h, const rart_gemm_pair2_desc* s
   d.src_off = h->src_row_off; d.dst_off = h->dst_row_off;
   RART_CHECK_ARG(d.src_off >= 0 && d.dst_off >= 0, "rart_gemm_pair_bf16: row offsets must be >= 0");
   d.flags = h->flags;
-  {
-    // non-temporal epilogue streams for outputs that do not stay cached anyway (lab switch: RART_PAIR_NT_MIN_MB, the output pair's size)
-    const char* e = getenv("RART_PAIR_NT_MIN_MB");
-    const long long min_mb = e ? atoll(e) : 0;
-    d.nt = (long long)d.M * d.N * 4 >= min_mb * (1ll << 20) ? 1 : 0;
-  }
-  const int nz = h->n_batched > 1 ? h->n_batched : 1;
-  RART_CHECK_ARG(nz <= 65535, "rart_gemm_pair_bf16: n_batched must be <= 65535");
+  // non-temporal epilogue streams for outputs that do not stay cached anyway (lab switch: the output pair's size)
+  d.nt = (long long)d.M * d.N * 4 >= lab.nt_min_mb * (1ll << 20) ? 1 : 0;
+  p.nz = h->n_batched > 1 ? h->n_batched : 1;
+  RART_CHECK_ARG(p.nz <= 65535, "rart_gemm_pair_bf16: n_batched must be <= 65535");
   d.z_inner = h->z_inner > 0 ? h->z_inner : 1;
   d.a_zo = h->a_z_outer; d.a_zi = h->a_z_inner; d.w_zo = h->w_z_outer; d.w_zi = h->w_z_inner; d.c_zo = h->c_z_outer; d.c_zi = h->c_z_inner;
+  d.m_begin = 0;
+  d.tile_rows = 256;
+  p.conv = conv; p.tile_m = h->tile_m; p.tile_n = h->tile_n;
+  return RART_OK;
+}
+
+// A launch runs in passes of one tile per CU and XCD: workgroup i goes to XCD i % GP_XCDS, and from 16 row tiles on the kernels enumerate
+// the row tiles in groups of GP_XCDS, XCD x taking the row tiles x, x + GP_XCDS, ... with all their column tiles (the A tile is re-read
+// from that XCD's L2).
+constexpr int GP_XCDS = 8;
+static int gp_row_enum(int mt) { return mt >= 16 ? (mt + GP_XCDS - 1) / GP_XCDS * GP_XCDS : mt; }      // row tiles a grid enumerates
+// passes of mt x nt tiles over `slots` resident workgroups per XCD
+static int gp_passes(int mt, int nt, int slots) {
+  if (slots < 1) slots = 1;
+  return ((mt >= 16 ? (mt + GP_XCDS - 1) / GP_XCDS * nt : (mt * nt + GP_XCDS - 1) / GP_XCDS) + slots - 1) / slots;
+}
+// the launch of rows m_begin .. M - 1 on tm x tn tiles that step tile_rows rows
+static rart_gemm_pair_launch_rec gp_record(int family, int tm, int tn, int tile_rows, int m_begin, int M, int N, unsigned grid_y) {
+  const long long tiles = (long long)gp_row_enum((M - m_begin + tile_rows - 1) / tile_rows) * ((N + tn - 1) / tn);
+  return rart_gemm_pair_launch_rec{family, tm, tn, tile_rows, m_begin, M, (unsigned)tiles, grid_y, 0u, family == RART_GP_TWO_STAGE ? tm * 2u : 512u};
+}
+
+// Step 2 of gp_launch: what to launch for a checked problem on a device of `cus` compute units.  A function of its arguments alone (no HIP
+// call, no environment, no state); false: the grid would be too large.
+static bool gp_plan(const GpProblem& p, const GpLab& lab, int cus, rart_gemm_pair_plan& plan) {
+  const GemmPairDev& d = p.d;
+  const bool conv = p.conv, src2 = d.a2_hi != nullptr, cls = d.n_cls > 0, forced = p.tile_m != 0 || p.tile_n != 0;
+  const int nz = p.nz, ncls = cls ? d.n_cls : 1;
   // A class launch takes the tiles of its longest class for all of them.  Measured at B = 256 (profiles/first_block_folds_per_part.txt): the
   // K = 640 + 3 x K = 128 classes of layer2's folded shortcut^T run 505 us as one 256 x 256 ping-pong grid against 560 us as two launches
   // with each class on the tiles its own K would choose (622 us before the fold).
   int tn, tm;
-  gp_tile_policy(conv, d.M, d.N, d.K, tm, tn, cd ? d.n_cls : 1);
-  if (h->tile_n == 64 || h->tile_n == 128 || h->tile_n == 256) tn = h->tile_n;
-  if (h->tile_m == 128 || h->tile_m == 256) tm = h->tile_m;
-  if (h->tile_m == 224) tm = 256;            // the ping-pong kernel's 224-row form (below)
+  gp_tile_policy(conv, d.M, d.N, d.K, lab.schedule, tm, tn, ncls);
+  if (p.tile_n == 64 || p.tile_n == 128 || p.tile_n == 256) tn = p.tile_n;
+  if (p.tile_m == 128 || p.tile_m == 256) tm = p.tile_m;
+  if (p.tile_m == 224) tm = 256;            // the ping-pong kernel's 224-row form (below)
   const int m_tiles = (d.M + tm - 1) / tm, n_tiles = (d.N + tn - 1) / tn;
-  const int m_enum = m_tiles >= 16 ? (m_tiles + 7) / 8 * 8 : m_tiles;     // the XCD remap enumerates row tiles in groups of 8
-  const long long blocks = (long long)m_enum * n_tiles;
-  RART_CHECK_ARG(blocks < (1ll << 31), "rart_gemm_pair_bf16: grid too large");
-  const int ncls = cd ? d.n_cls : 1;            // a class launch: blockIdx.y = class (conv mode is unbatched: nz == 1)
-  const dim3 grid((uint32_t)blocks, cd ? ncls : nz);
-  hipStream_t st = (hipStream_t)stream;
+  const long long blocks = (long long)gp_row_enum(m_tiles) * n_tiles;
+  if (blocks >= (1ll << 31)) return false;
+  const unsigned grid_y = cls ? ncls : nz;      // a class launch: blockIdx.y = class (conv mode is unbatched: nz == 1)
+  const int cx = cus / GP_XCDS;                 // CUs per XCD
+  const bool pp_tiles = tm == 256 && tn >= 128 && lab.schedule >= 1;      // the tiles the ping-pong kernel has
+  plan = rart_gemm_pair_plan{};
+  plan.n_launches = 1;
+  rart_gemm_pair_launch_rec& r = plan.launch[0];
   // the persistent kernel (256 x 128 tiles, deferred epilogue): one tap, no GELU epilogue, no row re-basing / batching, at least two tiles per
   // CU and a K loop with room for the 12 micro-steps of a tile's epilogue
-  if (gp_schedule() == 2 && !src2 && !cd && tm == 256 && tn >= 128 && h->tile_n == 0 && h->tile_m == 0 && nz == 1 && !d.map_rows && d.src_off == 0 &&
-      (conv ? d.n_taps == 1 : true) && !(h->flags & (GP_GELU | GP_GELU_BWD | GP_GELU_KEEP)) && d.K / GP_BK >= 6) {
-    const int cus = gp_cu_count();
-    const long long tiles = (long long)((d.M + 255) / 256) * ((d.N + 127) / 128);
-    if (tiles >= 2ll * cus) {
-      rart_gemm_pair_ps_launch(&d, conv, (unsigned)cus, st);
-      RART_CHECK_LAUNCH("rart_gemm_pair_bf16 (persistent)");
-      return RART_OK;
-    }
+  if (lab.schedule == 2 && !src2 && !cls && pp_tiles && !forced && nz == 1 && !d.map_rows && d.src_off == 0 && (!conv || d.n_taps == 1) &&
+      !(d.flags & (GP_GELU | GP_GELU_BWD | GP_GELU_KEEP)) && d.K / GP_BK >= 6 && (long long)((d.M + 255) / 256) * ((d.N + 127) / 128) >= 2ll * cus) {
+    r = rart_gemm_pair_launch_rec{RART_GP_PERSISTENT, 256, 128, 256, 0, d.M, (unsigned)cus, 1u, (unsigned)cus, 512u};      // one workgroup per CU
+    return true;
   }
-  d.m_begin = 0;
-  d.tile_rows = 256;
-  if (tm == 256 && tn >= 128 && gp_schedule() >= 1 && nz == 1 && (h->tile_m == 224 || (h->tile_m == 0 && gp_rows224()))) {
-    // Round 6: 224-row tiles.  A launch runs in passes of one tile per CU and XCD (above); ResNet-50's 50176 / 12544 rows are 196 / 49 tiles
-    // of 256 rows = 25 / 7 of an XCD's 32 CUs in the fullest XCD.  A tile that steps 224 rows (the kernel leaves its last 32-row block out;
-    // loads, waits and barriers unchanged) makes 224 / 56 row tiles = 28 / 7 per XCD: the same passes, 7/8 of the matrix work per tile.
-    auto passes = [&](int mt, int nt) { const int cx = gp_cu_count() / 8; return ((mt >= 16 ? (mt + 7) / 8 * nt : (mt * nt + 7) / 8) + cx - 1) / cx; };
+  if (pp_tiles && nz == 1 && (p.tile_m == 224 || (p.tile_m == 0 && lab.rows224)) && rart_gemm_pair_pp_has(tn, conv, src2, cls, false)) {
+    // Round 6: 224-row tiles.  ResNet-50's 50176 / 12544 rows are 196 / 49 tiles of 256 rows = 25 / 7 of an XCD's 32 CUs in the fullest
+    // XCD.  A tile that steps 224 rows (the kernel leaves its last 32-row block out; loads, waits and barriers unchanged) makes 224 / 56
+    // row tiles = 28 / 7 per XCD: the same passes, 7/8 of the matrix work per tile.
     const int mt224 = (d.M + 223) / 224;
     // A class launch streams ncls grids of unequal K through the CUs, so whole passes mean little: what 224-row tiles can still buy is the
     // balance between the XCDs -- row tiles on the fullest one, (m_tiles + 7) / 8, against 7/8 of the work in each of (mt224 + 7) / 8 --
     // and they cost about 6 % per unit of work (more tiles for the same rows).  Measured at B = 256: 12544 rows (49 -> 56 row tiles: 7 -> 7
     // x 7/8) 171 -> 167 us (3x3) and 333 -> 317 us (shortcut^T); 50176 rows (25 -> 28 x 7/8) 180 -> 189 us; 200704 rows 505 -> 530 us.
-    const bool rows224 = cd ? (mt224 + 7) / 8 * 0.875 * 1.06 < (m_tiles + 7) / 8 : passes(mt224, n_tiles) * 0.92 < passes(m_tiles, n_tiles) - 0.01;
-    if (h->tile_m == 224 || rows224) {
-      d.tile_rows = 224;
-      const int me = mt224 >= 16 ? (mt224 + 7) / 8 * 8 : mt224;
-      if (rart_gemm_pair_pp_launch(&d, tn, conv, (unsigned)(me * n_tiles), grid.y, st, 0)) {
-        RART_CHECK_LAUNCH("rart_gemm_pair_bf16 (ping-pong, 224-row tiles)");
-        return RART_OK;
-      }
-      d.tile_rows = 256;
+    const bool saves = cls ? (mt224 + GP_XCDS - 1) / GP_XCDS * 0.875 * 1.06 < (m_tiles + GP_XCDS - 1) / GP_XCDS
+                           : gp_passes(mt224, n_tiles, cx) * 0.92 < gp_passes(m_tiles, n_tiles, cx) - 0.01;
+    if (p.tile_m == 224 || saves) {
+      r = gp_record(RART_GP_PING_PONG, 256, tn, 224, 0, d.M, d.N, grid_y);
+      return true;
     }
   }
-  if (!conv && tm == 256 && tn == 256 && gp_schedule() >= 1 && gp_split() && nz == 1 && h->tile_n == 0 && h->tile_m == 0) {
-    // Round 6 (scratch/r6/time_pair_rounds.py, GRBM_GUI_ACTIVE per launch): a 256-row launch is quantised in passes of ONE TILE PER CU PER XCD
-    // -- workgroup i goes to XCD i % 8, and the row-tile enumeration gives XCD x the row tiles x, x + 8, ... -- so ViT-B/16's 50432 x 768
-    // outputs (197 x 3 tiles, 75 per XCD of 32 CUs) take THREE tile times for 2.3 passes of work.  Such a launch is issued as two: the row
-    // tiles of the whole passes on 256 x 256 tiles, the remaining rows (m_begin) on 256 x 128 tiles, which take about half a tile time.
+  if (!conv && pp_tiles && tn == 256 && lab.split && nz == 1 && !forced && rart_gemm_pair_pp_has(256, conv, src2, cls, false) &&
+      rart_gemm_pair_pp_has(128, conv, src2, cls, false)) {
+    // Round 6 (scratch/r6/time_pair_rounds.py, GRBM_GUI_ACTIVE per launch): ViT-B/16's 50432 x 768 outputs (197 x 3 tiles, 75 per XCD of
+    // 32 CUs) take THREE tile times for 2.3 passes of work.  Such a launch is issued as two: the row tiles of the whole passes on 256 x 256
+    // tiles, the remaining rows (m_begin) on 256 x 128 tiles, which take about half a tile time.
     // Same products in the same order per output element: same bits.  Plain products only: on the convolutions of ResNet-50 (short K, epilogue-
     // heavy tiles) the second launch costs what it saves (same-box A/B 19.53 vs 19.60 ms per gradient evaluation); ViT-B/16 66.9 -> 65.9 ms.
-    const int cx = gp_cu_count() / 8;                      // CUs per XCD
-    auto passes = [&](int mt, int nt) { return ((mt >= 16 ? (mt + 7) / 8 * nt : (mt * nt + 7) / 8) + cx - 1) / cx; };
     const double half_cost = 0.8;                          // measured: the second launch costs ~0.8 tile times (it starts when the first has drained)
-    const int n128 = (d.N + 127) / 128;
-    double best = passes(m_tiles, n_tiles);
+    const int n128 = (d.N + 127) / 128, whole = gp_passes(m_tiles, n_tiles, cx);
+    double best = whole;
     int best_ma = 0;
-    for (int pa = 1; pa < passes(m_tiles, n_tiles); ++pa) {
-      const int ma = pa * cx / n_tiles * 8;                // row tiles of the first launch: pa passes exactly on every XCD
+    for (int pa = 1; pa < whole; ++pa) {
+      const int ma = pa * cx / n_tiles * GP_XCDS;          // row tiles of the first launch: pa passes exactly on every XCD
       if (ma < 16 || ma >= m_tiles) continue;
-      const double c = passes(ma, n_tiles) + half_cost * passes(m_tiles - ma, n128) + 0.05;
+      const double c = gp_passes(ma, n_tiles, cx) + half_cost * gp_passes(m_tiles - ma, n128, cx) + 0.05;
       if (c < best - 0.1) { best = c; best_ma = ma; }
     }
     if (best_ma > 0) {
-      GemmPairDev da = d, db = d;
-      da.M = best_ma * 256;
-      db.m_begin = best_ma * 256;
-      const int mb = m_tiles - best_ma, mb_enum = mb >= 16 ? (mb + 7) / 8 * 8 : mb;
-      if (rart_gemm_pair_pp_launch(&da, 256, conv, (unsigned)(best_ma * n_tiles), 1, st, 0) &&
-          rart_gemm_pair_pp_launch(&db, 128, conv, (unsigned)(mb_enum * n128), 1, st, 0)) {
-        RART_CHECK_LAUNCH("rart_gemm_pair_bf16 (ping-pong, remainder split)");
-        return RART_OK;
-      }
+      plan.n_launches = 2;
+      r = gp_record(RART_GP_PING_PONG, 256, 256, 256, 0, best_ma * 256, d.N, 1);
+      plan.launch[1] = gp_record(RART_GP_PING_PONG, 256, 128, 256, best_ma * 256, d.M, d.N, 1);
+      return true;
     }
   }
   // schedule 3: launches of more than one tile per CU are WALKED by one workgroup per CU (k_gemm_pair_pp, OPT bit 1)
-  const unsigned walk_wgs = (gp_schedule() == 3 && !src2 && !cd && nz == 1 && blocks > (long long)gp_cu_count()) ? (unsigned)(gp_cu_count() & ~7) : 0u;
-  if (tm == 256 && tn >= 128 && gp_schedule() >= 1 && rart_gemm_pair_pp_launch(&d, tn, conv, grid.x, grid.y, st, walk_wgs)) {
-    RART_CHECK_LAUNCH("rart_gemm_pair_bf16 (ping-pong)");
-    return RART_OK;
+  const unsigned walk_wgs = (lab.schedule == 3 && !src2 && !cls && nz == 1 && blocks > (long long)cus) ? (unsigned)(cus & ~(GP_XCDS - 1)) : 0u;
+  if (pp_tiles && rart_gemm_pair_pp_has(tn, conv, src2, cls, walk_wgs > 0)) {
+    r = gp_record(RART_GP_PING_PONG, 256, tn, 256, 0, d.M, d.N, grid_y);
+    if (walk_wgs) {
+      r.walk_wgs = walk_wgs;
+      if (walk_wgs < r.grid_x) r.grid_x = walk_wgs;
+    }
+    return true;
   }
   // the two-stage kernel: tiles that step tm - 32 rows where that saves work per pass (resident workgroups per CU by LDS: 2 x STAGE bytes each)
-  d.tile_rows = tm;
-  dim3 grid2 = grid;
-  if ((gp_rows224() == 2 || (gp_rows224() == 3 && d.K >= 1024)) && nz == 1 && !cd && h->tile_m == 0 && h->tile_n == 0 && gp_schedule() >= 1) {   // (3: K-deep only)
-    const int lds = 2 * (2 * tm * 64 + 2 * tn * 64), res = lds > 80 * 1024 ? 1 : (lds > 53 * 1024 ? 2 : 3), cx = gp_cu_count() / 8 * res;
-    auto passes = [&](int mt) { return ((mt >= 16 ? (mt + 7) / 8 * n_tiles : (mt * n_tiles + 7) / 8) + cx - 1) / cx; };
-    const int rows = tm - 32, mt2 = (d.M + rows - 1) / rows;
-    if (passes(mt2) * (double)rows / tm * 1.03 < passes(m_tiles)) {
-      d.tile_rows = rows;
-      grid2 = dim3((uint32_t)((mt2 >= 16 ? (mt2 + 7) / 8 * 8 : mt2) * n_tiles), nz);
-    }
+  int rows = tm;
+  if ((lab.rows224 == 2 || (lab.rows224 == 3 && d.K >= 1024)) && nz == 1 && !cls && !forced && lab.schedule >= 1) {   // (3: K-deep only)
+    const int lds = 2 * (2 * tm * 64 + 2 * tn * 64), res = lds > 80 * 1024 ? 1 : (lds > 53 * 1024 ? 2 : 3);
+    const int less = tm - 32, mt_less = (d.M + less - 1) / less;
+    if (gp_passes(mt_less, n_tiles, cx * res) * (double)less / tm * 1.03 < gp_passes(m_tiles, n_tiles, cx * res)) rows = less;
   }
-#define RART_GP_LAUNCH(TM_, TN_, ...) hipLaunchKernelGGL((k_gemm_pair<TM_, TN_, __VA_ARGS__>), grid2, dim3(TM_ * 2), 0, st, d)
+  r = gp_record(RART_GP_TWO_STAGE, tm, tn, rows, 0, d.M, d.N, grid_y);
+  return true;
+}
+
+// Step 3 of gp_launch: the launches of a plan.  A record sets the descriptor's row range and tile step; nothing else differs between the
+// launches of a plan.
+static int gp_issue(const GpProblem& p, const rart_gemm_pair_plan& plan, rart_stream_t stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const char* what = "rart_gemm_pair_bf16";
+  for (int i = 0; i < plan.n_launches; ++i) {
+    const rart_gemm_pair_launch_rec& r = plan.launch[i];
+    GemmPairDev d = p.d;
+    d.M = r.M; d.m_begin = r.m_begin; d.tile_rows = r.tile_rows;
+    const int tm = r.tile_m, tn = r.tile_n;
+    if (r.family == RART_GP_PERSISTENT) {
+      rart_gemm_pair_ps_launch(&d, p.conv, r.grid_x, st);
+      what = "rart_gemm_pair_bf16 (persistent)";
+      continue;
+    }
+    if (r.family == RART_GP_PING_PONG) {
+      if (!rart_gemm_pair_pp_launch(&d, tn, p.conv, r.grid_x, r.grid_y, st, r.walk_wgs)) {
+        rart_set_error("rart_gemm_pair_bf16: internal error: the plan chose a ping-pong instance that does not exist (%d columns)", tn);
+        return RART_ERR_INVALID;
+      }
+      what = plan.n_launches == 2 ? "rart_gemm_pair_bf16 (ping-pong, remainder split)"
+                                  : (r.tile_rows == 224 ? "rart_gemm_pair_bf16 (ping-pong, 224-row tiles)" : "rart_gemm_pair_bf16 (ping-pong)");
+      continue;
+    }
+    const dim3 grid(r.grid_x, r.grid_y);
+#define RART_GP_LAUNCH(TM_, TN_, ...) hipLaunchKernelGGL((k_gemm_pair<TM_, TN_, __VA_ARGS__>), grid, dim3(TM_ * 2), 0, st, d)
 #define RART_GP_BY_TN(TM_, ...)                                            \
   do {                                                                     \
     if (tn == 64) RART_GP_LAUNCH(TM_, 64, __VA_ARGS__);                    \
     else if (tn == 128) RART_GP_LAUNCH(TM_, 128, __VA_ARGS__);             \
     else RART_GP_LAUNCH(TM_, 256, __VA_ARGS__);                            \
   } while (0)
-  if (cd) {
-    if (tm == 128) RART_GP_BY_TN(128, true, true, true);
-    else RART_GP_BY_TN(256, true, true, true);
-  } else if (src2) {
-    if (tm == 128) RART_GP_BY_TN(128, true, true);
-    else RART_GP_BY_TN(256, true, true);
-  } else if (conv) {
-    if (tm == 128) RART_GP_BY_TN(128, true);
-    else RART_GP_BY_TN(256, true);
-  } else {
-    if (tm == 128) RART_GP_BY_TN(128, false);
-    else RART_GP_BY_TN(256, false);
-  }
+    if (d.n_cls > 0) {
+      if (tm == 128) RART_GP_BY_TN(128, true, true, true);
+      else RART_GP_BY_TN(256, true, true, true);
+    } else if (d.a2_hi) {
+      if (tm == 128) RART_GP_BY_TN(128, true, true);
+      else RART_GP_BY_TN(256, true, true);
+    } else if (p.conv) {
+      if (tm == 128) RART_GP_BY_TN(128, true);
+      else RART_GP_BY_TN(256, true);
+    } else {
+      if (tm == 128) RART_GP_BY_TN(128, false);
+      else RART_GP_BY_TN(256, false);
+    }
 #undef RART_GP_BY_TN
 #undef RART_GP_LAUNCH
-  RART_CHECK_LAUNCH("rart_gemm_pair_bf16");
+  }
+  RART_CHECK_LAUNCH(what);
   return RART_OK;
 }
 
-extern "C" int rart_gemm_pair_bf16(const rart_gemm_pair_desc* h, rart_stream_t stream) { return gp_launch(h, nullptr, stream); }
+// One call of rart_gemm_pair_bf16 (s2 == nullptr), rart_gemm_pair2_bf16 (s2: the descriptor that carries the second A source) or
+// rart_gemm_pair_classes_bf16 (cd: the classes of the grid, checked by that entry; s2 = the second source of the class that has src2 set):
+// check, plan, issue.  plan_out: rart_gemm_pair_plan_bf16 -- the plan for `cus` compute units is returned instead of issued.
+static int gp_launch(const rart_gemm_pair_desc* h, const rart_gemm_pair2_desc* s2, rart_stream_t stream, const rart_gemm_pair_cls_desc* cd,
+                     rart_gemm_pair_plan* plan_out, int cus) {
+  const GpLab lab = gp_read_lab();
+  GpProblem p;
+  if (const int bad = gp_check_and_fill(h, s2, cd, lab, p)) return bad;
+  if (cus <= 0) cus = gp_cu_count();        // (after the checks: a bad descriptor is refused before any HIP call)
+  rart_gemm_pair_plan plan;
+  RART_CHECK_ARG(gp_plan(p, lab, cus, plan), "rart_gemm_pair_bf16: grid too large");
+  if (plan_out) {
+    *plan_out = plan;
+    return RART_OK;
+  }
+  return gp_issue(p, plan, stream);
+}
+
+extern "C" int rart_gemm_pair_bf16(const rart_gemm_pair_desc* h, rart_stream_t stream) { return gp_launch(h, nullptr, stream, nullptr, nullptr, 0); }
 
 // Two A sources (include/robustart_hip.h): the launch `one` describes, and when a2_hi is set the second source's K steps after its own.
-extern "C" int rart_gemm_pair2_bf16(const rart_gemm_pair2_desc* h, rart_stream_t stream) {
+static int gp_launch2(const rart_gemm_pair2_desc* h, rart_stream_t stream, rart_gemm_pair_plan* plan_out, int cus) {
   RART_CHECK_ARG(h != nullptr, "rart_gemm_pair2_bf16: null descriptor");
   RART_CHECK_ARG((h->a2_hi == nullptr) == (h->a2_lo == nullptr), "rart_gemm_pair2_bf16: the second source is a pair: both planes or none");
-  return gp_launch(&h->one, h->a2_hi ? h : nullptr, stream);
+  return gp_launch(&h->one, h->a2_hi ? h : nullptr, stream, nullptr, plan_out, cus);
 }
+extern "C" int rart_gemm_pair2_bf16(const rart_gemm_pair2_desc* h, rart_stream_t stream) { return gp_launch2(h, stream, nullptr, 0); }
 extern "C" int rart_gemm_pair_max_sources(void) { return 2; }
 
 // Up to four classes of a conv-mode pair launch in one grid (include/robustart_hip.h): the checks, then gp_launch with the class table.
 extern "C" int rart_gemm_pair_max_classes(void) { return 4; }
-extern "C" int rart_gemm_pair_classes_bf16(const rart_gemm_pair_cls_desc* c, rart_stream_t stream) {
+static int gp_launch_classes(const rart_gemm_pair_cls_desc* c, rart_stream_t stream, rart_gemm_pair_plan* plan_out, int cus) {
   RART_CHECK_ARG(c != nullptr, "rart_gemm_pair_classes_bf16: null descriptor");
   const rart_gemm_pair_desc& h = c->two.one;
   RART_CHECK_ARG(c->n_classes >= 1 && c->n_classes <= 4, "rart_gemm_pair_classes_bf16: 1..4 classes");
@@ -615,5 +685,12 @@ extern "C" int rart_gemm_pair_classes_bf16(const rart_gemm_pair_cls_desc* c, rar
                    "rart_gemm_pair_classes_bf16: every row's destination pixel must lie inside the destination image");
   }
   RART_CHECK_ARG(!has2 || c->cls[0].src2, "rart_gemm_pair_classes_bf16: a second source needs class 0 to take it (src2 = 1)");
-  return gp_launch(&h, has2 ? &c->two : nullptr, stream, c);
+  return gp_launch(&h, has2 ? &c->two : nullptr, stream, c, plan_out, cus);
+}
+extern "C" int rart_gemm_pair_classes_bf16(const rart_gemm_pair_cls_desc* c, rart_stream_t stream) { return gp_launch_classes(c, stream, nullptr, 0); }
+
+// The plan of the launching entry the descriptor belongs to (include/robustart_hip.h): that entry's checks, then steps 1 and 2 of gp_launch.
+extern "C" int rart_gemm_pair_plan_bf16(const rart_gemm_pair_cls_desc* c, int cus, rart_gemm_pair_plan* out) {
+  RART_CHECK_ARG(c != nullptr && out != nullptr, "rart_gemm_pair_plan_bf16: null descriptor or plan");
+  return c->n_classes != 0 ? gp_launch_classes(c, nullptr, out, cus) : gp_launch2(&c->two, nullptr, out, cus);
 }

@@ -768,6 +768,17 @@ bool pp_launch_opt(const GemmPairDev& d, int tn, bool conv, dim3 grid, hipStream
 }
 }  // namespace
 
+// Whether pp_launch_opt above has an instance: what rart_gemm_pair_pp_launch would answer, without launching.  gemm_pair.hip plans with it.
+__attribute__((visibility("hidden"))) bool rart_gemm_pair_pp_has(int tn, bool conv, bool src2, bool cls, bool walk) {
+#ifdef RART_PP_LAB
+  constexpr int opt = 0;                 // the lab build's option values are 0 and 1
+#else
+  constexpr int opt = RART_PP_DEFAULT_OPT;
+#endif
+  if (tn != 256 && tn != 128) return false;
+  return (cls || src2) ? conv && !walk && !(opt & 2) : true;
+}
+
 // Launch by column tile; `dev_desc` is gemm_pair.hip's filled GemmPairDev (same header, same layout).  Returns false when (tn) has no instance.
 // walk_wgs > 0 (grid_y == 1 only): that many workgroups walk the grid_x tiles (OPT bit 1).
 __attribute__((visibility("hidden"))) bool rart_gemm_pair_pp_launch(const void* dev_desc, int tn, bool conv, unsigned grid_x, unsigned grid_y,
