@@ -607,16 +607,28 @@ int rart_softmax_bwd_rows_pair(const void* probs_hi, const void* probs_lo, const
                                int n_valid, int ld_p, int ld_dp, int ld_out, float scale, rart_stream_t stream);
 int rart_vit_unpatchify_from_f32(const float* dpatches, float* grad, int n, int h, int w, int patch, int64_t ld, const float* std_host,
                                  rart_stream_t stream);
-/* Fused multi-head self-attention on pairs (head_dim 64, <= 224 tokens), one workgroup per (image, head): qkv pair [n*tokens][3*D]
+/* Fused multi-head self-attention on pairs (head_dim 64), the RESIDENT form: 1 <= tokens <= 224, one workgroup per (image, head) with the
+ * item's K and V in LDS (more tokens are refused: rart_vit_attention_stream_pair has no such limit).  qkv pair [n*tokens][3*D]
  * (q | k | v column blocks, heads of 64 inside each) -> out pair [n*tokens][D] = softmax(q k^T / 8) v, every contraction three MFMA
- * products, the soft-max in fp32 registers (timm Attention.forward; the reference runs it in fp32). */
+ * products, the soft-max in fp32 registers (timm Attention.forward; the reference runs it in fp32).  The planes have no slack rows. */
 int rart_vit_attention_pair(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, int n, int tokens, int heads, int head_dim,
                             rart_stream_t stream);
-/* Its backward (two launches, csrc/vit_pair.hip): dqkv pair [n*tokens][3*D] (dq | dk | dv) from the qkv pair, the forward's output pair, and
- * the gradient pair of that output.  stats: scratch of n * heads * 32 * ceil(tokens / 32) * 4 floats (per query: max, 1 / sum, delta). */
+/* Its backward (two launches, csrc/vit_pair.hip; head_dim 64, 1 <= tokens <= 224): dqkv pair [n*tokens][3*D] (dq | dk | dv) from the qkv
+ * pair, the forward's output pair, and the gradient pair of that output.  stats: scratch of n * heads * 32 * ceil(tokens / 32) * 4 floats
+ * (per query: max, 1 / sum, delta). */
 int rart_vit_attention_bwd_pair(const void* qkv_hi, const void* qkv_lo, const void* out_hi, const void* out_lo, const void* dout_hi,
                                 const void* dout_lo, void* dqkv_hi, void* dqkv_lo, float* stats, int n, int tokens, int heads, int head_dim,
                                 rart_stream_t stream);
+/* The same attention and its backward, STREAMING (csrc/vit_stream.hip): head_dim 64, any tokens >= 1 (up to 2^20; a shape beyond the
+ * kernels' 32-bit indices is refused with a message).  One workgroup per (image, head, block of at most eight 32-query tiles); K / V
+ * (backward, key side: Q / dO and the statistics) pass through LDS in chunks of 64 rows, the forward keeps a running maximum and sum per
+ * query.  Layouts, the three products per contraction and the stats formula are those of the resident entries; rows past n*tokens of
+ * any plane are never read.  No atomics: results are bit-reproducible and an image's rows do not depend on the batch. */
+int rart_vit_attention_stream_pair(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, int n, int tokens, int heads,
+                                   int head_dim, rart_stream_t stream);
+int rart_vit_attention_bwd_stream_pair(const void* qkv_hi, const void* qkv_lo, const void* out_hi, const void* out_lo, const void* dout_hi,
+                                       const void* dout_lo, void* dqkv_hi, void* dqkv_lo, float* stats, int n, int tokens, int heads,
+                                       int head_dim, rart_stream_t stream);
 
 /* 3x3 stride-1 "same" convolution, channels in = channels out = 64, 128 or 256 (256: images of at most 224 positions, one
  * image per workgroup), bf16 NHWC, with the input halo tile resident in LDS (csrc/conv3x3_halo.hip): ResNet-50's layer1 /
@@ -819,13 +831,23 @@ int rart_softmax_rows_bf16(const void* scores, void* probs, int64_t rows, int n_
                            float scale, rart_stream_t stream);
 /* Fused multi-head attention on the fused qkv activation [n][tokens][3*heads*head_dim] (q | k | v, heads contiguous,
  * timm layout): out[n][tokens][heads*head_dim] = softmax(q k^T / sqrt(head_dim)) v, bf16 in/out, fp32 statistics.
- * head_dim == 64, tokens <= 224.  (timm Attention.forward; model `vit_base`.) */
+ * The RESIDENT form: head_dim == 64, 1 <= tokens <= 224 (an item's K and V stay in LDS; more tokens are refused, see
+ * rart_vit_attention_stream).  (timm Attention.forward; model `vit_base`.) */
 int rart_vit_attention(const void* qkv, void* out, int n, int tokens, int heads, int head_dim, rart_stream_t stream);
-/* Backward of the same attention: dqkv[n][tokens][3*heads*head_dim] (dQ | dK | dV, qkv's layout) from qkv, the forward's
- * output out[n][tokens][heads*head_dim] and its gradient dout; one fused kernel per (image, head), nothing score-sized
- * leaves the chip. */
+/* Backward of the same attention (head_dim == 64, 1 <= tokens <= 224): dqkv[n][tokens][3*heads*head_dim] (dQ | dK | dV, qkv's
+ * layout) from qkv, the forward's output out[n][tokens][heads*head_dim] and its gradient dout; one fused kernel per
+ * (image, head) with Q, K, V and dO resident in LDS, nothing score-sized leaves the chip. */
 int rart_vit_attention_bwd(const void* qkv, const void* out, const void* dout, void* dqkv, int n, int tokens, int heads,
                            int head_dim, rart_stream_t stream);
+/* The same attention and its backward, STREAMING (csrc/vit_stream.hip): head_dim == 64, any tokens >= 1 (up to 2^20; a shape beyond
+ * the kernels' 32-bit indices is refused with a message).  One workgroup per (image, head, block of at most eight 32-query tiles);
+ * K / V pass through LDS in chunks of 64 rows under a running maximum and sum per query.  The backward is two launches (query side:
+ * dQ and the statistics; key side: dK, dV) and needs stats: scratch of n * heads * 32 * ceil(tokens / 32) * 4 floats (per query:
+ * max, 1 / sum, delta).  Layouts are those of the resident entries; the kernels read no row past n*tokens, so the slack rows of qkv
+ * may hold anything.  No atomics: results are bit-reproducible and an image's rows do not depend on the batch. */
+int rart_vit_attention_stream(const void* qkv, void* out, int n, int tokens, int heads, int head_dim, rart_stream_t stream);
+int rart_vit_attention_bwd_stream(const void* qkv, const void* out, const void* dout, void* dqkv, float* stats, int n, int tokens,
+                                  int heads, int head_dim, rart_stream_t stream);
 /* vt[n][heads][head_dim][t_pad] <- V slice of the fused qkv activation [n][tokens][qkv_ld] (zero padded). */
 int rart_vit_transpose_v(const void* qkv, void* vt, int n, int tokens, int heads, int head_dim, int qkv_ld, int v_off,
                          int t_pad, rart_stream_t stream);

@@ -125,6 +125,8 @@ SIGNATURES = {
     'rart_softmax_bwd_rows_pair': (c_int, [c_void_p] * 5 + [ctypes.c_int64, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     'rart_vit_attention_pair': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'rart_vit_attention_bwd_pair': (c_int, [c_void_p] * 9 + [c_int, c_int, c_int, c_int, c_void_p]),
+    'rart_vit_attention_stream_pair': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    'rart_vit_attention_bwd_stream_pair': (c_int, [c_void_p] * 9 + [c_int, c_int, c_int, c_int, c_void_p]),
     'rart_vit_unpatchify_from_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_int64, ctypes.POINTER(c_float), c_void_p]),
     'rart_engine_prep_input': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                        c_void_p]),
@@ -197,6 +199,8 @@ SIGNATURES = {
     'rart_softmax_rows_bf16': (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_int, c_int, c_int, c_float, c_void_p]),
     'rart_vit_attention': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'rart_vit_attention_bwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    'rart_vit_attention_stream': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    'rart_vit_attention_bwd_stream': (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_void_p]),
     'rart_vit_transpose_v': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'rart_gelu_bf16': (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     'rart_gelu_bwd_bf16': (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -9,9 +9,11 @@
 #include "rart_bf16_helpers.h"
 #include <stdlib.h>
 #include "rart_lds_dma.h"
+#include "rart_att_frag.h"
 
 namespace {
 using namespace rart_bf16;
+using namespace rart_att;
 constexpr int kBlock = 256;
 
 // P[row][0..n_valid) = softmax(scale * S[row][0..n_valid)) as a pair, P[row][n_valid..ld_out) = 0; S fp32 (the pair GEMM's fp32
@@ -100,20 +102,14 @@ __global__ __launch_bounds__(kBlock) void k_unpatchify_from_f32(const float* __r
 //      item's operands by LDS-DMA while the other seven compute).  The two forms of a family differ in how the operands reach LDS and in
 //      where the workgroup barriers stand; what a wave computes on a 32-row tile is the SAME text, the patt_* helpers below, so the two
 //      forms agree bit for bit by construction (tests/test_vit_x3_gpu.py compares them, tests/test_att_pair_bits_gpu.py holds both to a
-//      recording).  LDS images enter the helpers as plain pointers; they are inlined, so the accesses stay ds_ instructions.
-constexpr int PATT_HD = 64, PATT_LDK = PATT_HD + 8;
+//      recording).  The fragment helpers (patt_row_frag, patt_tr_frag, patt_split8, patt_load_frags, patt_store_row, RART_MFMA3) are in
+//      rart_att_frag.h, which the streaming kernels (csrc/vit_stream.hip) share.
 // Round 6: EIGHT waves per workgroup (512 threads) instead of four.  The LDS images keep these kernels at one workgroup per CU, so with four
 // waves every SIMD held ONE wave -- nothing ran beside its soft-max VALU work, its LDS gathers or its K / V staging, the matrix pipes were
 // busy 12-13 % of a launch (profiles/r05_x3_counters.json) -- and the seven 32-query tiles of ViT-B/16's 197 tokens took two rounds over
 // four waves.  With eight waves the seven tiles run in one round, two waves per SIMD, and one wave's MFMAs cover the other's vector work.
 constexpr int kAttBlock = 512;
 constexpr int PATT_MAX_TILES = kAttBlock / 64 - 1;       // 224 tokens: every 32-row tile of an item has a wave of its own; the walking kernels' wave 7 loads
-
-// every contraction is three MFMA products: lo.hi + hi.lo + hi.hi
-#define RART_MFMA3(ACC, AH, AL, BH, BL)                                   \
-  ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AL, BH, ACC, 0, 0, 0);    \
-  ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AH, BL, ACC, 0, 0, 0);    \
-  ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AH, BH, ACC, 0, 0, 0);
 
 // one plane of an operand into a row-major [t][72] LDS image, rows past T zero (the one-item kernels' staging)
 __device__ __forceinline__ void patt_load_rows(uint16_t* s, const uint16_t* g, int T, int TP, int ld, int tid) {
@@ -123,62 +119,6 @@ __device__ __forceinline__ void patt_load_rows(uint16_t* s, const uint16_t* g, i
     if (t < T) v = *reinterpret_cast<const uint4*>(g + (size_t)t * ld + c * 8);
     *reinterpret_cast<uint4*>(s + t * PATT_LDK + c * 8) = v;
   }
-}
-// A-operand fragment of a row-major [t][72] image: row t, channels 16 kb + 8 hh .. + 7
-__device__ __forceinline__ bf16x8 patt_row_frag(const uint16_t* s, int t, int kb, int hh) {
-  return *reinterpret_cast<const bf16x8*>(s + t * PATT_LDK + kb * 16 + hh * 8);
-}
-// A-operand fragment of the TRANSPOSE of a row-major [t][72] image: rows = channel d, k = the eight tokens t0 + {0,1,2,3,8,9,10,11}
-__device__ __forceinline__ bf16x8 patt_tr_frag(const uint16_t* s, int t0, int d) {
-  // round 6: two ds_read_b64_tr_b16 instead of eight 2-byte reads.  A 16-lane group reads a [4 tokens][16 channels] block of the row-major
-  // image -- lane a supplies the address of channels 4 (a & 3) .. + 3 of token a >> 2 -- and lane a receives channel a of the four tokens
-  // (the mapping csrc/wgrad_direct.hip uses; scratch/r4/probe_tr16.hip prints it).  Callers pass d = 32 nt + (lane & 31) and a t0 that is
-  // uniform over a 16-lane group, so a = d & 15 and the group's channel base is d - a.  144-byte rows: 8-byte aligned addresses.
-  typedef __attribute__((ext_vector_type(4))) short s16x4;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  const int a = d & 15;
-  const uint16_t* p = s + (t0 + (a >> 2)) * PATT_LDK + (d - a) + 4 * (a & 3);
-  const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-  const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p + 8 * PATT_LDK));
-  const s16x8 r = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-  return __builtin_bit_cast(bf16x8, r);
-}
-__device__ __forceinline__ void patt_split8(const float* v, bf16x8& hi, bf16x8& lo) {
-  uint4 h, l;
-  split8(v, h, l);
-  hi = *reinterpret_cast<bf16x8*>(&h);
-  lo = *reinterpret_cast<bf16x8*>(&l);
-}
-// the B fragments of one row of a pair in global memory (channels 16 kb + 8 hh .. + 7, kb = 0 .. 3 at gh / gl + off); zeros for a row past T
-__device__ __forceinline__ void patt_load_frags(bf16x8 (&bh)[4], bf16x8 (&bl)[4], const uint16_t* gh, const uint16_t* gl, size_t off, bool ok,
-                                                int hh) {
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb) {
-    uint4 vh = make_uint4(0, 0, 0, 0), vl = make_uint4(0, 0, 0, 0);
-    if (ok) {
-      vh = *reinterpret_cast<const uint4*>(gh + off + kb * 16 + hh * 8);
-      vl = *reinterpret_cast<const uint4*>(gl + off + kb * 16 + hh * 8);
-    }
-    bh[kb] = *reinterpret_cast<bf16x8*>(&vh);
-    bl[kb] = *reinterpret_cast<bf16x8*>(&vl);
-  }
-}
-// acc[nt][r] = X[the lane's row][d = nt*32 + (r&3) + 8*(r>>2) + 4*hh]: a lane owns runs of four channels of ITS row -> the value (times
-// `mul`: the forward's 1 / sum) split into hi + lo, one 8-byte store per plane; dh / dl: channel 0 of the lane's row in each plane
-template <bool SCALED>
-__device__ __forceinline__ void patt_store_row(const f32x16 (&acc)[2], float mul, uint16_t* dh, uint16_t* dl, int hh) {
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      float v[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = SCALED ? acc[nt][4 * g + j] * mul : acc[nt][4 * g + j];
-      uint2 vh, vl;
-      split4(v, vh, vl);
-      *reinterpret_cast<uint2*>(dh + nt * 32 + 8 * g + 4 * hh) = vh;
-      *reinterpret_cast<uint2*>(dl + nt * 32 + 8 * g + 4 * hh) = vl;
-    }
 }
 
 // ---- what the walking kernels share

@@ -9,7 +9,8 @@ GEMMs carry GELU' in their epilogue, the LayerNorm backward adds the residual gr
 'bf16': bf16 storage, fp32 accumulation and statistics: rart_conv_igemm_bf16, rart_layernorm[_bwd]_bf16, rart_vit_attention[_bwd],
 csrc/vit_aux.hip, csrc/vit_bwd.hip.  'bf16x3' (alias 'fp32x'), the reference-precision mode: every activation, gradient and weight a
 hi + lo pair of bf16 planes, rart_gemm_pair_bf16 (three MFMA products per contraction), rart_layernorm[_bwd]_pair,
-rart_vit_attention[_bwd]_pair, soft-max and GELU in fp32 on hi + lo (csrc/vit_pair.hip).  The LayerNorm entries of both precisions
+rart_vit_attention[_bwd]_pair, soft-max and GELU in fp32 on hi + lo (csrc/vit_pair.hip).  Above 224 tokens (`stream_attention`) the fused
+attention of both precisions is the streaming one, rart_vit_attention[_bwd]_stream[_pair] (csrc/vit_stream.hip).  The LayerNorm entries of both precisions
 are one kernel per direction (csrc/row_norm.hip), and so is the class-token / position add (csrc/vit_aux.hip).
 A module whose patch embedding is a ConvStem (`vit_base_cvst`) runs the chain of convstem_engine.py in place of patch extraction + patch GEMM.
 Reference module: robustart_amd/model/vit_torch.py."""
@@ -77,7 +78,8 @@ class ViTEngine(RowEngine):
         P = (Himg // ps) * (Wimg // ps)
         T = P + 1
         assert T == self.tokens, 'image size does not match the position embedding'
-        assert not self.x3 or T <= 256, 'the pair soft-max rows hold at most 256 keys'
+        if self.x3 and not (self.fused_attention and self._pair_fused(T)):
+            self._check_unfused_pair(T)
         kk = 3 * ps * ps
         rows = B * T
         x = self._act('x0' if keep else 'x', (B, T, D))
@@ -123,19 +125,39 @@ class ViTEngine(RowEngine):
         return self._head_logits(cls, B, D)
 
     # ------------------------------------------------------------------ attention, per (image, head)
+    RESIDENT_TOKENS = 224           # what the resident fused attention entries take: a whole (image, head) item in LDS
+    stream_attention = None         # None: the streaming fused entries above RESIDENT_TOKENS; True / False forces (the cross-check)
+
     def _pair_fused(self, T):
-        """the fused pair attention kernels take 64-wide heads and up to 224 tokens; the bf16 ones have no such condition"""
-        return self.hd == 64 and T <= 224
+        """the fused pair attention kernels take 64-wide heads; the bf16 ones have no such condition"""
+        return self.hd == 64
+
+    @staticmethod
+    def _check_unfused_pair(T):
+        if T > 256:
+            raise ValueError('%d tokens: the unfused pair attention holds soft-max rows of at most 256 keys (rart_softmax_rows_pair); '
+                             'the fused entries (64-wide heads) have no token limit' % T)
+
+    def _streams(self, T):
+        """whether the fused attention of T tokens runs on the streaming entries (K / V through LDS in chunks, any T) and not on the
+        resident ones (T <= 224)"""
+        return T > self.RESIDENT_TOKENS if self.stream_attention is None else bool(self.stream_attention)
+
+    def _att_stats(self, B, T):
+        """per-query statistics (max, 1 / sum, delta) between the two launches of a fused backward"""
+        return self._get('att_stats', (B * self.H, k32(T), 4), _lib.require_gpu().float32)
 
     def _attention(self, qkv, att, B, T):
         """att[rows][D] = softmax(Q K^T / sqrt(hd)) V of one layer's qkv[rows][3D]"""
         lib, sp = self.lib, _lib.stream_ptr()
         if self.x3 and self.fused_attention and self._pair_fused(T):
-            _lib.check(lib.rart_vit_attention_pair(*self._hl(qkv), *self._hl(att), B, T, self.H, self.hd, sp))
+            entry = lib.rart_vit_attention_stream_pair if self._streams(T) else lib.rart_vit_attention_pair
+            _lib.check(entry(*self._hl(qkv), *self._hl(att), B, T, self.H, self.hd, sp))
         elif self.x3:
             self._attention_unfused_pair(qkv, att, B, T)
         elif self.fused_attention:
-            _lib.check(lib.rart_vit_attention(_lib.ptr(qkv), _lib.ptr(att), B, T, self.H, self.hd, sp))
+            entry = lib.rart_vit_attention_stream if self._streams(T) else lib.rart_vit_attention
+            _lib.check(entry(_lib.ptr(qkv), _lib.ptr(att), B, T, self.H, self.hd, sp))
         else:
             self._attention_unfused(qkv, att, B, T)
 
@@ -143,12 +165,15 @@ class ViTEngine(RowEngine):
         """dqkv[rows][3D] from datt[rows][D] for one layer; att is the forward's output (the fused kernels' delta)"""
         lib, sp = self.lib, _lib.stream_ptr()
         if self.x3 and self.fused_attention_bwd and self._pair_fused(T):
-            torch = _lib.require_gpu()
-            stats = self._get('att_stats', (B * self.H, k32(T), 4), torch.float32)       # per-query statistics between its two launches
-            _lib.check(lib.rart_vit_attention_bwd_pair(*self._hl(qkv), *self._hl(att), *self._hl(datt), *self._hl(dqkv),
-                                                       _lib.ptr(stats), B, T, self.H, self.hd, sp))
+            entry = lib.rart_vit_attention_bwd_stream_pair if self._streams(T) else lib.rart_vit_attention_bwd_pair
+            _lib.check(entry(*self._hl(qkv), *self._hl(att), *self._hl(datt), *self._hl(dqkv), _lib.ptr(self._att_stats(B, T)), B, T,
+                             self.H, self.hd, sp))
         elif self.x3:
+            self._check_unfused_pair(T)
             self._attention_bwd_unfused_pair(qkv, datt, dqkv, B, T)
+        elif self.fused_attention_bwd and self._streams(T):
+            _lib.check(lib.rart_vit_attention_bwd_stream(_lib.ptr(qkv), _lib.ptr(att), _lib.ptr(datt), _lib.ptr(dqkv),
+                                                         _lib.ptr(self._att_stats(B, T)), B, T, self.H, self.hd, sp))
         elif self.fused_attention_bwd:
             _lib.check(lib.rart_vit_attention_bwd(_lib.ptr(qkv), _lib.ptr(att), _lib.ptr(datt), _lib.ptr(dqkv), B, T, self.H, self.hd, sp))
         else:

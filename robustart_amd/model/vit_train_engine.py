@@ -64,8 +64,7 @@ class ViTTrainEngine(RowTrainMixin, ViTEngine):
             self.on_grad_ready(blk.attn.proj.bias)
             datt = self._get('g_att', (rows, D))
             self._mm(dxm, L['proj_wd'], datt, rows, D, D)
-            _lib.check(lib.rart_vit_attention_bwd(_lib.ptr(qkv), _lib.ptr(att), _lib.ptr(datt), _lib.ptr(dqkv), B, T, self.H,
-                                                  self.hd, sp))
+            self._attention_bwd(qkv, att, datt, dqkv, B, T)
             self._ln(x_in, L['n1g'], L['n1b'], ln, rows, D)
             self._linear_grads(blk.attn.qkv, dqkv, 3 * D, ln, rows)
             self._colsum(dqkv, 3 * D, rows, 3 * D, blk.attn.qkv.bias.grad)
