@@ -586,7 +586,7 @@ int rart_conv3x3_tail_pair_get_staging(void);
 int rart_conv3x3_tail_pair_set_tables(int mode);
 int rart_conv3x3_tail_pair_get_tables(void);
 
-/* Row / elementwise kernels of the reference-precision ViT-B/16 engine (soft-max rows, unpatchify: csrc/vit_pair.hip; layernorm
+/* Row / elementwise kernels of the reference-precision ViT-B/16 engine (soft-max rows: csrc/vit_pair.hip; unpatchify: csrc/vit_bwd.hip, one kernel for bf16 and fp32 patches; layernorm
  * and its backward: csrc/row_norm.hip, one kernel per direction for this storage and for bf16; add_pos_cls: csrc/vit_aux.hip,
  * likewise): every tensor a pair of bf16 planes, the arithmetic in fp32 as the fp32 module (timm ViT-B/16,
  * RobustART/model/__init__.py:1 -> absent submodule) does it.
@@ -753,7 +753,7 @@ int rart_engine_avgpool_bwd(const void* y, const void* dpool, void* dz, int n, i
  * the [0,1] image (the 1/std of the normalisation applied). */
 int rart_engine_stem_col2im(const void* patches, float* grad, int n, int h, int w, int patch_cols,
                             const float* std_host, rart_stream_t stream);
-/* ---- reference-precision ("bf16x3") forms of the pools / converters (csrc/engine_aux_pair.hip) -----------------------------
+/* ---- reference-precision ("bf16x3") forms of the pools / converters (csrc/engine_aux.hip) ----------------------------------
  * Every tensor is a PAIR of bf16 planes, value = hi + lo (see rart_conv_desc flag 32): `*_hi` names the hi plane and the lo
  * plane sits `*_lo_off` ELEMENTS behind it (a positive multiple of 8).  Arithmetic: unpack to fp32 (hi + lo is exact),
  * compute as the bf16 kernel of the same name, split again.  Reference: the fp32 max_pool2d / adaptive_avg_pool2d and their

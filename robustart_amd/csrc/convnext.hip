@@ -199,15 +199,12 @@ __global__ __launch_bounds__(kBlock) void k_pool_bwd(const uint16_t* __restrict_
   }
 }
 
-struct Norm3 {
-  float mean[3], istd[3];
-};
 
 // out[b][py * gw + px][c * ps * ps + r * ps + s] = (x[b][c][py * ps + r][px * ps + s] - mean) / std as hi and lo bf16 planes, row
 // stride ld; columns 3 ps^2 .. ld are zero (K padded to the GEMM's granularity).  Eight columns per thread.
 template <bool SRC_U8>
 __global__ __launch_bounds__(kBlock) void k_patchify(const void* __restrict__ src, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo,
-                                                     int h, int w, int ps, int ld, uint32_t total8, Norm3 nm) {
+                                                     int h, int w, int ps, int ld, uint32_t total8, RartNorm3 nm) {
   const uint32_t gw = (uint32_t)(w / ps), gh = (uint32_t)(h / ps), ld8 = (uint32_t)ld / 8, kk = 3u * ps * ps;
   for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < total8; i += gridDim.x * kBlock) {
     const uint32_t k8 = i % ld8, pidx = i / ld8;
@@ -237,7 +234,6 @@ __global__ __launch_bounds__(kBlock) void k_patchify(const void* __restrict__ sr
   }
 }
 
-int grid_for(size_t items) { return rart_grid_for(items, kBlock, 256 * 16); }
 
 // the conv loads four channels per access: 8-byte activation, 16-byte weight / bias alignment
 bool al(const void* p, uintptr_t a) { return ((uintptr_t)p % a) == 0; }
@@ -308,7 +304,7 @@ int rart_cnx_pool_bwd_bf16(const void* dpool, void* dz, int n, int hw, int c, ra
   RART_CHECK_ARG(dpool && dz && n > 0 && hw > 0 && c > 0 && c % 8 == 0 && (size_t)n * hw * c / 8 < (1ull << 32),
                  "rart_cnx_pool_bwd_bf16: bad arguments (c a multiple of 8)");
   const size_t total8 = (size_t)n * hw * c / 8;
-  hipLaunchKernelGGL(k_pool_bwd<false>, dim3(grid_for(total8)), dim3(kBlock), 0, (hipStream_t)stream, (const uint16_t*)dpool,
+  hipLaunchKernelGGL(k_pool_bwd<false>, dim3(rart_grid_wide(total8)), dim3(kBlock), 0, (hipStream_t)stream, (const uint16_t*)dpool,
                      (const uint16_t*)dpool, (uint16_t*)dz, (uint16_t*)dz, hw, c, (uint32_t)total8);
   RART_CHECK_LAUNCH("rart_cnx_pool_bwd_bf16");
   return RART_OK;
@@ -318,7 +314,7 @@ int rart_cnx_pool_bwd_pair(const void* dpool_hi, const void* dpool_lo, void* dz_
   RART_CHECK_ARG(dpool_hi && dpool_lo && dz_hi && dz_lo && n > 0 && hw > 0 && c > 0 && c % 8 == 0 && (size_t)n * hw * c / 8 < (1ull << 32),
                  "rart_cnx_pool_bwd_pair: bad arguments (c a multiple of 8)");
   const size_t total8 = (size_t)n * hw * c / 8;
-  hipLaunchKernelGGL(k_pool_bwd<true>, dim3(grid_for(total8)), dim3(kBlock), 0, (hipStream_t)stream, (const uint16_t*)dpool_hi,
+  hipLaunchKernelGGL(k_pool_bwd<true>, dim3(rart_grid_wide(total8)), dim3(kBlock), 0, (hipStream_t)stream, (const uint16_t*)dpool_hi,
                      (const uint16_t*)dpool_lo, (uint16_t*)dz_hi, (uint16_t*)dz_lo, hw, c, (uint32_t)total8);
   RART_CHECK_LAUNCH("rart_cnx_pool_bwd_pair");
   return RART_OK;
@@ -330,17 +326,13 @@ int rart_cnx_patchify(const void* src, int src_is_u8, void* hi, void* lo, int n,
                  "rart_cnx_patchify: bad arguments (patch side 1..8 dividing the image)");
   RART_CHECK_ARG(ld >= 3 * patch * patch && ld % 8 == 0 && (size_t)n * (h / patch) * (w / patch) * ld / 8 < (1ull << 32),
                  "rart_cnx_patchify: the row stride ld must be a multiple of 8 and at least 3 * patch^2");
-  Norm3 nm;
-  for (int c = 0; c < 3; ++c) {
-    nm.mean[c] = mean_host ? mean_host[c] : 0.f;
-    nm.istd[c] = std_host ? 1.0f / std_host[c] : 1.f;
-  }
+  const RartNorm3 nm = rart_norm3(mean_host, std_host);
   const size_t total8 = (size_t)n * (h / patch) * (w / patch) * ld / 8;
   if (src_is_u8)
-    hipLaunchKernelGGL(k_patchify<true>, dim3(grid_for(total8)), dim3(kBlock), 0, (hipStream_t)stream, src, (uint16_t*)hi, (uint16_t*)lo,
+    hipLaunchKernelGGL(k_patchify<true>, dim3(rart_grid_wide(total8)), dim3(kBlock), 0, (hipStream_t)stream, src, (uint16_t*)hi, (uint16_t*)lo,
                        h, w, patch, ld, (uint32_t)total8, nm);
   else
-    hipLaunchKernelGGL(k_patchify<false>, dim3(grid_for(total8)), dim3(kBlock), 0, (hipStream_t)stream, src, (uint16_t*)hi, (uint16_t*)lo,
+    hipLaunchKernelGGL(k_patchify<false>, dim3(rart_grid_wide(total8)), dim3(kBlock), 0, (hipStream_t)stream, src, (uint16_t*)hi, (uint16_t*)lo,
                        h, w, patch, ld, (uint32_t)total8, nm);
   RART_CHECK_LAUNCH("rart_cnx_patchify");
   return RART_OK;

@@ -27,10 +27,6 @@ namespace {
 using namespace rart_bf16;
 constexpr int kBlock = 256;
 
-struct Norm3 {
-  float mean[3], istd[3];
-};
-
 template <bool PAIR>
 __device__ __forceinline__ void cs_zero8(uint16_t* __restrict__ h, uint16_t* __restrict__ l, size_t i) {
   *reinterpret_cast<uint4*>(h + i) = make_uint4(0, 0, 0, 0);
@@ -183,7 +179,7 @@ int launch_ln_gelu(const void* xh, const void* xl, const void* dyh, const void* 
 // channel c, 0 outside the image and for k >= 27.  Eight columns per thread.
 template <bool SRC_U8>
 __global__ __launch_bounds__(kBlock) void k_cvst_im2col(const void* __restrict__ src, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo,
-                                                        int h, int w, int ld, uint32_t total8, Norm3 nm) {
+                                                        int h, int w, int ld, uint32_t total8, RartNorm3 nm) {
   const uint32_t gw = (uint32_t)w / 2, gh = (uint32_t)h / 2, ld8 = (uint32_t)ld / 8;
   // the stride loop counts in 64 bits (total8 may come close to 2^32), an item's index fits 32
   for (uint64_t it = (uint64_t)blockIdx.x * kBlock + threadIdx.x; it < total8; it += (uint64_t)gridDim.x * kBlock) {
@@ -220,7 +216,7 @@ __global__ __launch_bounds__(kBlock) void k_cvst_im2col(const void* __restrict__
 // summed in that order; neighbours past the last patch row / column contribute nothing.
 template <int NX>
 __global__ __launch_bounds__(kBlock) void k_cvst_col2im(const float* __restrict__ dp, float* __restrict__ grad, int h, int w, int ld,
-                                                        uint32_t total, Norm3 nm) {
+                                                        uint32_t total, RartNorm3 nm) {
   const uint32_t gw = (uint32_t)w / 2, gh = (uint32_t)h / 2, gwn = gw / NX;
   for (uint64_t it = (uint64_t)blockIdx.x * kBlock + threadIdx.x; it < total; it += (uint64_t)gridDim.x * kBlock) {
     const uint32_t i = (uint32_t)it;
@@ -262,13 +258,6 @@ __global__ __launch_bounds__(kBlock) void k_cvst_col2im(const float* __restrict_
     }
   }
 }
-
-void norm3(Norm3& nm, const float* mean_host, const float* std_host) {
-  for (int c = 0; c < 3; ++c) {
-    nm.mean[c] = mean_host ? mean_host[c] : 0.f;
-    nm.istd[c] = std_host ? 1.0f / std_host[c] : 1.f;
-  }
-}
 }  // namespace
 
 int rart_cvst_im2col(const void* src, int src_is_u8, void* hi, void* lo, int n, int h, int w, int ld, const float* mean_host,
@@ -281,9 +270,8 @@ int rart_cvst_im2col(const void* src, int src_is_u8, void* hi, void* lo, int n, 
   RART_CHECK_ARG(ld >= 32 && ld % 8 == 0 && al16(hi) && al16(lo), "rart_cvst_im2col: ld a multiple of 8 and >= 32, planes 16-byte aligned");
   const size_t total8 = (size_t)n * (h / 2) * (w / 2) * ld / 8;
   RART_CHECK_ARG(total8 < (1ull << 32), "rart_cvst_im2col: too many patches for one launch (split the batch)");
-  Norm3 nm;
-  norm3(nm, mean_host, std_host);
-  const int grid = rart_grid_for(total8, kBlock, 256 * 16);
+  const RartNorm3 nm = rart_norm3(mean_host, std_host);
+  const int grid = rart_grid_wide(total8);
   if (src_is_u8)
     hipLaunchKernelGGL(k_cvst_im2col<true>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, src, (uint16_t*)hi, (uint16_t*)lo, h, w, ld,
                        (uint32_t)total8, nm);
@@ -302,11 +290,10 @@ int rart_cvst_col2im_f32(const float* dpatches, float* grad, int n, int h, int w
   }
   const size_t positions = (size_t)n * (h / 2) * (w / 2);
   RART_CHECK_ARG(positions < (1ull << 32), "rart_cvst_col2im_f32: too many patches for one launch (split the batch)");
-  Norm3 nm;
-  norm3(nm, nullptr, std_host);
+  const RartNorm3 nm = rart_norm3(nullptr, std_host);
   const bool wide = w % 4 == 0 && al16(grad);            // float4 stores: two patch positions per thread
   const size_t total = wide ? positions / 2 : positions;
-  const int grid = rart_grid_for(total, kBlock, 256 * 16);
+  const int grid = rart_grid_wide(total);
   if (wide)
     hipLaunchKernelGGL(k_cvst_col2im<2>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, dpatches, grad, h, w, ld, (uint32_t)total, nm);
   else

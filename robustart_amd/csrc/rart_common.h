@@ -49,6 +49,30 @@ static inline int rart_grid_for(size_t work_items, int block = 256, int max_bloc
   if (g > (size_t)max_blocks) g = max_blocks;
   return (int)g;
 }
+// the same with twice the cap: what the glue kernels of the engines (pools, converters, patch gathers) and the resize passes launch
+static inline int rart_grid_wide(size_t work_items) { return rart_grid_for(work_items, 256, 256 * 16); }
+
+// ---- per-channel normalisation constants of the image <-> activation boundary, passed to kernels by value.  Forward kernels take
+//      v = (x - mean[c]) * istd[c], the gradient kernels scale by istd[c] alone; a null mean is 0, a null std is 1.
+struct RartNorm3 {
+  float mean[3], istd[3];
+};
+struct RartIstd3 {
+  float v[3];
+};
+static inline RartNorm3 rart_norm3(const float* mean_host, const float* std_host) {
+  RartNorm3 nm;
+  for (int c = 0; c < 3; ++c) {
+    nm.mean[c] = mean_host ? mean_host[c] : 0.f;
+    nm.istd[c] = std_host ? 1.0f / std_host[c] : 1.f;
+  }
+  return nm;
+}
+static inline RartIstd3 rart_istd3(const float* std_host) {
+  RartIstd3 is;
+  for (int c = 0; c < 3; ++c) is.v[c] = std_host ? 1.0f / std_host[c] : 1.f;
+  return is;
+}
 
 // ---- per-severity tables (imagenet_c/corruptions.py) ------------
 struct RartSeverity {

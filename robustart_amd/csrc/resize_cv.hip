@@ -125,7 +125,6 @@ __global__ __launch_bounds__(kBlock) void k_cv_area_fast(const uint8_t* __restri
     out[i] = (uint8_t)clampi(v, 0, 255);
   }
 }
-int grid_for(size_t items) { return rart_grid_for(items, kBlock, 256 * 16); }
 
 struct CvPlan {
   int mode;          // PATH_*: 0 nearest, 1 two-pass fixed point, 2 area tables, 3 area fast
@@ -190,14 +189,14 @@ int rart_cv_resize_u8(const uint8_t* in, uint8_t* out, int n, int h, int w, int 
   const double scale_x = 1.0 / ((double)resize_w / w), scale_y = 1.0 / ((double)resize_h / h);
   const size_t out_items = (size_t)n * crop_h * crop_w * 3;
   if (p.mode == 0) {
-    hipLaunchKernelGGL(k_cv_nearest, dim3(grid_for(out_items / 3)), dim3(kBlock), 0, st, in, out, n, h, w, scale_x, scale_y,
+    hipLaunchKernelGGL(k_cv_nearest, dim3(rart_grid_wide(out_items / 3)), dim3(kBlock), 0, st, in, out, n, h, w, scale_x, scale_y,
                        crop_y, crop_x, crop_h, crop_w);
     RART_CHECK_LAUNCH("rart_cv_resize_u8 (nearest)");
     return RART_OK;
   }
   if (p.mode == 3) {
     const int isx = (int)lrint(scale_x), isy = (int)lrint(scale_y);
-    hipLaunchKernelGGL(k_cv_area_fast, dim3(grid_for(out_items)), dim3(kBlock), 0, st, in, out, n, h, w, isx, isy,
+    hipLaunchKernelGGL(k_cv_area_fast, dim3(rart_grid_wide(out_items)), dim3(kBlock), 0, st, in, out, n, h, w, isx, isy,
                        1.f / (float)(isx * isy), crop_y, crop_x, crop_h, crop_w);
     RART_CHECK_LAUNCH("rart_cv_resize_u8 (area, integer scale)");
     return RART_OK;
@@ -217,13 +216,13 @@ int rart_cv_resize_u8(const uint8_t* in, uint8_t* out, int n, int h, int w, int 
     return RART_ERR_HIP;
   }
   if (p.mode == 2) {
-    hipLaunchKernelGGL(k_cv_area, dim3(grid_for(out_items)), dim3(kBlock), 0, st, in, out, (const int*)tabx, p.ax->max_count,
+    hipLaunchKernelGGL(k_cv_area, dim3(rart_grid_wide(out_items)), dim3(kBlock), 0, st, in, out, (const int*)tabx, p.ax->max_count,
                        (const int*)taby, p.ay->max_count, n, h, w, crop_y, crop_x, crop_h, crop_w);
   } else {
     int* tmp = (int*)((uint8_t*)workspace + p.tabx_bytes + p.taby_bytes);
-    hipLaunchKernelGGL(k_cv_h, dim3(grid_for((size_t)n * p.y_count * crop_w * 3)), dim3(kBlock), 0, st, in, tmp,
+    hipLaunchKernelGGL(k_cv_h, dim3(rart_grid_wide((size_t)n * p.y_count * crop_w * 3)), dim3(kBlock), 0, st, in, tmp,
                        (const int*)tabx, p.tx->ksize, n, h, w, crop_x, crop_w, p.y_first, p.y_count);
-    hipLaunchKernelGGL(k_cv_v, dim3(grid_for(out_items)), dim3(kBlock), 0, st, (const int*)tmp, out, (const int*)taby,
+    hipLaunchKernelGGL(k_cv_v, dim3(rart_grid_wide(out_items)), dim3(kBlock), 0, st, (const int*)tmp, out, (const int*)taby,
                        p.ty->ksize, n, h, p.y_first, p.y_count, crop_y, crop_h, crop_w);
   }
   RART_CHECK_LAUNCH("rart_cv_resize_u8");

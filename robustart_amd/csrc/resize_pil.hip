@@ -67,7 +67,6 @@ __global__ __launch_bounds__(kBlock) void k_resize_nearest(const uint8_t* __rest
     out[i * 3 + 2] = s[2];
   }
 }
-int grid_for(size_t items) { return rart_grid_for(items, kBlock, 256 * 16); }
 
 struct Plan {
   int y_first, y_count, ks_h, ks_v;
@@ -119,7 +118,7 @@ int rart_pil_resize_u8(const uint8_t* in, uint8_t* out, int n, int h, int w, int
   if (filter == 0) {
     auto fix = [](double v) { return (int)floor(v * 65536.0 + 0.5); };
     const double a0 = (double)w / resize_w, a4 = (double)h / resize_h;
-    hipLaunchKernelGGL(k_resize_nearest, dim3(grid_for((size_t)n * crop_h * crop_w)), dim3(kBlock), 0, st, in, out, n, h,
+    hipLaunchKernelGGL(k_resize_nearest, dim3(rart_grid_wide((size_t)n * crop_h * crop_w)), dim3(kBlock), 0, st, in, out, n, h,
                        w, fix(a0 * 0.5), fix(a0), fix(a4 * 0.5), fix(a4), crop_y, crop_x, crop_h, crop_w);
     RART_CHECK_LAUNCH("rart_pil_resize_u8 (nearest)");
     return RART_OK;
@@ -140,9 +139,9 @@ int rart_pil_resize_u8(const uint8_t* in, uint8_t* out, int n, int h, int w, int
     rart_set_error("rart_pil_resize_u8: coefficient upload failed");
     return RART_ERR_HIP;
   }
-  hipLaunchKernelGGL(k_resample_h, dim3(grid_for((size_t)n * p.y_count * crop_w * 3)), dim3(kBlock), 0, st, in, tmp,
+  hipLaunchKernelGGL(k_resample_h, dim3(rart_grid_wide((size_t)n * p.y_count * crop_w * 3)), dim3(kBlock), 0, st, in, tmp,
                      (const int*)tab_h, p.ks_h, n, h, w, crop_x, crop_w, p.y_first, p.y_count);
-  hipLaunchKernelGGL(k_resample_v, dim3(grid_for((size_t)n * crop_h * crop_w * 3)), dim3(kBlock), 0, st,
+  hipLaunchKernelGGL(k_resample_v, dim3(rart_grid_wide((size_t)n * crop_h * crop_w * 3)), dim3(kBlock), 0, st,
                      (const uint8_t*)tmp, out, (const int*)tab_v, p.ks_v, n, p.y_first, p.y_count, crop_y, crop_h, crop_w);
   RART_CHECK_LAUNCH("rart_pil_resize_u8");
   return RART_OK;

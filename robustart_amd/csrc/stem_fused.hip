@@ -78,13 +78,12 @@ __device__ __forceinline__ void pool_bwd_class(uint4* sDz1, const uint4* sDp, co
   }
 }
 
-struct Istd3 { float v[3]; };
 
 __global__ __launch_bounds__(256, 2) void k_stem_bwd_fused(const uint4* __restrict__ dpool,   // [n][oh2][ow2][64] bf16
                                                            const uint2* __restrict__ arg,     // [n][oh2][ow2][64] u8
                                                            const uint16_t* __restrict__ wt,   // [16][1024] bf16
                                                            float* __restrict__ grad,          // [n][3][h][w]
-                                                           int h, int w, Istd3 istd) {
+                                                           int h, int w, RartIstd3 istd) {
   // one LDS object (a second one makes hipcc wait vmcnt(0) before LDS reads): dz1 tile | raw pooled tile (later: out tile)
   __shared__ __attribute__((aligned(16))) uint8_t lds[8 * NPOS_PAD * 16 + NPOOL * 192];
   uint4* sDz1 = reinterpret_cast<uint4*>(lds);                          // [8][NPOS_PAD]
@@ -185,8 +184,7 @@ extern "C" int rart_engine_stem_bwd_fused(const void* dpool, const void* argmax,
                                           int w, const float* std_host, rart_stream_t stream) {
   RART_CHECK_ARG(dpool && argmax && wtab && grad && n > 0 && n <= 65535, "rart_engine_stem_bwd_fused: bad arguments");
   RART_CHECK_ARG(h % 4 == 0 && w % 4 == 0 && h >= 4 && w >= 4, "rart_engine_stem_bwd_fused: h and w must be multiples of 4");
-  Istd3 is;
-  for (int c = 0; c < 3; ++c) is.v[c] = std_host ? 1.0f / std_host[c] : 1.0f;
+  const RartIstd3 is = rart_istd3(std_host);
   const int oh = h / 2, ow = w / 2;
   hipLaunchKernelGGL(k_stem_bwd_fused, dim3((ow + T - 1) / T, (oh + T - 1) / T, n), dim3(256), 0, (hipStream_t)stream,
                      (const uint4*)dpool, (const uint2*)argmax, (const uint16_t*)wtab, grad, h, w, is);
@@ -221,7 +219,6 @@ constexpr int SF_W_BYTES = 64 * SF_WROW;        // 29 696
 constexpr int SF_T_BYTES = SF_NPOS * SF_YROW;   // 41 616 (>= 2 * SF_PLANE: the tile aliases the patch)
 static_assert(SF_T_BYTES >= 2 * SF_PLANE, "the stem-output tile must cover the patch it aliases");
 
-struct StemNorm { float mean[3], istd[3]; };
 // the normalisation must round exactly like k_prep_input (engine_aux.hip): multiply, subtract, multiply -- no contraction
 #pragma clang fp contract(off)
 
@@ -229,7 +226,7 @@ template <bool SRC_U8>
 __global__ __launch_bounds__(256, 2) void k_stem_fwd_fused(const void* __restrict__ src, const uint16_t* __restrict__ wgt,
                                                            int wgt_row_stride, const float* __restrict__ bias,
                                                            uint4* __restrict__ p1, uint2* __restrict__ arg,
-                                                           uint8_t* __restrict__ sign, int n, int h, int w, StemNorm nm) {
+                                                           uint8_t* __restrict__ sign, int n, int h, int w, RartNorm3 nm) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[SF_W_BYTES + SF_T_BYTES];
   uint8_t* sW = lds;
   uint8_t* sP = lds + SF_W_BYTES;               // patch (hi plane, lo plane) / stem-output tile
@@ -386,11 +383,7 @@ extern "C" int rart_engine_stem_fwd_fused(const void* src, int src_is_u8, const 
                                           const float* mean_host, const float* std_host, rart_stream_t stream) {
   RART_CHECK_ARG(src && wgt && p1 && n > 0 && h % 4 == 0 && w % 4 == 0 && h >= 4 && w >= 4 && wgt_row_stride >= 224 &&
                  wgt_row_stride % 8 == 0, "rart_engine_stem_fwd_fused: bad arguments (h, w multiples of 4)");
-  StemNorm nm;
-  for (int c = 0; c < 3; ++c) {
-    nm.mean[c] = mean_host ? mean_host[c] : 0.f;
-    nm.istd[c] = std_host ? 1.0f / std_host[c] : 1.f;
-  }
+  const RartNorm3 nm = rart_norm3(mean_host, std_host);
   const long long tiles = (long long)n * ((h / 4 + SF_PT - 1) / SF_PT) * ((w / 4 + SF_PT - 1) / SF_PT);
   const int grid = (int)(tiles < 512 ? tiles : 512);              // persistent: 2 workgroups per CU
   if (src_is_u8)

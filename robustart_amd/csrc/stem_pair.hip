@@ -118,7 +118,6 @@ __device__ __forceinline__ void pool_bwd_class_pair(uint4* sDz1, const uint4* sD
   }
 }
 
-struct Istd3p { float v[3]; };
 
 __global__ __launch_bounds__(256, 2) void k_stem_bwd_pair(const uint4* __restrict__ dpool_h,    // [n][oh2][ow2][64] bf16, hi plane
                                                           const uint4* __restrict__ dpool_l,    // lo plane
@@ -126,7 +125,7 @@ __global__ __launch_bounds__(256, 2) void k_stem_bwd_pair(const uint4* __restric
                                                           const uint16_t* __restrict__ wt_h,    // [16][1024] bf16 (stem_fused.hip's table), hi
                                                           const uint16_t* __restrict__ wt_l,    // lo
                                                           float* __restrict__ grad,             // [n][3][h][w]
-                                                          int h, int w, Istd3p istd) {
+                                                          int h, int w, RartIstd3 istd) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[DZ_BYTES + RW_BYTES];
   uint4* sDz1 = reinterpret_cast<uint4*>(lds);                                     // [2][4][NPOS_PAD]
   uint4* sDp = reinterpret_cast<uint4*>(lds + DZ_BYTES);                           // [2][NPOOL_PAD][4] (window-major)
@@ -275,8 +274,7 @@ extern "C" int rart_engine_stem_bwd_fused_pair(const void* dpool_hi, const void*
   RART_CHECK_ARG(dpool_hi && dpool_lo && argmax && wtab_hi && wtab_lo && grad && n > 0 && n <= 65535,
                  "rart_engine_stem_bwd_fused_pair: bad arguments");
   RART_CHECK_ARG(h % 4 == 0 && w % 4 == 0 && h >= 4 && w >= 4, "rart_engine_stem_bwd_fused_pair: h and w must be multiples of 4");
-  Istd3p is;
-  for (int c = 0; c < 3; ++c) is.v[c] = std_host ? 1.0f / std_host[c] : 1.0f;
+  const RartIstd3 is = rart_istd3(std_host);
   const int oh = h / 2, ow = w / 2;
   hipLaunchKernelGGL(k_stem_bwd_pair, dim3((ow + T - 1) / T, (oh + T - 1) / T, n), dim3(256), 0, (hipStream_t)stream,
                      (const uint4*)dpool_hi, (const uint4*)dpool_lo, (const uint4*)argmax, (const uint16_t*)wtab_hi,
@@ -338,7 +336,6 @@ constexpr int SP_N_BYTES = 64 * SP_NROW;        // 9 216 per plane
 static_assert(2 * SP_N_BYTES + 64 * SP_YROW <= SP_T_BYTES, "pooled planes + result block fit the tile they alias");
 static_assert(2 * SP_W_BYTES + SP_T_BYTES + 2 * SP_N_BYTES <= 160 * 1024, "one workgroup per CU");
 
-struct StemNormP { float mean[3], istd[3]; };
 // the normalisation must round exactly like k_prep_input (engine_aux.hip): multiply, subtract, multiply -- no contraction
 #pragma clang fp contract(off)
 
@@ -354,7 +351,7 @@ template <bool SRC_U8, bool NEXT = false>
 __global__ __launch_bounds__(512, 1) void k_stem_fwd_pair(const void* __restrict__ src, const uint16_t* __restrict__ w_h,
                                                           const uint16_t* __restrict__ w_l, const float* __restrict__ bias,
                                                           uint4* __restrict__ p1_h, uint4* __restrict__ p1_l, uint2* __restrict__ arg,
-                                                          uint8_t* __restrict__ sign, int n, int h, int w, StemNormP nm, StemNextP nx) {
+                                                          uint8_t* __restrict__ sign, int n, int h, int w, RartNorm3 nm, StemNextP nx) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[2 * SP_W_BYTES + SP_T_BYTES + (NEXT ? 2 * SP_N_BYTES : 0)];
   uint8_t* sW = lds;                            // [hi | lo][64][SP_WROW]
   uint8_t* sP = lds + 2 * SP_W_BYTES;           // patch (hi plane, lo plane) / stem-output tile
@@ -616,11 +613,7 @@ static int stem_fwd_pair_launch(const void* src, int src_is_u8, const void* wgt_
                                 const float* std_host, rart_stream_t stream, const StemNextP* next) {
   RART_CHECK_ARG(src && wgt_hi && wgt_lo && p1_hi && p1_lo && n > 0 && h % 4 == 0 && w % 4 == 0 && h >= 4 && w >= 4,
                  "rart_engine_stem_fwd_fused_pair: bad arguments (h, w multiples of 4)");
-  StemNormP nm;
-  for (int c = 0; c < 3; ++c) {
-    nm.mean[c] = mean_host ? mean_host[c] : 0.f;
-    nm.istd[c] = std_host ? 1.0f / std_host[c] : 1.f;
-  }
+  const RartNorm3 nm = rart_norm3(mean_host, std_host);
   const long long tiles = (long long)n * ((h / 4 + SP_PT - 1) / SP_PT) * ((w / 4 + SP_PT - 1) / SP_PT);
   const int grid = (int)(tiles < 256 ? tiles : 256);              // persistent: one workgroup per CU
 #define RART_STEM_LAUNCH(U8_, NEXT_)                                                                                         \

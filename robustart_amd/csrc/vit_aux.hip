@@ -10,16 +10,13 @@
 namespace {
 using namespace rart_bf16;
 constexpr int kBlock = 256;
-struct Norm3 {
-  float mean[3], istd[3];
-};
 
 // out[b][p][c*ps*ps + r*ps + s] = (x[b][c][py*ps + r][px*ps + s] - mean)/std, as hi and lo bf16 planes.  A thread makes EIGHT consecutive
 // s of one (patch, channel, row): two 16-byte stores (ps % 8 == 0; the first version was one element per thread with 64-bit divisions:
 // 157 us per 256 images against a 25 us stream)
 template <bool SRC_U8>
 __global__ __launch_bounds__(kBlock) void k_patchify(const void* __restrict__ src, uint16_t* __restrict__ hi,
-                                                     uint16_t* __restrict__ lo, int n, int h, int w, int ps, Norm3 nm) {
+                                                     uint16_t* __restrict__ lo, int n, int h, int w, int ps, RartNorm3 nm) {
   const uint32_t gw = (uint32_t)(w / ps), gh = (uint32_t)(h / ps), kk8 = (uint32_t)(3 * ps * ps / 8), s8n = (uint32_t)(ps / 8);
   const uint32_t total = (uint32_t)n * gh * gw * kk8;                     // host: < 2^32
   for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < total; i += gridDim.x * kBlock) {
@@ -136,7 +133,6 @@ __global__ __launch_bounds__(kBlock) void k_transpose_v(const uint16_t* __restri
     *reinterpret_cast<uint4*>(vt + ((size_t)bh * hd + dd) * t_pad + t0 + tc * 8) = make_uint4(w[0], w[1], w[2], w[3]);
   }
 }
-int grid_for(size_t items) { return rart_grid_for(items, kBlock, 256 * 16); }
 
 // ---- fused multi-head attention (head_dim 64, tokens <= NKT*32), one workgroup per (image, head) -------------
 // S^T = K . Q^T on v_mfma_f32_32x32x16_bf16: in the accumulator layout lane (l & 31) is the QUERY and the 16
@@ -575,17 +571,13 @@ int rart_vit_patchify(const void* src, int src_is_u8, void* hi, void* lo, int n,
   RART_CHECK_ARG(src && hi && lo && n > 0 && patch > 0 && h % patch == 0 && w % patch == 0, "rart_vit_patchify: bad arguments");
   RART_CHECK_ARG(patch % 8 == 0 && (size_t)n * (h / patch) * (w / patch) * 3 * patch * patch / 8 < (1ull << 32),
                  "rart_vit_patchify: the patch side must be a multiple of 8 (eight pixels per thread) and the batch below 2^32 vectors");
-  Norm3 nm;
-  for (int c = 0; c < 3; ++c) {
-    nm.mean[c] = mean_host ? mean_host[c] : 0.f;
-    nm.istd[c] = std_host ? 1.0f / std_host[c] : 1.f;
-  }
+  const RartNorm3 nm = rart_norm3(mean_host, std_host);
   const size_t total = (size_t)n * (h / patch) * (w / patch) * 3 * patch * patch / 8;
   if (src_is_u8)
-    hipLaunchKernelGGL(k_patchify<true>, dim3(grid_for(total)), dim3(kBlock), 0, (hipStream_t)stream, src, (uint16_t*)hi,
+    hipLaunchKernelGGL(k_patchify<true>, dim3(rart_grid_wide(total)), dim3(kBlock), 0, (hipStream_t)stream, src, (uint16_t*)hi,
                        (uint16_t*)lo, n, h, w, patch, nm);
   else
-    hipLaunchKernelGGL(k_patchify<false>, dim3(grid_for(total)), dim3(kBlock), 0, (hipStream_t)stream, src,
+    hipLaunchKernelGGL(k_patchify<false>, dim3(rart_grid_wide(total)), dim3(kBlock), 0, (hipStream_t)stream, src,
                        (uint16_t*)hi, (uint16_t*)lo, n, h, w, patch, nm);
   RART_CHECK_LAUNCH("rart_vit_patchify");
   return RART_OK;
@@ -595,7 +587,7 @@ int rart_vit_add_pos_cls(void* x, const float* cls_pos0, const float* pos, int n
                          rart_stream_t stream) {
   RART_CHECK_ARG(x && cls_pos0 && pos && n > 0 && tokens > 0 && dim > 0 && dim % 8 == 0 && (size_t)n * tokens * dim / 8 < (1ull << 32),
                  "rart_vit_add_pos_cls: bad arguments (dim must be a multiple of 8)");
-  hipLaunchKernelGGL(k_add_pos_cls<false>, dim3(grid_for((size_t)n * tokens * dim / 8)), dim3(kBlock), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(k_add_pos_cls<false>, dim3(rart_grid_wide((size_t)n * tokens * dim / 8)), dim3(kBlock), 0, (hipStream_t)stream,
                      (uint16_t*)x, (uint16_t*)nullptr, cls_pos0, pos, n, tokens, dim);
   RART_CHECK_LAUNCH("rart_vit_add_pos_cls");
   return RART_OK;
@@ -605,7 +597,7 @@ int rart_vit_add_pos_cls_pair(void* x_hi, void* x_lo, const float* cls_pos0, con
                               rart_stream_t stream) {
   RART_CHECK_ARG(x_hi && x_lo && cls_pos0 && pos && n > 0 && tokens > 0 && dim > 0 && dim % 8 == 0 &&
                      (size_t)n * tokens * dim / 8 < (1ull << 32), "rart_vit_add_pos_cls_pair: bad arguments");
-  hipLaunchKernelGGL(k_add_pos_cls<true>, dim3(grid_for((size_t)n * tokens * dim / 8)), dim3(kBlock), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(k_add_pos_cls<true>, dim3(rart_grid_wide((size_t)n * tokens * dim / 8)), dim3(kBlock), 0, (hipStream_t)stream,
                      (uint16_t*)x_hi, (uint16_t*)x_lo, cls_pos0, pos, n, tokens, dim);
   RART_CHECK_LAUNCH("rart_vit_add_pos_cls_pair");
   return RART_OK;

@@ -78,33 +78,51 @@ __global__ __launch_bounds__(kBlock) void k_softmax_bwd_rows(const uint16_t* __r
 }
 
 // grad[b][c][y][x] = dpatch[b][patch(y, x)][c*ps*ps + (y % ps)*ps + (x % ps)] * istd[c]   (fp32 NCHW, pixels in [0,1])
-struct Istd3 { float v[3]; };
-__global__ __launch_bounds__(kBlock) void k_unpatchify(const uint16_t* __restrict__ dp, float* __restrict__ grad, int n, int h,
-                                                       int w, int ps, long long ld, Istd3 is) {
-  // eight consecutive x of one image row (ps % 8 == 0, ld % 8 == 0: they sit in one patch row): one 16-byte load, two 16-byte stores
-  const uint32_t gw = (uint32_t)(w / ps), gh = (uint32_t)(h / ps), w8 = (uint32_t)w / 8;
-  const uint32_t total = (uint32_t)n * 3u * (uint32_t)h * w8;              // host: < 2^32
+// T = uint16_t: bf16 patch gradients, T = float: the fp32 ones of the reference-precision engines.  A thread takes the PX = 8 or 4
+// consecutive x of one image row that one 16-byte load holds (host: ps % PX == 0, ld % PX == 0: they sit in one patch row)
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_unpatchify(const T* __restrict__ dp, float* __restrict__ grad, int n, int h, int w, int ps,
+                                                       long long ld, RartIstd3 is) {
+  constexpr uint32_t PX = 16 / sizeof(T);
+  const uint32_t gw = (uint32_t)(w / ps), gh = (uint32_t)(h / ps), wv = (uint32_t)w / PX;
+  const uint32_t total = (uint32_t)n * 3u * (uint32_t)h * wv;              // host: < 2^32
   for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < total; i += gridDim.x * kBlock) {
-    const uint32_t x8 = i % w8, t = i / w8, y = t % (uint32_t)h, t2 = t / (uint32_t)h, c = t2 % 3u, img = t2 / 3u;
-    const uint32_t x = x8 * 8, px = x / (uint32_t)ps, py = y / (uint32_t)ps;
+    const uint32_t xv = i % wv, t = i / wv, y = t % (uint32_t)h, t2 = t / (uint32_t)h, c = t2 % 3u, img = t2 / 3u;
+    const uint32_t x = xv * PX, px = x / (uint32_t)ps, py = y / (uint32_t)ps;
     const size_t prow = (size_t)img * gh * gw + (size_t)py * gw + px;
     const uint4 v = *reinterpret_cast<const uint4*>(dp + prow * ld + (size_t)c * ps * ps + (y % (uint32_t)ps) * ps + (x % (uint32_t)ps));
     const float sc = is.v[c];
-    float4* o = reinterpret_cast<float4*>(grad + (size_t)i * 8);
-    o[0] = make_float4(__uint_as_float(v.x << 16) * sc, __uint_as_float(v.x & 0xFFFF0000u) * sc, __uint_as_float(v.y << 16) * sc,
-                       __uint_as_float(v.y & 0xFFFF0000u) * sc);
-    o[1] = make_float4(__uint_as_float(v.z << 16) * sc, __uint_as_float(v.z & 0xFFFF0000u) * sc, __uint_as_float(v.w << 16) * sc,
-                       __uint_as_float(v.w & 0xFFFF0000u) * sc);
+    float4* o = reinterpret_cast<float4*>(grad + (size_t)i * PX);
+    if (sizeof(T) == 2) {
+      o[0] = make_float4(__uint_as_float(v.x << 16) * sc, __uint_as_float(v.x & 0xFFFF0000u) * sc, __uint_as_float(v.y << 16) * sc,
+                         __uint_as_float(v.y & 0xFFFF0000u) * sc);
+      o[1] = make_float4(__uint_as_float(v.z << 16) * sc, __uint_as_float(v.z & 0xFFFF0000u) * sc, __uint_as_float(v.w << 16) * sc,
+                         __uint_as_float(v.w & 0xFFFF0000u) * sc);
+    } else {
+      o[0] = make_float4(__uint_as_float(v.x) * sc, __uint_as_float(v.y) * sc, __uint_as_float(v.z) * sc, __uint_as_float(v.w) * sc);
+    }
   }
 }
-int grid_for(size_t items) { return rart_grid_for(items, kBlock, 256 * 16); }
+// the checks of the two entries differ in PX alone; `px_msg` is the entry's second message
+template <typename T>
+int launch_unpatchify(const void* dpatches, float* grad, int n, int h, int w, int patch, int64_t ld, const float* std_host,
+                      rart_stream_t stream, const char* what, const char* px_msg) {
+  constexpr int PX = 16 / (int)sizeof(T);
+  RART_CHECK_ARG(dpatches && grad && std_host && n > 0 && patch > 0 && h % patch == 0 && w % patch == 0 && ld >= 3 * patch * patch,
+                 "%s: bad arguments", what);
+  RART_CHECK_ARG(patch % PX == 0 && ld % PX == 0 && (size_t)n * 3 * h * w / PX < (1ull << 32), "%s: %s", what, px_msg);
+  hipLaunchKernelGGL(k_unpatchify<T>, dim3(rart_grid_wide((size_t)n * 3 * h * w / PX)), dim3(kBlock), 0, (hipStream_t)stream,
+                     (const T*)dpatches, grad, n, h, w, patch, (long long)ld, rart_istd3(std_host));
+  RART_CHECK_LAUNCH(what);
+  return RART_OK;
+}
 }  // namespace
 
 extern "C" {
 
 int rart_gelu_bf16(const void* u, void* out, size_t n, rart_stream_t stream) {
   RART_CHECK_ARG(u && out && n > 0 && n % 8 == 0, "rart_gelu_bf16: n must be a positive multiple of 8");
-  hipLaunchKernelGGL(k_gelu<0>, dim3(grid_for(n / 8)), dim3(kBlock), 0, (hipStream_t)stream, nullptr, (const uint4*)u,
+  hipLaunchKernelGGL(k_gelu<0>, dim3(rart_grid_wide(n / 8)), dim3(kBlock), 0, (hipStream_t)stream, nullptr, (const uint4*)u,
                      (uint4*)out, n / 8);
   RART_CHECK_LAUNCH("rart_gelu_bf16");
   return RART_OK;
@@ -112,7 +130,7 @@ int rart_gelu_bf16(const void* u, void* out, size_t n, rart_stream_t stream) {
 
 int rart_gelu_bwd_bf16(const void* dh, const void* u, void* du, size_t n, rart_stream_t stream) {
   RART_CHECK_ARG(dh && u && du && n > 0 && n % 8 == 0, "rart_gelu_bwd_bf16: n must be a positive multiple of 8");
-  hipLaunchKernelGGL(k_gelu<1>, dim3(grid_for(n / 8)), dim3(kBlock), 0, (hipStream_t)stream, (const uint4*)dh,
+  hipLaunchKernelGGL(k_gelu<1>, dim3(rart_grid_wide(n / 8)), dim3(kBlock), 0, (hipStream_t)stream, (const uint4*)dh,
                      (const uint4*)u, (uint4*)du, n / 8);
   RART_CHECK_LAUNCH("rart_gelu_bwd_bf16");
   return RART_OK;
@@ -133,16 +151,14 @@ int rart_softmax_bwd_rows_bf16(const void* probs, const void* dprobs, void* dsco
 
 int rart_vit_unpatchify_f32(const void* dpatches, float* grad, int n, int h, int w, int patch, int64_t ld,
                             const float* std_host, rart_stream_t stream) {
-  RART_CHECK_ARG(dpatches && grad && std_host && n > 0 && patch > 0 && h % patch == 0 && w % patch == 0 &&
-                     ld >= 3 * patch * patch, "rart_vit_unpatchify_f32: bad arguments");
-  RART_CHECK_ARG(patch % 8 == 0 && ld % 8 == 0 && (size_t)n * 3 * h * w / 8 < (1ull << 32),
-                 "rart_vit_unpatchify_f32: patch side and row stride must be multiples of 8 (eight pixels per thread)");
-  Istd3 is;
-  for (int c = 0; c < 3; ++c) is.v[c] = 1.0f / std_host[c];
-  hipLaunchKernelGGL(k_unpatchify, dim3(grid_for((size_t)n * 3 * h * w / 8)), dim3(kBlock), 0, (hipStream_t)stream,
-                     (const uint16_t*)dpatches, grad, n, h, w, patch, (long long)ld, is);
-  RART_CHECK_LAUNCH("rart_vit_unpatchify_f32");
-  return RART_OK;
+  return launch_unpatchify<uint16_t>(dpatches, grad, n, h, w, patch, ld, std_host, stream, "rart_vit_unpatchify_f32",
+                                     "patch side and row stride must be multiples of 8 (eight pixels per thread)");
+}
+
+int rart_vit_unpatchify_from_f32(const float* dpatches, float* grad, int n, int h, int w, int patch, int64_t ld, const float* std_host,
+                                 rart_stream_t stream) {
+  return launch_unpatchify<float>(dpatches, grad, n, h, w, patch, ld, std_host, stream, "rart_vit_unpatchify_from_f32",
+                                  "patch side and row stride must be multiples of 4 (four pixels per thread)");
 }
 
 }  // extern "C"

@@ -81,22 +81,6 @@ __global__ __launch_bounds__(kBlock) void k_softmax_bwd_rows_pair(const uint16_t
   }
 }
 
-// grad[b][c][y][x] = dpatch[b][patch(y, x)][c*ps*ps + (y % ps)*ps + (x % ps)] * istd[c]   (fp32 in, fp32 NCHW out)
-struct Istd3 { float v[3]; };
-__global__ __launch_bounds__(kBlock) void k_unpatchify_from_f32(const float* __restrict__ dp, float* __restrict__ grad, int n, int h,
-                                                                int w, int ps, long long ld, Istd3 is) {
-  const uint32_t gw = (uint32_t)(w / ps), gh = (uint32_t)(h / ps), w4 = (uint32_t)w / 4;
-  const uint32_t total = (uint32_t)n * 3u * (uint32_t)h * w4;              // host: < 2^32
-  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < total; i += gridDim.x * kBlock) {
-    const uint32_t x4 = i % w4, t = i / w4, y = t % (uint32_t)h, t2 = t / (uint32_t)h, c = t2 % 3u, img = t2 / 3u;
-    const uint32_t x = x4 * 4, px = x / (uint32_t)ps, py = y / (uint32_t)ps;
-    const size_t prow = (size_t)img * gh * gw + (size_t)py * gw + px;
-    const float4 v = *reinterpret_cast<const float4*>(dp + prow * ld + (size_t)c * ps * ps + (y % (uint32_t)ps) * ps + (x % (uint32_t)ps));
-    const float sc = is.v[c];
-    reinterpret_cast<float4*>(grad)[i] = make_float4(v.x * sc, v.y * sc, v.z * sc, v.w * sc);
-  }
-}
-
 // ---- fused multi-head attention on pairs (head_dim 64, tokens <= NKT*32): forward, backward-q and backward-kv, each as a ONE-ITEM kernel
 //      (one workgroup per (image, head)) and as a WALKING kernel (round 6: one workgroup per CU takes a run of items, wave 7 loads the next
 //      item's operands by LDS-DMA while the other seven compute).  The two forms of a family differ in how the operands reach LDS and in
@@ -791,7 +775,6 @@ __global__ __launch_bounds__(kAttBlock, 1) void k_vit_attention_bwd_kv_pair_walk
 #undef PATT_LDS_ADDR
 #undef RART_MFMA3
 
-int grid_for(size_t items) { return rart_grid_for(items, kBlock, 256 * 16); }
 
 // The walking decision of both attention entries: the number of workgroups to launch, one per CU, or 0 for the one-item kernels.  The
 // walking kernels exist for seven key tiles (wave 7 is free to load), pay off from four items per CU, and address a qkv plane with 32-bit
@@ -833,20 +816,6 @@ int rart_softmax_bwd_rows_pair(const void* probs_hi, const void* probs_lo, const
                      (hipStream_t)stream, (const uint16_t*)probs_hi, (const uint16_t*)probs_lo, dprobs, (uint16_t*)ds_hi, (uint16_t*)ds_lo,
                      (long long)rows, n_valid, ld_p, ld_dp, ld_out, scale);
   RART_CHECK_LAUNCH("rart_softmax_bwd_rows_pair");
-  return RART_OK;
-}
-
-int rart_vit_unpatchify_from_f32(const float* dpatches, float* grad, int n, int h, int w, int patch, int64_t ld, const float* std_host,
-                                 rart_stream_t stream) {
-  RART_CHECK_ARG(dpatches && grad && std_host && n > 0 && patch > 0 && h % patch == 0 && w % patch == 0 && ld >= 3 * patch * patch,
-                 "rart_vit_unpatchify_from_f32: bad arguments");
-  RART_CHECK_ARG(patch % 4 == 0 && ld % 4 == 0 && (size_t)n * 3 * h * w / 4 < (1ull << 32),
-                 "rart_vit_unpatchify_from_f32: patch side and row stride must be multiples of 4 (four pixels per thread)");
-  Istd3 is;
-  for (int c = 0; c < 3; ++c) is.v[c] = 1.0f / std_host[c];
-  hipLaunchKernelGGL(k_unpatchify_from_f32, dim3(grid_for((size_t)n * 3 * h * w / 4)), dim3(kBlock), 0, (hipStream_t)stream, dpatches,
-                     grad, n, h, w, patch, (long long)ld, is);
-  RART_CHECK_LAUNCH("rart_vit_unpatchify_from_f32");
   return RART_OK;
 }
 

@@ -1,5 +1,5 @@
 """Plain torch / numpy references and input generators for the stem glue kernels of the ResNet-50 engines (csrc/engine_aux.hip,
-csrc/engine_aux_pair.hip): input preparation, the 3x3/2 max pool with its argmax codes and sign bits, its backward, and the stem's
+both storages): input preparation, the 3x3/2 max pool with its argmax codes and sign bits, its backward, and the stem's
 col2im.  Nothing of the library is imported here.  tests/test_stem_glue_refs_cpu.py pins these functions and the properties of the
 generated inputs without a GPU; tests/test_stem_glue_kernels_gpu.py holds the kernels to them.
 

@@ -1,8 +1,8 @@
 """The kernels that four train engines share, each against a plain high-precision reference of the same operation on the MI355X:
 rart_layernorm_bwd_full_bf16 and rart_colsum_bf16 (csrc/vit_bwd.hip; the LayerNorm's load, statistics and dx write are
 csrc/rart_row_norm.h's, shared with csrc/row_norm.hip) against fp64 of the same bf16 operands, and the glue kernels
-every engine runs (rart_engine_avgpool[_bwd][_pair], rart_f32_to_bf16_rows, rart_f32_to_pair_rows, rart_vit_transpose_v,
-rart_vit_add_pos_cls).  The step kernels' share is in tests/test_train_steps_gpu.py.
+every engine runs (rart_engine_avgpool[_bwd][_pair], rart_f32_to_bf16_rows, rart_f32_to_pair_rows: csrc/engine_aux.hip, one kernel text
+per operation for bf16 and pair storage; rart_vit_transpose_v, rart_vit_add_pos_cls).  The step kernels' share is in tests/test_train_steps_gpu.py.
 
 Conventions: operands are bf16 and the reference is fp64 of those values; whatever a kernel must not read is NaN / +-inf, whatever it
 must not write holds a sentinel (the workspace is filled with NaN bytes, so a partial sum that is read without having been written

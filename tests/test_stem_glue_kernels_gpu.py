@@ -1,5 +1,5 @@
-"""The chain kernels of the ResNet-50 stem (csrc/engine_aux.hip, csrc/engine_aux_pair.hip), each against a plain reference of its own
-on the MI355X: rart_engine_prep_input, rart_engine_maxpool[_keep], rart_engine_maxpool_bwd, rart_engine_maxpool[_bwd]_pair,
+"""The chain kernels of the ResNet-50 stem (csrc/engine_aux.hip: one kernel text per operation, instantiated for bf16 and for pair
+storage), each against a plain reference of its own on the MI355X: rart_engine_prep_input, rart_engine_maxpool[_keep], rart_engine_maxpool_bwd, rart_engine_maxpool[_bwd]_pair,
 rart_engine_stem_col2im[_f32].  The fused stem kernels are tested as bit-identical to these chains; this module is what the chains
 themselves are held to.  The references and the inputs are in tests/_stem_glue_ref.py, pinned on the CPU by
 tests/test_stem_glue_refs_cpu.py (the tie rule, the code 15, the shares of tied windows, the exactness of the lattice sums).
@@ -27,7 +27,8 @@ Measured on the MI355X, worst |err| / bound of the randn cases (the same for the
     (0 at 2 x 2: one window per channel, so a gradient is copied and nothing is added or rounded)
   rart_engine_stem_col2im       std null / ImageNet: (1, 16, 32) 0.0000 / 0.0535   (2, 32, 64) 0.0262 / 0.0484   (1, 48, 32) 0.0000 / 0.0535
   rart_engine_stem_col2im_f32   std null / ImageNet: (1, 16, 32) 0.1104 / 0.1374   (2, 32, 64) 0.1516 / 0.1573   (1, 48, 32) 0.1543 / 0.1558
-Every bit-exact check holds.  Against a build of the two sources with seven deliberate, memory-safe mistakes (>= in the bf16 pool's
+Every bit-exact check holds.  Against a build of the two sources these kernels then had (one per storage) with seven deliberate,
+memory-safe mistakes (>= in the bf16 pool's
 comparison, code 15 only below zero in the pair pool, y < 0 as the backward's mask, the last window column skipped in the pair
 backward, the tap at patch column 0 / the last patch row dropped in the two col2im kernels, a stride one too long in prep_input's loop)
 53 of the 63 cases fail: every case but the small prep_input ones, the refusals and the pair forward's large case, which those

@@ -1,5 +1,5 @@
-"""CPU checks of tests/_stem_glue_ref.py, the references tests/test_stem_glue_kernels_gpu.py holds csrc/engine_aux.hip and
-csrc/engine_aux_pair.hip to.  The pool references (torch's max_pool2d and its autograd on the CPU) agree with a triple-loop model
+"""CPU checks of tests/_stem_glue_ref.py, the references tests/test_stem_glue_kernels_gpu.py holds csrc/engine_aux.hip (both
+storages) to.  The pool references (torch's max_pool2d and its autograd on the CPU) agree with a triple-loop model
 written from the header's words -- first maximum in scan order, code 15 where the window maximum is not > 0 --, col2im_ref with a loop
 over (r, s, p, q), prep_ref with (x - mean) / std in fp64.  The generated inputs have the properties the GPU tests rely on, so that
 no test can pass on a degenerate draw: enough tied windows, every code in every class of window, a wrong tie rule or a comparison of
