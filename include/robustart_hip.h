@@ -532,6 +532,18 @@ typedef struct rart_gemm_pair_plan {
 } rart_gemm_pair_plan;
 int rart_gemm_pair_plan_bf16(const rart_gemm_pair_cls_desc* desc_host, int cus, rart_gemm_pair_plan* out);
 
+/* The short-K wide 1x1 pair products of ResNet-50's identity blocks with the A rows resident in registers (csrc/expand_walk_pair.hip): a
+ * workgroup owns tile_rows rows (128 or 64; 0 = the library's default) and walks the N columns in chunks of 64 -- all of them, or with
+ * col_parts = 2 / 4 (0 = the library's default; a divisor of N / 64) a half / a quarter -- so the A planes go through the load path
+ * col_parts times instead of N / 64 times.  The descriptor is rart_gemm_pair_bf16's, restricted to what those launches use: conv = 1, one
+ * tap at (0, 0), stride 1, source = row grid = destination pixels (dst_s* = 1, dst_o* = 0), K = k_per_tap = 128 or 256, N a multiple of
+ * 64, ldc = N, a pair destination; bias, residual pair, mask_bits, sign_out and the ReLU flag as there (no other flag, no aux, no batching,
+ * no row re-basing; tile_m / tile_n are ignored).  Same products in the same order per output element and the same point-wise tail: every
+ * output bit equals rart_gemm_pair_bf16's.  rart_expand_walk_pair_max_k: the longest K the loaded library takes (256); the engine uses
+ * the entry only where it says so. */
+int rart_expand_walk_pair(const rart_gemm_pair_desc* desc_host, int tile_rows, int col_parts, rart_stream_t stream);
+int rart_expand_walk_pair_max_k(void);
+
 /* The second half of a ResNet Bottleneck of the reference-precision engine as ONE launch (csrc/conv_tail_pair.hip): 3x3 stride-1 pad-1
  * convolution (c_mid -> c_mid channels, c_mid = 64 or 128) + point-wise step + the 1x1 expansion (c_mid -> 4 c_mid) + skip pair +
  * point-wise step, on hi + lo planes of bf16 with three MFMA products per contraction; the c_mid-channel intermediate stays in registers.

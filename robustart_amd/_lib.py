@@ -117,6 +117,8 @@ SIGNATURES = {
     'rart_gemm_pair_set_schedule': (c_int, [c_int]),
     'rart_gemm_pair_get_schedule': (c_int, []),
     'rart_gemm_pair_plan_bf16': (c_int, [c_void_p, c_int, c_void_p]),
+    'rart_expand_walk_pair': (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    'rart_expand_walk_pair_max_k': (c_int, []),
     'rart_pack_jobs_bf16': (c_int, [c_void_p, c_int, c_int, c_void_p]),
     'rart_vit_add_pos_cls_pair': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     'rart_layernorm_pair': (c_int, [c_void_p] * 6 + [c_int, c_int, ctypes.c_int64, ctypes.c_int64, c_float, c_void_p]),

@@ -190,6 +190,13 @@ class ResNet50Engine(EngineBase):
         self.class_3x3_channels = (128, 256, 512)
         self.class_shortcut_channels = (256, 512, 1024)
         self.pair_classes = self.lib.rart_gemm_pair_max_classes() if split else 0
+        # reference precision: the short-K wide 1x1 launches of identity blocks (the expansion with its skip pair, conv1^T with the gradient
+        # as residual) on rart_expand_walk_pair (csrc/expand_walk_pair.hip): the A rows stay in registers while the workgroup walks all N
+        # columns.  For these K (layer2's 128 -> 512, layer3's 256 -> 1024); honoured only for K up to what the library says (the query is made once, here).
+        # Same bits as rart_gemm_pair_bf16.  False: every such launch on rart_gemm_pair_bf16 (cross-check)
+        self.expand_walk_pair = True
+        self.expand_walk_channels = (128, 256)
+        self.expand_walk_max_k = self.lib.rart_expand_walk_pair_max_k() if split else 0
         # reference-precision mode: layer1 block 0's conv1 + bias + ReLU inside the fused stem forward (rart_engine_stem_fwd_next_pair): the
         # pooled pair is not re-read by a launch of its own.  False: its own launch (cross-check).  Same bits either way.  Per source form,
         # by its own measurement at B = 256 (profiles/first_block_folds_per_part.txt): uint8 sources 549 -> 496 us for stem + conv1; fp32
@@ -486,10 +493,10 @@ class ResNet50Engine(EngineBase):
     # ------------------------------------------------------------------ launches
     def _gemm(self, src, wgt, dst, batch, grid, src_hw, src_pix, k_per_tap, taps, n_cols, dst_hw, dst_pix,
               bias=None, res=None, mask=None, flags=0, stride=(1, 1), dst_stride=(1, 1), dst_off=(0, 0),
-              tap_src_off=None, sign_out=None, pair=False, src2=None):
+              tap_src_off=None, sign_out=None, pair=False, src2=None, walk=False):
         if pair and self.pair_gemm_kernel and len(taps) <= 16 and k_per_tap >= 32 and (k_per_tap & (k_per_tap - 1)) == 0:
             return self._gemm_pair(src, wgt, dst, batch, grid, src_hw, src_pix, k_per_tap, taps, n_cols, dst_hw, dst_pix, bias, res,
-                                   mask, flags, stride, dst_stride, dst_off, sign_out, src2)
+                                   mask, flags, stride, dst_stride, dst_off, sign_out, src2, walk)
         assert src2 is None, 'a second source is served by rart_gemm_pair_bf16 only'
         dst_pair_off = res_pair_off = 0
         if pair:
@@ -508,13 +515,14 @@ class ResNet50Engine(EngineBase):
                                     dst_org=dst_off, tap_src_off=tap_src_off, dst_pair_off=dst_pair_off, res_pair_off=res_pair_off))
 
     def _gemm_pair(self, src, wgt, dst, batch, grid, src_hw, src_pix, k_per_tap, taps, n_cols, dst_hw, dst_pix, bias, res, mask, flags,
-                   stride, dst_stride, dst_off, sign_out, src2=None):
+                   stride, dst_stride, dst_off, sign_out, src2=None, walk=False):
         """One convolution / product of the reference-precision mode on rart_gemm_pair_bf16 (csrc/gemm_pair.hip, conv mode): the four
         operand planes of a K step staged once, three MFMAs per fragment pair -- round 3 listed the three products as 3 x the taps of
         rart_conv_igemm_bf16, which fetched x_hi twice and ran at a quarter of this kernel's MFMA rate.  src / dst / res: pair tensors
         [2][...]; wgt: the [rows][hi | lo | hi] table of `_Conv(split=True)` (w_hi = columns 0..K, w_lo = columns K..2K, row stride 3K);
         mask: 1-bit ReLU mask of the destination; an fp32 destination (F_OUT_F32) is a plain tensor.  src2 = (pair tensor, its hw, its
-        stride, elements per pixel, k2): a second source whose k2 channels follow in the rows of wgt (`_cat_k`)."""
+        stride, elements per pixel, k2): a second source whose k2 channels follow in the rows of wgt (`_cat_k`).  walk: the caller's
+        launch is one rart_expand_walk_pair serves (`_walk_ok`) -- the same descriptor goes to that entry."""
         assert src.shape[0] == 2
         k_tot = k_per_tap * len(taps) + (src2[4] if src2 is not None else 0)
         assert wgt.shape[1] == 3 * k_tot
@@ -533,10 +541,21 @@ class ResNet50Engine(EngineBase):
                 + rows * n_cols / 8.0 * ((mask is not None) + (sign_out is not None))
             if src2 is not None:
                 nbytes += 4.0 * batch * src2[1][0] * src2[1][1] * src2[4]
-        self._launch_pair(gemm_pair_desc(src, wgt, dst, n_cols, src_pix, 3 * k_tot, dst_pix, wgt.shape[0], bias=bias, res=res, mask_bits=mask,
-                                         sign_out=sign_out, flags=flags & (F_RELU | F_OUT_F32), w_lo_off=k_tot, w_il=il, batch=batch,
-                                         grid=grid, src_hw=src_hw, stride=stride, k_per_tap=k_per_tap, taps=taps, dst_hw=dst_hw,
-                                         dst_stride=dst_stride, dst_org=dst_off, tile=self.pair_tile, src2=src2), nbytes)
+        d = gemm_pair_desc(src, wgt, dst, n_cols, src_pix, 3 * k_tot, dst_pix, wgt.shape[0], bias=bias, res=res, mask_bits=mask,
+                           sign_out=sign_out, flags=flags & (F_RELU | F_OUT_F32), w_lo_off=k_tot, w_il=il, batch=batch,
+                           grid=grid, src_hw=src_hw, stride=stride, k_per_tap=k_per_tap, taps=taps, dst_hw=dst_hw,
+                           dst_stride=dst_stride, dst_org=dst_off, tile=self.pair_tile, src2=src2)
+        if not walk:
+            return self._launch_pair(d, nbytes)
+        ev = self._prof_begin()
+        _lib.check(self.lib.rart_expand_walk_pair(ctypes.byref(d), 0, 0, _lib.stream_ptr()))
+        if ev is not None:
+            self._prof_end(ev, 3 * 2.0 * d.M * d.N * d.K, 'gemm_pair', nbytes)
+
+    def _walk_ok(self, k, n, c):
+        """whether the 1x1 launch of conv c with K = k, N = n of an identity block goes to rart_expand_walk_pair"""
+        return self.expand_walk_pair and self.pair_gemm_kernel and not self.pair_w_interleaved and self.pair_tile == (0, 0) and \
+            c.r == 1 and c.s == 1 and c.stride == 1 and k in self.expand_walk_channels and k <= self.expand_walk_max_k and n >= 4 * k and n % 64 == 0
 
     def _classes_ok(self, tabs):
         """whether a launch with the class-ordered tables `tabs` = (table, classes) goes out as one class launch"""
@@ -722,20 +741,23 @@ class ResNet50Engine(EngineBase):
                 sum(m_ * c // 8 for c, t in ((c_mid, m1), (c_mid, m2), (c_io if not backward else cin_, m3)) if t is not None)
             self._prof_end(ev, 2.0 * B * hw[0] * hw[1] * c_mid * k_all, 'bottleneck', by)
 
-    def _conv_fwd(self, c, x, xhw, out, relu, res=None, sign=None, pair=False):
+    def _conv_fwd(self, c, x, xhw, out, relu, res=None, sign=None, pair=False, identity=False):
+        """identity: conv3 of an identity block (res = the block's input)"""
         B = x.shape[1] if pair else x.shape[0]
         oh, ow = xhw[0] // c.stride, xhw[1] // c.stride
         if pair:
             return self._gemm(x, c.w_fwd, out, B, (oh, ow), xhw, c.cin, c.cin, c.fwd_taps, c.cout, (oh, ow), c.cout, bias=c.bias,
-                              res=res, flags=F_RELU if relu else 0, stride=(c.stride, c.stride), sign_out=sign, pair=True)
+                              res=res, flags=F_RELU if relu else 0, stride=(c.stride, c.stride), sign_out=sign, pair=True,
+                              walk=identity and self._walk_ok(c.cin, c.cout, c))
         if res is None and self._halo_ok(c, xhw, B):
             return self._halo(x, c.w_fwd_frag, out, B, xhw, c.cin, c.fwd_taps, bias=c.bias, sign=sign, relu=relu)
         self._gemm(x, c.w_fwd, out, B, (oh, ow), xhw, c.cin, c.cin, c.fwd_taps, c.cout, (oh, ow), c.cout,
                    bias=c.bias, res=res, flags=F_RELU if relu else 0, stride=(c.stride, c.stride), sign_out=sign)
 
-    def _conv_bwd(self, c, dz, dz_hw, dx, dx_hw, res=None, mask=None, pair=False):
+    def _conv_bwd(self, c, dz, dz_hw, dx, dx_hw, res=None, mask=None, pair=False, identity=False):
         """dx = backward-to-input of conv c applied to dz (then + res, masked).  mask: the forward activation at dx's
-        place (bf16) or its 1-bit sign tensor (uint8, written by the forward GEMM's sign_out)."""
+        place (bf16) or its 1-bit sign tensor (uint8, written by the forward GEMM's sign_out).  identity: conv1 of an identity block
+        (res = the gradient at the block's output)."""
         torch = _lib.require_gpu()
         B = dz.shape[1] if pair else dz.shape[0]
         fl = F_MASK_BITS if (mask is not None and mask.dtype == torch.uint8) else 0
@@ -750,7 +772,7 @@ class ResNet50Engine(EngineBase):
         for parity, taps, w in c.bwd:
             if parity is None:
                 self._gemm(dz, w, dx, B, dx_hw, dz_hw, c.cout, c.cout, taps, c.cin, dx_hw, c.cin, res=res, mask=mask,
-                           flags=fl, pair=pair)
+                           flags=fl, pair=pair, walk=pair and identity and self._walk_ok(c.cout, c.cin, c))
             else:
                 ph, pw = parity
                 if not taps:
@@ -919,7 +941,7 @@ class ResNet50Engine(EngineBase):
                     self._gemm(yb, ds.w_cat, yc, B, ohw, ohw, cc.cin, cc.cin, cc.fwd_taps, cc.cout, ohw, cc.cout, bias=ds.bias_cat,
                                flags=F_RELU, sign_out=sc, pair=True, src2=(x, xhw, (ds.stride, ds.stride), ca.cin, ds.cin))
                 else:
-                    self._conv_fwd(cc, yb, ohw, yc, True, res=sk, sign=sc, pair=x3)
+                    self._conv_fwd(cc, yb, ohw, yc, True, res=sk, sign=sc, pair=x3, identity=ds is None)
         acts['b%d' % bi] = (x, xhw, ya, yb, yc, ohw)
         # the backward pass needs the activations only for their ReLU sign: the 1-bit tensors, or with `sign_bit_masks` off (bf16
         # cross-check) the activations themselves
@@ -1010,7 +1032,7 @@ class ResNet50Engine(EngineBase):
             dza = get('g_a', lead + (xhw[0], xhw[1], ca.cout))
             self._conv_bwd(cb, dzb, ohw, dza, xhw, mask=ma, pair=x3)
             if ds is None:
-                self._conv_bwd(ca, dza, xhw, dx, xhw, res=dz, mask=mx, pair=x3)            # identity skip
+                self._conv_bwd(ca, dza, xhw, dx, xhw, res=dz, mask=mx, pair=x3, identity=True)            # identity skip
             elif x3 and self.fused_shortcut_pair and self.pair_gemm_kernel and getattr(ds, 'w_cat_bwd', None) is not None:
                 # stride-1 projection skip (layer1's first block): conv1^T and the shortcut^T as one two-source launch, dx written once
                 self._gemm(dza, ds.w_cat_bwd, dx, B, xhw, xhw, ca.cout, ca.cout, ca.bwd[0][1], ca.cin, xhw, ca.cin, mask=mx,
