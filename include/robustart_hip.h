@@ -659,6 +659,33 @@ int rart_conv3x3_halo_bf16(const void* src, const void* wgt, const float* bias, 
                            void* dst, int n, int h, int w, int channels, const int* tap_dy, const int* tap_dx, int relu,
                            rart_stream_t stream);
 
+/* Grouped 3x3 convolution, channels in = channels out, groups of group_width = 4, 8, 16, 32 or 64 channels, NHWC, bf16 or split-bf16
+ * (hi + lo planes, the three products hi.hi + hi.lo + lo.hi as rart_gemm_pair_bf16 forms them) with the source tile of a workgroup
+ * resident in LDS (csrc/conv_grouped.hip): conv2 of a ResNeXt Bottleneck, forward and backward-to-input.  The channels are cut into
+ * slices of S = 32 consecutive channels (64 when group_width is 64); a slice holds whole groups and reads only itself.
+ *   dst(b, y * dst_stride + dst_oy, x * dst_stride + dst_ox, :) = act(sum_t W_t . src(b, y * stride + tap_dy[t], x * stride + tap_dx[t], :)
+ *   + bias) for the pixels (y, x) of a grid_h x grid_w grid; source pixels outside src_h x src_w read zero.  1 <= n_taps <= 9, taps in
+ * -1 .. 1, stride 1 or 2, the grid must map inside dst_h x dst_w.  One entry serves the forward (stride 1 / 2, dst_stride 1), the backward
+ * at stride 1 (flipped taps, per-group transposed weights) and each input-parity class of the stride-2 backward (stride 1, dst_stride 2,
+ * origin = the parity, the 1 / 2 / 2 / 4 taps of the class).
+ * wgt: per slice s the dense bf16 table T_s [S out][n_taps * S in] (k = tap * S + c, exact zeros off the block diagonal of the groups)
+ * in MFMA-fragment order: element (((s * n_taps * S / 16 + st) * (S / 32) + j) * 64 + l) * 8 + e = T_s[j * 32 + (l & 31)][st * 16 +
+ * (l >> 5) * 8 + e].  bias fp32 [channels]; mask_bits: 1 bit per destination element (byte e / 8 of element offset e), the value is zeroed
+ * where clear; sign_out: receives (stored hi value > 0), same indexing; relu: applied last.  bias / mask_bits / sign_out may be NULL.
+ * dst must not alias src.  rart_conv3x3_grouped_supported(channels, group_width, h, w, stride): 1 when the entries take a source of
+ * h x w pixels at this stride; where it says 0 they return RART_ERR_INVALID and write nothing.  rart_conv3x3_grouped_tile: the output
+ * pixels (rows x cols) one workgroup owns for this slice width, storage (pair != 0: split-bf16) and stride. */
+int rart_conv3x3_grouped_supported(int channels, int group_width, int h, int w, int stride);
+int rart_conv3x3_grouped_tile(int group_width, int pair, int stride, int* rows, int* cols);
+int rart_conv3x3_grouped_bf16(const void* src, const void* wgt, const float* bias, const void* mask_bits, void* sign_out, void* dst, int n,
+                              int src_h, int src_w, int channels, int group_width, int stride, int grid_h, int grid_w, int n_taps,
+                              const int* tap_dy, const int* tap_dx, int dst_h, int dst_w, int dst_stride, int dst_oy, int dst_ox, int relu,
+                              rart_stream_t stream);
+int rart_conv3x3_grouped_pair(const void* src_hi, const void* src_lo, const void* wgt_hi, const void* wgt_lo, const float* bias,
+                              const void* mask_bits, void* sign_out, void* dst_hi, void* dst_lo, int n, int src_h, int src_w, int channels,
+                              int group_width, int stride, int grid_h, int grid_w, int n_taps, const int* tap_dy, const int* tap_dx,
+                              int dst_h, int dst_w, int dst_stride, int dst_oy, int dst_ox, int relu, rart_stream_t stream);
+
 /* One identity Bottleneck (1x1 c_io -> c_mid, 3x3 c_mid -> c_mid, 1x1 c_mid -> c_io, + the block input) as ONE kernel with
  * both intermediates kept on chip (csrc/bottleneck_fused.hip); supported geometry: c_io 256, c_mid 64, 56 x 56 (ResNet-50
  * layer1 blocks 1-2).  Replaces three rart_conv_igemm_bf16 / rart_conv3x3_halo_bf16 launches and computes the same function.

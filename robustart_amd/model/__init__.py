@@ -9,8 +9,12 @@ mixer_train_engine.py, bf16, drop rates 0 only).
 `convnext_base_cvst` and `vit_base_cvst` / `vit_b16_224_cvst` are the ConvStem variants of ConvNeXt-B and ViT-B/16 (convstem_torch.py:
 the stem / patch embedding is a chain of 3x3 stride-2 convolutions, each followed by LayerNorm and GELU): forward + backward-to-input on
 the same two engines, the stem on the chain of convstem_engine.py; evaluation only, `cls_solver` refuses to train them.
+The Bottleneck family of `resnet50_official` runs on the same engine (engine.py, one launch chain): `resnet101_official`,
+`resnet152_official`, `wide_resnet50_2`, `wide_resnet101_2` (ungrouped: the fused kernels that accept their shapes, else the generic
+launches) and `resnext50_32x4d`, `resnext101_32x8d` (conv2 is a grouped 3x3: csrc/conv_grouped.hip); evaluation only, `cls_solver`
+refuses to train them.
 kwargs `num_classes` and `drop_path_rate` are accepted (drop path is identity in eval)."""
-from .resnet_torch import resnet50
+from .resnet_torch import resnet50, FAMILY as _RESNET_FAMILY
 from .vit_torch import vit_base
 from .convnext_torch import convnext_base, convnextv2_base
 from .mixer_torch import mixer_b16_224
@@ -20,6 +24,7 @@ _REGISTRY = {'resnet50_official': resnet50, 'resnet50': resnet50, 'vit_base': vi
              'vit_base_patch16_224': vit_base, 'convnext_base': convnext_base,
              'convnextv2_base': convnextv2_base, 'mixer_b16_224': mixer_b16_224, 'convnext_base_cvst': convnext_base_cvst,
              'vit_base_cvst': vit_base_cvst, 'vit_b16_224_cvst': vit_base_cvst}
+_REGISTRY.update(_RESNET_FAMILY)
 
 
 def get_model(config):
@@ -29,5 +34,5 @@ def get_model(config):
     kwargs = dict((config.get('kwargs') if isinstance(config, dict) else getattr(config, 'kwargs', None)) or {})
     kwargs.pop('bn', None)          # {use_sync_bn: False}: BN statistics are local
     if mtype not in _REGISTRY:
-        raise NotImplementedError('model type %r is outside the hot-path scope (ResNet-50 / ViT-B/16 / ConvNeXt-B / ConvNeXt-V2-B / MLP-Mixer-B/16 only)' % mtype)
+        raise NotImplementedError('model type %r is outside the hot-path scope (the ResNet Bottleneck family / ViT-B/16 / ConvNeXt-B / ConvNeXt-V2-B / MLP-Mixer-B/16 only)' % mtype)
     return _REGISTRY[mtype](**kwargs)

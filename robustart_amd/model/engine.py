@@ -20,7 +20,7 @@ import os as _os
 
 from .. import _lib
 from .engine_base import (F_MASK_BITS, F_OUT_F32, F_PAIR, F_RELU, EngineBase, cints as _cints, conv_desc, conv_tap_classes,
-                          gemm_pair_cls_desc, gemm_pair_desc, interleave_k32, k32, lo_off, pad_k, pad_rows, rows_mult, pair, split_hi_lo, stem_rows)
+                          gemm_pair_cls_desc, gemm_pair_desc, interleave_k32, lo_off, pad_k, pad_rows, rows_mult, pair, split_hi_lo, stem_rows)
 
 
 def _bf16(t):
@@ -83,7 +83,7 @@ def class_tables(ca, cb, ds):
     per-class tables of cb.bwd as one.  ds.cls_bwd = the same for dx = mask(W1^T . dza + Wds^T . dz): conv1^T read at the four parities of
     dza, the class (0, 0) with the shortcut^T as its second source (rows [W1^T | Wds^T]); the other three slices are W1^T again."""
     pow2 = lambda k: k >= 32 and (k & (k - 1)) == 0                      # noqa: E731
-    if cb.stride == 2 and all(taps and tab is not None for _, taps, tab in cb.bwd) and sum(len(t) for _, t, _ in cb.bwd) <= 16 and pow2(cb.cout):
+    if cb.groups == 1 and cb.stride == 2 and all(taps and tab is not None for _, taps, tab in cb.bwd) and sum(len(t) for _, t, _ in cb.bwd) <= 16 and pow2(cb.cout):
         tab, offs = _cat_classes([t for _, _, t in cb.bwd])
         cb.cls_bwd = (tab, [(taps, off, parity) for (parity, taps, _), off in zip(cb.bwd, offs)])
     if ds is not None and ds.stride == 2 and ds.r == 1 and ca.r == 1 and ca.stride == 1 and ca.cin == ds.cin and pow2(ca.cout) and ds.cout % 32 == 0:
@@ -105,12 +105,30 @@ class _Conv:
         else:
             b = conv.bias.detach().float() if conv.bias is not None else torch.zeros(w.shape[0])
         self.cout, self.cin, self.r, self.s = w.shape
+        self.groups = conv.groups
+        self.cin *= self.groups              # (a grouped weight is [cout][cin / groups][r][s])
         self.stride = conv.stride[0]
         self.pad = pad = conv.padding[0]
         self.w_folded = w                    # fp32, for the reference emulation in tests
         self.b_folded = b
         self.bias = b.contiguous().to(device)
         self.fwd_taps, rs_all, classes = conv_tap_classes(self.r, self.s, self.stride, pad)
+        self.split = split
+        if self.groups > 1:
+            # grouped 3x3 (ResNeXt's conv2): no dense table exists.  Per slice of S channels (`grouped_slice_tables`), for the forward
+            # and for every backward class: g_fwd / g_bwd[i] = (rows, frag) -- `rows` the [slices][64][K] tables ([hi | lo | hi] rows in
+            # reference precision) the generic entries take slice by slice, `frag` the same values in the fragment order of
+            # rart_conv3x3_grouped_* ([2][...]: hi and lo planes, in reference precision)
+            assert self.cin == self.cout and self.r == 3 and self.s == 3 and pad == 1, 'grouped convolutions: 3x3, pad 1, cin == cout'
+            self.gw = self.cin // self.groups
+            assert self.gw in (4, 8, 16, 32, 64), 'group widths 4, 8, 16, 32, 64'
+            self.slice = 64 if self.gw == 64 else 32
+            self.w_fwd = None
+            self.bwd = [(parity, taps, None) for parity, taps, _ in classes]
+            self._g_rs = [(rs_all, False)] + [(rs, True) for _, _, rs in classes]
+            tabs = [tuple(t.to(device) for t in tt) for tt in self._grouped_tables(w)]
+            self.g_fwd, self.g_bwd = tabs[0], tabs[1:]
+            return
         planes = _planes(w, split)
 
         def table(rs, transpose):
@@ -123,6 +141,47 @@ class _Conv:
         # backward to input: list of (input parity (ph, pw) or None, taps [(dy, dx)], table or None); a stride-2 conv has one table
         # per input-parity class, over the filter taps that reach it
         self.bwd = [(parity, taps, table(rs, True) if rs else None) for parity, taps, rs in classes]
+
+    def _grouped_tables(self, w):
+        """folded fp32 weight [C][gw][3][3] -> [(rows, frag)] for the forward, then for every backward class"""
+        import torch
+        S, out = self.slice, []
+        for rs, transpose in self._g_rs:
+            pl = [grouped_slice_tables(p, rs, transpose, S) for p in _planes(w, self.split)]           # [slices][S][K], bf16-exact fp32
+            rows = [torch.nn.functional.pad(p, (0, 0, 0, 64 - S)) for p in pl]                         # rows padded to the GEMM tile
+            rows = _bf16(torch.cat(rows + rows[:1], 2) if len(rows) == 2 else rows[0])
+            frag = [grouped_frag(p) for p in pl]
+            out.append((rows, _bf16(torch.stack(frag) if len(frag) == 2 else frag[0])))
+        return out
+
+    def refold_grouped(self, w):
+        """re-derive the grouped tables in place from the folded fp32 weight w (on the tables' device)"""
+        for (rows, frag), (nr, nf) in zip([self.g_fwd] + list(self.g_bwd), self._grouped_tables(w)):
+            rows.copy_(nr)
+            frag.copy_(nf)
+
+
+def grouped_slice_tables(w, rs, transpose, S):
+    """Grouped weight w [C][gw][r][s] (C in = C out, groups of gw channels) -> the dense per-slice tables [C / S][S][len(rs) * S] over the
+    filter taps rs: slice i covers channels i S .. i S + S - 1, which hold whole groups, so it reads only itself.  Row o, column
+    t * S + c = w[i S + o][c % gw][rs[t]] where c and o lie in the same group, exactly zero elsewhere; transpose (backward to the
+    input): row c, column t * S + o."""
+    import torch
+    C, gw, r, s = w.shape
+    ns = C // S
+    assert C % S == 0 and S % gw == 0
+    dense = w.new_zeros(ns, S, S // gw, gw, r, s)
+    o = torch.arange(S, device=w.device)
+    dense[:, o, o // gw] = w.reshape(ns, S, gw, r, s)
+    dense = dense.reshape(ns, S, S, r, s)                      # [slice][out][in][r][s]
+    return torch.cat([dense[:, :, :, a, b].transpose(1, 2) if transpose else dense[:, :, :, a, b] for a, b in rs], 2).contiguous()
+
+
+def grouped_frag(t):
+    """slice tables [slices][S][K] -> the fragment order of rart_conv3x3_grouped_*: [slices][K / 16][S / 32][64 lanes][8], lane l of
+    fragment (st, j) = T[j * 32 + (l & 31)][st * 16 + (l >> 5) * 8 ..]"""
+    ns, S, K = t.shape
+    return t.reshape(ns, S // 32, 32, K // 16, 2, 8).permute(0, 3, 1, 4, 2, 5).contiguous().view(-1)
 
 
 class ResNet50Engine(EngineBase):
@@ -204,6 +263,12 @@ class ResNet50Engine(EngineBase):
         # rart_gemm_pair_max_classes (the entry came with it)
         self.fused_stem_next_pair = True
         self.fused_stem_next_sources = ('u8',)
+        # grouped 3x3 (ResNeXt's conv2, either precision) on rart_conv3x3_grouped_* (csrc/conv_grouped.hip), for these group widths; False /
+        # a width not listed: the same slice tables through the generic entries, one launch per slice (cross-check and A/B baseline:
+        # profiles/grouped_conv_ab.py).  Measured at B = 256 on every conv2 shape of resnext50_32x4d, both directions and precisions
+        # (profiles/grouped_conv_ab.json): the new kernel wins all 28 cases, 1.3 x to 14 x, so every width stays listed
+        self.grouped_conv_kernel = True
+        self.grouped_kernel_widths = (4, 8, 16, 32, 64)
         self.pair_gemm_kernel = True     # reference-precision mode: False = the three products as 3 x the taps of the implicit GEMM (round 3; cross-check)
         self.blocks = []
         for layer in (m.layer1, m.layer2, m.layer3, m.layer4):
@@ -214,8 +279,13 @@ class ResNet50Engine(EngineBase):
         # ---- classifier: forward table [1024][2048], backward-to-input table [2048][1024] ([hi | lo | hi] rows in reference precision)
         wfc = m.fc.weight.detach().float()
         self.n_classes, self.fc_in = wfc.shape
-        self.fc_b = m.fc.bias.detach().float().contiguous().to(dev)
-        self.fc_kpad = k32(self.n_classes)                                # 1024
+        # (class counts that are no multiple of 8 -- small test heads: the forward launch writes n_cols8 columns, the bias is a view into a
+        # vector padded with zeros to that length, and K of the backward is padded to the 64-deep step of rart_gemm_small_m_bf16)
+        self.n_cols8 = (self.n_classes + 7) // 8 * 8
+        fc_b = torch.zeros(self.n_cols8, dtype=torch.float32)
+        fc_b[:self.n_classes] = m.fc.bias.detach().float()
+        self.fc_b = fc_b.to(dev)[:self.n_classes]
+        self.fc_kpad = (self.n_classes + 63) // 64 * 64                   # 1024
         pl = _planes(wfc, split)
         self.fc_w = _table(lambda p: pad_rows(p, 128), pl, dev)
         self.fc_wd = _table(lambda p: pad_k(p.t(), self.fc_kpad), pl, dev)
@@ -253,7 +323,7 @@ class ResNet50Engine(EngineBase):
                 class_tables(ca, cb, ds)
             if two_sources and ds is not None and fold_shortcut_tables(ca, cc, ds) and ds.stride == 1 and ds.cin == 64 and cc.cout == 4 * cb.cout:
                 ds.tail_x = frag(ds.w_fwd, ds.cout, ds.cin)        # layer1's first block: the shortcut inside the tail kernel
-            if not (cb.r == 3 and cb.stride == 1 and cb.pad == 1 and cb.cin == cb.cout and self.lib.rart_conv3x3_tail_pair_supported(cb.cin)):
+            if not (cb.groups == 1 and cb.r == 3 and cb.stride == 1 and cb.pad == 1 and cb.cin == cb.cout and self.lib.rart_conv3x3_tail_pair_supported(cb.cin)):
                 continue
             if cc.cin == cb.cout and cc.cout == 4 * cb.cout and cc.r == 1 and cc.stride == 1:
                 cc.tail_fwd = frag(cc.w_fwd, cc.cout, cc.cin)
@@ -288,6 +358,8 @@ class ResNet50Engine(EngineBase):
             else:
                 torch.add(a, b, out=out)
         for ca, cb, cc, ds in self.blocks:
+            if cb.groups > 1:        # a grouped 3x3 has no dense table: none of the fused kernels takes its block
+                continue
             if cb.r == 3 and cb.stride == 1 and cb.cin == cb.cout and cb.cin in (64, 128, 256, 512):
                 for name, tab in (('w_fwd_frag', cb.w_fwd), ('w_bwd_frag', cb.bwd[0][2])):
                     if getattr(cb, name, None) is None:
@@ -412,6 +484,8 @@ class ResNet50Engine(EngineBase):
         for w, scale, tab, c, trs, tr in st['big']:
             _lib.check(lib.rart_pack_conv_weight_bf16(w.data_ptr(), scale.data_ptr(), tab.data_ptr(), c.cout, c.cin, c.r, c.s, len(trs),
                                                       _cints([a for a, _ in trs]), _cints([b for _, b in trs]), tr, tab.shape[0], sp))
+        for c, w, scale in st['grouped']:
+            c.refold_grouped(w.detach() * scale.view(-1, 1, 1, 1))
         # stem extras (row-tap table, patches table, fused-backward table) and the classifier
         sc = st['scale'][:64]
         wb = (m.conv1.weight.detach() * sc.view(-1, 1, 1, 1)).to(torch.bfloat16)          # [64][3][7][7]
@@ -441,7 +515,7 @@ class ResNet50Engine(EngineBase):
         st = {'key': key, 'eps': eps.pop()}
         for nm in ('var', 'gamma', 'beta', 'mean', 'scale', 'tmp', 'bias'):
             st[nm] = torch.empty(n_tot, dtype=torch.float32, device=dev)
-        jobs, big, off = [], [], 0
+        jobs, big, grouped, off = [], [], [], 0
         for c, conv, bn in pairs:
             w = conv.weight
             assert w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()
@@ -449,6 +523,10 @@ class ResNet50Engine(EngineBase):
             c.bias = st['bias'][off:off + c.cout]           # a view: the flat fold writes every layer's bias at once
             c.bias.copy_(old)
             scale_ptr = st['scale'][off:off + c.cout].data_ptr()
+            if c.groups > 1:                                # grouped tables are re-derived by `_Conv.refold_grouped`, not by pack jobs
+                grouped.append((c, w, st['scale'][off:off + c.cout]))
+                off += c.cout
+                continue
             rs = [(r, s_) for r in range(c.r) for s_ in range(c.s)]
             todo = [(c.w_fwd, rs, 0)]
             for parity, taps, tab in c.bwd:
@@ -470,7 +548,7 @@ class ResNet50Engine(EngineBase):
             fj.append(j)
         st['pack_jobs'], st['n_pack'] = self._upload_jobs(jobs), len(jobs)
         st['frag_jobs'], st['n_frag'] = (self._upload_jobs(fj) if fj else None), len(fj)
-        st['bias_sums'], st['big'] = sums, big
+        st['bias_sums'], st['big'], st['grouped'] = sums, big, grouped
         st['_keep'] = (jobs, fj)
         self._refold_state = st
         return st
@@ -640,7 +718,7 @@ class ResNet50Engine(EngineBase):
         return n * hw[0] * hw[1] * channels < (1 << 31)
 
     def _halo_ok(self, c, hw, n=1):
-        return (self._fits32(n, hw, c.cin) and self.halo_conv3x3 and c.r == 3 and c.s == 3 and c.stride == 1 and c.pad == 1
+        return (c.groups == 1 and self._fits32(n, hw, c.cin) and self.halo_conv3x3 and c.r == 3 and c.s == 3 and c.stride == 1 and c.pad == 1
                 and c.cin == c.cout and getattr(c, 'w_fwd_frag', None) is not None and self.lib.rart_conv3x3_halo_supported(c.cin, hw[0], hw[1]))
 
     def _halo(self, src, w, dst, B, hw, ch, taps, bias=None, mask=None, sign=None, relu=False):
@@ -652,14 +730,14 @@ class ResNet50Engine(EngineBase):
             self._prof_end(ev, 2.0 * B * hw[0] * hw[1] * 9 * ch * ch, 'halo3x3')
 
     def _bneck_ok(self, ca, cb, cc, ds, xhw, n=1):
-        return (self._fits32(n, xhw, cc.cout) and self.fused_bottleneck and ds is None and cb.stride == 1 and cb.r == 3 and ca.r == 1 and cc.r == 1
+        return (cb.groups == 1 and self._fits32(n, xhw, cc.cout) and self.fused_bottleneck and ds is None and cb.stride == 1 and cb.r == 3 and ca.r == 1 and cc.r == 1
                 and ca.cin == cc.cout and getattr(cb, 'w_fwd_frag', None) is not None
                 and self.lib.rart_bottleneck_fused_supported(cc.cout, ca.cout, xhw[0], xhw[1]))
 
     def _image_block_fn(self, ca, cb, cc, ds, xhw, n=1):
         """-> the C entry point of the image-resident fused kernel for this identity block (layer3: 14 x 14, then layer2: 28 x 28, then
         layer4: 7 x 7) or None."""
-        if not (self._fits32(n, xhw, cc.cout) and self.fused_bottleneck14 and ds is None and getattr(ca, 'w_fwd_frag', None) is not None
+        if not (cb.groups == 1 and self._fits32(n, xhw, cc.cout) and self.fused_bottleneck14 and ds is None and getattr(ca, 'w_fwd_frag', None) is not None
                 and getattr(cb, 'w_fwd_frag', None) is not None and getattr(cc, 'w_fwd_frag', None) is not None):
             return None
         if self.lib.rart_bottleneck14_fused_supported(cc.cout, ca.cout, xhw[0], xhw[1]):
@@ -686,7 +764,7 @@ class ResNet50Engine(EngineBase):
                            by)
 
     def _s2_ok(self, ca, cb, cc, ds, xhw, n=1):
-        return (self.fused_bottleneck_s2 and ds is not None and getattr(ds, 's2_wd', None) is not None
+        return (cb.groups == 1 and self.fused_bottleneck_s2 and ds is not None and getattr(ds, 's2_wd', None) is not None
                 and self._fits32(n, xhw, ca.cin) and self.lib.rart_bottleneck_s2_fwd_supported(ca.cin, ca.cout, cc.cout, xhw[0], xhw[1]))
 
     @staticmethod
@@ -714,7 +792,7 @@ class ResNet50Engine(EngineBase):
             self._prof_end(ev, self._s2_flops(ca, cb, cc, ds, B, xhw), 'bottleneck_s2_bwd')
 
     def _first_ok(self, ca, cb, cc, ds, xhw, n=1):
-        return (self._fits32(n, xhw, cc.cout) and self.fused_bottleneck and ds is not None and getattr(ds, 'w_fwd_frag', None) is not None
+        return (cb.groups == 1 and self._fits32(n, xhw, cc.cout) and self.fused_bottleneck and ds is not None and getattr(ds, 'w_fwd_frag', None) is not None
                 and getattr(cb, 'w_fwd_frag', None) is not None
                 and self.lib.rart_bottleneck_first_supported(ca.cin, ca.cout, cc.cout, xhw[0], xhw[1]))
 
@@ -741,10 +819,61 @@ class ResNet50Engine(EngineBase):
                 sum(m_ * c // 8 for c, t in ((c_mid, m1), (c_mid, m2), (c_io if not backward else cin_, m3)) if t is not None)
             self._prof_end(ev, 2.0 * B * hw[0] * hw[1] * c_mid * k_all, 'bottleneck', by)
 
+    def _grouped_ok(self, c, src_hw, dst_hw, stride, B, mask):
+        """whether a launch of the grouped 3x3 c goes to rart_conv3x3_grouped_* (a mask must be a 1-bit tensor there)"""
+        torch = _lib.require_gpu()
+        return (self.grouped_conv_kernel and c.gw in self.grouped_kernel_widths and (mask is None or mask.dtype == torch.uint8)
+                and self._fits32(B, src_hw, c.cin) and self._fits32(B, dst_hw, c.cin)
+                and self.lib.rart_conv3x3_grouped_supported(c.cin, c.gw, src_hw[0], src_hw[1], stride))
+
+    def _grouped(self, c, tabs, taps, src, src_hw, dst, dst_hw, grid, B, pair, stride=1, dst_stride=1, dst_org=(0, 0), bias=None, mask=None,
+                 sign=None, relu=False):
+        """One launch of the grouped 3x3 convolution c (forward, backward at stride 1, or one input-parity class of the stride-2 backward):
+        grid pixel (y, x) reads src at (y * stride + dy, x * stride + dx) per tap and writes dst at (y * dst_stride + oy, x * dst_stride +
+        ox).  tabs = (rows, frag) of `_Conv`: the fragment-ordered table on rart_conv3x3_grouped_*, or (`grouped_conv_kernel` off, a
+        width outside `grouped_kernel_widths`) the row tables through the generic entries, one launch per slice."""
+        torch = _lib.require_gpu()
+        rows, frag = tabs
+        C, S = c.cin, c.slice
+        if self._grouped_ok(c, src_hw, dst_hw, stride, B, mask):
+            ev = self._prof_begin()
+            geom = (B, src_hw[0], src_hw[1], C, c.gw, stride, grid[0], grid[1], len(taps), _cints([t[0] for t in taps]),
+                    _cints([t[1] for t in taps]), dst_hw[0], dst_hw[1], dst_stride, dst_org[0], dst_org[1], 1 if relu else 0, _lib.stream_ptr())
+            if pair:
+                _lib.check(self.lib.rart_conv3x3_grouped_pair(_lib.ptr(src[0]), _lib.ptr(src[1]), _lib.ptr(frag[0]), _lib.ptr(frag[1]),
+                                                              _lib.ptr(bias), _lib.ptr(mask), _lib.ptr(sign), _lib.ptr(dst[0]), _lib.ptr(dst[1]),
+                                                              *geom))
+            else:
+                _lib.check(self.lib.rart_conv3x3_grouped_bf16(_lib.ptr(src), _lib.ptr(frag), _lib.ptr(bias), _lib.ptr(mask), _lib.ptr(sign),
+                                                              _lib.ptr(dst), *geom))
+            if ev is not None:
+                # MFMA FLOPs issued (the padded slices; three products in pair form); algorithmic bytes: the source pixels once, the grid's
+                # destination pixels once, 1 bit per destination element for a mask / sign tensor
+                px = B * grid[0] * grid[1]
+                eb = 4.0 if pair else 2.0
+                self._prof_end(ev, (3 if pair else 1) * 2.0 * px * len(taps) * S * C, 'grouped3x3',
+                               eb * C * (B * src_hw[0] * src_hw[1] + px) + px * C / 8.0 * ((mask is not None) + (sign is not None)))
+            return
+        fl = (F_RELU if relu else 0) | (F_MASK_BITS if (mask is not None and mask.dtype == torch.uint8) else 0)
+        cut = (lambda t, off: t.view(2, -1)[:, off:]) if pair else (lambda t, off: t.view(-1)[off:])
+        for i in range(C // S):
+            off = i * S
+            if mask is not None and mask.dtype != torch.uint8:
+                m_i = mask.view(-1)[off:]          # (bf16 cross-check: the activation itself, same element offsets as dst)
+            else:
+                m_i = None if mask is None else mask.view(-1)[off // 8:]
+            self._gemm(cut(src, off), rows[i], cut(dst, off), B, grid, src_hw, C, S, taps, S, dst_hw, C,
+                       bias=None if bias is None else bias[off:off + S], mask=m_i, flags=fl, stride=(stride, stride),
+                       dst_stride=(dst_stride, dst_stride), dst_off=dst_org, sign_out=None if sign is None else sign.view(-1)[off // 8:], pair=pair)
+
     def _conv_fwd(self, c, x, xhw, out, relu, res=None, sign=None, pair=False, identity=False):
-        """identity: conv3 of an identity block (res = the block's input)"""
+        """identity: conv3 of an identity block (res = the block's input) whose conv2 is ungrouped: the launch may go to the walk entry"""
         B = x.shape[1] if pair else x.shape[0]
         oh, ow = xhw[0] // c.stride, xhw[1] // c.stride
+        if c.groups > 1:
+            assert res is None
+            return self._grouped(c, c.g_fwd, c.fwd_taps, x, xhw, out, (oh, ow), (oh, ow), B, pair, stride=c.stride, bias=c.bias, sign=sign,
+                                 relu=relu)
         if pair:
             return self._gemm(x, c.w_fwd, out, B, (oh, ow), xhw, c.cin, c.cin, c.fwd_taps, c.cout, (oh, ow), c.cout, bias=c.bias,
                               res=res, flags=F_RELU if relu else 0, stride=(c.stride, c.stride), sign_out=sign, pair=True,
@@ -762,9 +891,18 @@ class ResNet50Engine(EngineBase):
         B = dz.shape[1] if pair else dz.shape[0]
         fl = F_MASK_BITS if (mask is not None and mask.dtype == torch.uint8) else 0
         assert not pair or mask is None or fl, 'the split-bf16 mode reads ReLU masks as 1-bit tensors only'
+        if c.groups > 1:
+            assert res is None
+            for (parity, taps, _), tabs in zip(c.bwd, c.g_bwd):     # stride 1: one class; stride 2: the four input-parity classes
+                if parity is None:
+                    self._grouped(c, tabs, taps, dz, dz_hw, dx, dx_hw, dx_hw, B, pair, mask=mask)
+                else:
+                    self._grouped(c, tabs, taps, dz, dz_hw, dx, dx_hw, (dx_hw[0] // 2, dx_hw[1] // 2), B, pair, mask=mask, dst_stride=2,
+                                  dst_org=parity)
+            return
         if not pair and res is None and (mask is None or fl) and self._halo_ok(c, dx_hw, B):
             return self._halo(dz, c.w_bwd_frag, dx, B, dx_hw, c.cin, c.bwd[0][1], mask=mask)
-        if pair and c.r == 3 and c.cin in self.class_3x3_channels and self._classes_ok(getattr(c, 'cls_bwd', None)) and \
+        if pair and c.groups == 1 and c.r == 3 and c.cin in self.class_3x3_channels and self._classes_ok(getattr(c, 'cls_bwd', None)) and \
                 dx_hw[0] % 2 == 0 and dx_hw[1] % 2 == 0:
             # stride-2 3x3: the four input-parity classes (1 / 2 / 2 / 4 taps) in one grid
             return self._gemm_pair_classes(dz, c.cls_bwd, dx, B, (dx_hw[0] // 2, dx_hw[1] // 2), dz_hw, c.cout, c.cout, c.cin, dx_hw, c.cin,
@@ -874,7 +1012,7 @@ class ResNet50Engine(EngineBase):
         'bneck' (bottleneck_fused.hip), the C entry of an image-resident kernel (14, then 28, then 7), 'first', 's2'."""
         if self.x3:
             c = ca if backward else cc       # the 1x1 of the launch; a block with a tail table has a stride-1 C -> C 3x3 (ohw = xhw)
-            return 'tail' if (self.fused_tail_pair and cb.cin in self.fused_tail_channels
+            return 'tail' if (cb.groups == 1 and self.fused_tail_pair and cb.cin in self.fused_tail_channels
                               and getattr(c, 'tail_bwd' if backward else 'tail_fwd', None) is not None
                               and self._fits32(B, xhw, c.cin if backward else c.cout)) else None
         if self._bneck_ok(ca, cb, cc, ds, xhw, B):
@@ -925,7 +1063,7 @@ class ResNet50Engine(EngineBase):
                 sk = x if ds is None else (None if fold else self._shortcut_fwd(bi, ds, x, xhw, ohw, B))
             if kind == 'tail':   # conv2 + relu + conv3 + skip + relu in one launch: the 3x3's output never exists in HBM
                 na = self.blocks[bi + 1][0] if bi + 1 < len(self.blocks) else None
-                if self.fused_next_pair and na is not None and getattr(na, 'next_fwd', None) is not None and cb.cout in self.fused_next_channels:
+                if self.fused_next_pair and cb.groups == 1 and na is not None and getattr(na, 'next_fwd', None) is not None and cb.cout in self.fused_next_channels:
                     # ... and the next block's conv1 + relu on the output tile: that block's own read of this output disappears
                     nxt = dict(tab=na.next_fwd, bias=na.bias, relu=True, dst=get('b%d_a' % (bi + 1), lead + (ohw[0], ohw[1], na.cout)),
                                sign=get('b%d_a_sign' % (bi + 1), (B, ohw[0], ohw[1], na.cout // 8), torch.uint8) if keep else None)
@@ -941,7 +1079,7 @@ class ResNet50Engine(EngineBase):
                     self._gemm(yb, ds.w_cat, yc, B, ohw, ohw, cc.cin, cc.cin, cc.fwd_taps, cc.cout, ohw, cc.cout, bias=ds.bias_cat,
                                flags=F_RELU, sign_out=sc, pair=True, src2=(x, xhw, (ds.stride, ds.stride), ca.cin, ds.cin))
                 else:
-                    self._conv_fwd(cc, yb, ohw, yc, True, res=sk, sign=sc, pair=x3, identity=ds is None)
+                    self._conv_fwd(cc, yb, ohw, yc, True, res=sk, sign=sc, pair=x3, identity=ds is None and cb.groups == 1)
         acts['b%d' % bi] = (x, xhw, ya, yb, yc, ohw)
         # the backward pass needs the activations only for their ReLU sign: the 1-bit tensors, or with `sign_bit_masks` off (bf16
         # cross-check) the activations themselves
@@ -961,13 +1099,13 @@ class ResNet50Engine(EngineBase):
         pooled = self._act('pooled', (B, self.fc_in))
         _lib.check((lib.rart_engine_avgpool_pair if x3 else lib.rart_engine_avgpool)(
             *self._po(x), *self._po(pooled), B, xhw[0] * xhw[1], self.fc_in, _lib.stream_ptr()))
-        logits = torch.empty(B, self.n_classes, dtype=torch.float32, device=self.device)
+        logits = torch.empty(B, self.n_cols8, dtype=torch.float32, device=self.device)
         if self.small_m_fc and not x3:
             self._fc(pooled, self.fc_w, logits, B, self.n_classes, self.fc_in, bias=self.fc_b)
         else:
-            self._gemm(pooled, self.fc_w, logits, B, (1, 1), (1, 1), self.fc_in, self.fc_in, [(0, 0)], self.n_classes,
-                       (1, 1), self.n_classes, bias=self.fc_b, flags=F_OUT_F32, pair=x3)
-        return logits
+            self._gemm(pooled, self.fc_w, logits, B, (1, 1), (1, 1), self.fc_in, self.fc_in, [(0, 0)], self.n_cols8,
+                       (1, 1), self.n_cols8, bias=self.fc_b, flags=F_OUT_F32, pair=x3)
+        return logits if self.n_cols8 == self.n_classes else logits[:, :self.n_classes].contiguous()
 
     def _head_bwd(self, acts, dl, B):
         """classifier^T + average-pool backward with the last block's ReLU mask -> gradient at the last block's output"""
@@ -1022,7 +1160,7 @@ class ResNet50Engine(EngineBase):
             if kind == 'tail':   # conv2^T + mask + conv1^T + identity-skip gradient + mask in one launch
                 nxt = None
                 pc = self.blocks[bi - 1][2] if bi > 0 else None
-                if self.fused_next_pair and pc is not None and getattr(pc, 'next_bwd', None) is not None and cb.cin in self.fused_next_channels:
+                if self.fused_next_pair and cb.groups == 1 and pc is not None and getattr(pc, 'next_bwd', None) is not None and cb.cin in self.fused_next_channels:
                     # ... and the previous block's conv3^T + mask on the input-gradient tile, when that block kept a mask
                     mask = acts['b%d_masks' % (bi - 1)][2]
                     if mask is not None:
@@ -1032,7 +1170,7 @@ class ResNet50Engine(EngineBase):
             dza = get('g_a', lead + (xhw[0], xhw[1], ca.cout))
             self._conv_bwd(cb, dzb, ohw, dza, xhw, mask=ma, pair=x3)
             if ds is None:
-                self._conv_bwd(ca, dza, xhw, dx, xhw, res=dz, mask=mx, pair=x3, identity=True)            # identity skip
+                self._conv_bwd(ca, dza, xhw, dx, xhw, res=dz, mask=mx, pair=x3, identity=cb.groups == 1)     # identity skip
             elif x3 and self.fused_shortcut_pair and self.pair_gemm_kernel and getattr(ds, 'w_cat_bwd', None) is not None:
                 # stride-1 projection skip (layer1's first block): conv1^T and the shortcut^T as one two-source launch, dx written once
                 self._gemm(dza, ds.w_cat_bwd, dx, B, xhw, xhw, ca.cout, ca.cout, ca.bwd[0][1], ca.cin, xhw, ca.cin, mask=mx,
@@ -1097,7 +1235,8 @@ class ResNet50Engine(EngineBase):
 
 
 def make_engine(torch_model, device='cuda', precision='bf16'):
-    """HIP engine for a model from robustart_amd.model.get_model: ResNet-50, ViT-B/16, ConvNeXt-B, ConvNeXt-V2-B (a ConvNeXt
+    """HIP engine for a model from robustart_amd.model.get_model: ResNet-50 and its Bottleneck family (ResNet-101/152, Wide-ResNet,
+    ResNeXt: the same ResNet50Engine, which reads block counts, widths and groups from the module), ViT-B/16, ConvNeXt-B, ConvNeXt-V2-B (a ConvNeXt
     subclass: ConvNeXtEngine runs its GRN blocks) or MLP-Mixer-B/16 (MixerEngine), each with forward and
     backward-to-input (`forward_backward`) on the hand-written kernels.  precision 'bf16x3' / 'fp32x': the
     reference-precision mode (both architectures: split-bf16 pairs, three MFMA products per contraction)."""
@@ -1116,7 +1255,7 @@ def make_engine(torch_model, device='cuda', precision='bf16'):
     if isinstance(torch_model, MlpMixer):
         from .mixer_engine import MixerEngine
         return MixerEngine(torch_model, device, precision)
-    raise NotImplementedError('no HIP engine for %s (ResNet-50 / ViT-B/16 / ConvNeXt-B / ConvNeXt-V2-B / MLP-Mixer-B/16 only)'
+    raise NotImplementedError('no HIP engine for %s (the ResNet Bottleneck family / ViT-B/16 / ConvNeXt-B / ConvNeXt-V2-B / MLP-Mixer-B/16 only)'
                               % type(torch_model).__name__)
 
 

@@ -1,4 +1,5 @@
-"""ResNet-50 (v1.5: stride on the 3x3) as a plain torch module.
+"""ResNet-50 (v1.5: stride on the 3x3) and the rest of its Bottleneck family (ResNet-101/152, Wide-ResNet-50/101-2,
+ResNeXt-50 32x4d / -101 32x8d: `groups`, `width_per_group`) as a plain torch module.
 
 Role: (1) the parameter container `get_model` returns (reference: RobustART/model/__init__.py:1 ->
 prototype.model.get_model, whose source is absent; `resnet50_official` == the public torchvision
@@ -14,13 +15,14 @@ import torch.nn as nn
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, width_per_group=64):
         super().__init__()
-        self.conv1 = nn.Conv2d(inplanes, planes, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(planes)
-        self.conv2 = nn.Conv2d(planes, planes, 3, stride=stride, padding=1, bias=False)
-        self.bn2 = nn.BatchNorm2d(planes)
-        self.conv3 = nn.Conv2d(planes, planes * 4, 1, bias=False)
+        mid = int(planes * width_per_group / 64) * groups       # ResNeXt / Wide-ResNet: the width of conv1's output and of the 3x3
+        self.conv1 = nn.Conv2d(inplanes, mid, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(mid)
+        self.conv2 = nn.Conv2d(mid, mid, 3, stride=stride, padding=1, groups=groups, bias=False)
+        self.bn2 = nn.BatchNorm2d(mid)
+        self.conv3 = nn.Conv2d(mid, planes * 4, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(planes * 4)
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
@@ -36,9 +38,10 @@ class Bottleneck(nn.Module):
 
 
 class ResNet(nn.Module):
-    def __init__(self, layers=(3, 4, 6, 3), num_classes=1000, width=64):
+    def __init__(self, layers=(3, 4, 6, 3), num_classes=1000, width=64, groups=1, width_per_group=64):
         super().__init__()
         self.inplanes = width
+        self.groups, self.width_per_group = groups, width_per_group
         self.conv1 = nn.Conv2d(3, width, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(width)
         self.relu = nn.ReLU(inplace=True)
@@ -61,10 +64,11 @@ class ResNet(nn.Module):
         if stride != 1 or self.inplanes != planes * 4:
             downsample = nn.Sequential(nn.Conv2d(self.inplanes, planes * 4, 1, stride=stride, bias=False),
                                        nn.BatchNorm2d(planes * 4))
-        layers = [Bottleneck(self.inplanes, planes, stride, downsample)]
+        kw = dict(groups=self.groups, width_per_group=self.width_per_group)
+        layers = [Bottleneck(self.inplanes, planes, stride, downsample, **kw)]
         self.inplanes = planes * 4
         for _ in range(1, blocks):
-            layers.append(Bottleneck(self.inplanes, planes))
+            layers.append(Bottleneck(self.inplanes, planes, **kw))
         return nn.Sequential(*layers)
 
     def forward(self, x):
@@ -75,6 +79,18 @@ class ResNet(nn.Module):
 
 def resnet50(num_classes=1000, **_):
     return ResNet((3, 4, 6, 3), num_classes)
+
+
+def _family(layers, groups=1, width_per_group=64):
+    def make(num_classes=1000, **_):
+        return ResNet(layers, num_classes, groups=groups, width_per_group=width_per_group)
+    return make
+
+
+# the other members of the Bottleneck family (public torchvision definitions: same module tree and state-dict keys as ResNet-50)
+FAMILY = {'resnet101_official': _family((3, 4, 23, 3)), 'resnet152_official': _family((3, 8, 36, 3)),
+          'wide_resnet50_2': _family((3, 4, 6, 3), 1, 128), 'wide_resnet101_2': _family((3, 4, 23, 3), 1, 128),
+          'resnext50_32x4d': _family((3, 4, 6, 3), 32, 4), 'resnext101_32x8d': _family((3, 4, 23, 3), 32, 8)}
 
 
 def randomize_bn_stats(model, seed=0):

@@ -29,6 +29,9 @@ class _TConv:
     """One conv (+ its BatchNorm) in training mode: packed tables, saved activations, geometry."""
 
     def __init__(self, conv, bn, device, torch):
+        if conv.groups != 1:
+            raise NotImplementedError('ResNetTrainEngine: a grouped convolution (groups = %d) has no train-mode kernels; ResNeXt is '
+                                      'evaluation only' % conv.groups)
         self.conv, self.bn = conv, bn
         self.cout, self.cin, self.r, self.s = conv.weight.shape
         self.stride, self.pad = conv.stride[0], conv.padding[0]

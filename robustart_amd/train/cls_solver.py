@@ -114,6 +114,10 @@ def train(cfg, args, rank, world, device):
     if convstem_of(model) is not None:         # before the model reaches the device: every reference config of these types evaluates
         raise NotImplementedError('training %r: the ConvStem models are evaluation only (forward and backward-to-input on the HIP '
                                   'engines; there is no train engine for the stem)' % (cfg['model']['type'],))
+    from ..model.resnet_torch import FAMILY as resnet_family
+    if cfg['model']['type'] in resnet_family:  # likewise: ResNet-101/152, Wide-ResNet and ResNeXt are evaluated, attacked and corrupted
+        raise NotImplementedError('training %r: this member of the ResNet family is evaluation only (forward and backward-to-input on '
+                                  'the HIP engine; ResNetTrainEngine is built and measured for resnet50_official alone)' % (cfg['model']['type'],))
     model = model.to(device)
     from ..model.convnext_torch import ConvNeXt, ConvNeXtV2
     from ..model.mixer_torch import MlpMixer
