@@ -376,6 +376,8 @@ static int gp_check_and_fill(const rart_gemm_pair_desc* h, const rart_gemm_pair2
                    "rart_gemm_pair_bf16 (conv): a source plane must stay below 2 GiB (32-bit byte offsets of the stage loads) and the destination "
                    "below 2^31 elements (split the batch)");
     RART_CHECK_ARG(h->lda % 8 == 0 || h->lda == 4, "rart_gemm_pair_bf16 (conv): source pixels must keep 16-byte alignment of the K chunks");
+    // (the conv instances are compiled without the GELU forms: gp_finish_segment<true, false>)
+    RART_CHECK_ARG(!(h->flags & (GP_GELU | GP_GELU_BWD | GP_GELU_KEEP)), "rart_gemm_pair_bf16 (conv): the GELU forms are served by plain products only");
     d.M = (int)M;
     d.K = h->k_per_tap * h->n_taps;
     if (src2) {

@@ -5,6 +5,7 @@
 #pragma once
 #include "rart_common.h"
 #include "rart_bf16_helpers.h"
+#include <type_traits>
 
 namespace {
 using namespace rart_bf16;
@@ -93,7 +94,9 @@ __device__ __forceinline__ void gp_nt_store(uint16_t* p, const uint4& v) {
 // The point-wise tail of one 8-column row segment (element offset e, CONV or plain): v = the fp32 accumulator values of the segment; residual
 // pair, GELU forms, 1-bit mask, ReLU, then hi / lo (two 16-byte stores) or fp32, and the sign byte.  Shared by gp_epilogue and the
 // persistent kernel's deferred epilogue (csrc/gemm_pair_pp.hip) so that both produce the same bits.
-template <bool CONV, bool GELU = true>
+// NT: -1 = the pair stores follow d.nt at run time; 0 / 1 = the caller made the choice (gp_epilogue makes it once per block, around all four
+// segments: with the choice per store hipcc merges the two arms of the CONV instances into one ORDINARY store and the hint is lost).
+template <bool CONV, bool GELU = true, int NT = -1>
 __device__ __forceinline__ void gp_finish_segment(const GemmPairDev& d, int flags, bool out_f32, long long e, float (&v)[8], const uint4& rh_q,
                                             const uint4& rl_q, const uint4& uh_q, const uint4& ul_q, uint32_t mb_q) {
   if (d.res_hi) {
@@ -142,7 +145,7 @@ __device__ __forceinline__ void gp_finish_segment(const GemmPairDev& d, int flag
   } else {
     uint4 ph, pl;
     split8(v, ph, pl);
-    if (d.nt) {
+    if (NT < 0 ? d.nt != 0 : NT != 0) {
       gp_nt_store(d.dst_hi + e, ph);
       gp_nt_store(d.dst_lo + e, pl);
     } else {
@@ -202,44 +205,56 @@ __device__ __forceinline__ void gp_epilogue(const GemmPairDev& d, uint8_t* lds, 
 #pragma unroll
   for (int i = 0; i < MI; ++i) {
     if (wm * RW + i * 32 >= tile_rows) continue;          // (wave-uniform) a 224-row tile of k_gemm_pair_pp: the block belongs to the next tile
-    long long eo[4];
-    uint4 rh[4], rl[4], uh[4], ul[4];
+    // The block's operands as straight-line loads, all requested back to back: a lane whose segment lies past M or past N reads the
+    // tile's last valid row / the last 8 columns instead (el, a valid element of every operand) and drops what it read (eo < 0); loads
+    // under per-lane conditions come out of the compiler with a vmcnt wait per pair, a load round trip each, in series
+    long long eo[4], el[4];
+    uint4 rh[4], rl[4], uh[4], ul[4];                     // uh / ul: the GELU' operands (plain products only; dead in the CONV instances)
     uint32_t mb[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int rt = wm * RW + i * 32 + q * 8 + rw;       // row inside the tile
       const int m = m0 + rt;
-      eo[q] = -1;
+      const int mc = min(m, d.M - 1), colc = col_ok ? col : d.N - 8;
+      if (CONV) {
+        el[q] = (long long)row_dst[mc - m0] + colc;
+      } else {
+        long long drow = mc;
+        if (d.map_rows) {
+          const int img = mc / d.rpi;
+          drow = (long long)img * d.dst_rpi + (mc - img * d.rpi);
+        }
+        el[q] = c_off + (drow + d.dst_off) * d.ldc + colc;
+      }
+      eo[q] = (m < d.M && col_ok) ? el[q] : -1;
       rh[q] = rl[q] = uh[q] = ul[q] = make_uint4(0, 0, 0, 0);
       mb[q] = 0xFFu;
-      if (m < d.M && col_ok) {
-        long long e;
-        if (CONV) {
-          e = (long long)row_dst[rt] + col;
-        } else {
-          long long drow = m;
-          if (d.map_rows) {
-            const int img = m / d.rpi;
-            drow = (long long)img * d.dst_rpi + (m - img * d.rpi);
-          }
-          e = c_off + (drow + d.dst_off) * d.ldc + col;
+    }
+    if (d.res_hi) {
+      if (d.nt) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          rh[q] = gp_nt_load(d.res_hi + el[q]);
+          rl[q] = gp_nt_load(d.res_lo + el[q]);
         }
-        eo[q] = e;
-        if (d.res_hi) {
-          if (d.nt) {
-            rh[q] = gp_nt_load(d.res_hi + e);
-            rl[q] = gp_nt_load(d.res_lo + e);
-          } else {
-            rh[q] = *reinterpret_cast<const uint4*>(d.res_hi + e);
-            rl[q] = *reinterpret_cast<const uint4*>(d.res_lo + e);
-          }
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          rh[q] = *reinterpret_cast<const uint4*>(d.res_hi + el[q]);
+          rl[q] = *reinterpret_cast<const uint4*>(d.res_lo + el[q]);
         }
-        if (flags & GP_GELU_BWD) {
-          uh[q] = gp_nt_load(d.aux_hi + e);
-          ul[q] = gp_nt_load(d.aux_lo + e);
-        }
-        if (CONV && d.mask_bits) mb[q] = d.mask_bits[e >> 3];
       }
+    }
+    if (!CONV && (flags & GP_GELU_BWD)) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        uh[q] = gp_nt_load(d.aux_hi + el[q]);
+        ul[q] = gp_nt_load(d.aux_lo + el[q]);
+      }
+    }
+    if (CONV && d.mask_bits) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) mb[q] = d.mask_bits[el[q] >> 3];
     }
 #pragma unroll
     for (int j = 0; j < 2; ++j)
@@ -248,16 +263,30 @@ __device__ __forceinline__ void gp_epilogue(const GemmPairDev& d, uint8_t* lds, 
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // vmcnt(0) as a builtin the compiler counts: the block's operands have landed (and the previous block's stores are acknowledged) before
+    // its first store.  Loads and stores share the counter; without this the compiler, once a store is pending, answers every later
+    // segment's first use of an operand with a full vmcnt(0) of its own: a store drain per segment instead of one per block
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    // the four segments, once per store form (non-temporal or ordinary pair stores: see gp_finish_segment's NT)
+    auto segments = [&](auto nt_form) {
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int r = q * 8 + rw;
-      const float4 v0 = *reinterpret_cast<const float4*>(sE + r * GP_LDE + cw * 8);
-      const float4 v1 = *reinterpret_cast<const float4*>(sE + r * GP_LDE + cw * 8 + 4);
-      const long long e = eo[q];
-      if (e >= 0) {
-        float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-        gp_finish_segment<CONV>(d, flags, out_f32, e, v, rh[q], rl[q], uh[q], ul[q], mb[q]);
+      for (int q = 0; q < 4; ++q) {
+        const int r = q * 8 + rw;
+        const float4 v0 = *reinterpret_cast<const float4*>(sE + r * GP_LDE + cw * 8);
+        const float4 v1 = *reinterpret_cast<const float4*>(sE + r * GP_LDE + cw * 8 + 4);
+        const long long e = eo[q];
+        if (e >= 0) {
+          float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+          // the CONV instances are compiled without the GELU forms (the host entry refuses them in conv mode)
+          gp_finish_segment<CONV, !CONV, decltype(nt_form)::value>(d, flags, out_f32, e, v, rh[q], rl[q], uh[q], ul[q], mb[q]);
+        }
       }
+    };
+    if constexpr (CONV) {
+      if (d.nt) segments(std::integral_constant<int, 1>{});
+      else segments(std::integral_constant<int, 0>{});
+    } else {      // (the plain instances keep both store forms apart with the choice per store, and spill with the segments twice)
+      segments(std::integral_constant<int, -1>{});
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
