@@ -687,6 +687,41 @@ int rart_conv3x3_grouped_pair(const void* src_hi, const void* src_lo, const void
                               int group_width, int stride, int grid_h, int grid_w, int n_taps, const int* tap_dy, const int* tap_dx,
                               int dst_h, int dst_w, int dst_stride, int dst_oy, int dst_ox, int relu, rart_stream_t stream);
 
+/* DenseNet's element kernels (csrc/densenet.hip), NHWC rows, bf16 or split-bf16 (hi + lo planes; the *_pair entries).  c = the channel
+ * count C, a positive multiple of 32; every row stride ld >= C with ld % 8 == 0; rows (or n * h * w) in 1 .. 2^31 - 1; tensors 16-byte
+ * aligned, sign tensors 4-byte; s, t: fp32 [C], the folded BatchNorm (scale, shift).  Anything else is RART_ERR_INVALID before any launch.
+ * The arithmetic is fp32 on hi + lo: a = fma(s, x, t), ReLU (a NaN stays a NaN), then one round-to-nearest-even into the storage.
+ *   rart_dn_preact_*: y[r][c] = relu(s[c] x[r][c] + t[c]) for c < C.  x: rows of stride ld_x (a channel prefix of a wider buffer, read
+ *     only); y: dense [rows][C].  sign_out (or NULL): 1 bit per element of y, byte (r * C + c) / 8, bit c & 7, set exactly when the
+ *     stored (hi) value is > 0.
+ *   rart_dn_preact_bwd_*: g[r][c] (accumulate = 0: =, 1: +=) bit[r][c] * s[c] * d[r][c] for c < C.  d: dense [rows][C]; bits: the sign
+ *     tensor of the forward; g: rows of stride ld_g, channels >= C of a row are neither read nor written; s may be NULL (= 1: the
+ *     caller folded it into the table that produced d).
+ *   rart_dn_preact_pool2_*: the same pre-activation followed by a 2 x 2 / 2 average pool (a transition: the pool commutes with the
+ *     bias-free 1x1 convolution after it).  x: [n][h][w] pixels of stride ld_x, h and w even; y: dense [n][h / 2][w / 2][C], the mean of
+ *     the four activated values, rounded once; sign_out (or NULL): [n][h][w][C / 8] at FULL resolution, bit = activated value > 0.
+ *   rart_dn_preact_pool2_bwd_*: g[b][y][x][c] (=|+=) bit * s[c] * d[b][y / 2][x / 2][c] / 4.  d: dense [n][h / 2][w / 2][C].
+ *   rart_dn_copy_*: dst[r][c] = src[r][c] for c < C, rows of stride ld_src / ld_dst: a channel slice into or out of a concat buffer. */
+int rart_dn_preact_bf16(const void* x, int ld_x, const float* s, const float* t, void* y, void* sign_out, long long rows, int c,
+                        rart_stream_t stream);
+int rart_dn_preact_pair(const void* x_hi, const void* x_lo, int ld_x, const float* s, const float* t, void* y_hi, void* y_lo, void* sign_out,
+                        long long rows, int c, rart_stream_t stream);
+int rart_dn_preact_bwd_bf16(const void* d, const void* bits, const float* s, void* g, int ld_g, int accumulate, long long rows, int c,
+                            rart_stream_t stream);
+int rart_dn_preact_bwd_pair(const void* d_hi, const void* d_lo, const void* bits, const float* s, void* g_hi, void* g_lo, int ld_g, int accumulate,
+                            long long rows, int c, rart_stream_t stream);
+int rart_dn_preact_pool2_bf16(const void* x, int ld_x, const float* s, const float* t, void* y, void* sign_out, int n, int h, int w, int c,
+                              rart_stream_t stream);
+int rart_dn_preact_pool2_pair(const void* x_hi, const void* x_lo, int ld_x, const float* s, const float* t, void* y_hi, void* y_lo,
+                              void* sign_out, int n, int h, int w, int c, rart_stream_t stream);
+int rart_dn_preact_pool2_bwd_bf16(const void* d, const void* bits, const float* s, void* g, int ld_g, int accumulate, int n, int h, int w,
+                                  int c, rart_stream_t stream);
+int rart_dn_preact_pool2_bwd_pair(const void* d_hi, const void* d_lo, const void* bits, const float* s, void* g_hi, void* g_lo, int ld_g,
+                                  int accumulate, int n, int h, int w, int c, rart_stream_t stream);
+int rart_dn_copy_bf16(const void* src, int ld_src, void* dst, int ld_dst, long long rows, int c, rart_stream_t stream);
+int rart_dn_copy_pair(const void* src_hi, const void* src_lo, int ld_src, void* dst_hi, void* dst_lo, int ld_dst, long long rows, int c,
+                      rart_stream_t stream);
+
 /* One identity Bottleneck (1x1 c_io -> c_mid, 3x3 c_mid -> c_mid, 1x1 c_mid -> c_io, + the block input) as ONE kernel with
  * both intermediates kept on chip (csrc/bottleneck_fused.hip); supported geometry: c_io 256, c_mid 64, 56 x 56 (ResNet-50
  * layer1 blocks 1-2).  Replaces three rart_conv_igemm_bf16 / rart_conv3x3_halo_bf16 launches and computes the same function.

@@ -94,6 +94,16 @@ SIGNATURES = {
     'rart_conv3x3_grouped_tile': (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     'rart_conv3x3_grouped_bf16': (c_int, [c_void_p] * 6 + [c_int] * 9 + [ctypes.POINTER(c_int), ctypes.POINTER(c_int)] + [c_int] * 6 + [c_void_p]),
     'rart_conv3x3_grouped_pair': (c_int, [c_void_p] * 9 + [c_int] * 9 + [ctypes.POINTER(c_int), ctypes.POINTER(c_int)] + [c_int] * 6 + [c_void_p]),
+    'rart_dn_preact_bf16': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_void_p]),
+    'rart_dn_preact_pair': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_void_p]),
+    'rart_dn_preact_bwd_bf16': (c_int, [c_void_p] * 4 + [c_int, c_int, ctypes.c_longlong, c_int, c_void_p]),
+    'rart_dn_preact_bwd_pair': (c_int, [c_void_p] * 6 + [c_int, c_int, ctypes.c_longlong, c_int, c_void_p]),
+    'rart_dn_preact_pool2_bf16': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
+    'rart_dn_preact_pool2_pair': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
+    'rart_dn_preact_pool2_bwd_bf16': (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
+    'rart_dn_preact_pool2_bwd_pair': (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_void_p]),
+    'rart_dn_copy_bf16': (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.c_longlong, c_int, c_void_p]),
+    'rart_dn_copy_pair': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_longlong, c_int, c_void_p]),
     'rart_bottleneck28_fused_supported': (c_int, [c_int, c_int, c_int, c_int]),
     'rart_bottleneck28_fused_bf16': (c_int, [c_void_p] * 11 + [c_int] * 5 + [ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int,
                                              c_void_p]),

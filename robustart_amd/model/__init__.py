@@ -13,18 +13,23 @@ The Bottleneck family of `resnet50_official` runs on the same engine (engine.py,
 `resnet152_official`, `wide_resnet50_2`, `wide_resnet101_2` (ungrouped: the fused kernels that accept their shapes, else the generic
 launches) and `resnext50_32x4d`, `resnext101_32x8d` (conv2 is a grouped 3x3: csrc/conv_grouped.hip); evaluation only, `cls_solver`
 refuses to train them.
+`densenet121`, `densenet169`, `densenet201` (densenet_torch.py: the public torchvision definition) run on DenseNetEngine
+(densenet_engine.py: the pre-activation and dense-concatenation kernels of csrc/densenet.hip around the shared GEMM entries), forward +
+backward-to-input in both precisions; evaluation only, `cls_solver` refuses to train them.
 kwargs `num_classes` and `drop_path_rate` are accepted (drop path is identity in eval)."""
 from .resnet_torch import resnet50, FAMILY as _RESNET_FAMILY
 from .vit_torch import vit_base
 from .convnext_torch import convnext_base, convnextv2_base
 from .mixer_torch import mixer_b16_224
 from .convstem_torch import convnext_base_cvst, vit_base_cvst
+from .densenet_torch import FAMILY as _DENSENET_FAMILY
 
 _REGISTRY = {'resnet50_official': resnet50, 'resnet50': resnet50, 'vit_base': vit_base, 'vit_b16_224': vit_base,
              'vit_base_patch16_224': vit_base, 'convnext_base': convnext_base,
              'convnextv2_base': convnextv2_base, 'mixer_b16_224': mixer_b16_224, 'convnext_base_cvst': convnext_base_cvst,
              'vit_base_cvst': vit_base_cvst, 'vit_b16_224_cvst': vit_base_cvst}
 _REGISTRY.update(_RESNET_FAMILY)
+_REGISTRY.update(_DENSENET_FAMILY)
 
 
 def get_model(config):
@@ -34,5 +39,5 @@ def get_model(config):
     kwargs = dict((config.get('kwargs') if isinstance(config, dict) else getattr(config, 'kwargs', None)) or {})
     kwargs.pop('bn', None)          # {use_sync_bn: False}: BN statistics are local
     if mtype not in _REGISTRY:
-        raise NotImplementedError('model type %r is outside the hot-path scope (the ResNet Bottleneck family / ViT-B/16 / ConvNeXt-B / ConvNeXt-V2-B / MLP-Mixer-B/16 only)' % mtype)
+        raise NotImplementedError('model type %r is outside the hot-path scope (the ResNet Bottleneck family / ViT-B/16 / ConvNeXt-B / ConvNeXt-V2-B / MLP-Mixer-B/16 / DenseNet-121/169/201 only)' % mtype)
     return _REGISTRY[mtype](**kwargs)

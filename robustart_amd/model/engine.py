@@ -201,20 +201,7 @@ class ResNet50Engine(EngineBase):
         m = model
         assert not m.training, 'the attack / eval engine folds BatchNorm: call model.eval() first'
         dev = self.device
-        # ---- stem: 7x7/2 conv on the padded 4-channel hi/lo image; a "tap" = one filter row, 8 px x 4 ch
-        st = _Conv(m.conv1, m.bn1, dev, split)
-        self.stem = st
-        pl = _planes(st.w_folded, split)                                  # [64][3][7][7]
-        # stem backward: patches[(r*7+s)*3+c] = sum_k dz[k] * W[k][c][r][s]; 147 rows zero-padded to the tile
-        self.stem_patch_cols = 152                                        # 147 rounded up to 8
-        self.stem_wd = _table(lambda p: pad_rows(p.permute(2, 3, 1, 0).reshape(147, 64), rows_mult(self.stem_patch_cols)), pl, dev)
-        if not split:
-            self.stem_w = _table(lambda p: stem_rows(p).repeat(1, 2), pl, dev)     # the image's hi taps then its lo taps
-            self.stem_wt = self._stem_bwd_table(pl[0]).to(dev)            # fused stem backward (stem_fused.hip)
-        else:
-            self.stem_w = _table(stem_rows, pl, dev)                     # x_hi.w_hi, x_hi.w_lo, x_lo.w_hi row taps
-            self.stem_w_pair = _bf16(torch.stack([stem_rows(p) for p in pl])).to(dev)     # fused pair stem forward (stem_pair.hip): [2][64][224]
-            self.stem_wt_pair = pair(self._stem_bwd_table(st.w_folded, dtype=torch.float32)).to(dev)     # fused pair stem backward
+        self._build_stem(m.conv1, m.bn1)
         self.fused_stem_bwd = True       # False: max-pool bwd -> patches GEMM -> col2im (kept as the cross-check)
         self.sign_bit_masks = True       # False: the backward reads the bf16 activations for their ReLU sign (cross-check)
         self.halo_conv3x3 = True         # False: layer1 / layer2 3x3 convs on the generic implicit GEMM (cross-check)
@@ -276,19 +263,7 @@ class ResNet50Engine(EngineBase):
                 ds = _Conv(blk.downsample[0], blk.downsample[1], dev, split) if blk.downsample is not None else None
                 self.blocks.append((_Conv(blk.conv1, blk.bn1, dev, split), _Conv(blk.conv2, blk.bn2, dev, split),
                                     _Conv(blk.conv3, blk.bn3, dev, split), ds))
-        # ---- classifier: forward table [1024][2048], backward-to-input table [2048][1024] ([hi | lo | hi] rows in reference precision)
-        wfc = m.fc.weight.detach().float()
-        self.n_classes, self.fc_in = wfc.shape
-        # (class counts that are no multiple of 8 -- small test heads: the forward launch writes n_cols8 columns, the bias is a view into a
-        # vector padded with zeros to that length, and K of the backward is padded to the 64-deep step of rart_gemm_small_m_bf16)
-        self.n_cols8 = (self.n_classes + 7) // 8 * 8
-        fc_b = torch.zeros(self.n_cols8, dtype=torch.float32)
-        fc_b[:self.n_classes] = m.fc.bias.detach().float()
-        self.fc_b = fc_b.to(dev)[:self.n_classes]
-        self.fc_kpad = (self.n_classes + 63) // 64 * 64                   # 1024
-        pl = _planes(wfc, split)
-        self.fc_w = _table(lambda p: pad_rows(p, 128), pl, dev)
-        self.fc_wd = _table(lambda p: pad_k(p.t(), self.fc_kpad), pl, dev)
+        self._build_head(m.fc)
         # round 5 experiment, OFF by default: the pair GEMM's weight tables with the hi and the lo slice of a 32-deep K step side by side (one
         # 128-byte line per row and step instead of two half lines K apart).  2-5 % per K-deep launch when a shape is replayed back to back
         # (profiles/r05_pair_knockouts.txt), nothing on the whole gradient evaluation (20.61 vs 20.63 ms) and +0.9 % on the forward
@@ -298,6 +273,43 @@ class ResNet50Engine(EngineBase):
             self._pack_frag_tables()
         else:
             self._pack_tail_tables()
+
+    def _build_stem(self, conv, bn):
+        """the tables of the stem `conv` + `bn` (7x7/2, 64 channels) in the engine's precision"""
+        import torch
+        split, dev = self.x3, self.device
+        # ---- stem: 7x7/2 conv on the padded 4-channel hi/lo image; a "tap" = one filter row, 8 px x 4 ch
+        st = _Conv(conv, bn, dev, split)
+        self.stem = st
+        pl = _planes(st.w_folded, split)                                  # [64][3][7][7]
+        # stem backward: patches[(r*7+s)*3+c] = sum_k dz[k] * W[k][c][r][s]; 147 rows zero-padded to the tile
+        self.stem_patch_cols = 152                                        # 147 rounded up to 8
+        self.stem_wd = _table(lambda p: pad_rows(p.permute(2, 3, 1, 0).reshape(147, 64), rows_mult(self.stem_patch_cols)), pl, dev)
+        if not split:
+            self.stem_w = _table(lambda p: stem_rows(p).repeat(1, 2), pl, dev)     # the image's hi taps then its lo taps
+            self.stem_wt = self._stem_bwd_table(pl[0]).to(dev)            # fused stem backward (stem_fused.hip)
+        else:
+            self.stem_w = _table(stem_rows, pl, dev)                     # x_hi.w_hi, x_hi.w_lo, x_lo.w_hi row taps
+            self.stem_w_pair = _bf16(torch.stack([stem_rows(p) for p in pl])).to(dev)     # fused pair stem forward (stem_pair.hip): [2][64][224]
+            self.stem_wt_pair = pair(self._stem_bwd_table(st.w_folded, dtype=torch.float32)).to(dev)     # fused pair stem backward
+
+    def _build_head(self, fc):
+        """the tables of the classifier `fc` in the engine's precision"""
+        import torch
+        split, dev = self.x3, self.device
+        # ---- classifier: forward table [1024][2048], backward-to-input table [2048][1024] ([hi | lo | hi] rows in reference precision)
+        wfc = fc.weight.detach().float()
+        self.n_classes, self.fc_in = wfc.shape
+        # (class counts that are no multiple of 8 -- small test heads: the forward launch writes n_cols8 columns, the bias is a view into a
+        # vector padded with zeros to that length, and K of the backward is padded to the 64-deep step of rart_gemm_small_m_bf16)
+        self.n_cols8 = (self.n_classes + 7) // 8 * 8
+        fc_b = torch.zeros(self.n_cols8, dtype=torch.float32)
+        fc_b[:self.n_classes] = fc.bias.detach().float()
+        self.fc_b = fc_b.to(dev)[:self.n_classes]
+        self.fc_kpad = (self.n_classes + 63) // 64 * 64                   # 1024
+        pl = _planes(wfc, split)
+        self.fc_w = _table(lambda p: pad_rows(p, 128), pl, dev)
+        self.fc_wd = _table(lambda p: pad_k(p.t(), self.fc_kpad), pl, dev)
 
     def _pack_tail_tables(self):
         """Reference-precision mode: the 1x1 expansion tables of rart_conv3x3_tail_pair in MFMA fragment order, as [2 (hi, lo)][rows * k]:
@@ -964,8 +976,8 @@ class ResNet50Engine(EngineBase):
         parg = self._get('p1_argmax', (B, h2, w2, 64), torch.uint8) if keep else None
         xs = self._get('p1_sign', (B, h2, w2, 8), torch.uint8) if bits else None
         y1 = None
-        ca = self.blocks[0][0]
-        nxt = self.fused_stem_fwd and x3 and self.fused_stem_next_pair and ('u8' if src_is_u8 else 'f32') in self.fused_stem_next_sources and \
+        ca = self.blocks[0][0] if self.blocks else None      # (an engine without Bottlenecks, DenseNetEngine, has no conv1 to fold in)
+        nxt = ca is not None and self.fused_stem_fwd and x3 and self.fused_stem_next_pair and ('u8' if src_is_u8 else 'f32') in self.fused_stem_next_sources and \
             self.pair_classes >= 4 and self.pair_gemm_kernel and ca.r == 1 and ca.stride == 1 and ca.cin == 64 and ca.cout == 64
         acts['stem_next'] = bool(nxt)        # block 0 starts with its conv1 done
         if nxt:                               # ... with layer1 block 0's conv1 + ReLU on the pooled tile
@@ -1237,7 +1249,7 @@ class ResNet50Engine(EngineBase):
 def make_engine(torch_model, device='cuda', precision='bf16'):
     """HIP engine for a model from robustart_amd.model.get_model: ResNet-50 and its Bottleneck family (ResNet-101/152, Wide-ResNet,
     ResNeXt: the same ResNet50Engine, which reads block counts, widths and groups from the module), ViT-B/16, ConvNeXt-B, ConvNeXt-V2-B (a ConvNeXt
-    subclass: ConvNeXtEngine runs its GRN blocks) or MLP-Mixer-B/16 (MixerEngine), each with forward and
+    subclass: ConvNeXtEngine runs its GRN blocks), MLP-Mixer-B/16 (MixerEngine) or DenseNet-121/169/201 (DenseNetEngine), each with forward and
     backward-to-input (`forward_backward`) on the hand-written kernels.  precision 'bf16x3' / 'fp32x': the
     reference-precision mode (both architectures: split-bf16 pairs, three MFMA products per contraction)."""
     from .resnet_torch import ResNet
@@ -1255,7 +1267,11 @@ def make_engine(torch_model, device='cuda', precision='bf16'):
     if isinstance(torch_model, MlpMixer):
         from .mixer_engine import MixerEngine
         return MixerEngine(torch_model, device, precision)
-    raise NotImplementedError('no HIP engine for %s (the ResNet Bottleneck family / ViT-B/16 / ConvNeXt-B / ConvNeXt-V2-B / MLP-Mixer-B/16 only)'
+    from .densenet_torch import DenseNet
+    if isinstance(torch_model, DenseNet):
+        from .densenet_engine import DenseNetEngine
+        return DenseNetEngine(torch_model, device, precision)
+    raise NotImplementedError('no HIP engine for %s (the ResNet Bottleneck family / ViT-B/16 / ConvNeXt-B / ConvNeXt-V2-B / MLP-Mixer-B/16 / DenseNet only)'
                               % type(torch_model).__name__)
 
 

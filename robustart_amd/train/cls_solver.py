@@ -118,6 +118,10 @@ def train(cfg, args, rank, world, device):
     if cfg['model']['type'] in resnet_family:  # likewise: ResNet-101/152, Wide-ResNet and ResNeXt are evaluated, attacked and corrupted
         raise NotImplementedError('training %r: this member of the ResNet family is evaluation only (forward and backward-to-input on '
                                   'the HIP engine; ResNetTrainEngine is built and measured for resnet50_official alone)' % (cfg['model']['type'],))
+    from ..model.densenet_torch import FAMILY as densenet_family
+    if cfg['model']['type'] in densenet_family:  # likewise: DenseNet-121/169/201 are evaluated, attacked and corrupted
+        raise NotImplementedError('training %r: the DenseNet models are evaluation only (forward and backward-to-input on the HIP '
+                                  'engine; there is no train engine for them)' % (cfg['model']['type'],))
     model = model.to(device)
     from ..model.convnext_torch import ConvNeXt, ConvNeXtV2
     from ..model.mixer_torch import MlpMixer
