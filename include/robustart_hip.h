@@ -722,6 +722,28 @@ int rart_dn_copy_bf16(const void* src, int ld_src, void* dst, int ld_dst, long l
 int rart_dn_copy_pair(const void* src_hi, const void* src_lo, int ld_src, void* dst_hi, void* dst_lo, int ld_dst, long long rows, int c,
                       rart_stream_t stream);
 
+/* One identity BasicBlock of ResNet-18 / -34 (3x3 C -> C, 3x3 C -> C, + the block input; stride 1, "same" padding) as ONE kernel with
+ * the intermediate kept on chip (csrc/basic_block.hip); channels 64 or 128, any h, w >= 1 with n * h * w * channels < 2^31.  Replaces the
+ * two rart_conv3x3_halo_bf16 / rart_conv_igemm_bf16 launches of the block and does their arithmetic: fp32 accumulation, the intermediate
+ * rounded to bf16 once (round-to-nearest-even).  x, out: bf16 NHWC [n][h][w][channels], out != x.  w1, w2: the 3x3 tables
+ * [channels][9 * channels] (k = tap * channels + c) in the fragment order of rart_conv3x3_pack_frag_bf16, with ONE tap list for both;
+ * b1, b2: fp32 [channels] or NULL.  m_mid / m_io: 1 bit per element of the intermediate / of out, indexed like the activation (byte
+ * e / 8, bit e % 8 of element offset e).
+ *   backward = 0: out = relu(w2 * relu(w1 * x + b1) + b2 + x); m_mid and m_io are OUTPUTS (stored value > 0), each may be NULL.  A NaN
+ *                 stays a NaN through both ReLUs.
+ *   backward = 1: x is the gradient at the block output (already masked by that output's ReLU), w1 / w2 the transposed tables of
+ *                 conv2 / conv1 with the flipped taps, no biases; out = m_io . (w2 * (m_mid . (w1 * x)) + x) with m_mid = the sign of
+ *                 the forward's intermediate (required) and m_io = of the block input (or NULL).
+ * Intermediate positions outside the image are zero (the second convolution's padding) and no tile reads a neighbouring image.
+ * Tensors must be 16-byte aligned, biases 4-byte.  rart_basic_block_supported: 1 when the entry takes this width and image size; where
+ * it says 0 the entry returns RART_ERR_INVALID and writes nothing.  rart_basic_block_tile: the output pixels (rows x cols of one image)
+ * a workgroup owns at this width. */
+int rart_basic_block_supported(int channels, int h, int w);
+int rart_basic_block_tile(int channels, int* rows, int* cols);
+int rart_basic_block_bf16(const void* x, const void* w1, const void* w2, const float* b1, const float* b2, void* m_mid, void* m_io,
+                          void* out, int n, int h, int w, int channels, const int* tap_dy, const int* tap_dx, int backward,
+                          rart_stream_t stream);
+
 /* One identity Bottleneck (1x1 c_io -> c_mid, 3x3 c_mid -> c_mid, 1x1 c_mid -> c_io, + the block input) as ONE kernel with
  * both intermediates kept on chip (csrc/bottleneck_fused.hip); supported geometry: c_io 256, c_mid 64, 56 x 56 (ResNet-50
  * layer1 blocks 1-2).  Replaces three rart_conv_igemm_bf16 / rart_conv3x3_halo_bf16 launches and computes the same function.

@@ -104,6 +104,9 @@ SIGNATURES = {
     'rart_dn_preact_pool2_bwd_pair': (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_void_p]),
     'rart_dn_copy_bf16': (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.c_longlong, c_int, c_void_p]),
     'rart_dn_copy_pair': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_longlong, c_int, c_void_p]),
+    'rart_basic_block_supported': (c_int, [c_int, c_int, c_int]),
+    'rart_basic_block_tile': (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    'rart_basic_block_bf16': (c_int, [c_void_p] * 8 + [c_int] * 4 + [ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_void_p]),
     'rart_bottleneck28_fused_supported': (c_int, [c_int, c_int, c_int, c_int]),
     'rart_bottleneck28_fused_bf16': (c_int, [c_void_p] * 11 + [c_int] * 5 + [ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int,
                                              c_void_p]),

@@ -16,6 +16,10 @@ refuses to train them.
 `densenet121`, `densenet169`, `densenet201` (densenet_torch.py: the public torchvision definition) run on DenseNetEngine
 (densenet_engine.py: the pre-activation and dense-concatenation kernels of csrc/densenet.hip around the shared GEMM entries), forward +
 backward-to-input in both precisions; evaluation only, `cls_solver` refuses to train them.
+`resnet18_official`, `resnet34_official` (resnet_basic_torch.py: the BasicBlock members of the ResNet family, torchvision's keys) run on
+BasicResNetEngine (basic_resnet_engine.py: ResNet-50's stem, head and convolution launchers; in bf16 an identity block of layer1 /
+layer2 is one launch of csrc/basic_block.hip where `basic_block_widths` lists its width), forward + backward-to-input in both
+precisions; evaluation only, `cls_solver` refuses to train them.  The bare names `resnet18` / `resnet34` are not registered.
 kwargs `num_classes` and `drop_path_rate` are accepted (drop path is identity in eval)."""
 from .resnet_torch import resnet50, FAMILY as _RESNET_FAMILY
 from .vit_torch import vit_base
@@ -23,6 +27,7 @@ from .convnext_torch import convnext_base, convnextv2_base
 from .mixer_torch import mixer_b16_224
 from .convstem_torch import convnext_base_cvst, vit_base_cvst
 from .densenet_torch import FAMILY as _DENSENET_FAMILY
+from .resnet_basic_torch import BASIC_FAMILY as _BASIC_FAMILY
 
 _REGISTRY = {'resnet50_official': resnet50, 'resnet50': resnet50, 'vit_base': vit_base, 'vit_b16_224': vit_base,
              'vit_base_patch16_224': vit_base, 'convnext_base': convnext_base,
@@ -30,6 +35,7 @@ _REGISTRY = {'resnet50_official': resnet50, 'resnet50': resnet50, 'vit_base': vi
              'vit_base_cvst': vit_base_cvst, 'vit_b16_224_cvst': vit_base_cvst}
 _REGISTRY.update(_RESNET_FAMILY)
 _REGISTRY.update(_DENSENET_FAMILY)
+_REGISTRY.update(_BASIC_FAMILY)          # (the bare names `resnet18` / `resnet34` stay unregistered)
 
 
 def get_model(config):
@@ -39,5 +45,5 @@ def get_model(config):
     kwargs = dict((config.get('kwargs') if isinstance(config, dict) else getattr(config, 'kwargs', None)) or {})
     kwargs.pop('bn', None)          # {use_sync_bn: False}: BN statistics are local
     if mtype not in _REGISTRY:
-        raise NotImplementedError('model type %r is outside the hot-path scope (the ResNet Bottleneck family / ViT-B/16 / ConvNeXt-B / ConvNeXt-V2-B / MLP-Mixer-B/16 / DenseNet-121/169/201 only)' % mtype)
+        raise NotImplementedError('model type %r is outside the hot-path scope (the ResNet Bottleneck family / ViT-B/16 / ConvNeXt-B / ConvNeXt-V2-B / MLP-Mixer-B/16 / DenseNet-121/169/201 / ResNet-18/34 as resnet18_official, resnet34_official only)' % mtype)
     return _REGISTRY[mtype](**kwargs)

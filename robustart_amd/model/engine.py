@@ -1249,7 +1249,8 @@ class ResNet50Engine(EngineBase):
 def make_engine(torch_model, device='cuda', precision='bf16'):
     """HIP engine for a model from robustart_amd.model.get_model: ResNet-50 and its Bottleneck family (ResNet-101/152, Wide-ResNet,
     ResNeXt: the same ResNet50Engine, which reads block counts, widths and groups from the module), ViT-B/16, ConvNeXt-B, ConvNeXt-V2-B (a ConvNeXt
-    subclass: ConvNeXtEngine runs its GRN blocks), MLP-Mixer-B/16 (MixerEngine) or DenseNet-121/169/201 (DenseNetEngine), each with forward and
+    subclass: ConvNeXtEngine runs its GRN blocks), MLP-Mixer-B/16 (MixerEngine), DenseNet-121/169/201 (DenseNetEngine) or ResNet-18/34
+    (BasicResNetEngine), each with forward and
     backward-to-input (`forward_backward`) on the hand-written kernels.  precision 'bf16x3' / 'fp32x': the
     reference-precision mode (both architectures: split-bf16 pairs, three MFMA products per contraction)."""
     from .resnet_torch import ResNet
@@ -1271,7 +1272,12 @@ def make_engine(torch_model, device='cuda', precision='bf16'):
     if isinstance(torch_model, DenseNet):
         from .densenet_engine import DenseNetEngine
         return DenseNetEngine(torch_model, device, precision)
-    raise NotImplementedError('no HIP engine for %s (the ResNet Bottleneck family / ViT-B/16 / ConvNeXt-B / ConvNeXt-V2-B / MLP-Mixer-B/16 / DenseNet only)'
+    from .resnet_basic_torch import BasicResNet
+    if isinstance(torch_model, BasicResNet):
+        from .basic_resnet_engine import BasicResNetEngine
+        return BasicResNetEngine(torch_model, device, precision)
+    raise NotImplementedError('no HIP engine for %s (the ResNet Bottleneck family / ViT-B/16 / ConvNeXt-B / ConvNeXt-V2-B / MLP-Mixer-B/16 / DenseNet / '
+                              'ResNet-18/34 only)'
                               % type(torch_model).__name__)
 
 

@@ -122,6 +122,10 @@ def train(cfg, args, rank, world, device):
     if cfg['model']['type'] in densenet_family:  # likewise: DenseNet-121/169/201 are evaluated, attacked and corrupted
         raise NotImplementedError('training %r: the DenseNet models are evaluation only (forward and backward-to-input on the HIP '
                                   'engine; there is no train engine for them)' % (cfg['model']['type'],))
+    from ..model.resnet_basic_torch import BasicResNet
+    if isinstance(model, BasicResNet):           # likewise: ResNet-18/34 are evaluated, attacked and corrupted
+        raise NotImplementedError('training %r: the BasicBlock ResNets are evaluation only (forward and backward-to-input on the HIP '
+                                  'engine; there is no train engine for them)' % (cfg['model']['type'],))
     model = model.to(device)
     from ..model.convnext_torch import ConvNeXt, ConvNeXtV2
     from ..model.mixer_torch import MlpMixer
